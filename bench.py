@@ -12,7 +12,12 @@ rank runs -- by its exchange step over RCCL/xGMI:
              all-gather of the N partial points + local additions.
 One process per GPU, rank = party; per-GPU work is fixed => "scaling": "weak".
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line: the headline `value` with the phase split and the
+roofline of the timed steps themselves.  --dump-outputs DIR then also writes the result of the last timed step to DIR (inputs
+are seeded: the same arguments give the same inputs, so two builds can be compared output for output).  --full adds every
+other leg listed below; it is what the tests, the profile collection and the runbooks use.
 
 N > 1 runs one process per GPU over torch.distributed (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the environment when a
 launcher provides them).  Started WITHOUT a launcher, `python bench.py --gpus N` launches itself: it re-executes under
@@ -22,7 +27,7 @@ mpc-net/src/multi.rs:330-352).  With fewer than N GPUs it prints a JSON line car
 ZK_BENCH_BACKEND=gloo (processes) / =local (party threads) exercise the N > 1 code path on a box with fewer GPUs than ranks
 (ranks then share GPUs round-robin; the exchanges travel through the host): functional records, not scaling figures.
 
-Rank 0 prints ONE JSON line.  Besides the contract fields it carries
+Rank 0 prints ONE JSON line.  Besides the contract fields it carries (the legs after msm_phase_ms / roofline with --full only)
   roofline       dominant kernel (bucket accumulation), HIP-event timed inside the library on its own stream
   strong         STRONG scaling of one primitive over the N ranks (zkhip/sharding.py): one 2^20 MSM, one
                  2^24 MSM, one 2^24 product sumcheck -- total work fixed, split N ways
@@ -289,11 +294,27 @@ def device_table(ctx, log2n: int, seed: int):
     return out
 
 
+def _at_least(lo: int):
+    def parse(s: str) -> int:
+        v = int(s)
+        if v < lo:
+            raise argparse.ArgumentTypeError(f"must be >= {lo}, got {v}")
+        return v
+
+    return parse
+
+
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=50)
-    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--steps", type=_at_least(1), default=50, help="timed steps (ms_per_step = their wall time / steps)")
+    ap.add_argument("--warmup", type=_at_least(0), default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="run every leg beside the headline (table-less and pipelined MSM, strong scaling, sumcheck family, end-to-end proofs, G2, "
+                         "CPU baseline); off: set up, warm up, time the steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the last step's MSM result (normalised Jacobian, 18 uint64 limbs) as DIR/msm_g1_result.npy "
+                         "(DIR/msm_g1_result_rank<r>.npy per rank when N > 1): float64, the limbs as little-endian 32-bit words, shape [..., 36]")
     ap.add_argument("--log2n", type=int, default=LOG2_N)
     ap.add_argument("--cpu-log2n", type=int, default=20, help="size of the bounded CPU-baseline MSM sample")
     ap.add_argument("--cpu-e2e-n", type=int, default=13, help="log2 constraints of the CPU end-to-end sample")
@@ -429,6 +450,7 @@ def run_rank(args, grp, gpu: int, ctx, net):
     from zkhip.field import int_to_limbs, random_fr
 
     world, rank, backend = grp.world, grp.rank, grp.backend
+    extra_legs = args.full and not args.no_extra  # a plain run does only what the headline needs
     n = 1 << args.log2n
     pp = None
     if world == 8:
@@ -464,10 +486,10 @@ def run_rank(args, grp, gpu: int, ctx, net):
     # The SRS is fixed for the life of a prover (PolynomialCommitmentCub::new, dpoly_comm.rs:37-67): like uploading it, the
     # window table 2^{o_w} P_i (zk_srs_precompute) is built once, outside the timed region.  With it every digit of a scalar
     # lands in ONE bucket set, so the window can be 19 bits wide at 2^20 points: 14 bucket additions per scalar instead of
-    # 16, one bucket reduction instead of 8.  The table-less path is timed first (a few steps) and reported beside it.
+    # 16, one bucket reduction instead of 8.  The table-less path is timed first (a few steps) and reported beside it (--full).
     default_path = None
     if not args.no_precompute:
-        if not args.no_extra:  # (profiling runs time the headline geometry only)
+        if extra_legs:  # (plain and profiling runs time the headline geometry only)
             for _ in range(2):
                 step()
             ph0 = np.zeros(6)
@@ -494,11 +516,16 @@ def run_rank(args, grp, gpu: int, ctx, net):
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = step()
         phase += ctx.msm_last_timing()
     barrier()
     dt = grp.allmax(time.perf_counter() - t0)
-    phase /= max(args.steps, 1)
+    phase /= args.steps
+    if args.dump_outputs:
+        # what a caller of the step receives (uint64 limbs), as float64 of its exact 32-bit words
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        words = np.ascontiguousarray(np.asarray(last, dtype="<u8")).view("<u4").astype(np.float64)
+        np.save(os.path.join(args.dump_outputs, "msm_g1_result.npy" if world == 1 else f"msm_g1_result_rank{rank}.npy"), words)
     # who ran: one entry per rank (the driver can see that RCCL really had N ranks on N distinct devices)
     rccl_ranks = int(ctx.comm_size) if (net is not None and type(net).__name__ == "RcclNet") else 0
     who = grp.all_gather_obj({"rank": rank, "gpu": gpu, "name": torch.cuda.get_device_name(gpu), "pid": os.getpid(), "zk_comm_size": rccl_ranks})
@@ -507,7 +534,7 @@ def run_rank(args, grp, gpu: int, ctx, net):
     # fix-up, 18 reduction passes, host chain -- runs beside the accumulation of the next two).  Every result is collected inside
     # the timed region.  Reported beside `value`, which stays the one-call-at-a-time figure.
     pipelined = None
-    if world == 1 and not args.no_extra:
+    if world == 1 and extra_legs:
         try:
             def run_pipelined(k, depth=3):
                 jobs = []
@@ -631,7 +658,7 @@ def run_rank(args, grp, gpu: int, ctx, net):
     # from the compiled host in its own process, self-checked by the host's own anchored verifier.  It runs BEFORE the other legs:
     # the n = 24 parameter set with its window tables and pass arenas wants most of the device, and this process holds only the
     # headline's 2^20-point level at this point.  Skipped -- and said so -- when the free HBM is below the footprint.
-    if world == 1 and not args.no_extra and not args.no_e2e and not args.no_e2e_n24:
+    if world == 1 and extra_legs and not args.no_e2e and not args.no_e2e_n24:
         try:
             ctx.trim()
             free_b, total_b = ctx.mem_info()
@@ -670,7 +697,7 @@ def run_rank(args, grp, gpu: int, ctx, net):
         except Exception as ex:
             extra["e2e_n24"] = {"error": repr(ex)}
 
-    if not args.no_extra:
+    if extra_legs:
         try:
             # ---- strong scaling of ONE primitive over the ranks (total work fixed) ----
             strong = {}
@@ -1009,7 +1036,7 @@ def run_rank(args, grp, gpu: int, ctx, net):
 
     out.update(extra)
 
-    if not args.no_cpu and world == 1:  # the CPU leg runs at N = 1 only (rank 0)
+    if args.full and not args.no_cpu and world == 1:  # the CPU leg runs at N = 1 only (rank 0)
         # CPU baseline leg: the oracle (C port of the reference's single-threaded path) on this
         # box's host cores.  Checker/baseline only -- never part of the measured GPU path.
         sys.path.insert(0, os.path.join(ROOT, "oracle"))

@@ -42,3 +42,9 @@ def test_bad_rank_counts_are_reported_not_asserted():
     assert r.returncode != 0 and "power of two" in line["error"] and "Traceback" not in r.stderr
     r, line = _bench("--gpus", "2", env={"WORLD_SIZE": "4"})
     assert r.returncode != 0 and "WORLD_SIZE=4" in line["error"] and "Traceback" not in r.stderr
+
+
+def test_steps_must_be_at_least_one():
+    """ms_per_step is the timed window over --steps: an empty window is refused before anything runs"""
+    r, _ = _bench("--steps", "0")
+    assert r.returncode == 2 and "--steps: must be >= 1" in r.stderr and "Traceback" not in r.stderr

@@ -41,7 +41,7 @@ def test_more_ranks_than_gpus_is_an_error_line():
 
 def test_gpus_2_self_launches_processes_over_gloo():
     """`python bench.py --gpus 2` re-executes itself under torch.distributed.run; one MSM over 2 x 2^16 points in two chunks"""
-    r, line = _bench("--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu", "--log2n", "16", "--big", "18", env={"ZK_BENCH_BACKEND": "gloo"})
+    r, line = _bench("--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu", "--log2n", "16", "--big", "18", env={"ZK_BENCH_BACKEND": "gloo"})
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     assert line["n_gpus"] == 2 and line["steps"] == 2 and line["value"] > 0 and line["scaling"] == "weak"
     assert [d["rank"] for d in line["ranks"]["devices"]] == [0, 1] and len({d["pid"] for d in line["ranks"]["devices"]}) == 2
@@ -53,7 +53,7 @@ def test_gpus_2_self_launches_processes_over_gloo():
 def test_gpus_8_party_threads_with_anchored_e2e():
     """one process, eight party threads (--party-threads): the 8-party d_msm as the step, and the 8-party protocol (n = 12) with
     every transcript chain anchored by all parties' values -- the check the 8-GPU run performs"""
-    r, line = _bench("--gpus", "8", "--party-threads", "--steps", "2", "--warmup", "1", "--no-cpu", "--log2n", "12", "--big", "14", "--e2e-n", "12",
+    r, line = _bench("--full", "--gpus", "8", "--party-threads", "--steps", "2", "--warmup", "1", "--no-cpu", "--log2n", "12", "--big", "14", "--e2e-n", "12",
                      env={"ZK_BENCH_BACKEND": "local"})
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     assert line["n_gpus"] == 8 and line["value"] > 0 and line["config"]["parties"] == 8
@@ -71,7 +71,7 @@ def test_gpus_8_line_carries_the_compiled_hosts_rccl_mode_proof():
     the line and the digest equals the Python host's 8-party run"""
     fake = os.path.join(ROOT, "tests", "native", "fake_rccl")
     subprocess.check_call(["make", "-C", os.path.join(ROOT, "tests", "native"), "-s", "fake_rccl/librccl.so.1"])
-    r, line = _bench("--gpus", "8", "--party-threads", "--steps", "2", "--warmup", "1", "--no-cpu", "--log2n", "12", "--big", "14", "--e2e-n", "12",
+    r, line = _bench("--full", "--gpus", "8", "--party-threads", "--steps", "2", "--warmup", "1", "--no-cpu", "--log2n", "12", "--big", "14", "--e2e-n", "12",
                      env={"ZK_BENCH_BACKEND": "local", "ZK_BENCH_CPP_RCCL": "share", "LD_LIBRARY_PATH": fake + os.pathsep + os.environ.get("LD_LIBRARY_PATH", "")})
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     leg = line["e2e_cpp_rccl"]
@@ -84,7 +84,7 @@ def test_gpus_8_line_carries_the_compiled_hosts_rccl_mode_proof():
 
 
 def test_single_gpu_line_has_the_record_fields():
-    r, line = _bench("--steps", "3", "--warmup", "1", "--no-cpu", "--big", "22", "--e2e-n", "12", timeout=1200)
+    r, line = _bench("--full", "--steps", "3", "--warmup", "1", "--no-cpu", "--big", "22", "--e2e-n", "12", timeout=1200)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     assert line["n_gpus"] == 1 and line["rccl_ranks"] == 0 and line["exchange_backend"].startswith("none")
     rf = line["roofline"]
@@ -107,3 +107,27 @@ def test_single_gpu_line_has_the_record_fields():
     cp = line["cpermcheck"]
     assert "error" not in cp and cp["self_check_ok"] is True and "5 recomputed" in cp["self_check"], cp
     assert 0 < cp["timers_s"]["Collaborative Permcheck"] < 1 and cp["scalar_muls_computed"] == 20 * (4 << 12) - 10
+
+
+def test_plain_run_times_the_headline_only_and_dumps_its_last_result(ctx, tmp_path):
+    """without --full the line carries the headline and nothing that needs runs of its own; --dump-outputs writes the last timed
+    step's MSM result, which must be the point this test computes from the same seeded inputs"""
+    import numpy as np
+
+    from zkhip.field import random_fr
+
+    lg, steps = 14, 4
+    r, line = _bench("--steps", str(steps), "--warmup", "1", "--log2n", str(lg), "--dump-outputs", str(tmp_path))
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    assert line["steps"] == steps and line["warmup"] == 1 and line["higher_is_better"] is True and line["dtype"] == "u32"
+    assert line["value"] > 0 and abs(line["value"] * line["ms_per_step"] * 1e-3 - (1 << lg)) < 1e-6 * (1 << lg)
+    assert not {"strong", "sumcheck", "d_sumcheck", "e2e", "e2e_n24", "cpermcheck", "g2", "ms_per_step_scalars_from_host", "cpu_baseline"} & set(line)
+    assert line["msm_without_window_table"] is None and line["msm_three_calls_in_flight"] is None
+    got = np.load(tmp_path / "msm_g1_result.npy")
+    n = 1 << lg
+    srs = ctx.srs_generate(0x1234567, 0x89ABCDE, n)  # bench.py's inputs at N = 1 (rank 0)
+    try:
+        want = ctx.msm_g1(srs, ctx.to_device(random_fr(n, 0x5CA1AB1E + 1000 * 2)), n)
+    finally:
+        srs.free()
+    assert got.dtype == np.float64 and got.shape == (36,) and (got == want.view("<u4").astype(np.float64)).all()

@@ -1,6 +1,8 @@
 set -u
 T=${1:-r03g}
-python bench.py > gpurun_out/${T}_bench.json 2> gpurun_out/${T}_bench.err
+# the bench lines of the collection (every leg: --full) go to $OUT_DIR; the profiling tools below write to their own output folder
+OUT=${OUT_DIR:-profile_out}; mkdir -p "$OUT"
+python bench.py --full > "$OUT/${T}_bench.json" 2> "$OUT/${T}_bench.err"
 tools/profile_bench.sh $T > gpurun_out/${T}_profile.log 2>&1
 tools/profile_valu.sh $T >> gpurun_out/${T}_profile.log 2>&1
 tools/sc_prof.sh $T 20 >> gpurun_out/${T}_profile.log 2>&1
@@ -39,9 +41,9 @@ python tools/sc_batch_time.py 18 > gpurun_out/${T}_sc_batch.txt 2>&1
 # N > 1 exactly as the driver launches it (`python bench.py --gpus N`, no launcher): functional runs on the one GPU of the box
 export HSA_ENABLE_IPC_MODE_LEGACY=0 ZK_BENCH_DEADLINE_S=600
 # (8 PROCESSES sharing one GPU: the n = 20 leg with its window tables and job-lane arenas, ~30 GB per rank, does not fit eight times: n = 16 there)
-for N in 2 8; do ZK_BENCH_BACKEND=gloo python bench.py --gpus $N --steps 3 --warmup 1 --no-cpu --e2e-n $((N == 8 ? 16 : 20)) 2>gpurun_out/${T}_gloo$N.err | tail -1; done > gpurun_out/${T}_bench_gloo_ranks_sharing_one_gpu.jsonl
+for N in 2 8; do ZK_BENCH_BACKEND=gloo python bench.py --full --gpus $N --steps 3 --warmup 1 --no-cpu --e2e-n $((N == 8 ? 16 : 20)) 2>"$OUT/${T}_gloo$N.err" | tail -1; done > "$OUT/${T}_bench_gloo_ranks_sharing_one_gpu.jsonl"
 sleep 5  # (the eight gloo ranks above release the GPU's memory when they exit)
-ZK_BENCH_BACKEND=local python bench.py --gpus 8 --party-threads --steps 3 --warmup 1 --no-cpu --e2e-n 16 2>gpurun_out/${T}_threads8.err | tail -1 > gpurun_out/${T}_bench_party_threads_sharing_one_gpu.jsonl
+ZK_BENCH_BACKEND=local python bench.py --full --gpus 8 --party-threads --steps 3 --warmup 1 --no-cpu --e2e-n 16 2>"$OUT/${T}_threads8.err" | tail -1 > "$OUT/${T}_bench_party_threads_sharing_one_gpu.jsonl"
 python bench.py --gpus 2 --no-cpu 2>/dev/null | tail -1 > gpurun_out/${T}_bench_gpus2_on_a_one_gpu_box_error_line.json
 # randomised differential runs against the C oracle, new seeds
 { STRESS_SEED=6061 python tools/stress_msm.py 120 | tail -1; STRESS_SEED=6062 STRESS_TABLE=1 python tools/stress_msm.py 120 | tail -1; STRESS_SEED=6063 python tools/stress_sumcheck.py 180 | tail -1; } > gpurun_out/${T}_stress.txt 2>&1

@@ -14,7 +14,7 @@ rm -rf /tmp/prof_stats /tmp/prof_FETCH_SIZE /tmp/prof_WRITE_SIZE
 rocprofv3 --kernel-trace --stats -f csv -d /tmp/prof_stats -o stats -- python $REPO/bench.py --steps 10 --no-cpu --no-extra > $OUT/${TAG}_bench_under_rocprof.json 2>/tmp/prof_stats.err
 cp $(find /tmp/prof_stats -name '*kernel_stats.csv' | head -1) $OUT/${TAG}_kernel_stats.csv
 for C in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --pmc $C -f csv -d /tmp/prof_$C -o pmc -- python $REPO/bench.py --steps 30 --no-cpu --no-e2e > /dev/null 2>/tmp/prof_$C.err
+  rocprofv3 --pmc $C -f csv -d /tmp/prof_$C -o pmc -- python $REPO/bench.py --full --steps 30 --no-cpu --no-e2e > /dev/null 2>/tmp/prof_$C.err
 done
 python $REPO/tools/pmc_summary.py $(find /tmp/prof_FETCH_SIZE -name '*counter_collection.csv' | head -1) $(find /tmp/prof_WRITE_SIZE -name '*counter_collection.csv' | head -1) > $OUT/${TAG}_pmc_hbm_traffic.csv
 head -12 $OUT/${TAG}_kernel_stats.csv
