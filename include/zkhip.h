@@ -332,6 +332,40 @@ int zk_scatter(zk_ctx *ctx, const void *d_send, size_t bytes, int root, void *d_
 int zk_d_msm(zk_ctx *ctx, size_t count, const zk_srs *const *srs, const size_t *offsets, const void *const *d_scalars,
              const size_t *n, const uint64_t *h_lambda, const uint64_t *h_coeffs, uint64_t *h_out);
 
+/* ---- the BLS12-381 pairing and PolynomialCommitment::verify (dist-primitive/src/dpoly_comm.rs:466-484) ----------------------
+ * Inputs: G1 affine 96-byte records (x||y, x = y = 0: infinity), G2 affine 192-byte records at g2_stride (192, or the Rust
+ * struct's stride: a nonzero flag byte at offset 192 marks infinity), G1 Jacobian 18 u64 (any representative; the library's
+ * results are normalised), Fr 4 u64 Montgomery.  Before anything is launched every point is checked to be canonical and on
+ * its curve (ZK_ERR_INVALID otherwise).  Membership in the prime-order subgroups is NOT checked -- as for zk_srs_register it is
+ * the caller's responsibility (arkworks' G1Affine / G2Affine guarantee it); off-subgroup points give meaningless values or
+ * verdicts, never a fault or a hang.  A pair with a point at infinity contributes a factor 1.  Every call ends in one
+ * synchronisation of the ctx stream.
+ *
+ * Values: e(P, Q) is the optimal ate Miller value f_{|x|,Q}(P) (|x| = 0xd201000000010000, not conjugated) after the final
+ * exponentiation, raised to ZK_PAIRING_EXP_MULTIPLE: f^(3 (q^12 - 1) / r).  3 is coprime to r, so a product of pairings is 1
+ * exactly when it is 1 under any other normalisation of the pairing.
+ * Output Fq12: ark's Fq12{c0: Fq6{c0, c1, c2: Fq2}, c1: Fq6} -- 72 u64, each Fq 6 u64 in Montgomery form (radix 2^384). */
+#define ZK_PAIRING_EXP_MULTIPLE 3
+/* e(P_i, Q_i) for count pairs; h_out: count x 72 u64 */
+int zk_pairing(zk_ctx *ctx, size_t count, const void *h_g1_96, const void *h_g2, size_t g2_stride, uint64_t *h_out);
+/* h_ok[g] = (prod_{h_start[g] <= i < h_start[g+1]} e(P_i, Q_i) == 1), one final exponentiation per group; h_start: groups + 1
+ * non-decreasing offsets from 0 (an empty group is 1).  The Miller loops of all pairs run in parallel; the product of a group
+ * is taken serially by one lane (one Fq12 multiplication per pair, ~0.1 ms each), so a group of thousands of pairs costs
+ * tenths of a second on its own: split very large products into groups of tens of pairs and compare their values instead. */
+int zk_pairing_product_check(zk_ctx *ctx, size_t groups, const size_t *h_start, const void *h_g1_96, const void *h_g2,
+                             size_t g2_stride, uint8_t *h_ok);
+/* the verifying key of PolynomialCommitment: g1 = powers_of_g[0][0] (NULL: the generator), powers_of_g2 = [g2, s_0 g2, ...]
+ * (n_g2 >= 1; host copies are kept) */
+typedef struct zk_pcs_vk zk_pcs_vk;
+int zk_pcs_vk_create(zk_ctx *ctx, const void *h_g1_96, const void *h_powers_g2, size_t g2_stride, size_t n_g2, zk_pcs_vk **out);
+int zk_pcs_vk_free(zk_ctx *ctx, zk_pcs_vk *vk);
+/* PolynomialCommitment::verify for count openings of nvars-variate polynomials (nvars + 1 <= n_g2, else ZK_ERR_INVALID):
+ * commitments count x 18 u64, values count x 4, proofs count x nvars x 18, points count x nvars x 4; h_ok[k] = 1 when
+ *   e(C_k - v_k g1, g2) == prod_i e(pi_ki, s_i g2 - u_ki g2),
+ * computed as e(A_k, g2) * prod_i e(-pi_ki, s_i g2) == 1 with A_k = C_k - v_k g1 + sum_i u_ki pi_ki. */
+int zk_pcs_verify_batch(zk_ctx *ctx, const zk_pcs_vk *vk, size_t nvars, size_t count, const uint64_t *h_commitments,
+                        const uint64_t *h_values, const uint64_t *h_proofs, const uint64_t *h_points, uint8_t *h_ok);
+
 /* (the zk_dbg_* test hooks of the library are declared in include/zkhip_test.h: they are not part of this surface) */
 
 #ifdef __cplusplus

@@ -1,6 +1,6 @@
 // dist-primitive/src/dpoly_comm.rs: commit / open / c_open with their MSMs and fold loops on the GPU; signatures unchanged
 // (`impl<E: Pairing> PolynomialCommitment<E>`).  UNCOMPILED here (no Rust toolchain).  `c_commit` (:244-267) and `d_commit`
-// (:276-297) need NO edit: they call `d_msm` / `d_local_commit`, which are patched.
+// (:276-297) need NO edit: they call `d_msm` / `d_local_commit`, which are patched.  `verify` (:466-484) runs on zk_pcs_verify_batch.
 use crate::zkhip_party::{check, is_bls12_381_g1, ZkParty};
 use crate::zkhip_sys::*;
 use std::os::raw::c_void;
@@ -80,6 +80,41 @@ impl<E: Pairing> PolynomialCommitment<E> {
         // Phase 2 on the l-vector re-using point[0..] (:452), each round pushing a local commit(q): :441-462 unchanged
         let value = self.c_open_phase2(&mut res, &mut current_r, point, pp);
         Ok((value, res))
+    }
+
+    /// :466-484: e(C - v g1, g2) == sum_i e(pi_i, s_i g2 - u_i g2) as ONE opening of zk_pcs_verify_batch (a device Miller loop per
+    /// pair and one final exponentiation); the vk is built from powers_of_g[0][0] and powers_of_g2 (affine, at the Rust stride)
+    pub fn verify(&self, commitment: E::G1, value: E::ScalarField, proof: &Vec<E::G1>, point: &Vec<E::ScalarField>) -> bool {
+        if let (true, Some(party)) = (is_bls12_381_g1::<E::G1>(), ZkParty::any()) {
+            assert_eq!(proof.len(), point.len());
+            let g1 = self.powers_of_g[0][0].into_affine();
+            let g2s = E::G2::normalize_batch(&self.powers_of_g2);
+            let mut vk: *mut ZkPcsVk = std::ptr::null_mut();
+            check(party.ctx, unsafe {
+                zk_pcs_vk_create(party.ctx, &g1 as *const _ as *const c_void, g2s.as_ptr() as *const c_void,
+                                 std::mem::size_of::<E::G2Affine>(), g2s.len(), &mut vk)
+            }).unwrap();
+            // G1 projective = 18 u64 (x, y, z), Fr = 4 u64 Montgomery: the buffers go as they are
+            let mut ok = [0u8; 1];
+            let rc = unsafe {
+                zk_pcs_verify_batch(party.ctx, vk, proof.len(), 1, &commitment as *const _ as *const u64, &value as *const _ as *const u64,
+                                    proof.as_ptr() as *const u64, point.as_ptr() as *const u64, ok.as_mut_ptr())
+            };
+            unsafe { zk_pcs_vk_free(party.ctx, vk) };
+            check(party.ctx, rc).unwrap();
+            return ok[0] == 1;
+        }
+        let g1 = self.powers_of_g[0][0];
+        let g2 = self.powers_of_g2[0];
+        let left = E::pairing(commitment - g1 * value, g2);
+        let right = {
+            let mut ans = PairingOutput::<E>::zero();
+            for i in 0..proof.len() {
+                ans += E::pairing(proof[i], self.powers_of_g2[i + 1] - g2 * (point[i]));
+            }
+            ans
+        };
+        left == right
     }
 }
 // `open_cpu`, `c_open_cpu`, `c_open_phase2`: the reference's statements at the cited lines moved into helpers (not reproduced).

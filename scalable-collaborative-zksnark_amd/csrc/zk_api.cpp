@@ -546,6 +546,29 @@ int zk_g1_lincomb_batch(zk_ctx* ctx, const uint64_t* h_points, const uint64_t* h
     NEED(ctx, (count == 0 || h_out) && (n == 0 || count == 0 || (h_points && h_scalars)));
     return g1_lincomb_batch_host(ctx, h_points, h_scalars, n, count, h_out);
 }
+int zk_pairing(zk_ctx* ctx, size_t count, const void* h_g1_96, const void* h_g2, size_t g2_stride, uint64_t* h_out) {
+    NEED(ctx, count == 0 || (h_g1_96 && h_g2 && h_out));
+    return pairing_values(ctx, count, h_g1_96, h_g2, g2_stride, h_out);
+}
+int zk_pairing_product_check(zk_ctx* ctx, size_t groups, const size_t* h_start, const void* h_g1_96, const void* h_g2, size_t g2_stride,
+                             uint8_t* h_ok) {
+    NEED(ctx, groups == 0 || (h_start && h_ok));
+    return pairing_product_check(ctx, groups, h_start, h_g1_96, h_g2, g2_stride, h_ok);
+}
+int zk_pcs_vk_create(zk_ctx* ctx, const void* h_g1_96, const void* h_powers_g2, size_t g2_stride, size_t n_g2, zk_pcs_vk** out) {
+    NEED(ctx, h_powers_g2 && out);
+    return pcs_vk_create(ctx, h_g1_96, h_powers_g2, g2_stride, n_g2, out);
+}
+int zk_pcs_vk_free(zk_ctx* ctx, zk_pcs_vk* vk) {
+    if (!ctx) return ZK_ERR_INVALID;
+    pcs_vk_free(vk);
+    return ZK_OK;
+}
+int zk_pcs_verify_batch(zk_ctx* ctx, const zk_pcs_vk* vk, size_t nvars, size_t count, const uint64_t* h_commitments,
+                        const uint64_t* h_values, const uint64_t* h_proofs, const uint64_t* h_points, uint8_t* h_ok) {
+    NEED(ctx, vk && (count == 0 || (h_commitments && h_values && h_ok && (nvars == 0 || (h_proofs && h_points)))));
+    return pcs_verify_batch(ctx, vk, nvars, count, h_commitments, h_values, h_proofs, h_points, h_ok);
+}
 int zk_msm_window(size_t n) { return msm_pick_window(n); }
 int zk_msm_set_window(zk_ctx* ctx, int c) {
     if (!ctx || c < 0 || c > 20) return ZK_ERR_INVALID;

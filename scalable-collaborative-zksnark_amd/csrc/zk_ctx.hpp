@@ -193,5 +193,13 @@ int msm_pick_window(size_t n);
 int g1_lincomb_batch_host(zk_ctx* ctx, const uint64_t* h_points_jac, const uint64_t* h_scalars_canon, size_t n, size_t count,
                           uint64_t* h_out);
 int g1_lincomb_host(zk_ctx* ctx, const uint64_t* h_points_jac, const uint64_t* h_scalars_canon, size_t n, uint64_t* h_out);
+// ---- zk_pairing.hip ----
+int pairing_values(zk_ctx* ctx, size_t count, const void* h_g1, const void* h_g2, size_t g2_stride, uint64_t* h_out);
+int pairing_product_check(zk_ctx* ctx, size_t groups, const size_t* h_start, const void* h_g1, const void* h_g2, size_t g2_stride,
+                          uint8_t* h_ok);
+int pcs_vk_create(zk_ctx* ctx, const void* h_g1_96, const void* h_powers_g2, size_t g2_stride, size_t n_g2, zk_pcs_vk** out);
+void pcs_vk_free(zk_pcs_vk* vk);
+int pcs_verify_batch(zk_ctx* ctx, const zk_pcs_vk* vk, size_t nvars, size_t count, const uint64_t* h_comm, const uint64_t* h_values,
+                     const uint64_t* h_proofs, const uint64_t* h_points, uint8_t* h_ok);
 
 }  // namespace zk

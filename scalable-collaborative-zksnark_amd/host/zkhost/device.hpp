@@ -40,6 +40,19 @@ struct CtxHandle {
     }
 };
 using CtxRef = std::shared_ptr<CtxHandle>;
+using G2 = std::array<uint64_t, 36>;  // normalised G2 projective (3 x Fq2), as zk_msm_g2 returns it
+
+// the verifying key of PolynomialCommitment held by the library (zk_pcs_vk: g1 and powers_of_g2)
+struct PcsVk {
+    CtxRef ctx;
+    zk_pcs_vk *h = nullptr;
+    size_t n_g2 = 0;
+    PcsVk(CtxRef c, zk_pcs_vk *h_, size_t n) : ctx(std::move(c)), h(h_), n_g2(n) {}
+    PcsVk(const PcsVk &) = delete;
+    ~PcsVk() {
+        if (h) zk_pcs_vk_free(ctx->h, h);
+    }
+};
 
 // a device allocation (zk_malloc / zk_free); DevPtr below shares it
 struct DevAlloc {
@@ -385,6 +398,35 @@ class Ctx {
         return out;
     }
     // out[r] = sum_i k_i P[r n + i]; k canonical (zk_g1_lincomb_batch: the leader's public maps on points)
+    // ---- G2 and the pairing ----
+    SrsPtr srs_register_g2(const void *bases, size_t stride, size_t n) {
+        zk_srs *s = nullptr;
+        check(zk_srs_register_g2(h_, bases, stride, n, &s));
+        return std::make_shared<Srs>(ref_, s);
+    }
+    G2 msm_g2(const Srs &srs, const DevPtr &scalars, size_t n, size_t offset = 0) {
+        G2 out;
+        check(zk_msm_g2(h_, srs.handle(), offset, scalars.get(), n, out.data()));
+        return out;
+    }
+    // g1_96: powers_of_g[0][0] as a 96-byte affine record (nullptr: the generator); powers_g2: n_g2 affine records at `stride`
+    std::shared_ptr<PcsVk> pcs_vk(const void *g1_96, const void *powers_g2, size_t stride, size_t n_g2) {
+        zk_pcs_vk *vk = nullptr;
+        check(zk_pcs_vk_create(h_, g1_96, powers_g2, stride, n_g2, &vk));
+        return std::make_shared<PcsVk>(ref_, vk, n_g2);
+    }
+    // count openings of nvars-variate polynomials: proofs count x nvars, points count x nvars -> one verdict per opening
+    std::vector<bool> pcs_verify_batch(const PcsVk &vk, size_t nvars, const G1Vec &commitments, const FrVec &values, const G1Vec &proofs,
+                                       const FrVec &points) {
+        size_t count = commitments.size();
+        need(values.size() == count && proofs.size() == count * nvars && points.size() == count * nvars, "pcs_verify_batch: list lengths differ");
+        std::vector<uint8_t> ok(count ? count : 1, 0);
+        if (count)
+            check(zk_pcs_verify_batch(h_, vk.h, nvars, count, commitments[0].data(), values[0].v, nvars ? proofs[0].data() : nullptr,
+                                      nvars ? points[0].v : nullptr, ok.data()));
+        return std::vector<bool>(ok.begin(), ok.begin() + count);
+    }
+
     G1Vec g1_lincomb_batch(const G1Vec &points, const FrVec &scalars_canonical, size_t count) {
         size_t n = scalars_canonical.size();
         need(points.size() == n * count, "g1_lincomb_batch: points != count x scalars");

@@ -420,6 +420,24 @@ inline Opening d_open(Ctx &be, const PowersOfG &pg, const DevPtr &peval, size_t 
     return top;
 }
 
+// PolynomialCommitment::verify (dpoly_comm.rs:466-484) on the device: e(C - v g1, g2) == prod_i e(pi_i, s_i g2 - u_i g2) for a batch of
+// openings of one vk (zk_pcs_verify_batch).  Points must lie in their subgroups (arkworks' types guarantee it).
+inline std::vector<bool> verify_batch(Ctx &be, const PcsVk &vk, const G1Vec &commitments, const FrVec &values, const std::vector<G1Vec> &proofs,
+                                      const std::vector<FrVec> &points) {
+    size_t nvars = proofs.empty() ? 0 : proofs[0].size();
+    G1Vec pf;
+    FrVec pt;
+    for (size_t k = 0; k < proofs.size(); ++k) {
+        if (proofs[k].size() != nvars || points[k].size() != nvars) throw ZkError(ZK_ERR_INVALID, "verify_batch: openings of different sizes");
+        pf.insert(pf.end(), proofs[k].begin(), proofs[k].end());
+        pt.insert(pt.end(), points[k].begin(), points[k].end());
+    }
+    return be.pcs_verify_batch(vk, nvars, commitments, values, pf, pt);
+}
+inline bool verify(Ctx &be, const PcsVk &vk, const G1 &commitment, const Fr &value, const G1Vec &proof, const FrVec &point) {
+    return verify_batch(be, vk, G1Vec{commitment}, FrVec{value}, {proof}, {point})[0];
+}
+
 // dpoly_comm.rs:401-464: n fold rounds producing every q_i, ONE batched d_msm over them (:436), pss2ss of the last value,
 // then log2(l) more rounds on the l-vector re-using point[0..] (:452) -> (value, n + log2 l proofs)
 inline Opening c_open(Ctx &be, const PowersOfG &pg, const DevPtr &peval, size_t len, const FrVec &point, const PackedSharingParams &pp, Net &net) {

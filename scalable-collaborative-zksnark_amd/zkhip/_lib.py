@@ -87,6 +87,11 @@ SYMBOLS = [
     ("zk_d_msm", _i, [_vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("zk_arena_plan_export", _i, [_vp, _vp]),
     ("zk_arena_plan_import", _i, [_vp, _vp]),
+    ("zk_pairing", _i, [_vp, _sz, _vp, _vp, _sz, _vp]),
+    ("zk_pairing_product_check", _i, [_vp, _sz, _vp, _vp, _vp, _sz, _vp]),
+    ("zk_pcs_vk_create", _i, [_vp, _vp, _vp, _sz, _sz, _pp]),
+    ("zk_pcs_vk_free", _i, [_vp, _vp]),
+    ("zk_pcs_verify_batch", _i, [_vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp]),
 ]
 
 # include/zkhip_test.h: the zk_dbg_* test hooks -- not part of the ABI, resolved only when a test / tool asks (test_hooks())

@@ -164,6 +164,30 @@ class Srs:
             pass
 
 
+class PcsVk:
+    """zk_pcs_vk: g1 and powers_of_g2 of a PolynomialCommitment, held by the library for zk_pcs_verify_batch"""
+
+    def __init__(self, ctx: "Ctx", powers_g2, g1_96=None, g2_stride: int = 192):
+        self.ctx, self.h = ctx, 0
+        pg2 = np.ascontiguousarray(powers_g2)
+        n = pg2.nbytes // g2_stride
+        g1 = None if g1_96 is None else np.ascontiguousarray(g1_96, dtype=np.uint64).reshape(12)
+        h = ctypes.c_void_p()
+        ctx._check(ctx.lib.zk_pcs_vk_create(ctx.h, _h(g1) if g1 is not None else None, _h(pg2), g2_stride, n, ctypes.byref(h)))
+        self.h, self.n_g2 = h.value, n
+
+    def free(self):
+        if self.h and getattr(self.ctx, "h", None):
+            self.ctx.lib.zk_pcs_vk_free(self.ctx.h, self.h)
+        self.h = 0
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 def comm_init_all(ctxs) -> None:
     """zk_comm_init_all: one process holding a ctx per GPU (the reference's one-task-per-party model,
     mpc-net/src/multi.rs:330-352); ctxs[p] becomes party p.  Drive every party from its own thread afterwards."""
@@ -605,6 +629,46 @@ class Ctx:
         if count:
             self._check(self.lib.zk_g1_lincomb_batch(self.h, _h(pts), _h(sc), n, count, _h(out)))
         return out
+
+    # ---- the pairing and PolynomialCommitment::verify (dpoly_comm.rs:466-484) ----
+    def pairing(self, g1_96: np.ndarray, g2, g2_stride: int = 192) -> np.ndarray:
+        """e(P_i, Q_i): g1 [count, 12] affine, g2 [count, 24] affine (or raw records at g2_stride bytes) -> [count, 72] u64, ark's
+        Fq12 layout (zkhip.pairing.fq12_from_ark); the value is zkhip.pairing.pairing(Q, P) ** ZK_PAIRING_EXP_MULTIPLE"""
+        g1 = np.ascontiguousarray(g1_96, dtype=np.uint64).reshape(-1, 12)
+        g2 = np.ascontiguousarray(g2)
+        count = len(g1)
+        assert g2.nbytes >= count * g2_stride or count == 0
+        out = np.zeros((count, 72), dtype=np.uint64)
+        self._check(self.lib.zk_pairing(self.h, count, _h(g1), _h(g2), g2_stride, _h(out)))
+        return out
+
+    def pairing_product_check(self, starts, g1_96: np.ndarray, g2, g2_stride: int = 192) -> np.ndarray:
+        """ok[g] = prod_{starts[g] <= i < starts[g+1]} e(P_i, Q_i) == 1; starts: groups + 1 offsets -> [groups] bool"""
+        st = np.ascontiguousarray(starts, dtype=np.uint64)
+        groups = max(len(st) - 1, 0)
+        g1 = np.ascontiguousarray(g1_96, dtype=np.uint64).reshape(-1, 12)
+        g2 = np.ascontiguousarray(g2)
+        ok = np.zeros(max(groups, 1), dtype=np.uint8)
+        self._check(self.lib.zk_pairing_product_check(self.h, groups, _h(st), _h(g1), _h(g2), g2_stride, _h(ok)))
+        return ok[:groups].astype(bool)
+
+    def pcs_vk(self, powers_g2, g1_96=None, g2_stride: int = 192) -> "PcsVk":
+        """the verifying key of PolynomialCommitment: g1 = powers_of_g[0][0] ([12] affine; None: the generator), powers_of_g2 [n, 24]"""
+        return PcsVk(self, powers_g2, g1_96, g2_stride)
+
+    def pcs_verify_batch(self, vk: "PcsVk", commitments, values, proofs, points) -> np.ndarray:
+        """PolynomialCommitment::verify for count openings: commitments [count, 18] Jacobian, values [count, 4] Montgomery Fr,
+        proofs [count, nvars, 18], points [count, nvars, 4] -> [count] bool"""
+        cm = np.ascontiguousarray(commitments, dtype=np.uint64).reshape(-1, 18)
+        count = len(cm)
+        vals = np.ascontiguousarray(values, dtype=np.uint64).reshape(count, 4)
+        pf = np.ascontiguousarray(proofs, dtype=np.uint64)
+        nvars = pf.shape[1] if pf.ndim == 3 else (pf.size // (18 * count) if count else 0)
+        pf = pf.reshape(count, nvars, 18)
+        pts = np.ascontiguousarray(points, dtype=np.uint64).reshape(count, nvars, 4)
+        ok = np.zeros(max(count, 1), dtype=np.uint8)
+        self._check(self.lib.zk_pcs_verify_batch(self.h, vk.h, nvars, count, _h(cm), _h(vals), _h(pf), _h(pts), _h(ok)))
+        return ok[:count].astype(bool)
 
     # ---- party exchanges through the C ABI (RCCL communicator inside the ctx) ----
     def comm_unique_id(self) -> bytes:

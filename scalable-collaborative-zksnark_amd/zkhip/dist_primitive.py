@@ -956,6 +956,37 @@ def verify(powers_of_g2, commitment: np.ndarray, value: np.ndarray, proof: np.nd
     return pr.verify(g1 or pr.G1_GEN, powers_of_g2, jacobian_to_affine_ints(commitment), fr_from_mont(value), pts, _fr_vec_to_ints(point))
 
 
+def pcs_vk(be, powers_of_g2, g1=None):
+    """the verifying key of a PolynomialCommitment on the device (zk_pcs_vk): powers_of_g2 as python-int affine points
+    (zkhip.pairing.powers_of_g2) or [n, 24] Montgomery records; g1 = powers_of_g[0][0] (python ints or [12]; None: the generator)"""
+    from .field import affine_ints_to_mont, fq_mont
+
+    pg2 = powers_of_g2
+    if not isinstance(pg2, np.ndarray):
+        pg2 = np.stack([np.zeros(24, dtype=np.uint64) if P is None else
+                        np.concatenate([fq_mont(P[0][0]), fq_mont(P[0][1]), fq_mont(P[1][0]), fq_mont(P[1][1])]) for P in pg2])
+    if g1 is not None and not isinstance(g1, np.ndarray):
+        g1 = affine_ints_to_mont(g1)
+    return be.pcs_vk(pg2, g1)
+
+
+def verify_batch(be, vk, commitments, values, proofs, points) -> np.ndarray:
+    """
+    PolynomialCommitment::verify (dpoly_comm.rs:466-484) for a batch of openings on the device (zk_pcs_verify_batch): commitments
+    [count, 18] Jacobian, values [count, 4] Montgomery Fr, proofs [count, nvars, 18], points [count, nvars, 4]; vk from pcs_vk.
+    Returns one verdict per opening -- the same as `verify` on every input whose points lie in their subgroups.
+    """
+    return be.pcs_verify_batch(vk, commitments, values, proofs, points)
+
+
+def verify_device(be, powers_of_g2, commitment: np.ndarray, value: np.ndarray, proof: np.ndarray, point: np.ndarray, g1=None) -> bool:
+    """`verify` with the reference's arguments, on the device: one opening through verify_batch"""
+    vk = powers_of_g2 if hasattr(powers_of_g2, "n_g2") else pcs_vk(be, powers_of_g2, g1)
+    pf = np.asarray(proof, dtype=np.uint64).reshape(1, -1, 18)
+    return bool(verify_batch(be, vk, np.asarray(commitment, dtype=np.uint64).reshape(1, 18), np.asarray(value, dtype=np.uint64).reshape(1, 4),
+                             pf, np.asarray(point, dtype=np.uint64).reshape(1, pf.shape[1], 4))[0])
+
+
 def fix_variable(be, evaluations, length: int, points: np.ndarray):
     """mle.rs:88-105 -> device buffer of length >> min(n, len(points))"""
     return be.fold(evaluations, length, points)

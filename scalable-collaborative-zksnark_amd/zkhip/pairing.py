@@ -313,3 +313,39 @@ def verify(g1, powers_g2: Sequence, commitment, value: int, proof: Sequence, poi
     for i, pi in enumerate(proof):
         pairs.append((pi, g2_add(powers_g2[i + 1], g2_neg(g2_mul(g2, point[i])))))
     return pairing_product_is_one(pairs)
+
+
+# ---- the device pairing's output layout (include/zkhip.h zk_pairing): ark's Fq12 <-> this module's Fq12 ----
+# ark: Fq12 = Fq6[w]/(w^2 - v), Fq6 = Fq2[v]/(v^3 - (1 + u)); the 72 u64 are c0.c0.c0, c0.c0.c1, c0.c1.c0, ..., c1.c2.c1, each Fq
+# 6 u64 in Montgomery form (radix 2^384).  Here v = w^2 and u = w^6 - 1, so the Fq2 coefficient (a0 + a1 u) of w^i v^j is the
+# pair of coefficients c[e] = a0 - a1, c[e + 6] = a1 with e = i + 2 j: a relabelling, no arithmetic beyond that.
+_FQ_R384 = (1 << 384) % Q
+_FQ_R384_INV = pow(1 << 384, -1, Q)
+_ARK_SLOTS = [(i, j) for i in range(2) for j in range(3)]  # (i, j) of the six Fq2 coefficients in ark's order
+
+
+def fq12_from_ark(words) -> Fq12:
+    """72 u64 (ark layout, Montgomery Fq) -> Fq12"""
+    w = [int(x) for x in words]
+    assert len(w) == 72
+    fq = [sum(w[6 * k + m] << (64 * m) for m in range(6)) * _FQ_R384_INV % Q for k in range(12)]
+    c = [0] * 12
+    for s, (i, j) in enumerate(_ARK_SLOTS):
+        a0, a1 = fq[2 * s], fq[2 * s + 1]
+        e = i + 2 * j
+        c[e] += a0 - a1
+        c[e + 6] += a1
+    return Fq12(c)
+
+
+def fq12_to_ark(f: Fq12) -> List[int]:
+    """Fq12 -> 72 u64 (ark layout, Montgomery Fq)"""
+    out: List[int] = []
+    for i, j in _ARK_SLOTS:
+        e = i + 2 * j
+        a1 = f.c[e + 6]
+        a0 = (f.c[e] + a1) % Q
+        for x in (a0, a1):
+            m = x * _FQ_R384 % Q
+            out.extend((m >> (64 * k)) & ((1 << 64) - 1) for k in range(6))
+    return out
