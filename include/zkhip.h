@@ -132,6 +132,23 @@ int zk_sumcheck_product(zk_ctx *ctx, const void *d_f, const void *d_g, size_t le
 /* fix_variable (mle.rs:88-105): fold min(n, n_points) times; d_out receives len >> rounds Fr. */
 int zk_fold(zk_ctx *ctx, const void *d_tab, size_t len, const uint64_t *h_points, size_t n_points,
             void *d_out);
+/* eq table of a point tau of n variables: d_out[x] = prod_i (x_i ? tau_i : 1 - tau_i), x_0 the TOP index bit (the variable
+ * round 0 of the sumchecks binds), len = 2^n Fr; h_point: n Fr.  Built by doubling.  sum_x out[x] = 1, and zk_fold(out, r)
+ * leaves eq(tau, r) = prod_i (tau_i r_i + (1 - tau_i)(1 - r_i)).  The real form of the `eq` vector the reference samples
+ * at random (hyperplonk/src/hyperplonk.rs:69-71, dhyperplonk.rs:218-222).  n = 0 gives [1].  ASYNCHRONOUS on the ctx stream like the
+ * element-wise calls: h_point is copied before the call returns, d_out is complete for later calls on this ctx or after zk_ctx_sync. */
+int zk_eq_table(zk_ctx *ctx, const uint64_t *h_point, size_t n, void *d_out);
+/* The gate identity as ONE sumcheck -- the virtual circuit the reference simulates with six independent product sumchecks
+ * (hyperplonk.rs:66-93, dhyperplonk.rs:218-260): the prover's rounds for
+ *     G(x) = eq(x) [ q1(x) (a(x) + b(x)) + q2(x) a(x) b(x) - c(x) + in(x) ]
+ * over seven tables of len = 2^n Fr (not modified).  Round i writes five Fr to h_out_evals: the round polynomial (degree 4)
+ * at t = 0, 1, 2, 3, 4, every table extended as (1 - t) lo + t hi (dsumcheck.rs:52-66), then folds the seven tables with
+ * h_chal[i].  h_out_evals: 5n Fr; h_last: the seven remaining elements (eq, q1, q2, a, b, c, in), 7 Fr.
+ * Blocking: the results are on the host when it returns.  len < 2, not a power of two or > 2^35, or a null pointer: ZK_ERR_INVALID;
+ * nothing is written on error. */
+int zk_sumcheck_gate(zk_ctx *ctx, const void *d_eq, const void *d_q1, const void *d_q2, const void *d_a,
+                     const void *d_b, const void *d_c, const void *d_in, size_t len, const uint64_t *h_chal,
+                     uint64_t *h_out_evals, uint64_t *h_last);
 /* Phase 1 of open / d_local_open / c_open (dpoly_comm.rs:309-323 = :337-351 = :418-432):
  * for every round q_i = hi - lo then fold with point[i].  d_q_out receives len-1 Fr: q_0 (len/2)
  * followed by q_1 (len/4) ... q_{n-1} (1) -- exactly the scalar vectors of the n commitments.

@@ -20,6 +20,7 @@ static const TuneKey kTuneKeys[] = {
     {"sc_kf", &Tuning::sc_kf}, {"sc_plain_flat", &Tuning::sc_plain_flat}, {"sc_kp", &Tuning::sc_kp}, {"sc_k0", &Tuning::sc_k0},
     {"sc_flat_wg", &Tuning::sc_flat_wg}, {"sc_plain_wg", &Tuning::sc_plain_wg}, {"sc_pre", &Tuning::sc_pre},
     {"sc_pinned_out", &Tuning::sc_pinned_out}, {"sc_t1_device", &Tuning::sc_t1_device}, {"sc_handover", &Tuning::sc_handover},
+    {"gate_local_e", &Tuning::gate_local_e}, {"gate_pass_wg", &Tuning::gate_pass_wg},
     {"msm_table_dc", &Tuning::msm_table_dc}, {"msm_qstep", &Tuning::msm_qstep}, {"msm_tile", &Tuning::msm_tile}, {"msm_pair", &Tuning::msm_pair},
     {"msm_fixq", &Tuning::msm_fixq}, {"msm_quad", &Tuning::msm_quad}, {"msm_stage", &Tuning::msm_stage}, {"msm_split", &Tuning::msm_split},
     {"msm_np", &Tuning::msm_np}, {"msm_fused_min", &Tuning::msm_fused_min}, {"msm_l2_tiled", &Tuning::msm_l2_tiled}, {"msm_tab_spt", &Tuning::msm_tab_spt}, {"msm_idx_ahead", &Tuning::msm_idx_ahead}, {"msm_share_l1", &Tuning::msm_share_l1}, {"srs_table_batched", &Tuning::srs_table_batched}, {"msm_debug", &Tuning::msm_debug}, {"msm_serial", &Tuning::msm_serial}, {"msm_size_classes", &Tuning::msm_size_classes},
@@ -401,6 +402,16 @@ int zk_fold(zk_ctx* ctx, const void* d_tab, size_t len, const uint64_t* h_points
     size_t n = (size_t)log2_exact(len);
     size_t rounds = n_points < n ? n_points : n;  // min(n, points_cnt), mle.rs:94
     return multilinear_run(ctx, 2, d_tab, nullptr, len, h_points, rounds, nullptr, nullptr, nullptr, d_out, nullptr);
+}
+int zk_eq_table(zk_ctx* ctx, const uint64_t* h_point, size_t n, void* d_out) {
+    NEED(ctx, d_out && (n == 0 || h_point));
+    return eq_table(ctx, h_point, n, d_out);
+}
+int zk_sumcheck_gate(zk_ctx* ctx, const void* d_eq, const void* d_q1, const void* d_q2, const void* d_a, const void* d_b, const void* d_c,
+                     const void* d_in, size_t len, const uint64_t* h_chal, uint64_t* h_out_evals, uint64_t* h_last) {
+    NEED(ctx, d_eq && d_q1 && d_q2 && d_a && d_b && d_c && d_in && h_chal && h_out_evals && h_last);
+    const void* tabs[7] = {d_eq, d_q1, d_q2, d_a, d_b, d_c, d_in};
+    return sumcheck_gate(ctx, tabs, len, h_chal, h_out_evals, h_last);
 }
 int zk_open_rounds(zk_ctx* ctx, const void* d_tab, size_t len, const uint64_t* h_point, void* d_q_out, uint64_t h_value[4]) {
     NEED(ctx, d_tab && h_value && (len <= 1 || (h_point && d_q_out)));

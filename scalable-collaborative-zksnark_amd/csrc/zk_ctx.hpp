@@ -70,6 +70,7 @@ struct zk_ctx {
     size_t pool_bytes = 0;
     std::mutex pool_mu;  // a garbage collector may release buffers from another thread
     int cu_count = 256;
+    bool gate_lds_raised = false;  // zk_gate.hip: k_gate_local's dynamic LDS limit has been raised on this ctx's device
     // party exchanges (zk_comm.cpp): an RCCL communicator bound to this ctx's GPU
     void* comm = nullptr;
     int comm_rank = 0, comm_world = 1;
@@ -99,6 +100,9 @@ struct Tuning {
     long sc_pinned_out = 1;   // results written straight into pinned host memory
     long sc_handover = 1;     // the pass before a multi-workgroup local stage stores that stage's slices contiguously
     long sc_t1_device = 0;    // TEST SWITCH: t1 = sum f_hi g_hi of EVERY round computed on the device (never derived)
+    // gate sumcheck (zk_gate.hip)
+    long gate_local_e = 512;  // longest table (elements, a power of two <= 512) the single-workgroup LDS stage takes over; 1: HBM passes down to the last element
+    long gate_pass_wg = 0;    // workgroups per CU of the HBM passes (0: 2)
     // MSM (zk_msm.hip)
     long msm_table_dc = 0;    // window-table width delta (sweeps)
     long msm_qstep = 2;       // window-class quantisation step of batches
@@ -159,6 +163,11 @@ int multilinear_run(zk_ctx* ctx, int mode, const void* d_f, const void* d_g, siz
 int multilinear_batch(zk_ctx* ctx, const zk_sc_item* items, size_t count);
 int product_tree(zk_ctx* ctx, const void* d_x, size_t N, void* d_tree);
 int dbg_fq(zk_ctx* ctx, int op, const void* a, const void* b, void* out, size_t n);
+
+// ---- zk_gate.hip ----
+int eq_table(zk_ctx* ctx, const uint64_t* h_point, size_t n, void* d_out);
+// d_tabs: eq, q1, q2, a, b, c, in
+int sumcheck_gate(zk_ctx* ctx, const void* const* d_tabs, size_t len, const uint64_t* h_chal, uint64_t* h_out_evals, uint64_t* h_last);
 
 // ---- zk_msm.hip ----
 struct MsmItem {

@@ -12,16 +12,9 @@
 
 #include "zkhost/dist_primitive.hpp"
 #include "zkhost/hyperplonk.hpp"
-#include "zkhost/serialize.hpp"
+#include "zkhost/pcs_vk.hpp"
 
 using namespace zkhost;
-
-// the BLS12-381 G2 generator, canonical little-endian limbs (x.c0, x.c1, y.c0, y.c1)
-static const uint64_t kG2Gen[4][6] = {
-    {0xd48056c8c121bdb8ull, 0x0bac0326a805bbefull, 0xb4510b647ae3d177ull, 0xc6e47ad4fa403b02ull, 0x260805272dc51051ull, 0x024aa2b2f08f0a91ull},
-    {0xe5ac7d055d042b7eull, 0x334cf11213945d57ull, 0xb5da61bbdc7f5049ull, 0x596bd0d09920b61aull, 0x7dacd3a088274f65ull, 0x13e02b6052719f60ull},
-    {0xe193548608b82801ull, 0x923ac9cc3baca289ull, 0x6d429a695160d12cull, 0xadfd9baa8cbdd3a7ull, 0x8cc9cdc6da2e351aull, 0x0ce5d527727d6e11ull},
-    {0xaaa9075ff05f79beull, 0x3f370d275cec1da1ull, 0x267492ab572e99abull, 0xcb3e287e85a763afull, 0x32acd2b02bc28b99ull, 0x0606c4a02ea734ccull}};
 
 int main(int argc, char **argv) {
     size_t n = 6;
@@ -47,21 +40,7 @@ int main(int argc, char **argv) {
         const G1 C = commit(be, pg, be.to_device(poly), len), C2 = commit(be, pg, be.to_device(poly2), len);
         const Opening op = open(be, pg, be.to_device(poly), len, u);
 
-        // powers_of_g2 = [g2, s_0 g2, ..., s_{n-1} g2] (:59-62)
-        std::vector<uint64_t> g2rec(24);
-        for (int c = 0; c < 4; ++c) {
-            Fq x = Fq::zero();
-            std::memcpy(x.v, kG2Gen[c], 48);
-            x = Fq::from_canonical(x);
-            std::memcpy(&g2rec[6 * c], x.v, 48);
-        }
-        SrsPtr g2srs = be.srs_register_g2(g2rec.data(), 192, 1);
-        std::vector<uint64_t> pg2(g2rec);
-        for (size_t i = 0; i < n; ++i) {
-            G2 p = be.msm_g2(*g2srs, be.to_device(FrVec{s[i]}), 1);  // normalised: (x, y, 1)
-            pg2.insert(pg2.end(), p.begin(), p.begin() + 24);
-        }
-        std::shared_ptr<PcsVk> vk = be.pcs_vk(nullptr, pg2.data(), 192, n + 1);
+        std::shared_ptr<PcsVk> vk = make_pcs_vk(be, s);  // powers_of_g2 = [g2, s_0 g2, ..., s_{n-1} g2] (dpoly_comm.rs:59-62)
 
         // the generator g1 = powers_of_g[0][0] as a normalised Jacobian point, infinity as (1, 1, 0)
         uint64_t g1a[12];

@@ -221,6 +221,23 @@ class Ctx {
         check(zk_fold(h_, tab.get(), len, points.empty() ? nullptr : points[0].v, points.size(), out.get()));
         return out;
     }
+    // zk_eq_table: eq(point, x) over the cube, x_0 the top index bit
+    DevPtr eq_table(const FrVec &point) {
+        DevPtr out = alloc_fr(size_t(1) << point.size());
+        check(zk_eq_table(h_, point.empty() ? nullptr : point[0].v, point.size(), out.get()));
+        return out;
+    }
+    // zk_sumcheck_gate: tabs = eq, q1, q2, a, b, c, in -> r.sums = 5 Fr per round (t = 0 .. 4), `last` = the seven remaining elements
+    ScResult sumcheck_gate(const std::array<DevPtr, 7> &tabs, size_t len, const FrVec &chal, FrVec &last) {
+        size_t n = log2_exact(len);
+        need(n >= 1 && chal.size() >= n, "sumcheck_gate: fewer challenges than rounds");
+        ScResult r;
+        r.sums.resize(5 * n);
+        last.assign(7, Fr::zero());
+        check(zk_sumcheck_gate(h_, tabs[0].get(), tabs[1].get(), tabs[2].get(), tabs[3].get(), tabs[4].get(), tabs[5].get(), tabs[6].get(), len, chal[0].v,
+                               r.sums[0].v, last[0].v));
+        return r;
+    }
     ScResult open_rounds(const DevPtr &tab, size_t len, const FrVec &point) {
         need(point.size() >= log2_exact(len), "open: fewer point coordinates than rounds");
         ScResult r;

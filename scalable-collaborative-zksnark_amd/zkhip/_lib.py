@@ -42,6 +42,8 @@ SYMBOLS = [
     ("zk_sumcheck", _i, [_vp, _vp, _sz, _vp, _vp, _vp]),
     ("zk_sumcheck_product", _i, [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
     ("zk_fold", _i, [_vp, _vp, _sz, _vp, _sz, _vp]),
+    ("zk_eq_table", _i, [_vp, _vp, _sz, _vp]),
+    ("zk_sumcheck_gate", _i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
     ("zk_open_rounds", _i, [_vp, _vp, _sz, _vp, _vp, _vp]),
     ("zk_sumcheck_batch", _i, [_vp, _sz, _vp]),
     ("zk_product_tree", _i, [_vp, _vp, _sz, _vp]),

@@ -467,6 +467,24 @@ class Ctx:
         self._check(self.lib.zk_fold(self.h, _ptr(tab), length, _h(points), len(points), _ptr(out)))
         return out
 
+    def eq_table(self, point: np.ndarray, out=None):
+        """eq(point, x) over the cube, x_0 the top index bit -> device buffer of 2^n Fr (zk_eq_table)"""
+        point = np.ascontiguousarray(point, dtype=np.uint64).reshape(-1, 4)
+        out = out or self.alloc(32 << len(point))
+        self._check(self.lib.zk_eq_table(self.h, _h(point), len(point), _ptr(out)))
+        return out
+
+    def sumcheck_gate(self, eq, q1, q2, a, b, c, inp, length: int, chal: np.ndarray):
+        """the gate identity eq [q1 (a + b) + q2 a b - c + in] as one degree-4 sumcheck -> (evals [n,5,4], last [7,4])"""
+        n = max(length.bit_length() - 1, 0)
+        chal = np.ascontiguousarray(chal, dtype=np.uint64).reshape(-1, 4)
+        if len(chal) < n:
+            raise ValueError(f"{n} challenges needed, {len(chal)} given")
+        out = np.zeros((n, 5, 4), dtype=np.uint64)
+        last = np.zeros((7, 4), dtype=np.uint64)
+        self._check(self.lib.zk_sumcheck_gate(self.h, _ptr(eq), _ptr(q1), _ptr(q2), _ptr(a), _ptr(b), _ptr(c), _ptr(inp), length, _h(chal), _h(out), _h(last)))
+        return out, last
+
     def open_rounds(self, tab, length: int, point: np.ndarray, q_out=None):
         """-> (q device buffer with length-1 Fr, value [4])"""
         point = np.ascontiguousarray(point, dtype=np.uint64).reshape(-1, 4)
