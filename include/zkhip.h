@@ -149,6 +149,20 @@ int zk_eq_table(zk_ctx *ctx, const uint64_t *h_point, size_t n, void *d_out);
 int zk_sumcheck_gate(zk_ctx *ctx, const void *d_eq, const void *d_q1, const void *d_q2, const void *d_a,
                      const void *d_b, const void *d_c, const void *d_in, size_t len, const uint64_t *h_chal,
                      uint64_t *h_out_evals, uint64_t *h_last);
+/* The wiring identity (HyperPlonk's ProductCheck) as ONE sumcheck -- the reference simulates it with six independent product
+ * sumchecks on six unrelated polynomials (hyperplonk.rs:94-141): the prover's rounds for
+ *     F(x) = eq(x) [ v(1,x) - v(x,0) v(x,1) + gamma ( den(x) h(x) - num(x) ) ]
+ * where v = d_tree is the 2N Fr of zk_product_tree(h), h = num / den, and with index bit 0 the TOP bit
+ *     v(0,x) = h = tree[x],  v(1,x) = tree[N + x],  v(x,0) = tree[2x],  v(x,1) = tree[2x + 1].
+ * d_eq, d_num, d_den: N = 2^mu Fr each; d_tree: 2N Fr; none is modified, and the four views are read in place (no
+ * deinterleaved copies by the caller or the library).  Round i writes four Fr to h_out_evals: the round polynomial (degree 3) at
+ * t = 0, 1, 2, 3, every table extended as (1 - t) lo + t hi, then folds the seven tables with h_chal[i].
+ * h_out_evals: 4 mu Fr; h_last: the seven remaining elements in the order eq, v1x, vx0, vx1, h, num, den, 7 Fr.
+ * Blocking: the results are on the host when it returns.  N < 2, not a power of two or > 2^35, or a null pointer: ZK_ERR_INVALID;
+ * nothing is written on error. */
+int zk_sumcheck_wiring(zk_ctx *ctx, const void *d_eq, const void *d_tree, const void *d_num, const void *d_den,
+                       size_t N, const uint64_t h_gamma[4], const uint64_t *h_chal, uint64_t *h_out_evals,
+                       uint64_t *h_last);
 /* Phase 1 of open / d_local_open / c_open (dpoly_comm.rs:309-323 = :337-351 = :418-432):
  * for every round q_i = hi - lo then fold with point[i].  d_q_out receives len-1 Fr: q_0 (len/2)
  * followed by q_1 (len/4) ... q_{n-1} (1) -- exactly the scalar vectors of the n commitments.

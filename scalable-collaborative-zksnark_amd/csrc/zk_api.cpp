@@ -21,6 +21,7 @@ static const TuneKey kTuneKeys[] = {
     {"sc_flat_wg", &Tuning::sc_flat_wg}, {"sc_plain_wg", &Tuning::sc_plain_wg}, {"sc_pre", &Tuning::sc_pre},
     {"sc_pinned_out", &Tuning::sc_pinned_out}, {"sc_t1_device", &Tuning::sc_t1_device}, {"sc_handover", &Tuning::sc_handover},
     {"gate_local_e", &Tuning::gate_local_e}, {"gate_pass_wg", &Tuning::gate_pass_wg},
+    {"wiring_local_e", &Tuning::wiring_local_e}, {"wiring_pass_wg", &Tuning::wiring_pass_wg},
     {"msm_table_dc", &Tuning::msm_table_dc}, {"msm_qstep", &Tuning::msm_qstep}, {"msm_tile", &Tuning::msm_tile}, {"msm_pair", &Tuning::msm_pair},
     {"msm_fixq", &Tuning::msm_fixq}, {"msm_quad", &Tuning::msm_quad}, {"msm_stage", &Tuning::msm_stage}, {"msm_split", &Tuning::msm_split},
     {"msm_np", &Tuning::msm_np}, {"msm_fused_min", &Tuning::msm_fused_min}, {"msm_l2_tiled", &Tuning::msm_l2_tiled}, {"msm_tab_spt", &Tuning::msm_tab_spt}, {"msm_idx_ahead", &Tuning::msm_idx_ahead}, {"msm_share_l1", &Tuning::msm_share_l1}, {"srs_table_batched", &Tuning::srs_table_batched}, {"msm_debug", &Tuning::msm_debug}, {"msm_serial", &Tuning::msm_serial}, {"msm_size_classes", &Tuning::msm_size_classes},
@@ -412,6 +413,11 @@ int zk_sumcheck_gate(zk_ctx* ctx, const void* d_eq, const void* d_q1, const void
     NEED(ctx, d_eq && d_q1 && d_q2 && d_a && d_b && d_c && d_in && h_chal && h_out_evals && h_last);
     const void* tabs[7] = {d_eq, d_q1, d_q2, d_a, d_b, d_c, d_in};
     return sumcheck_gate(ctx, tabs, len, h_chal, h_out_evals, h_last);
+}
+int zk_sumcheck_wiring(zk_ctx* ctx, const void* d_eq, const void* d_tree, const void* d_num, const void* d_den, size_t N, const uint64_t h_gamma[4],
+                       const uint64_t* h_chal, uint64_t* h_out_evals, uint64_t* h_last) {
+    NEED(ctx, d_eq && d_tree && d_num && d_den && h_gamma && h_chal && h_out_evals && h_last);
+    return sumcheck_wiring(ctx, d_eq, d_tree, d_num, d_den, N, h_gamma, h_chal, h_out_evals, h_last);
 }
 int zk_open_rounds(zk_ctx* ctx, const void* d_tab, size_t len, const uint64_t* h_point, void* d_q_out, uint64_t h_value[4]) {
     NEED(ctx, d_tab && h_value && (len <= 1 || (h_point && d_q_out)));

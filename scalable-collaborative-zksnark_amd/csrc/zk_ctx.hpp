@@ -71,6 +71,7 @@ struct zk_ctx {
     std::mutex pool_mu;  // a garbage collector may release buffers from another thread
     int cu_count = 256;
     bool gate_lds_raised = false;  // zk_gate.hip: k_gate_local's dynamic LDS limit has been raised on this ctx's device
+    bool wiring_lds_raised = false;  // zk_wiring.hip: the same for k_wiring_local
     // party exchanges (zk_comm.cpp): an RCCL communicator bound to this ctx's GPU
     void* comm = nullptr;
     int comm_rank = 0, comm_world = 1;
@@ -103,6 +104,9 @@ struct Tuning {
     // gate sumcheck (zk_gate.hip)
     long gate_local_e = 512;  // longest table (elements, a power of two <= 512) the single-workgroup LDS stage takes over; 1: HBM passes down to the last element
     long gate_pass_wg = 0;    // workgroups per CU of the HBM passes (0: 2)
+    // wiring sumcheck (zk_wiring.hip)
+    long wiring_local_e = 512;  // longest table (elements, a power of two <= 512) the single-workgroup LDS stage takes over; 1: HBM passes down to the last element
+    long wiring_pass_wg = 0;    // workgroups per CU of the HBM passes (0: 2)
     // MSM (zk_msm.hip)
     long msm_table_dc = 0;    // window-table width delta (sweeps)
     long msm_qstep = 2;       // window-class quantisation step of batches
@@ -168,6 +172,11 @@ int dbg_fq(zk_ctx* ctx, int op, const void* a, const void* b, void* out, size_t 
 int eq_table(zk_ctx* ctx, const uint64_t* h_point, size_t n, void* d_out);
 // d_tabs: eq, q1, q2, a, b, c, in
 int sumcheck_gate(zk_ctx* ctx, const void* const* d_tabs, size_t len, const uint64_t* h_chal, uint64_t* h_out_evals, uint64_t* h_last);
+
+// ---- zk_wiring.hip ----
+// d_tree: the 2N Fr of product_tree; h_last: eq, v1x, vx0, vx1, h, num, den
+int sumcheck_wiring(zk_ctx* ctx, const void* d_eq, const void* d_tree, const void* d_num, const void* d_den, size_t N, const uint64_t* h_gamma,
+                    const uint64_t* h_chal, uint64_t* h_out_evals, uint64_t* h_last);
 
 // ---- zk_msm.hip ----
 struct MsmItem {

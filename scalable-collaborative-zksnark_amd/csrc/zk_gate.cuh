@@ -1,0 +1,83 @@
+// zk_gate.cuh -- what the fused sumchecks (zk_gate.hip: gate identity, zk_wiring.hip: wiring identity) share: launch geometry, the
+// argument blocks of their kernels and the 544-bit lazily reduced sums (one 80-byte slot per wave, evaluation and pass).
+#pragma once
+#include "fp.cuh"
+#include "zk_ctx.hpp"
+
+namespace zk {
+
+static constexpr int kGateBlock = 256;
+static constexpr unsigned kGateLocalMax = 512;  // 7 x 512 x 32 B = 112 KiB of the CU's 160 KiB
+static constexpr int kGateWideBytes = 80;       // 17 limbs + 3 words of padding (the slot of zk_fr.hip's Wide)
+static constexpr int kGateMaxPasses = 40;
+static constexpr int kGateMaxLog = 35;         // longest table: 2^35 elements (capacity of the 544-bit sums, see k_gate_pass)
+
+struct GateChal {
+    Fr r;
+};
+struct GateTail {
+    uint64_t c[10 * 4];  // challenges of the local stage (at most log2(kGateLocalMax) = 9) / the seed levels of the eq table (10)
+};
+struct GateReducePlan {
+    unsigned nbw[kGateMaxPasses];   // 544-bit partials per sum of pass p (one per wave)
+    unsigned off[kGateMaxPasses];   // first slot of pass p in the partials block
+};
+
+__device__ __forceinline__ void gate_wide_add(u32 (&a)[17], const u32 (&b)[17]) {
+    u32 c = 0;
+#pragma unroll
+    for (int i = 0; i < 17; i++) a[i] = addc(a[i], b[i], c);
+}
+__device__ __forceinline__ void gate_wide_store(void* base, size_t slot, const u32 (&v)[17]) {
+    uint4* p = reinterpret_cast<uint4*>(reinterpret_cast<char*>(base) + slot * kGateWideBytes);
+#pragma unroll
+    for (int i = 0; i < 4; i++) p[i] = make_uint4(v[4 * i], v[4 * i + 1], v[4 * i + 2], v[4 * i + 3]);
+    p[4] = make_uint4(v[16], 0, 0, 0);
+}
+__device__ __forceinline__ void gate_wide_load(u32 (&v)[17], const void* base, size_t slot) {
+    const uint4* p = reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(base) + slot * kGateWideBytes);
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const uint4 x = p[i];
+        v[4 * i] = x.x, v[4 * i + 1] = x.y, v[4 * i + 2] = x.z, v[4 * i + 3] = x.w;
+    }
+    v[16] = p[4].x;
+}
+
+// One workgroup of kGateBlock lanes adds the nbw per-wave partials from slot `base` on and reduces W0 + W1 R + W2 R^2 (a sum of
+// integer products of Montgomery forms) to W0 R^-1 + W1 + W2 R mod r, canonical, into evals[out].  lds: (kGateBlock / 64) slots.
+__device__ __forceinline__ void gate_reduce_block(const void* __restrict__ partials, size_t base, unsigned nbw, uint4* lds, void* __restrict__ evals, size_t out) {
+    u32 v[17];
+#pragma unroll
+    for (int i = 0; i < 17; i++) v[i] = 0;
+    for (unsigned i = threadIdx.x; i < nbw; i += kGateBlock) {
+        u32 x[17];
+        gate_wide_load(x, partials, base + i);
+        gate_wide_add(v, x);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        u32 o[17];
+#pragma unroll
+        for (int i = 0; i < 17; i++) o[i] = __shfl_down(v[i], off, 64);
+        gate_wide_add(v, o);
+    }
+    if ((threadIdx.x & 63) == 0) gate_wide_store(lds, threadIdx.x >> 6, v);
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    for (int g = 1; g < kGateBlock / 64; g++) {
+        u32 x[17];
+        gate_wide_load(x, lds, g);
+        gate_wide_add(v, x);
+    }
+    Fr w0, w1, w2 = fp_zero<FrCfg>(), one = fp_zero<FrCfg>(), r2;
+#pragma unroll
+    for (int i = 0; i < 8; i++) w0.l[i] = v[i], w1.l[i] = v[8 + i], r2.l[i] = FrCfg::R2(i);
+    w2.l[0] = v[16];
+    one.l[0] = 1;
+    w0 = fp_reduce_once<FrCfg>(fp_reduce_once<FrCfg>(w0));  // 2^256 < 3 r
+    w1 = fp_reduce_once<FrCfg>(fp_reduce_once<FrCfg>(w1));
+    fr_store(evals, out, fr_add(fr_add(fr_mul(w0, one), w1), fr_mul(w2, r2)));
+}
+
+}  // namespace zk

@@ -11,21 +11,15 @@
 // of the seven tables, writes the seven folded elements to ping-pong scratch and adds its five products eq(t) * [..](t) as
 // 512-bit integers into five 544-bit sums -- one Montgomery reduction per sum and call, in k_gate_reduce), then every
 // remaining round in one workgroup on tables held in LDS (k_gate_local).
-#include "fp.cuh"
-#include "zk_ctx.hpp"
+#include "zk_gate.cuh"
 
 #include <algorithm>
 #include <cstring>
 
 namespace zk {
 
-static constexpr int kGateBlock = 256;
 static constexpr int kGateTabs = 7;     // eq, q1, q2, a, b, c, in
 static constexpr int kGateEvals = 5;    // t = 0 .. 4
-static constexpr unsigned kGateLocalMax = 512;  // 7 x 512 x 32 B = 112 KiB of the CU's 160 KiB
-static constexpr int kGateWideBytes = 80;       // 17 limbs + 3 words of padding (the slot of zk_fr.hip's Wide)
-static constexpr int kGateMaxPasses = 40;
-static constexpr int kGateMaxLog = 35;         // longest table: 2^35 elements (capacity of the 544-bit sums, see k_gate_pass)
 
 struct GateIn {
     const void* t[kGateTabs];
@@ -33,43 +27,12 @@ struct GateIn {
 struct GateOut {
     void* t[kGateTabs];
 };
-struct GateChal {
-    Fr r;
-};
-struct GateTail {
-    uint64_t c[10 * 4];  // challenges of the local stage (at most log2(kGateLocalMax) = 9) / the seed levels of the eq table (10)
-};
-struct GateReducePlan {
-    unsigned nbw[kGateMaxPasses];   // 544-bit partials per sum of pass p (one per wave)
-    unsigned off[kGateMaxPasses];   // first slot of pass p in the partials block
-};
 
 // [ q1 (a + b) + (q2 a) b - c + in ] of one point: three multiplications
 __device__ __forceinline__ Fr gate_inner(const Fr& q1, const Fr& q2, const Fr& a, const Fr& b, const Fr& c, const Fr& in) {
     const Fr s = fr_mul(q1, fr_add(a, b));
     const Fr p = fr_mul(fr_mul(q2, a), b);
     return fr_add(fr_sub(fr_add(s, p), c), in);
-}
-
-__device__ __forceinline__ void gate_wide_add(u32 (&a)[17], const u32 (&b)[17]) {
-    u32 c = 0;
-#pragma unroll
-    for (int i = 0; i < 17; i++) a[i] = addc(a[i], b[i], c);
-}
-__device__ __forceinline__ void gate_wide_store(void* base, size_t slot, const u32 (&v)[17]) {
-    uint4* p = reinterpret_cast<uint4*>(reinterpret_cast<char*>(base) + slot * kGateWideBytes);
-#pragma unroll
-    for (int i = 0; i < 4; i++) p[i] = make_uint4(v[4 * i], v[4 * i + 1], v[4 * i + 2], v[4 * i + 3]);
-    p[4] = make_uint4(v[16], 0, 0, 0);
-}
-__device__ __forceinline__ void gate_wide_load(u32 (&v)[17], const void* base, size_t slot) {
-    const uint4* p = reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(base) + slot * kGateWideBytes);
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        const uint4 x = p[i];
-        v[4 * i] = x.x, v[4 * i + 1] = x.y, v[4 * i + 2] = x.z, v[4 * i + 3] = x.w;
-    }
-    v[16] = p[4].x;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -119,42 +82,11 @@ k_gate_pass(GateIn in, GateOut out, size_t half, GateChal ch, void* __restrict__
 }
 
 // The sums of all passes of a call in one launch: block (t, p) adds the per-wave partials of evaluation t of pass p and
-// reduces W0 + W1 R + W2 R^2 (a sum of integer products of Montgomery forms) to W0 R^-1 + W1 + W2 R mod r, canonical.
+// reduces them (gate_reduce_block, zk_gate.cuh).
 __global__ void __launch_bounds__(kGateBlock) k_gate_reduce(const void* __restrict__ partials, GateReducePlan plan, void* __restrict__ evals) {
     __shared__ uint4 lds[(kGateBlock / 64) * (kGateWideBytes / 16)];
     const unsigned t = blockIdx.x, p = blockIdx.y, nbw = plan.nbw[p];
-    const size_t base = (size_t)plan.off[p] + (size_t)t * nbw;
-    u32 v[17];
-#pragma unroll
-    for (int i = 0; i < 17; i++) v[i] = 0;
-    for (unsigned i = threadIdx.x; i < nbw; i += kGateBlock) {
-        u32 x[17];
-        gate_wide_load(x, partials, base + i);
-        gate_wide_add(v, x);
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        u32 o[17];
-#pragma unroll
-        for (int i = 0; i < 17; i++) o[i] = __shfl_down(v[i], off, 64);
-        gate_wide_add(v, o);
-    }
-    if ((threadIdx.x & 63) == 0) gate_wide_store(lds, threadIdx.x >> 6, v);
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-    for (int g = 1; g < kGateBlock / 64; g++) {
-        u32 x[17];
-        gate_wide_load(x, lds, g);
-        gate_wide_add(v, x);
-    }
-    Fr w0, w1, w2 = fp_zero<FrCfg>(), one = fp_zero<FrCfg>(), r2;
-#pragma unroll
-    for (int i = 0; i < 8; i++) w0.l[i] = v[i], w1.l[i] = v[8 + i], r2.l[i] = FrCfg::R2(i);
-    w2.l[0] = v[16];
-    one.l[0] = 1;
-    w0 = fp_reduce_once<FrCfg>(fp_reduce_once<FrCfg>(w0));  // 2^256 < 3 r
-    w1 = fp_reduce_once<FrCfg>(fp_reduce_once<FrCfg>(w1));
-    fr_store(evals, (size_t)p * kGateEvals + t, fr_add(fr_add(fr_mul(w0, one), w1), fr_mul(w2, r2)));
+    gate_reduce_block(partials, (size_t)plan.off[p] + (size_t)t * nbw, nbw, lds, evals, (size_t)p * kGateEvals + t);
 }
 
 // ---------------------------------------------------------------------------------------

@@ -238,6 +238,17 @@ class Ctx {
                                r.sums[0].v, last[0].v));
         return r;
     }
+    // zk_sumcheck_wiring: tree = the 2N Fr of product_tree -> r.sums = 4 Fr per round (t = 0 .. 3), `last` = eq, v1x, vx0, vx1, h, num, den
+    ScResult sumcheck_wiring(const DevPtr &eq, const DevPtr &tree, const DevPtr &num, const DevPtr &den, size_t N, const Fr &gamma, const FrVec &chal,
+                             FrVec &last) {
+        size_t mu = log2_exact(N);
+        need(mu >= 1 && chal.size() >= mu, "sumcheck_wiring: fewer challenges than rounds");
+        ScResult r;
+        r.sums.resize(4 * mu);
+        last.assign(7, Fr::zero());
+        check(zk_sumcheck_wiring(h_, eq.get(), tree.get(), num.get(), den.get(), N, gamma.v, chal[0].v, r.sums[0].v, last[0].v));
+        return r;
+    }
     ScResult open_rounds(const DevPtr &tab, size_t len, const FrVec &point) {
         need(point.size() >= log2_exact(len), "open: fewer point coordinates than rounds");
         ScResult r;

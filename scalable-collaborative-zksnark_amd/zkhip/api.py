@@ -485,6 +485,19 @@ class Ctx:
         self._check(self.lib.zk_sumcheck_gate(self.h, _ptr(eq), _ptr(q1), _ptr(q2), _ptr(a), _ptr(b), _ptr(c), _ptr(inp), length, _h(chal), _h(out), _h(last)))
         return out, last
 
+    def sumcheck_wiring(self, eq, tree, num, den, N: int, gamma: np.ndarray, chal: np.ndarray):
+        """the wiring identity eq [v(1,x) - v(x,0) v(x,1) + gamma (den h - num)] on the product tree of h (2N Fr, read in place) as one
+        degree-3 sumcheck -> (evals [mu,4,4], last [7,4]: eq, v1x, vx0, vx1, h, num, den)"""
+        mu = max(N.bit_length() - 1, 0)
+        chal = np.ascontiguousarray(chal, dtype=np.uint64).reshape(-1, 4)
+        gamma = np.ascontiguousarray(gamma, dtype=np.uint64).reshape(4)
+        if len(chal) < mu:
+            raise ValueError(f"{mu} challenges needed, {len(chal)} given")
+        out = np.zeros((mu, 4, 4), dtype=np.uint64)
+        last = np.zeros((7, 4), dtype=np.uint64)
+        self._check(self.lib.zk_sumcheck_wiring(self.h, _ptr(eq), _ptr(tree), _ptr(num), _ptr(den), N, _h(gamma), _h(chal), _h(out), _h(last)))
+        return out, last
+
     def open_rounds(self, tab, length: int, point: np.ndarray, q_out=None):
         """-> (q device buffer with length-1 Fr, value [4])"""
         point = np.ascontiguousarray(point, dtype=np.uint64).reshape(-1, 4)
