@@ -163,6 +163,25 @@ int zk_sumcheck_gate(zk_ctx *ctx, const void *d_eq, const void *d_q1, const void
 int zk_sumcheck_wiring(zk_ctx *ctx, const void *d_eq, const void *d_tree, const void *d_num, const void *d_den,
                        size_t N, const uint64_t h_gamma[4], const uint64_t *h_chal, uint64_t *h_out_evals,
                        uint64_t *h_last);
+/* ---- batch opening: K claims f_{j_k}(z_k) = v_k on J tables of one size -> one degree-2 sumcheck and one opening ---- */
+/* d_acc[x] += weight * eq(point, x) over the cube of n variables (x_0 the TOP index bit), d_acc: 2^n Fr, read and written.  The
+ * doubling scheme of zk_eq_table seeded with the weight; the last level is added into d_acc instead of stored, so a claim costs
+ * one level of scratch (2^(n-1) Fr), not a table.  Coordinates 0 and 1 come out exact: the point (1,..,1,0) adds the weight to one
+ * entry and zero to the others.  n = 0 adds the weight to d_acc[0].  ASYNCHRONOUS on the ctx stream like zk_eq_table. */
+int zk_eq_table_acc(zk_ctx *ctx, const uint64_t *h_point, size_t n, const uint64_t h_weight[4], void *d_acc);
+/* d_out[x] = sum_j c_j * d_tabs[j][x], x < len, 1 <= count <= 16; h_coeffs: count Fr (Montgomery).  d_out may be one of the inputs.
+ * Wide multiply-accumulates and ONE Montgomery reduction per output: 32 (count + 1) len bytes of traffic.  ASYNCHRONOUS on the ctx
+ * stream (the pointer array and the coefficients are copied before the call returns).  count 0 or > 16, or a null pointer:
+ * ZK_ERR_INVALID. */
+int zk_fr_lincomb(zk_ctx *ctx, size_t count, const void *const *d_tabs, const uint64_t *h_coeffs, size_t len, void *d_out);
+/* The prover's rounds of  sum_x sum_j E_j(x) f_j(x)  over count <= 16 pairs of tables of len = 2^n Fr (not modified): round i writes
+ * (t0, t1, t2), the round polynomial at t = 0, 1, 2 -- the triple of zk_sumcheck_product (dsumcheck.rs:38-72) summed over j -- and
+ * folds all 2 count tables with h_chal[i].  h_out_triples: 3n Fr; h_last_e / h_last_f: count Fr each, E_j(chal) and f_j(chal).
+ * count = 1 is zk_sumcheck_product bit for bit.  Blocking: the results are on the host when it returns.
+ * Capacity: the sums of a round are 544-bit integers of count * len / 2 products < 2^512, so count * len <= 2^33.
+ * count 0 or > 16, len < 2 or not a power of two, count * len > 2^33, or a null pointer: ZK_ERR_INVALID; nothing is written on error. */
+int zk_sumcheck_multi(zk_ctx *ctx, size_t count, const void *const *d_e, const void *const *d_f, size_t len,
+                      const uint64_t *h_chal, uint64_t *h_out_triples, uint64_t *h_last_e, uint64_t *h_last_f);
 /* Phase 1 of open / d_local_open / c_open (dpoly_comm.rs:309-323 = :337-351 = :418-432):
  * for every round q_i = hi - lo then fold with point[i].  d_q_out receives len-1 Fr: q_0 (len/2)
  * followed by q_1 (len/4) ... q_{n-1} (1) -- exactly the scalar vectors of the n commitments.

@@ -22,6 +22,7 @@ static const TuneKey kTuneKeys[] = {
     {"sc_pinned_out", &Tuning::sc_pinned_out}, {"sc_t1_device", &Tuning::sc_t1_device}, {"sc_handover", &Tuning::sc_handover},
     {"gate_local_e", &Tuning::gate_local_e}, {"gate_pass_wg", &Tuning::gate_pass_wg},
     {"wiring_local_e", &Tuning::wiring_local_e}, {"wiring_pass_wg", &Tuning::wiring_pass_wg},
+    {"multi_local_e", &Tuning::multi_local_e}, {"multi_pass_wg", &Tuning::multi_pass_wg},
     {"msm_table_dc", &Tuning::msm_table_dc}, {"msm_qstep", &Tuning::msm_qstep}, {"msm_tile", &Tuning::msm_tile}, {"msm_pair", &Tuning::msm_pair},
     {"msm_fixq", &Tuning::msm_fixq}, {"msm_quad", &Tuning::msm_quad}, {"msm_stage", &Tuning::msm_stage}, {"msm_split", &Tuning::msm_split},
     {"msm_np", &Tuning::msm_np}, {"msm_fused_min", &Tuning::msm_fused_min}, {"msm_l2_tiled", &Tuning::msm_l2_tiled}, {"msm_tab_spt", &Tuning::msm_tab_spt}, {"msm_idx_ahead", &Tuning::msm_idx_ahead}, {"msm_share_l1", &Tuning::msm_share_l1}, {"srs_table_batched", &Tuning::srs_table_batched}, {"msm_debug", &Tuning::msm_debug}, {"msm_serial", &Tuning::msm_serial}, {"msm_size_classes", &Tuning::msm_size_classes},
@@ -418,6 +419,19 @@ int zk_sumcheck_wiring(zk_ctx* ctx, const void* d_eq, const void* d_tree, const 
                        const uint64_t* h_chal, uint64_t* h_out_evals, uint64_t* h_last) {
     NEED(ctx, d_eq && d_tree && d_num && d_den && h_gamma && h_chal && h_out_evals && h_last);
     return sumcheck_wiring(ctx, d_eq, d_tree, d_num, d_den, N, h_gamma, h_chal, h_out_evals, h_last);
+}
+int zk_eq_table_acc(zk_ctx* ctx, const uint64_t* h_point, size_t n, const uint64_t h_weight[4], void* d_acc) {
+    NEED(ctx, d_acc && h_weight && (n == 0 || h_point));
+    return eq_table_acc(ctx, h_point, n, h_weight, d_acc);
+}
+int zk_fr_lincomb(zk_ctx* ctx, size_t count, const void* const* d_tabs, const uint64_t* h_coeffs, size_t len, void* d_out) {
+    NEED(ctx, d_tabs && h_coeffs && d_out);
+    return fr_lincomb(ctx, count, d_tabs, h_coeffs, len, d_out);
+}
+int zk_sumcheck_multi(zk_ctx* ctx, size_t count, const void* const* d_e, const void* const* d_f, size_t len, const uint64_t* h_chal,
+                      uint64_t* h_out_triples, uint64_t* h_last_e, uint64_t* h_last_f) {
+    NEED(ctx, d_e && d_f && h_chal && h_out_triples && h_last_e && h_last_f);
+    return sumcheck_multi(ctx, count, d_e, d_f, len, h_chal, h_out_triples, h_last_e, h_last_f);
 }
 int zk_open_rounds(zk_ctx* ctx, const void* d_tab, size_t len, const uint64_t* h_point, void* d_q_out, uint64_t h_value[4]) {
     NEED(ctx, d_tab && h_value && (len <= 1 || (h_point && d_q_out)));

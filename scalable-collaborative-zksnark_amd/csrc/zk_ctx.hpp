@@ -72,6 +72,7 @@ struct zk_ctx {
     int cu_count = 256;
     bool gate_lds_raised = false;  // zk_gate.hip: k_gate_local's dynamic LDS limit has been raised on this ctx's device
     bool wiring_lds_raised = false;  // zk_wiring.hip: the same for k_wiring_local
+    bool multi_lds_raised = false;   // zk_batchopen.hip: the same for k_multi_local
     // party exchanges (zk_comm.cpp): an RCCL communicator bound to this ctx's GPU
     void* comm = nullptr;
     int comm_rank = 0, comm_world = 1;
@@ -107,6 +108,9 @@ struct Tuning {
     // wiring sumcheck (zk_wiring.hip)
     long wiring_local_e = 512;  // longest table (elements, a power of two <= 512) the single-workgroup LDS stage takes over; 1: HBM passes down to the last element
     long wiring_pass_wg = 0;    // workgroups per CU of the HBM passes (0: 2)
+    // batch-opening sumcheck (zk_batchopen.hip)
+    long multi_local_e = 512;   // longest table (elements, a power of two <= 512) the single-workgroup LDS stage takes over when the 2 count tables fit; 1: HBM passes down to the last element
+    long multi_pass_wg = 0;     // workgroups per CU of the HBM passes (0: 4)
     // MSM (zk_msm.hip)
     long msm_table_dc = 0;    // window-table width delta (sweeps)
     long msm_qstep = 2;       // window-class quantisation step of batches
@@ -166,10 +170,13 @@ int multilinear_run(zk_ctx* ctx, int mode, const void* d_f, const void* d_g, siz
                     size_t rounds, uint64_t* h_sums, uint64_t* h_last_f, uint64_t* h_last_g, void* d_out, void* d_q);
 int multilinear_batch(zk_ctx* ctx, const zk_sc_item* items, size_t count);
 int product_tree(zk_ctx* ctx, const void* d_x, size_t N, void* d_tree);
+// sums: rounds x (t0, t1, t2) Montgomery Fr on the host; t1 of round 0 is the device's, every later one is derived from the round before
+void derive_t1(uint64_t* sums, const uint64_t* chal, size_t rounds);
 int dbg_fq(zk_ctx* ctx, int op, const void* a, const void* b, void* out, size_t n);
 
 // ---- zk_gate.hip ----
 int eq_table(zk_ctx* ctx, const uint64_t* h_point, size_t n, void* d_out);
+int eq_table_seeded(zk_ctx* ctx, const uint64_t* h_point, size_t n, const uint64_t* h_seed, void* d_out);  // out[x] = seed * eq(point, x)
 // d_tabs: eq, q1, q2, a, b, c, in
 int sumcheck_gate(zk_ctx* ctx, const void* const* d_tabs, size_t len, const uint64_t* h_chal, uint64_t* h_out_evals, uint64_t* h_last);
 
@@ -177,6 +184,12 @@ int sumcheck_gate(zk_ctx* ctx, const void* const* d_tabs, size_t len, const uint
 // d_tree: the 2N Fr of product_tree; h_last: eq, v1x, vx0, vx1, h, num, den
 int sumcheck_wiring(zk_ctx* ctx, const void* d_eq, const void* d_tree, const void* d_num, const void* d_den, size_t N, const uint64_t* h_gamma,
                     const uint64_t* h_chal, uint64_t* h_out_evals, uint64_t* h_last);
+
+// ---- zk_batchopen.hip ----
+int eq_table_acc(zk_ctx* ctx, const uint64_t* h_point, size_t n, const uint64_t* h_weight, void* d_acc);
+int fr_lincomb(zk_ctx* ctx, size_t count, const void* const* d_tabs, const uint64_t* h_coeffs, size_t len, void* d_out);
+int sumcheck_multi(zk_ctx* ctx, size_t count, const void* const* d_e, const void* const* d_f, size_t len, const uint64_t* h_chal,
+                   uint64_t* h_out_triples, uint64_t* h_last_e, uint64_t* h_last_f);
 
 // ---- zk_msm.hip ----
 struct MsmItem {

@@ -924,7 +924,7 @@ static int launch_fold_flat(zk_ctx* ctx, hipStream_t st, const void* f, void* fo
 
 
 // sums: rounds x (t0, t1, t2) Montgomery Fr on the host; t1 of round 0 is the device's, every later one is derived
-static void derive_t1(uint64_t* sums, const uint64_t* chal, size_t rounds) {
+void derive_t1(uint64_t* sums, const uint64_t* chal, size_t rounds) {
     using namespace hfr;
     for (size_t rd = 1; rd < rounds; rd++) {
         F a, b, c, x, t0;

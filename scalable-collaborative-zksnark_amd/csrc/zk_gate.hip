@@ -155,9 +155,9 @@ __global__ void __launch_bounds__(kGateBlock) k_gate_local(GateIn in, unsigned E
 // taking tau_{k-1} in as the new top bit is  out[j + size] = out[j] tau,  out[j] = out[j] - out[j + size]  -- in place, one
 // multiplication per two outputs.  k_eq_seed builds the first levels (up to 2^10 entries) in one workgroup.
 // ---------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(1024) k_eq_seed(void* __restrict__ out, GateTail tau, int levels) {
+__global__ void __launch_bounds__(1024) k_eq_seed(void* __restrict__ out, GateTail tau, int levels, GateChal seed) {
     const unsigned tid = threadIdx.x;
-    if (tid == 0) fr_store(out, 0, fp_one<FrCfg>());
+    if (tid == 0) fr_store(out, 0, seed.r);  // 1 (zk_eq_table), or the weight of zk_eq_table_acc (zk_batchopen.hip)
     __syncthreads();
     for (int k = 0; k < levels; k++) {  // tau.c[k]: the variable taken in at level k (the last one first)
         const unsigned size = 1u << k;
@@ -180,14 +180,21 @@ __global__ void __launch_bounds__(kGateBlock) k_eq_double(void* __restrict__ out
 // ---------------------------------------------------------------------------------------
 // host drivers
 // ---------------------------------------------------------------------------------------
-int eq_table(zk_ctx* ctx, const uint64_t* h_point, size_t n, void* d_out) {
-    if (n > 40) return fail(ctx, ZK_ERR_INVALID, "zk_eq_table: %zu variables", n);
+static const uint64_t kFrOneMont[4] = {0x00000001fffffffeULL, 0x5884b7fa00034802ULL, 0x998c4fefecbc4ff5ULL, 0x1824b159acc5056fULL};  // R mod r
+
+int eq_table(zk_ctx* ctx, const uint64_t* h_point, size_t n, void* d_out) { return eq_table_seeded(ctx, h_point, n, kFrOneMont, d_out); }
+
+// d_out[x] = seed * eq(point, x): the doubling scheme started from `seed` instead of 1
+int eq_table_seeded(zk_ctx* ctx, const uint64_t* h_point, size_t n, const uint64_t* h_seed, void* d_out) {
+    if (n > 40) return fail(ctx, ZK_ERR_INVALID, "eq table of %zu variables (at most 40)", n);
     ZK_HIP(ctx, hipSetDevice(ctx->device));
+    GateChal sd;
+    std::memcpy(&sd.r, h_seed, 32);
     const int seed = (int)(n < 10 ? n : 10);
     GateTail tl;
     std::memset(&tl, 0, sizeof(tl));
     for (int k = 0; k < seed; k++) std::memcpy(tl.c + 4 * k, h_point + 4 * (n - 1 - k), 32);
-    hipLaunchKernelGGL(k_eq_seed, dim3(1), dim3(1024), 0, ctx->stream, d_out, tl, seed);
+    hipLaunchKernelGGL(k_eq_seed, dim3(1), dim3(1024), 0, ctx->stream, d_out, tl, seed, sd);
     ZK_HIP(ctx, hipGetLastError());
     for (size_t k = seed; k < n; k++) {
         const size_t size = (size_t)1 << k;

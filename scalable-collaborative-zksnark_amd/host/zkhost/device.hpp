@@ -249,6 +249,35 @@ class Ctx {
         check(zk_sumcheck_wiring(h_, eq.get(), tree.get(), num.get(), den.get(), N, gamma.v, chal[0].v, r.sums[0].v, last[0].v));
         return r;
     }
+    // zk_eq_table_acc: acc[x] += weight * eq(point, x), acc = 2^n Fr (asynchronous)
+    void eq_table_acc(const FrVec &point, const Fr &weight, const DevPtr &acc) {
+        check(zk_eq_table_acc(h_, point.empty() ? nullptr : point[0].v, point.size(), weight.v, acc.get()));
+    }
+    // zk_fr_lincomb: out[x] = sum_j coeffs[j] tabs[j][x], 1 .. 16 tables of len Fr (asynchronous)
+    DevPtr fr_lincomb(const std::vector<DevPtr> &tabs, const FrVec &coeffs, size_t len) {
+        need(!tabs.empty() && tabs.size() == coeffs.size(), "fr_lincomb: one coefficient per table");
+        std::vector<const void *> p;
+        for (const DevPtr &t : tabs) p.push_back(t.get());
+        DevPtr out = alloc_fr(len);
+        check(zk_fr_lincomb(h_, p.size(), p.data(), coeffs[0].v, len, out.get()));
+        return out;
+    }
+    // zk_sumcheck_multi: the rounds of sum_j es[j] fs[j] -> r.sums = 3 Fr per round (t0, t1, t2); last_e / last_f = the folded-out values
+    ScResult sumcheck_multi(const std::vector<DevPtr> &es, const std::vector<DevPtr> &fs, size_t len, const FrVec &chal, FrVec &last_e,
+                            FrVec &last_f) {
+        size_t n = log2_exact(len);
+        need(!es.empty() && es.size() == fs.size(), "sumcheck_multi: one eq table per table");
+        need(n >= 1 && chal.size() >= n, "sumcheck_multi: fewer challenges than rounds");
+        std::vector<const void *> pe, pf;
+        for (const DevPtr &t : es) pe.push_back(t.get());
+        for (const DevPtr &t : fs) pf.push_back(t.get());
+        ScResult r;
+        r.sums.resize(3 * n);
+        last_e.assign(es.size(), Fr::zero());
+        last_f.assign(es.size(), Fr::zero());
+        check(zk_sumcheck_multi(h_, pe.size(), pe.data(), pf.data(), len, chal[0].v, r.sums[0].v, last_e[0].v, last_f[0].v));
+        return r;
+    }
     ScResult open_rounds(const DevPtr &tab, size_t len, const FrVec &point) {
         need(point.size() >= log2_exact(len), "open: fewer point coordinates than rounds");
         ScResult r;

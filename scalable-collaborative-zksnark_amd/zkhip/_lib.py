@@ -45,6 +45,9 @@ SYMBOLS = [
     ("zk_eq_table", _i, [_vp, _vp, _sz, _vp]),
     ("zk_sumcheck_gate", _i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
     ("zk_sumcheck_wiring", _i, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
+    ("zk_eq_table_acc", _i, [_vp, _vp, _sz, _vp, _vp]),
+    ("zk_fr_lincomb", _i, [_vp, _sz, _vp, _vp, _sz, _vp]),
+    ("zk_sumcheck_multi", _i, [_vp, _sz, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
     ("zk_open_rounds", _i, [_vp, _vp, _sz, _vp, _vp, _vp]),
     ("zk_sumcheck_batch", _i, [_vp, _sz, _vp]),
     ("zk_product_tree", _i, [_vp, _vp, _sz, _vp]),

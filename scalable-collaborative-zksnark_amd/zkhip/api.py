@@ -498,6 +498,43 @@ class Ctx:
         self._check(self.lib.zk_sumcheck_wiring(self.h, _ptr(eq), _ptr(tree), _ptr(num), _ptr(den), N, _h(gamma), _h(chal), _h(out), _h(last)))
         return out, last
 
+    @staticmethod
+    def _ptr_array(bufs):
+        arr = (ctypes.c_void_p * len(bufs))()
+        for i, b in enumerate(bufs):
+            arr[i] = _ptr(b)
+        return arr
+
+    def eq_table_acc(self, point: np.ndarray, weight: np.ndarray, acc):
+        """acc[x] += weight * eq(point, x), acc a device buffer of 2^n Fr (zk_eq_table_acc; asynchronous) -> acc"""
+        point = np.ascontiguousarray(point, dtype=np.uint64).reshape(-1, 4)
+        weight = np.ascontiguousarray(weight, dtype=np.uint64).reshape(4)
+        self._check(self.lib.zk_eq_table_acc(self.h, _h(point), len(point), _h(weight), _ptr(acc)))
+        return acc
+
+    def fr_lincomb(self, tabs, coeffs: np.ndarray, length: int, out=None):
+        """out[x] = sum_j coeffs[j] * tabs[j][x] over 1 .. 16 device buffers of `length` Fr (zk_fr_lincomb; asynchronous)"""
+        coeffs = np.ascontiguousarray(coeffs, dtype=np.uint64).reshape(-1, 4)
+        if len(coeffs) != len(tabs):
+            raise ValueError(f"{len(tabs)} tables, {len(coeffs)} coefficients")
+        out = out or self.alloc(max(32 * length, 1))
+        self._check(self.lib.zk_fr_lincomb(self.h, len(tabs), self._ptr_array(tabs), _h(coeffs), length, _ptr(out)))
+        return out
+
+    def sumcheck_multi(self, es, fs, length: int, chal: np.ndarray):
+        """the rounds of sum_x sum_j es[j](x) fs[j](x) as one degree-2 sumcheck over 1 .. 16 pairs of device buffers of `length` Fr
+        -> (triples [n,3,4], last_e [count,4], last_f [count,4])"""
+        if len(es) != len(fs):
+            raise ValueError(f"{len(es)} eq tables, {len(fs)} tables")
+        n = max(length.bit_length() - 1, 0)
+        chal = np.ascontiguousarray(chal, dtype=np.uint64).reshape(-1, 4)
+        if len(chal) < n:
+            raise ValueError(f"{n} challenges needed, {len(chal)} given")
+        out = np.zeros((n, 3, 4), dtype=np.uint64)
+        le, lf = np.zeros((len(es), 4), dtype=np.uint64), np.zeros((len(es), 4), dtype=np.uint64)
+        self._check(self.lib.zk_sumcheck_multi(self.h, len(es), self._ptr_array(es), self._ptr_array(fs), length, _h(chal), _h(out), _h(le), _h(lf)))
+        return out, le, lf
+
     def open_rounds(self, tab, length: int, point: np.ndarray, q_out=None):
         """-> (q device buffer with length-1 Fr, value [4])"""
         point = np.ascontiguousarray(point, dtype=np.uint64).reshape(-1, 4)

@@ -177,6 +177,22 @@ def wiring_verify(be, vk_mu, vk_mu1, proof: dict, alpha, beta, gamma, tau, chal)
     return bool(np.all(ok))
 
 
+def wiring_prove_batched(be, pcs, w, sid, ssigma, N: int, alpha, beta, gamma, tau, chal, b_alpha, rho_mu, rho_mu1, commitments: dict | None = None,
+                         timing: dict | None = None) -> dict:
+    """wiring_prove with TWO opening proofs instead of eight: one batch instance of mu variables (w, sid, ssigma at r) and one of mu + 1
+    (the tree at the five V_POINTS), weight base b_alpha, challenges rho_mu / rho_mu1 (zkhip.batch_open, where the record is described)"""
+    from .batch_open import wiring_prove_batched as impl
+
+    return impl(be, pcs, w, sid, ssigma, N, alpha, beta, gamma, tau, chal, b_alpha, rho_mu, rho_mu1, commitments, timing)
+
+
+def wiring_verify_batched(be, vk_mu, vk_mu1, proof: dict, alpha, beta, gamma, tau, chal, b_alpha, rho_mu, rho_mu1) -> bool:
+    """checks 1-3 of failed_checks on the claimed values, then the two batch instances that certify them (vk_mu, vk_mu1)"""
+    from .batch_open import wiring_verify_batched as impl
+
+    return impl(be, vk_mu, vk_mu1, proof, alpha, beta, gamma, tau, chal, b_alpha, rho_mu, rho_mu1)
+
+
 def proof_digest(proof: dict) -> str:
     """SHA-256 over the record's little-endian words: rounds; per opening commitment | value | proof; the tree's commitment; per
     opening of it value | proof"""

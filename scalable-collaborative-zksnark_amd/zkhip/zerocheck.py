@@ -129,6 +129,21 @@ def gate_zerocheck_verify(be, vk, proof: dict, tau, chal) -> bool:
     return bool(np.all(ok))
 
 
+def gate_zerocheck_prove_batched(be, pcs, tables: dict, tau, chal, alpha, rho, commitments: dict | None = None, timing: dict | None = None) -> dict:
+    """gate_zerocheck_prove with ONE opening proof: the six openings at r become six claims of one batch instance with weight base alpha
+    and challenges rho (zkhip.batch_open, where the record is described)"""
+    from .batch_open import gate_zerocheck_prove_batched as impl
+
+    return impl(be, pcs, tables, tau, chal, alpha, rho, commitments, timing)
+
+
+def gate_zerocheck_verify_batched(be, vk, proof: dict, tau, chal, alpha, rho) -> bool:
+    """verify_rounds on the claimed values, then the batch instance that certifies them: one zk_pcs_verify_batch call of one opening"""
+    from .batch_open import gate_zerocheck_verify_batched as impl
+
+    return impl(be, vk, proof, tau, chal, alpha, rho)
+
+
 def proof_digest(proof: dict) -> str:
     """SHA-256 over the record's little-endian words: rounds, then per opening commitment | value | opening proof"""
     h = hashlib.sha256()
