@@ -182,6 +182,39 @@ int zk_fr_lincomb(zk_ctx *ctx, size_t count, const void *const *d_tabs, const ui
  * count 0 or > 16, len < 2 or not a power of two, count * len > 2^33, or a null pointer: ZK_ERR_INVALID; nothing is written on error. */
 int zk_sumcheck_multi(zk_ctx *ctx, size_t count, const void *const *d_e, const void *const *d_f, size_t len,
                       const uint64_t *h_chal, uint64_t *h_out_triples, uint64_t *h_last_e, uint64_t *h_last_f);
+/* ---- Fiat-Shamir on the device: a transcript whose state lives in device memory, and the three fused sumchecks driven by it ----
+ * The transcript is a SHA-256 hash chain on a 32-byte state (normative: the device, both hosts and the test model agree byte for byte):
+ *   init(label):   state = SHA256("zkhip-fs-v1" || label)
+ *   absorb(data):  state = SHA256(state || 0x00 || data); field elements and points go in as they sit in proof records (little-endian
+ *                  u64 limbs, Montgomery form), integers such as n as one little-endian u64
+ *   challenge():   d = SHA256(state || 0x01), state = d; the challenge is d read as a little-endian 256-bit integer with its top two
+ *                  bits cleared: < 2^254 < r, so there is no rejection loop.
+ * A transcript belongs to the ctx it was created on (any other: ZK_ERR_INVALID) and is freed BEFORE that ctx.  create, absorb and
+ * absorb_device are ASYNCHRONOUS on the ctx stream (host bytes are copied before the call returns); challenges and state wait for it.
+ * ONE lane hashes an absorb, byte by byte: it is meant for statements, commitments and values.  An absorb of more than 2^20 bytes
+ * is refused with ZK_ERR_INVALID (commit to a table and absorb the commitment instead). */
+typedef struct zk_transcript zk_transcript;
+int zk_transcript_create(zk_ctx *ctx, const void *h_label, size_t label_len, zk_transcript **out); /* label_len <= 2048 */
+void zk_transcript_free(zk_transcript *t);
+int zk_transcript_absorb(zk_ctx *ctx, zk_transcript *t, const void *h_bytes, size_t len);
+int zk_transcript_absorb_device(zk_ctx *ctx, zk_transcript *t, const void *d_ptr, size_t len);
+/* count successive challenges; h_out: count Fr in Montgomery form */
+int zk_transcript_challenges(zk_ctx *ctx, zk_transcript *t, size_t count, uint64_t *h_out);
+int zk_transcript_state(zk_ctx *ctx, zk_transcript *t, uint8_t h_state32[32]);
+/* zk_sumcheck_gate / zk_sumcheck_wiring / zk_sumcheck_multi with every challenge DERIVED: round i's evaluations are absorbed as they
+ * appear in the output (5, 4 or 3 Fr) and one challenge is drawn, on the device, between the kernels of ONE enqueue -- no host read and
+ * one stream synchronisation per call.  h_chal_out: the n challenges that were used (Montgomery Fr); every other argument, the
+ * outputs, the limits and the error cases are those of the parent, and for the challenges in h_chal_out the parent returns the same
+ * bits.  The transcript has absorbed all n rounds when the call returns.  A null transcript or one of another ctx: ZK_ERR_INVALID. */
+int zk_sumcheck_gate_fs(zk_ctx *ctx, const void *d_eq, const void *d_q1, const void *d_q2, const void *d_a,
+                        const void *d_b, const void *d_c, const void *d_in, size_t len, zk_transcript *t,
+                        uint64_t *h_out_evals, uint64_t *h_last, uint64_t *h_chal_out);
+int zk_sumcheck_wiring_fs(zk_ctx *ctx, const void *d_eq, const void *d_tree, const void *d_num, const void *d_den,
+                          size_t N, const uint64_t h_gamma[4], zk_transcript *t, uint64_t *h_out_evals,
+                          uint64_t *h_last, uint64_t *h_chal_out);
+int zk_sumcheck_multi_fs(zk_ctx *ctx, size_t count, const void *const *d_e, const void *const *d_f, size_t len,
+                         zk_transcript *t, uint64_t *h_out_triples, uint64_t *h_last_e, uint64_t *h_last_f,
+                         uint64_t *h_chal_out);
 /* Phase 1 of open / d_local_open / c_open (dpoly_comm.rs:309-323 = :337-351 = :418-432):
  * for every round q_i = hi - lo then fold with point[i].  d_q_out receives len-1 Fr: q_0 (len/2)
  * followed by q_1 (len/4) ... q_{n-1} (1) -- exactly the scalar vectors of the n commitments.

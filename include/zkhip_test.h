@@ -16,6 +16,8 @@ extern "C" {
  * EVERY round on the device instead of deriving it from the previous round polynomial (the cross-check of
  * tests/test_gpu_bigsizes.py).  Returns ZK_ERR_INVALID for an unknown key. */
 int zk_dbg_tune(const char *key, long value);
+/* the current value of a knob (so that a test can put back what it found); ZK_ERR_INVALID for an unknown key or a null pointer */
+int zk_dbg_tune_get(const char *key, long *value);
 int zk_dbg_fq_mul(zk_ctx *ctx, const void *d_a, const void *d_b, void *d_out, size_t n);
 int zk_dbg_fq_add(zk_ctx *ctx, const void *d_a, const void *d_b, void *d_out, size_t n);
 int zk_dbg_fq_sub(zk_ctx *ctx, const void *d_a, const void *d_b, void *d_out, size_t n);

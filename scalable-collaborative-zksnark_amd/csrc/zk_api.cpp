@@ -433,6 +433,43 @@ int zk_sumcheck_multi(zk_ctx* ctx, size_t count, const void* const* d_e, const v
     NEED(ctx, d_e && d_f && h_chal && h_out_triples && h_last_e && h_last_f);
     return sumcheck_multi(ctx, count, d_e, d_f, len, h_chal, h_out_triples, h_last_e, h_last_f);
 }
+int zk_transcript_create(zk_ctx* ctx, const void* h_label, size_t label_len, zk_transcript** out) {
+    NEED(ctx, out && (label_len == 0 || h_label));
+    return transcript_create(ctx, h_label, label_len, out);
+}
+void zk_transcript_free(zk_transcript* t) { transcript_free(t); }
+int zk_transcript_absorb(zk_ctx* ctx, zk_transcript* t, const void* h_bytes, size_t len) {
+    NEED(ctx, len == 0 || h_bytes);
+    return transcript_absorb(ctx, t, h_bytes, len);
+}
+int zk_transcript_absorb_device(zk_ctx* ctx, zk_transcript* t, const void* d_ptr, size_t len) {
+    NEED(ctx, len == 0 || d_ptr);
+    return transcript_absorb_device(ctx, t, d_ptr, len);
+}
+int zk_transcript_challenges(zk_ctx* ctx, zk_transcript* t, size_t count, uint64_t* h_out) {
+    NEED(ctx, count == 0 || h_out);
+    return transcript_challenges(ctx, t, count, h_out);
+}
+int zk_transcript_state(zk_ctx* ctx, zk_transcript* t, uint8_t h_state32[32]) {
+    NEED(ctx, h_state32);
+    return transcript_state(ctx, t, h_state32);
+}
+int zk_sumcheck_gate_fs(zk_ctx* ctx, const void* d_eq, const void* d_q1, const void* d_q2, const void* d_a, const void* d_b, const void* d_c,
+                        const void* d_in, size_t len, zk_transcript* t, uint64_t* h_out_evals, uint64_t* h_last, uint64_t* h_chal_out) {
+    NEED(ctx, d_eq && d_q1 && d_q2 && d_a && d_b && d_c && d_in && h_out_evals && h_last && h_chal_out);
+    const void* tabs[7] = {d_eq, d_q1, d_q2, d_a, d_b, d_c, d_in};
+    return sumcheck_gate_fs(ctx, tabs, len, t, h_out_evals, h_last, h_chal_out);
+}
+int zk_sumcheck_wiring_fs(zk_ctx* ctx, const void* d_eq, const void* d_tree, const void* d_num, const void* d_den, size_t N, const uint64_t h_gamma[4],
+                          zk_transcript* t, uint64_t* h_out_evals, uint64_t* h_last, uint64_t* h_chal_out) {
+    NEED(ctx, d_eq && d_tree && d_num && d_den && h_gamma && h_out_evals && h_last && h_chal_out);
+    return sumcheck_wiring_fs(ctx, d_eq, d_tree, d_num, d_den, N, h_gamma, t, h_out_evals, h_last, h_chal_out);
+}
+int zk_sumcheck_multi_fs(zk_ctx* ctx, size_t count, const void* const* d_e, const void* const* d_f, size_t len, zk_transcript* t,
+                         uint64_t* h_out_triples, uint64_t* h_last_e, uint64_t* h_last_f, uint64_t* h_chal_out) {
+    NEED(ctx, d_e && d_f && h_out_triples && h_last_e && h_last_f && h_chal_out);
+    return sumcheck_multi_fs(ctx, count, d_e, d_f, len, t, h_out_triples, h_last_e, h_last_f, h_chal_out);
+}
 int zk_open_rounds(zk_ctx* ctx, const void* d_tab, size_t len, const uint64_t* h_point, void* d_q_out, uint64_t h_value[4]) {
     NEED(ctx, d_tab && h_value && (len <= 1 || (h_point && d_q_out)));
     return multilinear_run(ctx, 3, d_tab, nullptr, len, h_point, (size_t)log2_exact(len), nullptr, h_value, nullptr, nullptr, d_q_out);
@@ -618,6 +655,15 @@ int zk_sumcheck_last_timing(zk_ctx* ctx, float h_ms[2]) {
     return ZK_OK;
 }
 int zk_dbg_tune(const char* key, long value) { return tune_set(key, value); }
+int zk_dbg_tune_get(const char* key, long* value) {
+    if (!key || !value) return ZK_ERR_INVALID;
+    for (const TuneKey& k : kTuneKeys)
+        if (!std::strcmp(k.name, key)) {
+            *value = tuning().*(k.field);
+            return ZK_OK;
+        }
+    return ZK_ERR_INVALID;
+}
 
 int zk_dbg_fq_mul2add(zk_ctx* ctx, const void* a, const void* b, void* out, size_t n) { return dbg_fq(ctx, 3, a, b, out, n); }
 int zk_dbg_fq_add(zk_ctx* ctx, const void* a, const void* b, void* out, size_t n) { return dbg_fq(ctx, 0, a, b, out, n); }

@@ -18,22 +18,6 @@
 
 namespace zk {
 
-static constexpr int kMultiMax = 16;  // pairs per call (two pointer blocks of kernel arguments)
-// Capacity of the shared sums: the factors of t2 are unreduced sums < 2r, so a product is < 4 r^2 < 2^512 (r < 0.4529 * 2^256) and a
-// 544-bit integer holds 2^32 of them; k_multi_reduce adds ALL count * len / 2 products of a round into one, hence
-// count * len <= 2^33 (t0 and t1, products of factors < r, are below that).  include/zkhip.h states the bound.
-static constexpr int kMultiMaxLog = 33;
-static constexpr size_t kMultiLdsBytes = 112 * 1024;  // tables of the local stage (the gate's share of the CU's 160 KiB)
-
-struct MultiIn {
-    const void* e[kMultiMax];
-    const void* f[kMultiMax];
-};
-// table (j, which) of the folded set: base + (2 j + which) * stride elements
-struct MultiOut {
-    void* base;
-    size_t stride;
-};
 struct LincombIn {
     const void* t[kMultiMax];
     Fr c[kMultiMax];

@@ -73,11 +73,24 @@ struct zk_ctx {
     bool gate_lds_raised = false;  // zk_gate.hip: k_gate_local's dynamic LDS limit has been raised on this ctx's device
     bool wiring_lds_raised = false;  // zk_wiring.hip: the same for k_wiring_local
     bool multi_lds_raised = false;   // zk_batchopen.hip: the same for k_multi_local
+    bool fs_lds_raised[3] = {false, false, false};  // zk_fs.hip: the same for its three local kernels (gate, wiring, multi)
     // party exchanges (zk_comm.cpp): an RCCL communicator bound to this ctx's GPU
     void* comm = nullptr;
     int comm_rank = 0, comm_world = 1;
     void* h_comm = nullptr;  // pinned staging of zk_d_msm (its own block: the MSM pass may re-allocate h_pinned)
     size_t h_comm_cap = 0;
+};
+
+// Fiat-Shamir transcript (zk_transcript.hip): the 32-byte state of the hash chain in device memory, bound to one ctx
+struct zk_transcript {
+    zk_ctx* ctx = nullptr;
+    uint32_t* d_state = nullptr;
+    // staging of host strings too long for a kernel argument: pinned block, device block, "the copy out of it is done"
+    unsigned char* h_stage = nullptr;
+    unsigned char* d_stage = nullptr;
+    size_t stage_cap = 0;
+    hipEvent_t staged = nullptr;
+    bool stage_busy = false;
 };
 
 namespace zk {
@@ -190,6 +203,22 @@ int eq_table_acc(zk_ctx* ctx, const uint64_t* h_point, size_t n, const uint64_t*
 int fr_lincomb(zk_ctx* ctx, size_t count, const void* const* d_tabs, const uint64_t* h_coeffs, size_t len, void* d_out);
 int sumcheck_multi(zk_ctx* ctx, size_t count, const void* const* d_e, const void* const* d_f, size_t len, const uint64_t* h_chal,
                    uint64_t* h_out_triples, uint64_t* h_last_e, uint64_t* h_last_f);
+
+// ---- zk_transcript.hip ----
+int transcript_create(zk_ctx* ctx, const void* h_label, size_t label_len, zk_transcript** out);
+void transcript_free(zk_transcript* t);
+int transcript_absorb(zk_ctx* ctx, zk_transcript* t, const void* h_bytes, size_t len);
+int transcript_absorb_device(zk_ctx* ctx, zk_transcript* t, const void* d_ptr, size_t len);
+int transcript_challenges(zk_ctx* ctx, zk_transcript* t, size_t count, uint64_t* h_out);
+int transcript_state(zk_ctx* ctx, zk_transcript* t, uint8_t* h_state32);
+
+// ---- zk_fs.hip: the fused sumchecks with their challenges drawn from a transcript on the device ----
+// the arguments of sumcheck_gate / sumcheck_wiring / sumcheck_multi with the transcript in the place of h_chal; h_chal_out: rounds Fr
+int sumcheck_gate_fs(zk_ctx* ctx, const void* const* d_tabs, size_t len, zk_transcript* t, uint64_t* h_out_evals, uint64_t* h_last, uint64_t* h_chal_out);
+int sumcheck_wiring_fs(zk_ctx* ctx, const void* d_eq, const void* d_tree, const void* d_num, const void* d_den, size_t N, const uint64_t* h_gamma,
+                       zk_transcript* t, uint64_t* h_out_evals, uint64_t* h_last, uint64_t* h_chal_out);
+int sumcheck_multi_fs(zk_ctx* ctx, size_t count, const void* const* d_e, const void* const* d_f, size_t len, zk_transcript* t,
+                      uint64_t* h_out_triples, uint64_t* h_last_e, uint64_t* h_last_f, uint64_t* h_chal_out);
 
 // ---- zk_msm.hip ----
 struct MsmItem {

@@ -1,4 +1,4 @@
-// zk_gate.cuh -- what the fused sumchecks (zk_gate.hip: gate identity, zk_wiring.hip: wiring identity) share: launch geometry, the
+// zk_gate.cuh -- what the fused sumchecks (zk_gate.hip: gate identity, zk_wiring.hip: wiring identity, zk_batchopen.hip, zk_fs.hip) share: launch geometry, the
 // argument blocks of their kernels and the 544-bit lazily reduced sums (one 80-byte slot per wave, evaluation and pass).
 #pragma once
 #include "fp.cuh"
@@ -23,6 +23,24 @@ struct GateReducePlan {
     unsigned off[kGateMaxPasses];   // first slot of pass p in the partials block
 };
 
+// the batch-opening sumcheck (zk_batchopen.hip, its transcript-driven form in zk_fs.hip)
+static constexpr int kMultiMax = 16;  // pairs per call (two pointer blocks of kernel arguments)
+// Capacity of the shared sums: the factors of t2 are unreduced sums < 2r, so a product is < 4 r^2 < 2^512 (r < 0.4529 * 2^256) and a
+// 544-bit integer holds 2^32 of them; k_multi_reduce adds ALL count * len / 2 products of a round into one, hence
+// count * len <= 2^33 (t0 and t1, products of factors < r, are below that).  include/zkhip.h states the bound.
+static constexpr int kMultiMaxLog = 33;
+static constexpr size_t kMultiLdsBytes = 112 * 1024;  // tables of the local stage (the gate's share of the CU's 160 KiB)
+
+struct MultiIn {
+    const void* e[kMultiMax];
+    const void* f[kMultiMax];
+};
+// table (j, which) of the folded set: base + (2 j + which) * stride elements
+struct MultiOut {
+    void* base;
+    size_t stride;
+};
+
 __device__ __forceinline__ void gate_wide_add(u32 (&a)[17], const u32 (&b)[17]) {
     u32 c = 0;
 #pragma unroll
@@ -44,9 +62,25 @@ __device__ __forceinline__ void gate_wide_load(u32 (&v)[17], const void* base, s
     v[16] = p[4].x;
 }
 
+// the brackets of the two identities (zk_gate.hip / zk_wiring.hip and their transcript-driven forms in zk_fs.hip)
+// [ q1 (a + b) + (q2 a) b - c + in ] of one point: three multiplications
+__device__ __forceinline__ Fr gate_inner(const Fr& q1, const Fr& q2, const Fr& a, const Fr& b, const Fr& c, const Fr& in) {
+    const Fr s = fr_mul(q1, fr_add(a, b));
+    const Fr p = fr_mul(fr_mul(q2, a), b);
+    return fr_add(fr_sub(fr_add(s, p), c), in);
+}
+
+// [ v1x - vx0 vx1 + gamma (den h - num) ] of one point: three multiplications
+__device__ __forceinline__ Fr wiring_inner(const Fr& gamma, const Fr& v1x, const Fr& vx0, const Fr& vx1, const Fr& h, const Fr& num, const Fr& den) {
+    const Fr p = fr_mul(vx0, vx1);
+    const Fr q = fr_mul(gamma, fr_sub(fr_mul(den, h), num));
+    return fr_add(fr_sub(v1x, p), q);
+}
+
 // One workgroup of kGateBlock lanes adds the nbw per-wave partials from slot `base` on and reduces W0 + W1 R + W2 R^2 (a sum of
-// integer products of Montgomery forms) to W0 R^-1 + W1 + W2 R mod r, canonical, into evals[out].  lds: (kGateBlock / 64) slots.
-__device__ __forceinline__ void gate_reduce_block(const void* __restrict__ partials, size_t base, unsigned nbw, uint4* lds, void* __restrict__ evals, size_t out) {
+// integer products of Montgomery forms) to W0 R^-1 + W1 + W2 R mod r, canonical: the value is lane 0's (the other lanes get zero).
+// lds: (kGateBlock / 64) slots, free again after the call's barrier.
+__device__ __forceinline__ Fr gate_reduce_value(const void* __restrict__ partials, size_t base, unsigned nbw, uint4* lds) {
     u32 v[17];
 #pragma unroll
     for (int i = 0; i < 17; i++) v[i] = 0;
@@ -64,7 +98,7 @@ __device__ __forceinline__ void gate_reduce_block(const void* __restrict__ parti
     }
     if ((threadIdx.x & 63) == 0) gate_wide_store(lds, threadIdx.x >> 6, v);
     __syncthreads();
-    if (threadIdx.x != 0) return;
+    if (threadIdx.x != 0) return fp_zero<FrCfg>();
     for (int g = 1; g < kGateBlock / 64; g++) {
         u32 x[17];
         gate_wide_load(x, lds, g);
@@ -77,7 +111,12 @@ __device__ __forceinline__ void gate_reduce_block(const void* __restrict__ parti
     one.l[0] = 1;
     w0 = fp_reduce_once<FrCfg>(fp_reduce_once<FrCfg>(w0));  // 2^256 < 3 r
     w1 = fp_reduce_once<FrCfg>(fp_reduce_once<FrCfg>(w1));
-    fr_store(evals, out, fr_add(fr_add(fr_mul(w0, one), w1), fr_mul(w2, r2)));
+    return fr_add(fr_add(fr_mul(w0, one), w1), fr_mul(w2, r2));
+}
+// ... into evals[out]
+__device__ __forceinline__ void gate_reduce_block(const void* __restrict__ partials, size_t base, unsigned nbw, uint4* lds, void* __restrict__ evals, size_t out) {
+    const Fr s = gate_reduce_value(partials, base, nbw, lds);
+    if (threadIdx.x == 0) fr_store(evals, out, s);
 }
 
 }  // namespace zk

@@ -28,13 +28,6 @@ struct GateOut {
     void* t[kGateTabs];
 };
 
-// [ q1 (a + b) + (q2 a) b - c + in ] of one point: three multiplications
-__device__ __forceinline__ Fr gate_inner(const Fr& q1, const Fr& q2, const Fr& a, const Fr& b, const Fr& c, const Fr& in) {
-    const Fr s = fr_mul(q1, fr_add(a, b));
-    const Fr p = fr_mul(fr_mul(q2, a), b);
-    return fr_add(fr_sub(fr_add(s, p), c), in);
-}
-
 // ---------------------------------------------------------------------------------------
 // One round over tables of length 2 * half living in HBM.  partials: [t * nbw + 4 block + wave], 80-byte slots.
 // The values at t = 1 .. 4 come from v(t) = v(t-1) + (hi - lo): per t four multiplications (three reduced ones inside the

@@ -33,13 +33,6 @@ struct WireOut {
     void* t[kWireTabs];
 };
 
-// [ v1x - vx0 vx1 + gamma (den h - num) ] of one point: three multiplications
-__device__ __forceinline__ Fr wiring_inner(const Fr& gamma, const Fr& v1x, const Fr& vx0, const Fr& vx1, const Fr& h, const Fr& num, const Fr& den) {
-    const Fr p = fr_mul(vx0, vx1);
-    const Fr q = fr_mul(gamma, fr_sub(fr_mul(den, h), num));
-    return fr_add(fr_sub(v1x, p), q);
-}
-
 // ---------------------------------------------------------------------------------------
 // One round over tables of length 2 * half living in HBM.  partials: [t * nbw + 4 block + wave], 80-byte slots.
 // TREE (the first pass of a call): in.t[1] is the tree; table 4 (h) is its lower half, table 1 (v1x) its upper half, and the

@@ -1,66 +1,3 @@
-// SHA-256 (FIPS 180-4) for the transcript digests of examples/hyperplonk.cpp --digest: a diagnostic that lets a run of the
-// C++ host at full size be compared with a run of the Python host on the same tables (hashlib.sha256 on the same bytes).
+// moved: the transcript of zkhost/transcript.hpp uses it too
 #pragma once
-#include <algorithm>
-#include <cstdint>
-#include <cstring>
-#include <string>
-
-class Sha256 {
-  public:
-    Sha256() {
-        static const uint32_t iv[8] = {0x6a09e667, 0xbb67ae85, 0x3c6ef372, 0xa54ff53a, 0x510e527f, 0x9b05688c, 0x1f83d9ab, 0x5be0cd19};
-        std::memcpy(h_, iv, sizeof iv);
-    }
-    void update(const void *data, size_t n) {
-        const uint8_t *p = (const uint8_t *)data;
-        total_ += n;
-        while (n) {
-            size_t take = std::min(n, (size_t)64 - fill_);
-            std::memcpy(buf_ + fill_, p, take);
-            fill_ += take, p += take, n -= take;
-            if (fill_ == 64) block(buf_), fill_ = 0;
-        }
-    }
-    std::string hex() {
-        uint64_t bits = total_ * 8;
-        uint8_t pad[72] = {0x80};
-        size_t padlen = (fill_ < 56 ? 56 : 120) - fill_;
-        uint8_t len[8];
-        for (int i = 0; i < 8; ++i) len[i] = (uint8_t)(bits >> (56 - 8 * i));
-        update(pad, padlen);
-        update(len, 8);
-        static const char *d = "0123456789abcdef";
-        std::string s;
-        for (int i = 0; i < 8; ++i)
-            for (int b = 28; b >= 0; b -= 4) s.push_back(d[(h_[i] >> b) & 15]);
-        return s;
-    }
-
-  private:
-    static uint32_t rotr(uint32_t x, int r) { return (x >> r) | (x << (32 - r)); }
-    void block(const uint8_t *p) {
-        static const uint32_t k[64] = {
-            0x428a2f98, 0x71374491, 0xb5c0fbcf, 0xe9b5dba5, 0x3956c25b, 0x59f111f1, 0x923f82a4, 0xab1c5ed5, 0xd807aa98, 0x12835b01, 0x243185be, 0x550c7dc3, 0x72be5d74,
-            0x80deb1fe, 0x9bdc06a7, 0xc19bf174, 0xe49b69c1, 0xefbe4786, 0x0fc19dc6, 0x240ca1cc, 0x2de92c6f, 0x4a7484aa, 0x5cb0a9dc, 0x76f988da, 0x983e5152, 0xa831c66d,
-            0xb00327c8, 0xbf597fc7, 0xc6e00bf3, 0xd5a79147, 0x06ca6351, 0x14292967, 0x27b70a85, 0x2e1b2138, 0x4d2c6dfc, 0x53380d13, 0x650a7354, 0x766a0abb, 0x81c2c92e,
-            0x92722c85, 0xa2bfe8a1, 0xa81a664b, 0xc24b8b70, 0xc76c51a3, 0xd192e819, 0xd6990624, 0xf40e3585, 0x106aa070, 0x19a4c116, 0x1e376c08, 0x2748774c, 0x34b0bcb5,
-            0x391c0cb3, 0x4ed8aa4a, 0x5b9cca4f, 0x682e6ff3, 0x748f82ee, 0x78a5636f, 0x84c87814, 0x8cc70208, 0x90befffa, 0xa4506ceb, 0xbef9a3f7, 0xc67178f2};
-        uint32_t w[64], a = h_[0], b = h_[1], c = h_[2], d = h_[3], e = h_[4], f = h_[5], g = h_[6], h = h_[7];
-        for (int i = 0; i < 16; ++i) w[i] = (uint32_t)p[4 * i] << 24 | (uint32_t)p[4 * i + 1] << 16 | (uint32_t)p[4 * i + 2] << 8 | p[4 * i + 3];
-        for (int i = 16; i < 64; ++i) {
-            uint32_t s0 = rotr(w[i - 15], 7) ^ rotr(w[i - 15], 18) ^ (w[i - 15] >> 3), s1 = rotr(w[i - 2], 17) ^ rotr(w[i - 2], 19) ^ (w[i - 2] >> 10);
-            w[i] = w[i - 16] + s0 + w[i - 7] + s1;
-        }
-        for (int i = 0; i < 64; ++i) {
-            uint32_t t1 = h + (rotr(e, 6) ^ rotr(e, 11) ^ rotr(e, 25)) + ((e & f) ^ (~e & g)) + k[i] + w[i];
-            uint32_t t2 = (rotr(a, 2) ^ rotr(a, 13) ^ rotr(a, 22)) + ((a & b) ^ (a & c) ^ (b & c));
-            h = g, g = f, f = e, e = d + t1, d = c, c = b, b = a, a = t1 + t2;
-        }
-        h_[0] += a, h_[1] += b, h_[2] += c, h_[3] += d, h_[4] += e, h_[5] += f, h_[6] += g, h_[7] += h;
-    }
-    uint32_t h_[8];
-    uint8_t buf_[64];
-    size_t fill_ = 0;
-    uint64_t total_ = 0;
-};
+#include "zkhost/sha256.hpp"

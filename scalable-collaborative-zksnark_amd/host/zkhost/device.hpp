@@ -54,6 +54,17 @@ struct PcsVk {
     }
 };
 
+// a Fiat-Shamir transcript whose state lives on the device (zk_transcript); freed before its ctx because it holds the ctx
+struct DeviceTranscript {
+    CtxRef ctx;
+    zk_transcript *h = nullptr;
+    DeviceTranscript(CtxRef c, zk_transcript *h_) : ctx(std::move(c)), h(h_) {}
+    DeviceTranscript(const DeviceTranscript &) = delete;
+    ~DeviceTranscript() {
+        if (h) zk_transcript_free(h);
+    }
+};
+
 // a device allocation (zk_malloc / zk_free); DevPtr below shares it
 struct DevAlloc {
     CtxRef ctx;
@@ -276,6 +287,56 @@ class Ctx {
         last_e.assign(es.size(), Fr::zero());
         last_f.assign(es.size(), Fr::zero());
         check(zk_sumcheck_multi(h_, pe.size(), pe.data(), pf.data(), len, chal[0].v, r.sums[0].v, last_e[0].v, last_f[0].v));
+        return r;
+    }
+    // ---- Fiat-Shamir: the transcript on the device and the three sumchecks driven by it (`chal` receives the derived challenges) ----
+    std::shared_ptr<DeviceTranscript> transcript(const std::string &label) {
+        zk_transcript *t = nullptr;
+        check(zk_transcript_create(h_, label.data(), label.size(), &t));
+        return std::make_shared<DeviceTranscript>(ref_, t);
+    }
+    void absorb(DeviceTranscript &t, const void *bytes, size_t n) { check(zk_transcript_absorb(h_, t.h, bytes, n)); }
+    FrVec challenges(DeviceTranscript &t, size_t count) {
+        FrVec out(count);
+        if (count) check(zk_transcript_challenges(h_, t.h, count, out[0].v));
+        return out;
+    }
+    ScResult sumcheck_gate_fs(const std::array<DevPtr, 7> &tabs, size_t len, DeviceTranscript &t, FrVec &last, FrVec &chal) {
+        size_t n = log2_exact(len);
+        need(n >= 1, "sumcheck_gate_fs: at least one round");
+        ScResult r;
+        r.sums.resize(5 * n);
+        last.assign(7, Fr::zero());
+        chal.assign(n, Fr::zero());
+        check(zk_sumcheck_gate_fs(h_, tabs[0].get(), tabs[1].get(), tabs[2].get(), tabs[3].get(), tabs[4].get(), tabs[5].get(), tabs[6].get(), len, t.h, r.sums[0].v,
+                                  last[0].v, chal[0].v));
+        return r;
+    }
+    ScResult sumcheck_wiring_fs(const DevPtr &eq, const DevPtr &tree, const DevPtr &num, const DevPtr &den, size_t N, const Fr &gamma, DeviceTranscript &t, FrVec &last,
+                                FrVec &chal) {
+        size_t mu = log2_exact(N);
+        need(mu >= 1, "sumcheck_wiring_fs: at least one round");
+        ScResult r;
+        r.sums.resize(4 * mu);
+        last.assign(7, Fr::zero());
+        chal.assign(mu, Fr::zero());
+        check(zk_sumcheck_wiring_fs(h_, eq.get(), tree.get(), num.get(), den.get(), N, gamma.v, t.h, r.sums[0].v, last[0].v, chal[0].v));
+        return r;
+    }
+    ScResult sumcheck_multi_fs(const std::vector<DevPtr> &es, const std::vector<DevPtr> &fs, size_t len, DeviceTranscript &t, FrVec &last_e, FrVec &last_f,
+                               FrVec &chal) {
+        size_t n = log2_exact(len);
+        need(!es.empty() && es.size() == fs.size(), "sumcheck_multi_fs: one eq table per table");
+        need(n >= 1, "sumcheck_multi_fs: at least one round");
+        std::vector<const void *> pe, pf;
+        for (const DevPtr &x : es) pe.push_back(x.get());
+        for (const DevPtr &x : fs) pf.push_back(x.get());
+        ScResult r;
+        r.sums.resize(3 * n);
+        last_e.assign(es.size(), Fr::zero());
+        last_f.assign(es.size(), Fr::zero());
+        chal.assign(n, Fr::zero());
+        check(zk_sumcheck_multi_fs(h_, pe.size(), pe.data(), pf.data(), len, t.h, r.sums[0].v, last_e[0].v, last_f[0].v, chal[0].v));
         return r;
     }
     ScResult open_rounds(const DevPtr &tab, size_t len, const FrVec &point) {

@@ -48,6 +48,15 @@ SYMBOLS = [
     ("zk_eq_table_acc", _i, [_vp, _vp, _sz, _vp, _vp]),
     ("zk_fr_lincomb", _i, [_vp, _sz, _vp, _vp, _sz, _vp]),
     ("zk_sumcheck_multi", _i, [_vp, _sz, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
+    ("zk_transcript_create", _i, [_vp, ctypes.c_char_p, _sz, _pp]),
+    ("zk_transcript_free", None, [_vp]),
+    ("zk_transcript_absorb", _i, [_vp, _vp, ctypes.c_char_p, _sz]),
+    ("zk_transcript_absorb_device", _i, [_vp, _vp, _vp, _sz]),
+    ("zk_transcript_challenges", _i, [_vp, _vp, _sz, _vp]),
+    ("zk_transcript_state", _i, [_vp, _vp, _vp]),
+    ("zk_sumcheck_gate_fs", _i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
+    ("zk_sumcheck_wiring_fs", _i, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
+    ("zk_sumcheck_multi_fs", _i, [_vp, _sz, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
     ("zk_open_rounds", _i, [_vp, _vp, _sz, _vp, _vp, _vp]),
     ("zk_sumcheck_batch", _i, [_vp, _sz, _vp]),
     ("zk_product_tree", _i, [_vp, _vp, _sz, _vp]),
@@ -103,6 +112,7 @@ SYMBOLS = [
 # include/zkhip_test.h: the zk_dbg_* test hooks -- not part of the ABI, resolved only when a test / tool asks (test_hooks())
 TEST_SYMBOLS = [
     ("zk_dbg_tune", _i, [ctypes.c_char_p, ctypes.c_long]),
+    ("zk_dbg_tune_get", _i, [ctypes.c_char_p, ctypes.POINTER(ctypes.c_long)]),
     ("zk_dbg_fq_mul", _i, [_vp, _vp, _vp, _vp, _sz]),
     ("zk_dbg_fq_add", _i, [_vp, _vp, _vp, _vp, _sz]),
     ("zk_dbg_fq_sub", _i, [_vp, _vp, _vp, _vp, _sz]),

@@ -535,6 +535,38 @@ class Ctx:
         self._check(self.lib.zk_sumcheck_multi(self.h, len(es), self._ptr_array(es), self._ptr_array(fs), length, _h(chal), _h(out), _h(le), _h(lf)))
         return out, le, lf
 
+    # ---- the same three sumchecks with their challenges drawn from a device transcript (zkhip.transcript.Transcript) ----
+    @staticmethod
+    def _tr(transcript) -> int:
+        return getattr(transcript, "h", transcript) or 0
+
+    def sumcheck_gate_fs(self, eq, q1, q2, a, b, c, inp, length: int, transcript):
+        """sumcheck_gate with round i's challenge = hash of round i's evaluations -> (evals [n,5,4], last [7,4], chal [n,4])"""
+        n = max(length.bit_length() - 1, 0)
+        out, last, chal = np.zeros((n, 5, 4), dtype=np.uint64), np.zeros((7, 4), dtype=np.uint64), np.zeros((n, 4), dtype=np.uint64)
+        self._check(self.lib.zk_sumcheck_gate_fs(self.h, _ptr(eq), _ptr(q1), _ptr(q2), _ptr(a), _ptr(b), _ptr(c), _ptr(inp), length, self._tr(transcript), _h(out),
+                                                 _h(last), _h(chal)))
+        return out, last, chal
+
+    def sumcheck_wiring_fs(self, eq, tree, num, den, N: int, gamma: np.ndarray, transcript):
+        """sumcheck_wiring with derived challenges -> (evals [mu,4,4], last [7,4], chal [mu,4])"""
+        mu = max(N.bit_length() - 1, 0)
+        gamma = np.ascontiguousarray(gamma, dtype=np.uint64).reshape(4)
+        out, last, chal = np.zeros((mu, 4, 4), dtype=np.uint64), np.zeros((7, 4), dtype=np.uint64), np.zeros((mu, 4), dtype=np.uint64)
+        self._check(self.lib.zk_sumcheck_wiring_fs(self.h, _ptr(eq), _ptr(tree), _ptr(num), _ptr(den), N, _h(gamma), self._tr(transcript), _h(out), _h(last), _h(chal)))
+        return out, last, chal
+
+    def sumcheck_multi_fs(self, es, fs, length: int, transcript):
+        """sumcheck_multi with derived challenges -> (triples [n,3,4], last_e [count,4], last_f [count,4], chal [n,4])"""
+        if len(es) != len(fs):
+            raise ValueError(f"{len(es)} eq tables, {len(fs)} tables")
+        n = max(length.bit_length() - 1, 0)
+        out, chal = np.zeros((n, 3, 4), dtype=np.uint64), np.zeros((n, 4), dtype=np.uint64)
+        le, lf = np.zeros((len(es), 4), dtype=np.uint64), np.zeros((len(es), 4), dtype=np.uint64)
+        self._check(self.lib.zk_sumcheck_multi_fs(self.h, len(es), self._ptr_array(es), self._ptr_array(fs), length, self._tr(transcript), _h(out), _h(le), _h(lf),
+                                                  _h(chal)))
+        return out, le, lf, chal
+
     def open_rounds(self, tab, length: int, point: np.ndarray, q_out=None):
         """-> (q device buffer with length-1 Fr, value [4])"""
         point = np.ascontiguousarray(point, dtype=np.uint64).reshape(-1, 4)

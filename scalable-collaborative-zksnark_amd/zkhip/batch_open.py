@@ -13,7 +13,8 @@ The verifier: (1) the chain from S, (2) C_g = sum_j e_j C_j (zk_g1_lincomb) with
 (3) one zk_pcs_verify_batch call with the single opening (C_g, y, proof, rho).
 
 Proof record: {"rounds": [n, 3, 4], "opening": [n, 18]}.  The claimed values v_k belong to the statement, beside the commitments.
-alpha and rho are INPUTS, as everywhere in this code base: no Fiat-Shamir.  Single party only.  Index bit 0 is the TOP bit, round 0
+alpha and rho are INPUTS of the functions here; zkhip.nizk derives them from a Fiat-Shamir transcript (zk_sumcheck_multi_fs draws rho
+on the device).  Single party only.  Index bit 0 is the TOP bit, round 0
 binds it, rho is the opening point as it stands.  One instance per table size.
 """
 from __future__ import annotations

@@ -19,9 +19,9 @@ The SRS has mu + 1 variables (the tree's); level k of PolynomialCommitmentCub.ne
 mu-variate table verifies against [g2, s_1 g2, .., s_mu g2] = [pg2[0]] + pg2[2:], not against the full powers_of_g2: the verifier
 holds two verifying keys (`verifying_keys`) and makes two zk_pcs_verify_batch calls, 3 openings at mu variables and 5 at mu + 1.
 
-alpha, beta, gamma, tau and the challenges are INPUTS, as everywhere in this code base (the reference pre-samples every challenge,
-dhyperplonk.rs:103-109): deriving them from the transcript (Fiat-Shamir) is out of scope, and so is soundness against a prover
-who picks its tables after seeing them.  Single party only: the distributed and packed-share forms are not defined.
+alpha, beta, gamma, tau and the challenges are INPUTS of the functions here (the reference pre-samples every challenge,
+dhyperplonk.rs:103-109).  The non-interactive form, with every challenge derived from a Fiat-Shamir transcript that lives on the
+device, is zkhip.nizk.wiring_prove_ni / wiring_verify_ni.  Single party only: the distributed and packed-share forms are not defined.
 """
 from __future__ import annotations
 

@@ -9,9 +9,9 @@ vector (hyperplonk/src/hyperplonk.rs:66-93, dhyperplonk.rs:218-260).  Here it is
 proved by one degree-4 sumcheck (zk_eq_table, zk_sumcheck_gate), closed by openings of a, b, c, in, q1, q2 at the sumcheck
 point through the existing commit / open path, and verified with one batched pairing check (zk_pcs_verify_batch).
 
-`tau` and the challenges are INPUTS, as everywhere in this code base (the reference pre-samples every challenge,
-dhyperplonk.rs:103-109): deriving them from the transcript (Fiat-Shamir) is out of scope, and so is soundness against a prover
-who picks its tables after seeing them.  Single party only: the distributed and packed-share forms are not defined.
+`tau` and the challenges are INPUTS of the functions here (the reference pre-samples every challenge, dhyperplonk.rs:103-109).
+The non-interactive form, with every challenge derived from a Fiat-Shamir transcript that lives on the device, is
+zkhip.nizk.gate_prove_ni / gate_verify_ni.  Single party only: the distributed and packed-share forms are not defined.
 """
 from __future__ import annotations
 
