@@ -163,6 +163,27 @@ int zk_sumcheck_gate(zk_ctx *ctx, const void *d_eq, const void *d_q1, const void
 int zk_sumcheck_wiring(zk_ctx *ctx, const void *d_eq, const void *d_tree, const void *d_num, const void *d_den,
                        size_t N, const uint64_t h_gamma[4], const uint64_t *h_chal, uint64_t *h_out_evals,
                        uint64_t *h_last);
+/* ---- the wiring identity over the THREE wire columns of a Plonk gate (a, b, c = columns j = 0, 1, 2 of N = 2^mu rows) ----
+ * Slot j N + x is wire j of row x; sigma permutes the 3N slots and ssigma_j(x) = sigma(j N + x) as a field element.
+ *     n_j(x) = w_j(x) + alpha (j N + x) + beta,   d_j(x) = w_j(x) + alpha ssigma_j(x) + beta
+ * zk_perm3_terms writes the six linear tables, P = n_0 n_1 n_2 and Q = d_0 d_1 d_2 in ONE pass (N Fr each; the slot number is formed in
+ * the kernel: no table of slot numbers exists).  h = zk_fr_batch_div(P, Q) (a zero denominator: ZK_ERR_DIV_ZERO there), and
+ * v = zk_product_tree(h).  The inputs are not modified; an output may not alias an input.  ASYNCHRONOUS on the ctx stream like the
+ * element-wise calls.  N < 2, not a power of two or > 2^35, or a null pointer: ZK_ERR_INVALID, nothing is launched. */
+int zk_perm3_terms(zk_ctx *ctx, const void *const d_w[3], const void *const d_ssigma[3], size_t N,
+                   const uint64_t h_alpha[4], const uint64_t h_beta[4], void *const d_num[3], void *const d_den[3],
+                   void *d_P, void *d_Q);
+/* The prover's rounds for
+ *     F(x) = eq(x) [ v(1,x) - v(x,0) v(x,1) + gamma ( h(x) d_0(x) d_1(x) d_2(x) - n_0(x) n_1(x) n_2(x) ) ]
+ * with v = d_tree the 2N Fr of zk_product_tree(h) and its four views read in place as in zk_sumcheck_wiring.  d_eq, d_num[j], d_den[j]:
+ * N Fr each; none is modified.  Round i writes six Fr to h_out_evals: the round polynomial (degree 5) at t = 0 .. 5, every table
+ * extended as (1 - t) lo + t hi, then folds the eleven tables with h_chal[i].  h_out_evals: 6 mu Fr; h_last: the eleven remaining
+ * elements in the order eq, v1x, vx0, vx1, h, n_0, n_1, n_2, d_0, d_1, d_2, 11 Fr.  Blocking: the results are on the host when it
+ * returns.  N < 2, not a power of two or > 2^35, a null pointer, or the knob perm3_local_e not a power of two in [1, 256]:
+ * ZK_ERR_INVALID; nothing is launched or written on error. */
+int zk_sumcheck_perm3(zk_ctx *ctx, const void *d_eq, const void *d_tree, const void *const d_num[3],
+                      const void *const d_den[3], size_t N, const uint64_t h_gamma[4], const uint64_t *h_chal,
+                      uint64_t *h_out_evals, uint64_t *h_last);
 /* ---- batch opening: K claims f_{j_k}(z_k) = v_k on J tables of one size -> one degree-2 sumcheck and one opening ---- */
 /* d_acc[x] += weight * eq(point, x) over the cube of n variables (x_0 the TOP index bit), d_acc: 2^n Fr, read and written.  The
  * doubling scheme of zk_eq_table seeded with the weight; the last level is added into d_acc instead of stored, so a claim costs
@@ -201,8 +222,8 @@ int zk_transcript_absorb_device(zk_ctx *ctx, zk_transcript *t, const void *d_ptr
 /* count successive challenges; h_out: count Fr in Montgomery form */
 int zk_transcript_challenges(zk_ctx *ctx, zk_transcript *t, size_t count, uint64_t *h_out);
 int zk_transcript_state(zk_ctx *ctx, zk_transcript *t, uint8_t h_state32[32]);
-/* zk_sumcheck_gate / zk_sumcheck_wiring / zk_sumcheck_multi with every challenge DERIVED: round i's evaluations are absorbed as they
- * appear in the output (5, 4 or 3 Fr) and one challenge is drawn, on the device, between the kernels of ONE enqueue -- no host read and
+/* zk_sumcheck_gate / zk_sumcheck_wiring / zk_sumcheck_perm3 / zk_sumcheck_multi with every challenge DERIVED: round i's evaluations are
+ * absorbed as they appear in the output (5, 4, 6 or 3 Fr) and one challenge is drawn, on the device, between the kernels of ONE enqueue -- no host read and
  * one stream synchronisation per call.  h_chal_out: the n challenges that were used (Montgomery Fr); every other argument, the
  * outputs, the limits and the error cases are those of the parent, and for the challenges in h_chal_out the parent returns the same
  * bits.  The transcript has absorbed all n rounds when the call returns.  A null transcript or one of another ctx: ZK_ERR_INVALID. */
@@ -212,6 +233,9 @@ int zk_sumcheck_gate_fs(zk_ctx *ctx, const void *d_eq, const void *d_q1, const v
 int zk_sumcheck_wiring_fs(zk_ctx *ctx, const void *d_eq, const void *d_tree, const void *d_num, const void *d_den,
                           size_t N, const uint64_t h_gamma[4], zk_transcript *t, uint64_t *h_out_evals,
                           uint64_t *h_last, uint64_t *h_chal_out);
+int zk_sumcheck_perm3_fs(zk_ctx *ctx, const void *d_eq, const void *d_tree, const void *const d_num[3],
+                         const void *const d_den[3], size_t N, const uint64_t h_gamma[4], zk_transcript *t,
+                         uint64_t *h_out_evals, uint64_t *h_last, uint64_t *h_chal_out);
 int zk_sumcheck_multi_fs(zk_ctx *ctx, size_t count, const void *const *d_e, const void *const *d_f, size_t len,
                          zk_transcript *t, uint64_t *h_out_triples, uint64_t *h_last_e, uint64_t *h_last_f,
                          uint64_t *h_chal_out);

@@ -73,7 +73,8 @@ struct zk_ctx {
     bool gate_lds_raised = false;  // zk_gate.hip: k_gate_local's dynamic LDS limit has been raised on this ctx's device
     bool wiring_lds_raised = false;  // zk_wiring.hip: the same for k_wiring_local
     bool multi_lds_raised = false;   // zk_batchopen.hip: the same for k_multi_local
-    bool fs_lds_raised[3] = {false, false, false};  // zk_fs.hip: the same for its three local kernels (gate, wiring, multi)
+    bool fs_lds_raised[4] = {false, false, false, false};  // zk_fs.hip: the same for its four local kernels (gate, wiring, multi, perm3)
+    bool perm3_lds_raised = false;   // zk_perm3.hip: the same for k_perm3_local
     // party exchanges (zk_comm.cpp): an RCCL communicator bound to this ctx's GPU
     void* comm = nullptr;
     int comm_rank = 0, comm_world = 1;
@@ -124,6 +125,8 @@ struct Tuning {
     // batch-opening sumcheck (zk_batchopen.hip)
     long multi_local_e = 512;   // longest table (elements, a power of two <= 512) the single-workgroup LDS stage takes over when the 2 count tables fit; 1: HBM passes down to the last element
     long multi_pass_wg = 0;     // workgroups per CU of the HBM passes (0: 4)
+    // three-column wiring sumcheck (zk_perm3.hip)
+    long perm3_local_e = 256;   // longest table (elements, a power of two <= 256: eleven tables of 512 would be 176 KiB of LDS) the single-workgroup LDS stage takes over; 1: HBM passes down to the last element
     // MSM (zk_msm.hip)
     long msm_table_dc = 0;    // window-table width delta (sweeps)
     long msm_qstep = 2;       // window-class quantisation step of batches
@@ -198,6 +201,14 @@ int sumcheck_gate(zk_ctx* ctx, const void* const* d_tabs, size_t len, const uint
 int sumcheck_wiring(zk_ctx* ctx, const void* d_eq, const void* d_tree, const void* d_num, const void* d_den, size_t N, const uint64_t* h_gamma,
                     const uint64_t* h_chal, uint64_t* h_out_evals, uint64_t* h_last);
 
+// ---- zk_perm3.hip ----
+// d_w, d_ssigma, d_num, d_den: three tables of N Fr each; d_P = n_0 n_1 n_2, d_Q = d_0 d_1 d_2
+int perm3_terms(zk_ctx* ctx, const void* const* d_w, const void* const* d_ssigma, size_t N, const uint64_t* h_alpha, const uint64_t* h_beta, void* const* d_num,
+                void* const* d_den, void* d_P, void* d_Q);
+// h_out_evals: mu x 6 Fr; h_last: eq, v1x, vx0, vx1, h, n_0, n_1, n_2, d_0, d_1, d_2
+int sumcheck_perm3(zk_ctx* ctx, const void* d_eq, const void* d_tree, const void* const* d_num, const void* const* d_den, size_t N, const uint64_t* h_gamma,
+                   const uint64_t* h_chal, uint64_t* h_out_evals, uint64_t* h_last);
+
 // ---- zk_batchopen.hip ----
 int eq_table_acc(zk_ctx* ctx, const uint64_t* h_point, size_t n, const uint64_t* h_weight, void* d_acc);
 int fr_lincomb(zk_ctx* ctx, size_t count, const void* const* d_tabs, const uint64_t* h_coeffs, size_t len, void* d_out);
@@ -219,6 +230,8 @@ int sumcheck_wiring_fs(zk_ctx* ctx, const void* d_eq, const void* d_tree, const 
                        zk_transcript* t, uint64_t* h_out_evals, uint64_t* h_last, uint64_t* h_chal_out);
 int sumcheck_multi_fs(zk_ctx* ctx, size_t count, const void* const* d_e, const void* const* d_f, size_t len, zk_transcript* t,
                       uint64_t* h_out_triples, uint64_t* h_last_e, uint64_t* h_last_f, uint64_t* h_chal_out);
+int sumcheck_perm3_fs(zk_ctx* ctx, const void* d_eq, const void* d_tree, const void* const* d_num, const void* const* d_den, size_t N, const uint64_t* h_gamma,
+                      zk_transcript* t, uint64_t* h_out_evals, uint64_t* h_last, uint64_t* h_chal_out);
 
 // ---- zk_msm.hip ----
 struct MsmItem {

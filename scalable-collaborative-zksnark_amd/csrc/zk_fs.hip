@@ -1,4 +1,4 @@
-// zk_fs.hip -- the three fused sumchecks (zk_gate.hip, zk_wiring.hip, zk_batchopen.hip) with their challenges drawn from a
+// zk_fs.hip -- the four fused sumchecks (zk_gate.hip, zk_wiring.hip, zk_perm3.hip, zk_batchopen.hip) with their challenges drawn from a
 // Fiat-Shamir transcript ON THE DEVICE (zk_transcript.hip, sha256.cuh): challenge r_p is a hash of round p's evaluations, so the
 // fold by r_p cannot share a sweep with round p's sums as it does in the preset-challenge kernels.  The shape here:
 //   pass 0            evaluate only: the sums of round 0 over the caller's tables (nothing is written but the partials),
@@ -21,36 +21,42 @@
 
 namespace zk {
 
-static constexpr int kFsTabs = 7;  // both seven-table identities
-
-// Table k, element i, is the Fr at t[k] + 32 (i << sh[k]) (the views of the product tree, zk_wiring.hip's WireIn)
-struct FsIn {
-    const void* t[kFsTabs];
-    unsigned sh[kFsTabs];
-};
-struct FsOut {
-    void* t[kFsTabs];
-};
-
+// An identity eq(x) [ inner(tables 1 .. kTabs - 1) ]: its table count, the evaluations of a round (degree + 1), the longest table of
+// the local stage (kTabs tables of kLocalMax elements fit the CU's LDS), its slot of zk_ctx::fs_lds_raised, the waves per SIMD its pass is
+// compiled for, and the bracket.
 struct GateKind {  // eq, q1, q2, a, b, c, in
+    static constexpr int kTabs = 7;
     static constexpr int kEvals = 5;
     static constexpr int kSlot = 0;
-    __device__ static __forceinline__ Fr inner(const Fr&, const Fr (&v)[kFsTabs]) { return gate_inner(v[1], v[2], v[3], v[4], v[5], v[6]); }
+    static constexpr unsigned kLocalMax = kGateLocalMax;
+    static constexpr int kWaves = 2;
+    __device__ static __forceinline__ Fr inner(const Fr&, const Fr (&v)[kTabs]) { return gate_inner(v[1], v[2], v[3], v[4], v[5], v[6]); }
 };
 struct WireKind {  // eq, v1x, vx0, vx1, h, num, den
+    static constexpr int kTabs = 7;
     static constexpr int kEvals = 4;
     static constexpr int kSlot = 1;
-    __device__ static __forceinline__ Fr inner(const Fr& gamma, const Fr (&v)[kFsTabs]) { return wiring_inner(gamma, v[1], v[2], v[3], v[4], v[5], v[6]); }
+    static constexpr unsigned kLocalMax = kGateLocalMax;
+    static constexpr int kWaves = 2;
+    __device__ static __forceinline__ Fr inner(const Fr& gamma, const Fr (&v)[kTabs]) { return wiring_inner(gamma, v[1], v[2], v[3], v[4], v[5], v[6]); }
+};
+struct Perm3Kind {  // eq, v1x, vx0, vx1, h, n_0, n_1, n_2, d_0, d_1, d_2
+    static constexpr int kTabs = kPerm3Tabs;
+    static constexpr int kEvals = kPerm3Evals;
+    static constexpr int kSlot = 3;
+    static constexpr unsigned kLocalMax = kPerm3LocalMax;
+    static constexpr int kWaves = 1;  // 22 table registers of 8 limbs and six 17-limb sums: the 264 .. 512 register bracket
+    __device__ static __forceinline__ Fr inner(const Fr& gamma, const Fr (&v)[kTabs]) { return perm3_inner(gamma, v); }
 };
 
 // ---------------------------------------------------------------------------------------
-// One round of a seven-table identity over HBM.  FOLD: the tables at `in` have 4 * half elements and are folded with *d_chal
+// One round of an identity of K::kTabs tables over HBM.  FOLD: the tables at `in` have 4 * half elements and are folded with *d_chal
 // into `out` (2 * half elements each) first; otherwise they have 2 * half elements and nothing is stored.
 // partials: [t * nbw + 4 block + wave], 80-byte slots, as k_gate_pass.
 // ---------------------------------------------------------------------------------------
 template <class K, bool FOLD>
-__global__ void __launch_bounds__(kGateBlock) __attribute__((amdgpu_waves_per_eu(1, 2)))
-k_fs_pass(FsIn in, FsOut out, size_t half, const void* __restrict__ d_chal, GateChal gamma, void* __restrict__ partials) {
+__global__ void __launch_bounds__(kGateBlock) __attribute__((amdgpu_waves_per_eu(1, K::kWaves)))
+k_fs_pass(FsIn<K::kTabs> in, FsOut<K::kTabs> out, size_t half, const void* __restrict__ d_chal, GateChal gamma, void* __restrict__ partials) {
     u32 w[K::kEvals][17];
 #pragma unroll
     for (int t = 0; t < K::kEvals; t++)
@@ -59,9 +65,9 @@ k_fs_pass(FsIn in, FsOut out, size_t half, const void* __restrict__ d_chal, Gate
     Fr r = fp_zero<FrCfg>();
     if (FOLD) r = fr_load(d_chal, 0);
     for (size_t j = (size_t)blockIdx.x * kGateBlock + threadIdx.x; j < half; j += (size_t)gridDim.x * kGateBlock) {
-        Fr v[kFsTabs], d[kFsTabs];
+        Fr v[K::kTabs], d[K::kTabs];
 #pragma unroll
-        for (int k = 0; k < kFsTabs; k++) {
+        for (int k = 0; k < K::kTabs; k++) {
             const unsigned sh = in.sh[k];
             if (FOLD) {
                 const Fr a0 = fr_load(in.t[k], j << sh), a1 = fr_load(in.t[k], (j + half) << sh);
@@ -81,7 +87,7 @@ k_fs_pass(FsIn in, FsOut out, size_t half, const void* __restrict__ d_chal, Gate
             fp_mac_wide(w[t], v[0], K::inner(gamma.r, v));
             if (t + 1 < K::kEvals) {
 #pragma unroll
-                for (int k = 0; k < kFsTabs; k++) v[k] = fr_add(v[k], d[k]);
+                for (int k = 0; k < K::kTabs; k++) v[k] = fr_add(v[k], d[k]);
             }
         }
     }
@@ -124,30 +130,30 @@ __global__ void __launch_bounds__(kGateBlock) k_fs_reduce_hash(const void* __res
 }
 
 // ---------------------------------------------------------------------------------------
-// Local stage of a seven-table identity: tables of E <= 512 elements in LDS.  d_pending (or null): the challenge of the last HBM
+// Local stage of an identity of K::kTabs tables: tables of E <= K::kLocalMax elements in LDS.  d_pending (or null): the challenge of the last HBM
 // pass -- the tables at `in` then have 2 E elements and are folded while they are loaded.  Per round: the sums (wave shuffle, one
 // LDS slot per wave), barrier, lane 0 finishes them, hashes and leaves the challenge in LDS, barrier, the fold in place (a lane
 // reads elements j and j + h of each table and writes j), barrier.
 // ---------------------------------------------------------------------------------------
 template <class K>
-__global__ void __launch_bounds__(kGateBlock) k_fs_local(FsIn in, unsigned E, int rounds, const void* __restrict__ d_pending, GateChal gamma, u32* __restrict__ state,
+__global__ void __launch_bounds__(kGateBlock) k_fs_local(FsIn<K::kTabs> in, unsigned E, int rounds, const void* __restrict__ d_pending, GateChal gamma, u32* __restrict__ state,
                                                         void* __restrict__ evals, void* __restrict__ h_chal, void* __restrict__ last) {
     extern __shared__ uint4 flds[];
-    uint4* red = flds + 2 * (size_t)kFsTabs * E;              // [wave][t] Fr
+    uint4* red = flds + 2 * (size_t)K::kTabs * E;              // [wave][t] Fr
     uint4* cs = red + 2 * (size_t)(kGateBlock / 64) * K::kEvals;  // the round's challenge
     const unsigned tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     if (d_pending) {
         const Fr r = fr_load(d_pending, 0);
         for (unsigned i = tid; i < E; i += kGateBlock)
 #pragma unroll
-            for (int k = 0; k < kFsTabs; k++) {
+            for (int k = 0; k < K::kTabs; k++) {
                 const Fr lo = fr_load(in.t[k], (size_t)i << in.sh[k]), hi = fr_load(in.t[k], (size_t)(i + E) << in.sh[k]);
                 fr_store(flds, (size_t)k * E + i, fr_add(lo, fr_mul(r, fr_sub(hi, lo))));
             }
     } else {
         for (unsigned i = tid; i < E; i += kGateBlock)
 #pragma unroll
-            for (int k = 0; k < kFsTabs; k++) fr_store(flds, (size_t)k * E + i, fr_load(in.t[k], (size_t)i << in.sh[k]));
+            for (int k = 0; k < K::kTabs; k++) fr_store(flds, (size_t)k * E + i, fr_load(in.t[k], (size_t)i << in.sh[k]));
     }
     __syncthreads();
     u32 st[8];
@@ -159,9 +165,9 @@ __global__ void __launch_bounds__(kGateBlock) k_fs_local(FsIn in, unsigned E, in
 #pragma unroll
         for (int t = 0; t < K::kEvals; t++) acc[t] = fp_zero<FrCfg>();
         for (unsigned j = tid; j < h; j += kGateBlock) {
-            Fr v[kFsTabs], d[kFsTabs];
+            Fr v[K::kTabs], d[K::kTabs];
 #pragma unroll
-            for (int k = 0; k < kFsTabs; k++) {
+            for (int k = 0; k < K::kTabs; k++) {
                 v[k] = fr_load(flds, (size_t)k * E + j);
                 d[k] = fr_sub(fr_load(flds, (size_t)k * E + j + h), v[k]);
             }
@@ -170,7 +176,7 @@ __global__ void __launch_bounds__(kGateBlock) k_fs_local(FsIn in, unsigned E, in
                 acc[t] = fr_add(acc[t], fr_mul(v[0], K::inner(gamma.r, v)));
                 if (t + 1 < K::kEvals) {
 #pragma unroll
-                    for (int k = 0; k < kFsTabs; k++) v[k] = fr_add(v[k], d[k]);
+                    for (int k = 0; k < K::kTabs; k++) v[k] = fr_add(v[k], d[k]);
                 }
             }
         }
@@ -202,7 +208,7 @@ __global__ void __launch_bounds__(kGateBlock) k_fs_local(FsIn in, unsigned E, in
         const Fr r = fr_load(cs, 0);
         for (unsigned j = tid; j < h; j += kGateBlock)
 #pragma unroll
-            for (int k = 0; k < kFsTabs; k++) {
+            for (int k = 0; k < K::kTabs; k++) {
                 const Fr lo = fr_load(flds, (size_t)k * E + j), hi = fr_load(flds, (size_t)k * E + j + h);
                 fr_store(flds, (size_t)k * E + j, fr_add(lo, fr_mul(r, fr_sub(hi, lo))));
             }
@@ -210,7 +216,7 @@ __global__ void __launch_bounds__(kGateBlock) k_fs_local(FsIn in, unsigned E, in
         L = h;
     }
     if (tid == 0 && rounds > 0) fs_state_store(state, st);
-    if (tid < kFsTabs) fr_store(last, tid, fr_load(flds, (size_t)tid * E));
+    if (tid < K::kTabs) fr_store(last, tid, fr_load(flds, (size_t)tid * E));
 }
 
 // ---------------------------------------------------------------------------------------
@@ -395,36 +401,36 @@ static int fs_plan(zk_ctx* ctx, const char* who, const zk_transcript* t, size_t 
     return ZK_OK;
 }
 
-static int local_e(zk_ctx* ctx, long knob, const char* name, size_t& emax) {
+static int local_e(zk_ctx* ctx, long knob, const char* name, size_t& emax, unsigned local_max = kGateLocalMax) {
     emax = (size_t)knob;
-    if (emax < 1 || emax > kGateLocalMax || (emax & (emax - 1))) return fail(ctx, ZK_ERR_INVALID, "%s must be a power of two in [1, %u]", name, kGateLocalMax);
+    if (emax < 1 || emax > local_max || (emax & (emax - 1))) return fail(ctx, ZK_ERR_INVALID, "%s must be a power of two in [1, %u]", name, local_max);
     return ZK_OK;
 }
 
 template <class K>
-static int run7_fs(zk_ctx* ctx, const char* who, const FsIn& first, size_t len, size_t emax, size_t per_cu, const GateChal& gamma, zk_transcript* t,
+static int run_fs(zk_ctx* ctx, const char* who, const FsIn<K::kTabs>& first, size_t len, size_t emax, size_t per_cu, const GateChal& gamma, zk_transcript* t,
                    uint64_t* h_out_evals, uint64_t* h_last, uint64_t* h_chal_out) {
     FsPlan pl;
-    const int rc = fs_plan(ctx, who, t, len, kGateMaxLog, emax, per_cu, K::kEvals, kFsTabs, pl);
+    const int rc = fs_plan(ctx, who, t, len, kGateMaxLog, emax, per_cu, K::kEvals, K::kTabs, pl);
     if (rc) return rc;
     const size_t fr = 32, rounds = pl.rounds, npass = pl.npass;
-    char* res = (char*)pinned(ctx, (rounds * K::kEvals + kFsTabs + rounds) * fr);  // evaluations | last | challenges, written by the kernels
+    char* res = (char*)pinned(ctx, (rounds * K::kEvals + K::kTabs + rounds) * fr);  // evaluations | last | challenges, written by the kernels
     if (!res) return ZK_ERR_OOM;
     char* res_last = res + rounds * K::kEvals * fr;
-    char* res_chal = res_last + kFsTabs * fr;
-    FsIn cur = first;
+    char* res_chal = res_last + K::kTabs * fr;
+    FsIn<K::kTabs> cur = first;
     for (size_t p = 0; p < npass; p++) {
         const size_t half = len >> (p + 1);
         if (p == 0) {
-            hipLaunchKernelGGL((k_fs_pass<K, false>), dim3((unsigned)pl.blocks[p]), dim3(kGateBlock), 0, ctx->stream, cur, FsOut{}, half, (const void*)nullptr, gamma,
+            hipLaunchKernelGGL((k_fs_pass<K, false>), dim3((unsigned)pl.blocks[p]), dim3(kGateBlock), 0, ctx->stream, cur, FsOut<K::kTabs>{}, half, (const void*)nullptr, gamma,
                                (void*)pl.part);
         } else {
-            FsOut o;
+            FsOut<K::kTabs> o;
             const size_t stride = ((p - 1) & 1) ? len / 4 : len / 2;
-            for (int k = 0; k < kFsTabs; k++) o.t[k] = pl.buf[(p - 1) & 1] + (size_t)k * stride * fr;
+            for (int k = 0; k < K::kTabs; k++) o.t[k] = pl.buf[(p - 1) & 1] + (size_t)k * stride * fr;
             hipLaunchKernelGGL((k_fs_pass<K, true>), dim3((unsigned)pl.blocks[p]), dim3(kGateBlock), 0, ctx->stream, cur, o, half, (const void*)(pl.chal + (p - 1) * fr),
                                gamma, (void*)pl.part);
-            for (int k = 0; k < kFsTabs; k++) cur.t[k] = o.t[k], cur.sh[k] = 0;
+            for (int k = 0; k < K::kTabs; k++) cur.t[k] = o.t[k], cur.sh[k] = 0;
         }
         ZK_HIP(ctx, hipGetLastError());
         hipLaunchKernelGGL(k_fs_reduce_hash<K::kEvals>, dim3(1), dim3(kGateBlock), 0, ctx->stream, (const void*)pl.part, (unsigned)(pl.blocks[p] * (kGateBlock / 64)),
@@ -433,7 +439,7 @@ static int run7_fs(zk_ctx* ctx, const char* who, const FsIn& first, size_t len, 
     }
     {
         const size_t E = len >> npass;
-        const size_t lds = (2 * (size_t)kFsTabs * E + 2 * (kGateBlock / 64) * K::kEvals + 2) * sizeof(uint4);
+        const size_t lds = (2 * (size_t)K::kTabs * E + 2 * (kGateBlock / 64) * K::kEvals + 2) * sizeof(uint4);
         if (lds > 64 * 1024 && !ctx->fs_lds_raised[K::kSlot]) {  // once per ctx (= per device)
             ZK_HIP(ctx, hipFuncSetAttribute((const void*)k_fs_local<K>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
             ctx->fs_lds_raised[K::kSlot] = true;
@@ -445,7 +451,7 @@ static int run7_fs(zk_ctx* ctx, const char* who, const FsIn& first, size_t len, 
     }
     ZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     std::memcpy(h_out_evals, res, rounds * K::kEvals * fr);
-    std::memcpy(h_last, res_last, kFsTabs * fr);
+    std::memcpy(h_last, res_last, K::kTabs * fr);
     std::memcpy(h_chal_out, res_chal, rounds * fr);
     return ZK_OK;
 }
@@ -454,11 +460,11 @@ int sumcheck_gate_fs(zk_ctx* ctx, const void* const* d_tabs, size_t len, zk_tran
     size_t emax;
     const int rc = local_e(ctx, tuning().gate_local_e, "gate_local_e", emax);
     if (rc) return rc;
-    FsIn first;
-    for (int k = 0; k < kFsTabs; k++) first.t[k] = d_tabs[k], first.sh[k] = 0;
+    FsIn<GateKind::kTabs> first;
+    for (int k = 0; k < GateKind::kTabs; k++) first.t[k] = d_tabs[k], first.sh[k] = 0;
     GateChal none;
     std::memset(&none, 0, sizeof(none));
-    return run7_fs<GateKind>(ctx, "zk_sumcheck_gate_fs", first, len, emax, tuning().gate_pass_wg > 0 ? (size_t)tuning().gate_pass_wg : 2, none, t, h_out_evals, h_last,
+    return run_fs<GateKind>(ctx, "zk_sumcheck_gate_fs", first, len, emax, tuning().gate_pass_wg > 0 ? (size_t)tuning().gate_pass_wg : 2, none, t, h_out_evals, h_last,
                              h_chal_out);
 }
 
@@ -469,10 +475,24 @@ int sumcheck_wiring_fs(zk_ctx* ctx, const void* d_eq, const void* d_tree, const 
     if (rc) return rc;
     // the views of the tree: v1x its upper half, (vx0, vx1) every other element from its base / one element on, h its lower half
     const char* tree = (const char*)d_tree;
-    const FsIn first = {{d_eq, tree + N * 32, tree, tree + 32, tree, d_num, d_den}, {0, 0, 1, 1, 0, 0, 0}};
+    const FsIn<WireKind::kTabs> first = {{d_eq, tree + N * 32, tree, tree + 32, tree, d_num, d_den}, {0, 0, 1, 1, 0, 0, 0}};
     GateChal gamma;
     std::memcpy(&gamma.r, h_gamma, 32);
-    return run7_fs<WireKind>(ctx, "zk_sumcheck_wiring_fs", first, N, emax, tuning().wiring_pass_wg > 0 ? (size_t)tuning().wiring_pass_wg : 2, gamma, t, h_out_evals,
+    return run_fs<WireKind>(ctx, "zk_sumcheck_wiring_fs", first, N, emax, tuning().wiring_pass_wg > 0 ? (size_t)tuning().wiring_pass_wg : 2, gamma, t, h_out_evals,
+                             h_last, h_chal_out);
+}
+
+int sumcheck_perm3_fs(zk_ctx* ctx, const void* d_eq, const void* d_tree, const void* const* d_num, const void* const* d_den, size_t N, const uint64_t* h_gamma,
+                      zk_transcript* t, uint64_t* h_out_evals, uint64_t* h_last, uint64_t* h_chal_out) {
+    size_t emax;
+    const int rc = local_e(ctx, tuning().perm3_local_e, "perm3_local_e", emax, kPerm3LocalMax);
+    if (rc) return rc;
+    const char* tree = (const char*)d_tree;
+    const FsIn<kPerm3Tabs> first = {{d_eq, tree + N * 32, tree, tree + 32, tree, d_num[0], d_num[1], d_num[2], d_den[0], d_den[1], d_den[2]},
+                                    {0, 0, 1, 1, 0, 0, 0, 0, 0, 0, 0}};
+    GateChal gamma;
+    std::memcpy(&gamma.r, h_gamma, 32);
+    return run_fs<Perm3Kind>(ctx, "zk_sumcheck_perm3_fs", first, N, emax, 1, gamma, t, h_out_evals,
                              h_last, h_chal_out);
 }
 

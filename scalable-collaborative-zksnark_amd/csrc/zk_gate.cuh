@@ -1,4 +1,4 @@
-// zk_gate.cuh -- what the fused sumchecks (zk_gate.hip: gate identity, zk_wiring.hip: wiring identity, zk_batchopen.hip, zk_fs.hip) share: launch geometry, the
+// zk_gate.cuh -- what the fused sumchecks (zk_gate.hip: gate identity, zk_wiring.hip: wiring identity, zk_batchopen.hip, zk_perm3.hip, zk_fs.hip) share: launch geometry, the
 // argument blocks of their kernels and the 544-bit lazily reduced sums (one 80-byte slot per wave, evaluation and pass).
 #pragma once
 #include "fp.cuh"
@@ -21,6 +21,18 @@ struct GateTail {
 struct GateReducePlan {
     unsigned nbw[kGateMaxPasses];   // 544-bit partials per sum of pass p (one per wave)
     unsigned off[kGateMaxPasses];   // first slot of pass p in the partials block
+};
+
+// The table set of a fused identity of NT tables (zk_perm3.hip, zk_fs.hip): table k, element i, is the Fr at t[k] + 32 (i << sh[k]) --
+// sh = 1 reads every other element of the product tree (its views v(x,0) and v(x,1)), sh = 0 an ordinary table.
+template <int NT>
+struct FsIn {
+    const void* t[NT];
+    unsigned sh[NT];
+};
+template <int NT>
+struct FsOut {
+    void* t[NT];
 };
 
 // the batch-opening sumcheck (zk_batchopen.hip, its transcript-driven form in zk_fs.hip)
@@ -75,6 +87,19 @@ __device__ __forceinline__ Fr wiring_inner(const Fr& gamma, const Fr& v1x, const
     const Fr p = fr_mul(vx0, vx1);
     const Fr q = fr_mul(gamma, fr_sub(fr_mul(den, h), num));
     return fr_add(fr_sub(v1x, p), q);
+}
+
+// the three-column wiring identity (zk_perm3.hip, its transcript-driven form in zk_fs.hip): eq, v1x, vx0, vx1, h, n_0..2, d_0..2
+static constexpr int kPerm3Tabs = 11;
+static constexpr int kPerm3Evals = 6;             // t = 0 .. 5
+static constexpr unsigned kPerm3LocalMax = 256;  // 11 x 256 x 32 B = 88 KiB of the CU's 160 KiB (512 elements would be 176 KiB)
+
+// [ v1x - vx0 vx1 + gamma ( h d_0 d_1 d_2 - n_0 n_1 n_2 ) ] of one point, v in the table order above: seven multiplications
+__device__ __forceinline__ Fr perm3_inner(const Fr& gamma, const Fr (&v)[kPerm3Tabs]) {
+    const Fr p = fr_mul(v[2], v[3]);
+    const Fr dd = fr_mul(fr_mul(fr_mul(v[8], v[9]), v[10]), v[4]);
+    const Fr nn = fr_mul(fr_mul(v[5], v[6]), v[7]);
+    return fr_add(fr_sub(v[1], p), fr_mul(gamma, fr_sub(dd, nn)));
 }
 
 // One workgroup of kGateBlock lanes adds the nbw per-wave partials from slot `base` on and reduces W0 + W1 R + W2 R^2 (a sum of

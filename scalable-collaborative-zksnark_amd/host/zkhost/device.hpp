@@ -260,6 +260,35 @@ class Ctx {
         check(zk_sumcheck_wiring(h_, eq.get(), tree.get(), num.get(), den.get(), N, gamma.v, chal[0].v, r.sums[0].v, last[0].v));
         return r;
     }
+    // zk_perm3_terms: the derived tables of the three-column wiring identity in one pass (asynchronous)
+    struct Perm3Terms {
+        std::array<DevPtr, 3> num, den;
+        DevPtr P, Q;
+    };
+    Perm3Terms perm3_terms(const std::array<DevPtr, 3> &w, const std::array<DevPtr, 3> &ssigma, size_t N, const Fr &alpha, const Fr &beta) {
+        Perm3Terms t;
+        const void *pw[3], *ps[3];
+        void *pn[3], *pd[3];
+        for (int j = 0; j < 3; j++) {
+            t.num[j] = alloc_fr(N), t.den[j] = alloc_fr(N);
+            pw[j] = w[j].get(), ps[j] = ssigma[j].get(), pn[j] = t.num[j].get(), pd[j] = t.den[j].get();
+        }
+        t.P = alloc_fr(N), t.Q = alloc_fr(N);
+        check(zk_perm3_terms(h_, pw, ps, N, alpha.v, beta.v, pn, pd, t.P.get(), t.Q.get()));
+        return t;
+    }
+    // zk_sumcheck_perm3: tree = the 2N Fr of product_tree -> r.sums = 6 Fr per round (t = 0 .. 5), `last` = eq, v1x, vx0, vx1, h, n_0..2, d_0..2
+    ScResult sumcheck_perm3(const DevPtr &eq, const DevPtr &tree, const std::array<DevPtr, 3> &num, const std::array<DevPtr, 3> &den, size_t N, const Fr &gamma,
+                            const FrVec &chal, FrVec &last) {
+        size_t mu = log2_exact(N);
+        need(mu >= 1 && chal.size() >= mu, "sumcheck_perm3: fewer challenges than rounds");
+        ScResult r;
+        r.sums.resize(6 * mu);
+        last.assign(11, Fr::zero());
+        const void *pn[3] = {num[0].get(), num[1].get(), num[2].get()}, *pd[3] = {den[0].get(), den[1].get(), den[2].get()};
+        check(zk_sumcheck_perm3(h_, eq.get(), tree.get(), pn, pd, N, gamma.v, chal[0].v, r.sums[0].v, last[0].v));
+        return r;
+    }
     // zk_eq_table_acc: acc[x] += weight * eq(point, x), acc = 2^n Fr (asynchronous)
     void eq_table_acc(const FrVec &point, const Fr &weight, const DevPtr &acc) {
         check(zk_eq_table_acc(h_, point.empty() ? nullptr : point[0].v, point.size(), weight.v, acc.get()));
@@ -321,6 +350,18 @@ class Ctx {
         last.assign(7, Fr::zero());
         chal.assign(mu, Fr::zero());
         check(zk_sumcheck_wiring_fs(h_, eq.get(), tree.get(), num.get(), den.get(), N, gamma.v, t.h, r.sums[0].v, last[0].v, chal[0].v));
+        return r;
+    }
+    ScResult sumcheck_perm3_fs(const DevPtr &eq, const DevPtr &tree, const std::array<DevPtr, 3> &num, const std::array<DevPtr, 3> &den, size_t N, const Fr &gamma,
+                               DeviceTranscript &t, FrVec &last, FrVec &chal) {
+        size_t mu = log2_exact(N);
+        need(mu >= 1, "sumcheck_perm3_fs: at least one round");
+        ScResult r;
+        r.sums.resize(6 * mu);
+        last.assign(11, Fr::zero());
+        chal.assign(mu, Fr::zero());
+        const void *pn[3] = {num[0].get(), num[1].get(), num[2].get()}, *pd[3] = {den[0].get(), den[1].get(), den[2].get()};
+        check(zk_sumcheck_perm3_fs(h_, eq.get(), tree.get(), pn, pd, N, gamma.v, t.h, r.sums[0].v, last[0].v, chal[0].v));
         return r;
     }
     ScResult sumcheck_multi_fs(const std::vector<DevPtr> &es, const std::vector<DevPtr> &fs, size_t len, DeviceTranscript &t, FrVec &last_e, FrVec &last_f,

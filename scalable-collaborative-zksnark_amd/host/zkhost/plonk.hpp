@@ -1,0 +1,308 @@
+// HyperPlonk for ONE circuit -- the compiled counterpart of zkhip/plonk.py, bit for bit: the gate ZeroCheck and the wiring PermCheck
+// over the three wire columns on the SAME committed wires, under one Fiat-Shamir transcript, closed by two opening proofs.
+//
+// N = 2^mu rows with selectors q1, q2 and wires a, b, c (columns 0, 1, 2; slot j N + x = wire j of row x), a permutation sigma of the 3N
+// slots, ssigma_j(x) = sigma(j N + x), l = 2^k <= N / 2 public inputs in rows 0 .. l - 1 of `in`.
+//     n_j = w_j + alpha (j N + x) + beta,  d_j = w_j + alpha ssigma_j + beta,  h = n_0 n_1 n_2 / (d_0 d_1 d_2),  v = product_tree(h)
+//
+// Schedule (label "plonk"):
+//   1. absorb mu, l (one u64 each), the five vk commitments (q1, q2, ssigma_0..2), the l public inputs;
+//   2. absorb the commitments of a, b, c;  alpha, beta <- challenges;
+//   3. the derived tables and the tree; absorb the tree's commitment;  gamma <- challenge;
+//   4. tau_p <- mu challenges; zk_sumcheck_perm3_fs: per round absorb its six evaluations, r_p[i] <- challenge;
+//   5. tau_g <- mu challenges; zk_sumcheck_gate_fs on (eq, q1, q2, a, b, c, in): per round absorb its five evaluations, r_g[i] <- challenge;
+//   6. absorb q1, q2, a, b, c at r_g; a, b, c, ssigma_0..2 at r_p; the tree at the five v_points of r_p;  b_alpha <- challenge;
+//   7. the mu-variate batch instance (eleven claims on q1, q2, a, b, c, ssigma_0..2), then the (mu + 1)-variate one (five claims on the
+//      tree): per round absorb (t0, t1, t2), rho[i] <- challenge.  Two opening proofs.
+// The SRS has mu + 1 variables; the mu-variate tables use the last mu of them.  Single party only.
+#pragma once
+#include "nizk.hpp"
+
+namespace zkhost {
+
+struct PlonkCircuit {
+    size_t mu = 0, l = 0;
+    FrVec q1, q2, a, b, c, public_inputs, s;  // s: the SRS trapdoor, mu + 1 elements
+    std::vector<uint64_t> sigma;              // 3N slot numbers
+};
+struct PlonkVk {
+    size_t mu = 0, l = 0;
+    G1Vec commitments;  // q1, q2, ssigma_0, ssigma_1, ssigma_2
+};
+struct PlonkPk {
+    size_t mu = 0, l = 0;
+    DevPtr q1, q2;
+    std::array<DevPtr, 3> ssigma;
+    G1Vec commitments;
+};
+struct PlonkProof {
+    size_t mu = 0, l = 0;
+    G1Vec commitments;  // a, b, c
+    G1 v_commitment;
+    std::vector<std::array<Fr, 6>> p_rounds;
+    std::vector<std::array<Fr, 5>> g_rounds;
+    FrVec g_values, p_values, v_values;  // 5, 6, 5
+    BatchOpenProof batch, v_batch;
+};
+struct PlonkChallenges {
+    Fr alpha, beta, gamma, b_alpha;
+    FrVec tau_p, r_p, tau_g, r_g, rho_mu, rho_mu1;
+};
+
+// The test circuit of zkhip.plonk.sample_circuit (the same SplitMix64 streams: 1 public inputs, 2 q1, 3 q2, 4 picks, 5 trapdoor).
+// break_gate K adds 1 to c[K] after the fact; break_wire K (K >= l) adds 1 to a[K] and recomputes c[K].  -1: none.
+inline PlonkCircuit sample_circuit(size_t mu, uint64_t seed, long long break_gate = -1, long long break_wire = -1) {
+    if (mu < 2) throw ZkError(ZK_ERR_INVALID, "sample_circuit: mu >= 2");
+    PlonkCircuit c;
+    const size_t N = size_t(1) << mu, l = N / 2 < 4 ? N / 2 : 4;
+    const uint64_t base = 0x91A70000ull + 1000 * seed;
+    c.mu = mu, c.l = l;
+    c.public_inputs = SplitMix64(base + 1).fr_vec(l);
+    c.q1 = SplitMix64(base + 2).fr_vec(N), c.q2 = SplitMix64(base + 3).fr_vec(N);
+    const FrVec pick = SplitMix64(base + 4).fr_vec(N);
+    c.a.assign(N, Fr::zero()), c.b.assign(N, Fr::zero()), c.c.assign(N, Fr::zero());
+    for (size_t x = 0; x < l; ++x) c.q1[x] = Fr::zero(), c.q2[x] = Fr::zero(), c.c[x] = c.public_inputs[x];
+    std::vector<size_t> ia(N, 0), ib(N, 0);
+    auto gate = [&](size_t x) { return c.q1[x] * (c.a[x] + c.b[x]) + c.q2[x] * c.a[x] * c.b[x]; };
+    for (size_t x = l; x < N; ++x) {
+        ia[x] = pick[x].v[0] % x, ib[x] = pick[x].v[1] % x;
+        c.a[x] = c.c[ia[x]], c.b[x] = c.c[ib[x]];
+        c.c[x] = gate(x);
+    }
+    if (break_wire >= 0) {
+        if ((size_t)break_wire < l || (size_t)break_wire >= N) throw ZkError(ZK_ERR_INVALID, "sample_circuit: break_wire must name a row past the input rows");
+        c.a[break_wire] += Fr::one();
+        c.c[break_wire] = gate(break_wire);
+    }
+    if (break_gate >= 0) c.c[break_gate] += Fr::one();
+    // sigma: one cycle per value -- the c slot of row y, then the a / b slots that copy it in ascending slot order
+    std::vector<std::vector<uint64_t>> users(N);
+    for (size_t x = l; x < N; ++x) users[ia[x]].push_back(x);
+    for (size_t x = l; x < N; ++x) users[ib[x]].push_back(N + x);
+    c.sigma.resize(3 * N);
+    for (size_t i = 0; i < 3 * N; ++i) c.sigma[i] = i;
+    for (size_t y = 0; y < N; ++y) {
+        uint64_t prev = 2 * N + y;
+        for (uint64_t u : users[y]) c.sigma[prev] = u, prev = u;
+        c.sigma[prev] = 2 * N + y;
+    }
+    c.s = SplitMix64(base + 5).fr_vec(mu + 1);
+    return c;
+}
+
+// ---- the verifier's closed forms ----
+template <size_t K>
+inline Fr round_poly_nodes(const std::array<Fr, K> &e, const Fr &x) {  // the polynomial of degree K - 1 through (k, e[k]) at x
+    Fr acc = Fr::zero();
+    for (size_t k = 0; k < K; ++k) {
+        Fr num = Fr::one(), den = Fr::one();
+        for (size_t m = 0; m < K; ++m)
+            if (m != k) num *= x - Fr::from_u64(m), den *= Fr::from_u64(k) - Fr::from_u64(m);
+        acc += e[k] * num * den.inverse();
+    }
+    return acc;
+}
+// in(r): prod_{i < mu - k} (1 - r_i) * sum_y pi[y] eq(y, r_{mu-k..}), index bit 0 the TOP bit
+inline Fr in_eval(const FrVec &pi, const FrVec &r) {
+    size_t k = 0;
+    while ((size_t(1) << k) < pi.size()) ++k;
+    const size_t mu = r.size();
+    Fr head = Fr::one();
+    for (size_t i = 0; i + k < mu; ++i) head *= Fr::one() - r[i];
+    const FrVec tail(r.begin() + (mu - k), r.end());
+    Fr acc = Fr::zero();
+    for (size_t y = 0; y < pi.size(); ++y) {
+        FrVec bits(k);
+        for (size_t i = 0; i < k; ++i) bits[i] = ((y >> (k - 1 - i)) & 1) ? Fr::one() : Fr::zero();
+        acc += pi[y] * eq_eval(bits, tail);
+    }
+    return head * acc;
+}
+// the multilinear extension of x -> x at r
+inline Fr slot_eval(const FrVec &r) {
+    Fr acc = Fr::zero();
+    for (const Fr &x : r) acc = acc + acc + x;
+    return acc;
+}
+
+// ---- keys ----
+inline PlonkPk preprocess(Ctx &be, const PowersOfG &pg, const PlonkCircuit &c, PlonkVk &vk) {
+    const size_t N = size_t(1) << c.mu;
+    if (c.mu < 1 || c.l < 1 || (c.l & (c.l - 1)) || 2 * c.l > N || c.sigma.size() != 3 * N || c.q1.size() != N || c.q2.size() != N)
+        throw ZkError(ZK_ERR_INVALID, "preprocess: mu >= 1, l = 2^k <= N / 2, q1, q2 of N and sigma of 3N elements are needed");
+    PlonkPk pk;
+    pk.mu = vk.mu = c.mu, pk.l = vk.l = c.l;
+    pk.q1 = be.to_device(c.q1), pk.q2 = be.to_device(c.q2);
+    for (size_t j = 0; j < 3; ++j) {
+        FrVec col(N);
+        for (size_t x = 0; x < N; ++x) col[x] = Fr::from_u64(c.sigma[j * N + x]);
+        pk.ssigma[j] = be.to_device(col);
+    }
+    for (const DevPtr &t : {pk.q1, pk.q2, pk.ssigma[0], pk.ssigma[1], pk.ssigma[2]}) pk.commitments.push_back(commit(be, pg, t, N));
+    vk.commitments = pk.commitments;
+    return pk;
+}
+
+namespace detail {
+inline void plonk_claims(const PlonkProof &p, const FrVec &r_g, const FrVec &r_p, std::vector<Claim> &claims, std::vector<Claim> &v_claims) {
+    // tables of the mu-variate instance: q1, q2, a, b, c, ssigma_0..2
+    for (size_t k = 0; k < 5; ++k) claims.push_back(Claim{k, r_g, p.g_values[k]});
+    for (size_t k = 0; k < 6; ++k) claims.push_back(Claim{2 + k, r_p, p.p_values[k]});
+    const std::vector<FrVec> vp = v_points(r_p);
+    for (size_t k = 0; k < 5; ++k) v_claims.push_back(Claim{0, vp[k], p.v_values[k]});
+}
+}  // namespace detail
+
+// ---- prover ----  (pg: the levels of a PolynomialCommitment over mu + 1 variables; a zero alpha, of probability 2^-254, is refused)
+inline PlonkProof plonk_prove(Ctx &be, const PowersOfG &pg, const PlonkPk &pk, const DevPtr &a, const DevPtr &b, const DevPtr &c, const FrVec &public_inputs) {
+    const size_t mu = pk.mu, l = pk.l, N = size_t(1) << mu;
+    if (public_inputs.size() != l) throw ZkError(ZK_ERR_INVALID, "plonk_prove: l public inputs are needed");
+    PlonkProof p;
+    p.mu = mu, p.l = l;
+    const std::array<DevPtr, 3> w = {a, b, c};
+    for (const DevPtr &t : w) p.commitments.push_back(commit(be, pg, t, N));
+    std::shared_ptr<DeviceTranscript> tr = be.transcript("plonk");
+    const uint64_t mu64 = mu, l64 = l;
+    be.absorb(*tr, &mu64, 8);
+    be.absorb(*tr, &l64, 8);
+    be.absorb(*tr, pk.commitments.data(), 144 * 5);
+    be.absorb(*tr, public_inputs.data(), 32 * l);
+    be.absorb(*tr, p.commitments.data(), 144 * 3);
+    const FrVec ab = be.challenges(*tr, 2);
+    const Fr alpha = ab[0], beta = ab[1];
+    if (alpha.is_zero()) throw ZkError(ZK_ERR_INVALID, "plonk_prove: the challenge alpha is zero");
+    Ctx::Perm3Terms t = be.perm3_terms(w, pk.ssigma, N, alpha, beta);
+    DevPtr tree = be.product_tree(be.fr_batch_div(t.P, t.Q, N), N);
+    p.v_commitment = commit(be, pg, tree, 2 * N);
+    be.absorb(*tr, p.v_commitment.data(), 144);
+    const Fr gamma = be.challenges(*tr, 1)[0];
+    FrVec p_last, r_p, g_last, r_g;
+    {
+        DevPtr eq = be.eq_table(be.challenges(*tr, mu));
+        ScResult sc = be.sumcheck_perm3_fs(eq, tree, t.num, t.den, N, gamma, *tr, p_last, r_p);
+        p.p_rounds.resize(mu);
+        for (size_t i = 0; i < mu; ++i)
+            for (int k = 0; k < 6; ++k) p.p_rounds[i][k] = sc.sums[6 * i + k];
+    }
+    {
+        DevPtr eq = be.eq_table(be.challenges(*tr, mu));
+        FrVec inp(N, Fr::zero());
+        for (size_t y = 0; y < l; ++y) inp[y] = public_inputs[y];
+        ScResult sc = be.sumcheck_gate_fs({eq, pk.q1, pk.q2, a, b, c, be.to_device(inp)}, N, *tr, g_last, r_g);
+        p.g_rounds.resize(mu);
+        for (size_t i = 0; i < mu; ++i)
+            for (int k = 0; k < 5; ++k) p.g_rounds[i][k] = sc.sums[5 * i + k];
+    }
+    p.g_values = {g_last[1], g_last[2], g_last[3], g_last[4], g_last[5]};  // the folded-out values ARE q1, q2, a, b, c at r_g
+    // the folded-out n_j, d_j at r_p give the wires and the permutation columns there: both are linear in them
+    const Fr ids = slot_eval(r_p), ainv = alpha.inverse();
+    FrVec w_r(3), s_r(3);
+    for (size_t j = 0; j < 3; ++j) {
+        w_r[j] = p_last[5 + j] - alpha * (Fr::from_u64(j * N) + ids) - beta;
+        s_r[j] = (p_last[8 + j] - w_r[j] - beta) * ainv;
+    }
+    p.p_values = {w_r[0], w_r[1], w_r[2], s_r[0], s_r[1], s_r[2]};
+    Fr prod;  // the tree at (0,r) = h, (1,r) = v1x, (r,0) = vx0, (r,1) = vx1 are folded-out values too; (1,..,1,0) is tree[2N - 2]
+    be.check(zk_memcpy_d2h(be.handle(), prod.v, (const char *)tree.get() + 32 * (2 * N - 2), 32));
+    p.v_values = {p_last[4], p_last[1], p_last[2], p_last[3], prod};
+    be.absorb(*tr, p.g_values.data(), 32 * 5);
+    be.absorb(*tr, p.p_values.data(), 32 * 6);
+    be.absorb(*tr, p.v_values.data(), 32 * 5);
+    const Fr b_alpha = be.challenges(*tr, 1)[0];
+    std::vector<Claim> claims, v_claims;
+    detail::plonk_claims(p, r_g, r_p, claims, v_claims);
+    p.batch = detail::batch_prove_ni(be, pg, {pk.q1, pk.q2, a, b, c, pk.ssigma[0], pk.ssigma[1], pk.ssigma[2]}, N, claims, b_alpha, *tr);
+    p.v_batch = detail::batch_prove_ni(be, pg, {tree}, 2 * N, v_claims, b_alpha, *tr);
+    return p;
+}
+
+// ---- verifier ----
+// the replay of the schedule on the host transcript; false on a malformed record or statement
+inline bool plonk_challenges(const PlonkVk &vk, const FrVec &pi, const PlonkProof &p, PlonkChallenges &c) {
+    const size_t mu = vk.mu;
+    if (mu < 1 || p.mu != mu || p.l != vk.l || pi.size() != vk.l || vk.commitments.size() != 5 || p.commitments.size() != 3 || p.p_rounds.size() != mu ||
+        p.g_rounds.size() != mu || p.batch.rounds.size() != mu || p.v_batch.rounds.size() != mu + 1 || p.g_values.size() != 5 || p.p_values.size() != 6 ||
+        p.v_values.size() != 5)
+        return false;
+    HostTranscript tr("plonk");
+    tr.absorb_u64(mu).absorb_u64(vk.l).absorb(vk.commitments.data(), 144 * 5).absorb(pi);
+    tr.absorb(p.commitments.data(), 144 * 3);
+    c.alpha = tr.challenge(), c.beta = tr.challenge();
+    c.gamma = tr.absorb(p.v_commitment.data(), 144).challenge();
+    c.tau_p = tr.challenges(mu);
+    c.r_p = detail::replay_rounds(tr, p.p_rounds);
+    c.tau_g = tr.challenges(mu);
+    c.r_g = detail::replay_rounds(tr, p.g_rounds);
+    c.b_alpha = tr.absorb(p.g_values).absorb(p.p_values).absorb(p.v_values).challenge();
+    c.rho_mu = detail::replay_rounds(tr, p.batch.rounds);
+    c.rho_mu1 = detail::replay_rounds(tr, p.v_batch.rounds);
+    return true;
+}
+
+// The verifier's field arithmetic (no GPU, no pairing) -> a bit per failed check (0: all hold; bit 0: malformed): 1 the wiring chain,
+// 2 the gate chain, 3 the gate's last value with in(r_g) formed here, 4 the wiring's last value with n_j formed here, 5 v(1,..,1,0) == 1,
+// 6 the chains of the two batch instances (zkhip.plonk.failed_checks).
+inline unsigned plonk_failed_checks(const PlonkVk &vk, const FrVec &pi, const PlonkProof &p, const PlonkChallenges &c) {
+    const size_t mu = vk.mu, N = size_t(1) << mu;
+    unsigned bad = 0;
+    Fr p_target = Fr::zero(), g_target = Fr::zero();
+    for (size_t i = 0; i < mu; ++i) {
+        if (p.p_rounds[i][0] + p.p_rounds[i][1] != p_target) {
+            bad |= 1u << 1;
+            break;
+        }
+        p_target = round_poly_nodes(p.p_rounds[i], c.r_p[i]);
+    }
+    for (size_t i = 0; i < mu; ++i) {
+        if (p.g_rounds[i][0] + p.g_rounds[i][1] != g_target) {
+            bad |= 1u << 2;
+            break;
+        }
+        g_target = round_poly_nodes(p.g_rounds[i], c.r_g[i]);
+    }
+    const FrVec &g = p.g_values, &v = p.p_values, &t = p.v_values;  // g: q1, q2, a, b, c;  t: v(0,r), v(1,r), v(r,0), v(r,1), v(1,..,1,0)
+    if (!(bad & (1u << 2)) && g_target != eq_eval(c.tau_g, c.r_g) * (g[0] * (g[2] + g[3]) + g[1] * g[2] * g[3] - g[4] + in_eval(pi, c.r_g))) bad |= 1u << 3;
+    const Fr ids = slot_eval(c.r_p);
+    Fr nn = Fr::one(), dd = Fr::one();
+    for (size_t j = 0; j < 3; ++j) {
+        nn *= v[j] + c.alpha * (Fr::from_u64(j * N) + ids) + c.beta;
+        dd *= v[j] + c.alpha * v[3 + j] + c.beta;
+    }
+    if (!(bad & (1u << 1)) && p_target != eq_eval(c.tau_p, c.r_p) * (t[1] - t[2] * t[3] + c.gamma * (t[0] * dd - nn))) bad |= 1u << 4;
+    if (t[4] != Fr::one()) bad |= 1u << 5;
+    std::vector<Claim> claims, v_claims;
+    detail::plonk_claims(p, c.r_g, c.r_p, claims, v_claims);
+    if (failed_checks(8, claims, p.batch, c.b_alpha, c.rho_mu) || failed_checks(1, v_claims, p.v_batch, c.b_alpha, c.rho_mu1)) bad |= 1u << 6;
+    return bad;
+}
+
+inline bool plonk_verify(Ctx &be, const PcsVk &vk_mu, const PcsVk &vk_mu1, const PlonkVk &vk, const FrVec &pi, const PlonkProof &p) {
+    PlonkChallenges c;
+    if (!plonk_challenges(vk, pi, p, c) || plonk_failed_checks(vk, pi, p, c)) return false;
+    std::vector<Claim> claims, v_claims;
+    detail::plonk_claims(p, c.r_g, c.r_p, claims, v_claims);
+    const G1Vec comms = {vk.commitments[0], vk.commitments[1], p.commitments[0], p.commitments[1], p.commitments[2], vk.commitments[2], vk.commitments[3],
+                         vk.commitments[4]};
+    return batch_open_verify(be, vk_mu, comms, claims, p.batch, c.b_alpha, c.rho_mu) &&
+           batch_open_verify(be, vk_mu1, G1Vec{p.v_commitment}, v_claims, p.v_batch, c.b_alpha, c.rho_mu1);
+}
+
+// zkhip.plonk.proof_digest: the record's words in the order of the schedule
+inline std::string proof_digest(const PlonkProof &p) {
+    Sha256 h;
+    const uint64_t mu = p.mu, l = p.l;
+    h.update(&mu, 8);
+    h.update(&l, 8);
+    h.update(p.commitments.data(), 144 * p.commitments.size());
+    h.update(p.v_commitment.data(), 144);
+    for (auto &r : p.p_rounds) h.update(r.data(), 6 * 32);
+    for (auto &r : p.g_rounds) h.update(r.data(), 5 * 32);
+    h.update(p.g_values.data(), 32 * p.g_values.size());
+    h.update(p.p_values.data(), 32 * p.p_values.size());
+    h.update(p.v_values.data(), 32 * p.v_values.size());
+    detail::digest_batch(h, p.batch);
+    detail::digest_batch(h, p.v_batch);
+    return h.hex();
+}
+
+}  // namespace zkhost

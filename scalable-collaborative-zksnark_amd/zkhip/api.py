@@ -505,6 +505,33 @@ class Ctx:
             arr[i] = _ptr(b)
         return arr
 
+    def perm3_terms(self, ws, ssigmas, N: int, alpha: np.ndarray, beta: np.ndarray):
+        """the derived tables of the three-column wiring identity in one pass (zk_perm3_terms; asynchronous): ws, ssigmas three device
+        buffers of N Fr each -> (nums [3], dens [3], P = n_0 n_1 n_2, Q = d_0 d_1 d_2), device buffers of N Fr"""
+        if len(ws) != 3 or len(ssigmas) != 3:
+            raise ValueError("three wire columns and three permutation columns are needed")
+        al, be = np.ascontiguousarray(alpha, dtype=np.uint64).reshape(4), np.ascontiguousarray(beta, dtype=np.uint64).reshape(4)
+        nums, dens = [self.alloc(max(32 * N, 1)) for _ in range(3)], [self.alloc(max(32 * N, 1)) for _ in range(3)]
+        P, Q = self.alloc(max(32 * N, 1)), self.alloc(max(32 * N, 1))
+        self._check(self.lib.zk_perm3_terms(self.h, self._ptr_array(ws), self._ptr_array(ssigmas), N, _h(al), _h(be), self._ptr_array(nums), self._ptr_array(dens),
+                                            _ptr(P), _ptr(Q)))
+        return nums, dens, P, Q
+
+    def sumcheck_perm3(self, eq, tree, nums, dens, N: int, gamma: np.ndarray, chal: np.ndarray):
+        """the three-column wiring identity eq [v(1,x) - v(x,0) v(x,1) + gamma (h d_0 d_1 d_2 - n_0 n_1 n_2)] on the product tree of h (2N Fr,
+        read in place) as one degree-5 sumcheck -> (evals [mu,6,4], last [11,4]: eq, v1x, vx0, vx1, h, n_0..2, d_0..2)"""
+        if len(nums) != 3 or len(dens) != 3:
+            raise ValueError("three numerator and three denominator tables are needed")
+        mu = max(N.bit_length() - 1, 0)
+        chal = np.ascontiguousarray(chal, dtype=np.uint64).reshape(-1, 4)
+        gamma = np.ascontiguousarray(gamma, dtype=np.uint64).reshape(4)
+        if len(chal) < mu:
+            raise ValueError(f"{mu} challenges needed, {len(chal)} given")
+        out = np.zeros((mu, 6, 4), dtype=np.uint64)
+        last = np.zeros((11, 4), dtype=np.uint64)
+        self._check(self.lib.zk_sumcheck_perm3(self.h, _ptr(eq), _ptr(tree), self._ptr_array(nums), self._ptr_array(dens), N, _h(gamma), _h(chal), _h(out), _h(last)))
+        return out, last
+
     def eq_table_acc(self, point: np.ndarray, weight: np.ndarray, acc):
         """acc[x] += weight * eq(point, x), acc a device buffer of 2^n Fr (zk_eq_table_acc; asynchronous) -> acc"""
         point = np.ascontiguousarray(point, dtype=np.uint64).reshape(-1, 4)
@@ -535,7 +562,7 @@ class Ctx:
         self._check(self.lib.zk_sumcheck_multi(self.h, len(es), self._ptr_array(es), self._ptr_array(fs), length, _h(chal), _h(out), _h(le), _h(lf)))
         return out, le, lf
 
-    # ---- the same three sumchecks with their challenges drawn from a device transcript (zkhip.transcript.Transcript) ----
+    # ---- the same sumchecks with their challenges drawn from a device transcript (zkhip.transcript.Transcript) ----
     @staticmethod
     def _tr(transcript) -> int:
         return getattr(transcript, "h", transcript) or 0
@@ -554,6 +581,17 @@ class Ctx:
         gamma = np.ascontiguousarray(gamma, dtype=np.uint64).reshape(4)
         out, last, chal = np.zeros((mu, 4, 4), dtype=np.uint64), np.zeros((7, 4), dtype=np.uint64), np.zeros((mu, 4), dtype=np.uint64)
         self._check(self.lib.zk_sumcheck_wiring_fs(self.h, _ptr(eq), _ptr(tree), _ptr(num), _ptr(den), N, _h(gamma), self._tr(transcript), _h(out), _h(last), _h(chal)))
+        return out, last, chal
+
+    def sumcheck_perm3_fs(self, eq, tree, nums, dens, N: int, gamma: np.ndarray, transcript):
+        """sumcheck_perm3 with derived challenges -> (evals [mu,6,4], last [11,4], chal [mu,4])"""
+        if len(nums) != 3 or len(dens) != 3:
+            raise ValueError("three numerator and three denominator tables are needed")
+        mu = max(N.bit_length() - 1, 0)
+        gamma = np.ascontiguousarray(gamma, dtype=np.uint64).reshape(4)
+        out, last, chal = np.zeros((mu, 6, 4), dtype=np.uint64), np.zeros((11, 4), dtype=np.uint64), np.zeros((mu, 4), dtype=np.uint64)
+        self._check(self.lib.zk_sumcheck_perm3_fs(self.h, _ptr(eq), _ptr(tree), self._ptr_array(nums), self._ptr_array(dens), N, _h(gamma), self._tr(transcript),
+                                                  _h(out), _h(last), _h(chal)))
         return out, last, chal
 
     def sumcheck_multi_fs(self, es, fs, length: int, transcript):

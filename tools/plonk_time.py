@@ -1,0 +1,161 @@
+"""
+The three-column wiring sumcheck and the one-circuit proof against what the library offered before them -- one process, warm-up 3,
+median of --reps:
+
+  sumcheck  zk_sumcheck_perm3 and zk_sumcheck_perm3_fs on N = 2^mu rows against zk_sumcheck_wiring at mu + 2 (the 3N slots laid out
+            as one table of 4N elements, a tree of 8N), mu in --mu; tables are device-derived filler (the time does not depend on values);
+  proof     plonk.prove / plonk.verify at mu in --proof-mu against gate_prove_ni at mu plus wiring_prove_ni at mu + 2 (and the matching
+            verifiers); the last of three runs is reported (the first ones grow the arenas).
+
+    python tools/plonk_time.py [--mu 16,20,22,24] [--proof-mu 16,20] [--reps 20] [--out FILE] [--trace-mu M]
+
+--trace-mu M runs five zk_sumcheck_perm3 calls at 2^M and nothing else (the subject of a kernel trace).  One JSON line per result goes
+to stdout and to --out (default profiles/plonk_time.txt; '-' for stdout only).
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "scalable-collaborative-zksnark_amd"))
+
+
+def timed(fn, warm, reps):
+    for _ in range(warm):
+        fn()
+    ts = []
+    for _ in range(reps):
+        t = time.perf_counter()
+        fn()
+        ts.append(time.perf_counter() - t)
+    return statistics.median(ts) * 1e3
+
+
+def once(fn):
+    t = time.perf_counter()
+    r = fn()
+    return r, (time.perf_counter() - t) * 1e3
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--mu", default="16,20,22,24")
+    ap.add_argument("--proof-mu", default="16,20")
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--seed", type=int, default=7)
+    ap.add_argument("--trace-mu", type=int, default=0)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "plonk_time.txt"), help="file the JSON lines are written to ('-': stdout only)")
+    a = ap.parse_args()
+    import zkhip
+    from zkhip import dist_primitive as dp
+    from zkhip import nizk, plonk
+    from zkhip import pairing as pr
+    from zkhip import wiring as wr
+    from zkhip import zerocheck as zc
+    from zkhip.field import fr_from_mont, fr_mont, splitmix_fr
+    from zkhip.transcript import Transcript
+
+    be = zkhip.Ctx(0)
+    out = None if a.out == "-" or a.trace_mu else open(a.out, "w")
+
+    def emit(rec):
+        line = json.dumps(rec)
+        print(line, flush=True)
+        if out:  # line by line: a run that is cut short keeps what it measured
+            out.write(line + "\n")
+            out.flush()
+
+    chunk = 1 << 14
+    base = be.to_device(splitmix_fr(chunk, 1))
+
+    def filler(n, k):
+        """n elements: chunk i is coef_k * base + i"""
+        buf, coef = be.alloc(32 * n), splitmix_fr(1, 50 + k)[0]
+        for i in range(max(n // chunk, 1)):
+            be.fr_axpb(None, base, coef, fr_mont(i + 1), min(chunk, n), out=buf.at(32 * chunk * i))
+        return buf
+
+    def perm3_tables(mu):
+        N = 1 << mu
+        return filler(N, 0), filler(2 * N, 1), [filler(N, 2 + j) for j in range(3)], [filler(N, 5 + j) for j in range(3)]
+
+    if a.trace_mu:
+        mu = a.trace_mu
+        eq, tree, nums, dens = perm3_tables(mu)
+        gamma, chal = splitmix_fr(1, 3)[0], splitmix_fr(mu, 4)
+        for _ in range(5):
+            be.sumcheck_perm3(eq, tree, nums, dens, 1 << mu, gamma, chal)
+        be.close()
+        return 0
+
+    free = be.mem_info()[0]
+    for mu in [int(x) for x in a.mu.split(",") if x]:
+        N = 1 << mu
+        # the two table sets are never resident together: perm3 holds eq, a 2N tree, six tables and ping-pong scratch of 11 x (N/2 + N/4);
+        # the baseline eq, num, den of 4N, a tree of 8N and scratch of 7 x (2N + N)
+        need = 32 * max(N * (1 + 2 + 6) + 11 * 3 * N // 4, 4 * N * 3 + 8 * N + 21 * N)
+        if need > 0.8 * free:
+            emit({"sumcheck_mu": mu, "skipped": "needs %.1f GiB of %.1f GiB free" % (need / 2**30, free / 2**30)})
+            continue
+        gamma, chal = splitmix_fr(1, 3)[0], splitmix_fr(mu + 2, 4)
+        eq, tree, nums, dens = perm3_tables(mu)
+        perm3 = timed(lambda: be.sumcheck_perm3(eq, tree, nums, dens, N, gamma, chal), 3, a.reps)
+        tr = Transcript(be, b"time")
+        perm3_fs = timed(lambda: be.sumcheck_perm3_fs(eq, tree, nums, dens, N, gamma, tr), 3, a.reps)
+        tr.free()
+        del eq, tree, nums, dens
+        eq4, tree4, num4, den4 = filler(4 * N, 0), filler(8 * N, 1), filler(4 * N, 2), filler(4 * N, 3)
+        wiring = timed(lambda: be.sumcheck_wiring(eq4, tree4, num4, den4, 4 * N, gamma, chal), 3, a.reps)
+        del eq4, tree4, num4, den4
+        emit({"sumcheck_mu": mu, "perm3_ms": perm3, "perm3_fs_ms": perm3_fs, "wiring_4N_ms": wiring, "perm3_over_wiring_4N": perm3 / wiring,
+              "predicted_by_multiplications": 59 / 92})
+
+    ints = lambda s: [fr_from_mont(x) for x in s]
+    for mu in [int(x) for x in a.proof_mu.split(",") if x]:
+        N = 1 << mu
+        c = plonk.sample_circuit(mu, a.seed)
+        pcs = dp.PolynomialCommitmentCub.new(be, c["s"]).mature()
+        pk, vk = plonk.preprocess(be, pcs, c, pr.powers_of_g2(ints(c["s"])))
+        wires = [be.to_device(c[k]) for k in ("a", "b", "c")]
+        g = {"proof_mu": mu}
+        for rep in range(3):
+            tb = {}
+            proof, g["prove_ms"] = once(lambda: plonk.prove(be, pk, *wires, c["public_inputs"], timing=tb))
+            g.update({"prove_" + k.replace("_s", "_ms"): v * 1e3 for k, v in tb.items()})
+        for rep in range(2):
+            ok, g["verify_ms"] = once(lambda: plonk.verify(be, vk, c["public_inputs"], proof))
+        del pk, vk, pcs, wires, proof
+        # the baseline: two unrelated proofs, the gate identity at mu and the single-column wiring at mu + 2
+        tabs, _tau, _chal, s = zc.satisfied_circuit(be, mu, a.seed)
+        pcs = dp.PolynomialCommitmentCub.new(be, s).mature()
+        gvk = dp.pcs_vk(be, pr.powers_of_g2(ints(s)))
+        for rep in range(3):
+            gp, g["gate_prove_ni_ms"] = once(lambda: nizk.gate_prove_ni(be, pcs, tabs))
+        for rep in range(2):
+            ok_g, g["gate_verify_ni_ms"] = once(lambda: nizk.gate_verify_ni(be, gvk, gp))
+        del tabs, pcs, gvk, gp
+        w, sid, ssigma, *_rest, s = wr.permuted_circuit(be, mu + 2, a.seed)
+        pcs = dp.PolynomialCommitmentCub.new(be, s).mature()
+        vk_mu, vk_mu1 = wr.verifying_keys(be, pr.powers_of_g2(ints(s)))
+        for rep in range(3):
+            tb = {}
+            wp, g["wiring_prove_ni_4N_ms"] = once(lambda: nizk.wiring_prove_ni(be, pcs, w, sid, ssigma, 4 * N, timing=tb))
+            g["wiring_4N_commit_ms"] = tb["commit_s"] * 1e3
+        for rep in range(2):
+            ok_w, g["wiring_verify_ni_4N_ms"] = once(lambda: nizk.wiring_verify_ni(be, vk_mu, vk_mu1, wp))
+        del w, sid, ssigma, pcs, vk_mu, vk_mu1, wp
+        g["verdicts"] = [bool(ok), bool(ok_g), bool(ok_w)]
+        g["prove_over_baseline"] = g["prove_ms"] / (g["gate_prove_ni_ms"] + g["wiring_prove_ni_4N_ms"])
+        g["verify_over_baseline"] = g["verify_ms"] / (g["gate_verify_ni_ms"] + g["wiring_verify_ni_4N_ms"])
+        emit(g)
+    if out:
+        out.close()
+    be.close()
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
