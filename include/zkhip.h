@@ -184,6 +184,16 @@ int zk_perm3_terms(zk_ctx *ctx, const void *const d_w[3], const void *const d_ss
 int zk_sumcheck_perm3(zk_ctx *ctx, const void *d_eq, const void *d_tree, const void *const d_num[3],
                       const void *const d_den[3], size_t N, const uint64_t h_gamma[4], const uint64_t *h_chal,
                       uint64_t *h_out_evals, uint64_t *h_last);
+/* The WIDE Plonk gate as ONE sumcheck: six selectors (a constant, separate weights of the two additive wires, an output selector) and a
+ * fifth-power term, so that an S-box row c = a^5 + const is one row: the prover's rounds for
+ *     W(x) = eq(x) [ qL(x) a(x) + qR(x) b(x) + qM(x) a(x) b(x) + qH(x) a(x)^5 - qO(x) c(x) + qC(x) + in(x) ]
+ * over the eleven tables d_tabs = eq, qL, qR, qM, qO, qC, qH, a, b, c, in of len = 2^n Fr each (not modified).  Round i writes eight Fr
+ * to h_out_evals: the round polynomial (degree 7) at t = 0 .. 7, every table extended as (1 - t) lo + t hi, then folds the eleven
+ * tables with h_chal[i].  h_out_evals: 8 n Fr; h_last: the eleven remaining elements in the order of d_tabs, 11 Fr.  Blocking: the
+ * results are on the host when it returns.  len < 2, not a power of two or > 2^35, a null pointer, or the knob gatew_local_e not a
+ * power of two in [1, 256]: ZK_ERR_INVALID; nothing is launched or written on error. */
+int zk_sumcheck_gate_wide(zk_ctx *ctx, const void *const d_tabs[11], size_t len, const uint64_t *h_chal,
+                          uint64_t *h_out_evals, uint64_t *h_last);
 /* ---- batch opening: K claims f_{j_k}(z_k) = v_k on J tables of one size -> one degree-2 sumcheck and one opening ---- */
 /* d_acc[x] += weight * eq(point, x) over the cube of n variables (x_0 the TOP index bit), d_acc: 2^n Fr, read and written.  The
  * doubling scheme of zk_eq_table seeded with the weight; the last level is added into d_acc instead of stored, so a claim costs
@@ -222,8 +232,8 @@ int zk_transcript_absorb_device(zk_ctx *ctx, zk_transcript *t, const void *d_ptr
 /* count successive challenges; h_out: count Fr in Montgomery form */
 int zk_transcript_challenges(zk_ctx *ctx, zk_transcript *t, size_t count, uint64_t *h_out);
 int zk_transcript_state(zk_ctx *ctx, zk_transcript *t, uint8_t h_state32[32]);
-/* zk_sumcheck_gate / zk_sumcheck_wiring / zk_sumcheck_perm3 / zk_sumcheck_multi with every challenge DERIVED: round i's evaluations are
- * absorbed as they appear in the output (5, 4, 6 or 3 Fr) and one challenge is drawn, on the device, between the kernels of ONE enqueue -- no host read and
+/* zk_sumcheck_gate / zk_sumcheck_wiring / zk_sumcheck_perm3 / zk_sumcheck_gate_wide / zk_sumcheck_multi with every challenge DERIVED: round i's evaluations are
+ * absorbed as they appear in the output (5, 4, 6, 8 or 3 Fr) and one challenge is drawn, on the device, between the kernels of ONE enqueue -- no host read and
  * one stream synchronisation per call.  h_chal_out: the n challenges that were used (Montgomery Fr); every other argument, the
  * outputs, the limits and the error cases are those of the parent, and for the challenges in h_chal_out the parent returns the same
  * bits.  The transcript has absorbed all n rounds when the call returns.  A null transcript or one of another ctx: ZK_ERR_INVALID. */
@@ -236,6 +246,8 @@ int zk_sumcheck_wiring_fs(zk_ctx *ctx, const void *d_eq, const void *d_tree, con
 int zk_sumcheck_perm3_fs(zk_ctx *ctx, const void *d_eq, const void *d_tree, const void *const d_num[3],
                          const void *const d_den[3], size_t N, const uint64_t h_gamma[4], zk_transcript *t,
                          uint64_t *h_out_evals, uint64_t *h_last, uint64_t *h_chal_out);
+int zk_sumcheck_gate_wide_fs(zk_ctx *ctx, const void *const d_tabs[11], size_t len, zk_transcript *t,
+                             uint64_t *h_out_evals, uint64_t *h_last, uint64_t *h_chal_out);
 int zk_sumcheck_multi_fs(zk_ctx *ctx, size_t count, const void *const *d_e, const void *const *d_f, size_t len,
                          zk_transcript *t, uint64_t *h_out_triples, uint64_t *h_last_e, uint64_t *h_last_f,
                          uint64_t *h_chal_out);

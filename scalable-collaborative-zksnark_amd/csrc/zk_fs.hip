@@ -1,4 +1,4 @@
-// zk_fs.hip -- the four fused sumchecks (zk_gate.hip, zk_wiring.hip, zk_perm3.hip, zk_batchopen.hip) with their challenges drawn from a
+// zk_fs.hip -- the five fused sumchecks (zk_gate.hip, zk_wiring.hip, zk_perm3.hip, zk_gatew.hip, zk_batchopen.hip) with their challenges drawn from a
 // Fiat-Shamir transcript ON THE DEVICE (zk_transcript.hip, sha256.cuh): challenge r_p is a hash of round p's evaluations, so the
 // fold by r_p cannot share a sweep with round p's sums as it does in the preset-challenge kernels.  The shape here:
 //   pass 0            evaluate only: the sums of round 0 over the caller's tables (nothing is written but the partials),
@@ -47,6 +47,14 @@ struct Perm3Kind {  // eq, v1x, vx0, vx1, h, n_0, n_1, n_2, d_0, d_1, d_2
     static constexpr unsigned kLocalMax = kPerm3LocalMax;
     static constexpr int kWaves = 1;  // 22 table registers of 8 limbs and six 17-limb sums: the 264 .. 512 register bracket
     __device__ static __forceinline__ Fr inner(const Fr& gamma, const Fr (&v)[kTabs]) { return perm3_inner(gamma, v); }
+};
+struct GatewKind {  // eq, qL, qR, qM, qO, qC, qH, a, b, c, in
+    static constexpr int kTabs = kGatewTabs;
+    static constexpr int kEvals = kGatewEvals;
+    static constexpr int kSlot = 4;
+    static constexpr unsigned kLocalMax = kGatewLocalMax;
+    static constexpr int kWaves = 1;  // 22 table registers of 8 limbs and eight 17-limb sums: the 264 .. 512 register bracket
+    __device__ static __forceinline__ Fr inner(const Fr&, const Fr (&v)[kTabs]) { return gatew_inner(v); }
 };
 
 // ---------------------------------------------------------------------------------------
@@ -494,6 +502,17 @@ int sumcheck_perm3_fs(zk_ctx* ctx, const void* d_eq, const void* d_tree, const v
     std::memcpy(&gamma.r, h_gamma, 32);
     return run_fs<Perm3Kind>(ctx, "zk_sumcheck_perm3_fs", first, N, emax, 1, gamma, t, h_out_evals,
                              h_last, h_chal_out);
+}
+
+int sumcheck_gate_wide_fs(zk_ctx* ctx, const void* const* d_tabs, size_t len, zk_transcript* t, uint64_t* h_out_evals, uint64_t* h_last, uint64_t* h_chal_out) {
+    size_t emax;
+    const int rc = local_e(ctx, tuning().gatew_local_e, "gatew_local_e", emax, kGatewLocalMax);
+    if (rc) return rc;
+    FsIn<kGatewTabs> first;
+    for (int k = 0; k < kGatewTabs; k++) first.t[k] = d_tabs[k], first.sh[k] = 0;
+    GateChal none;
+    std::memset(&none, 0, sizeof(none));
+    return run_fs<GatewKind>(ctx, "zk_sumcheck_gate_wide_fs", first, len, emax, 1, none, t, h_out_evals, h_last, h_chal_out);
 }
 
 int sumcheck_multi_fs(zk_ctx* ctx, size_t count, const void* const* d_e, const void* const* d_f, size_t len, zk_transcript* t, uint64_t* h_out_triples,

@@ -102,6 +102,21 @@ __device__ __forceinline__ Fr perm3_inner(const Fr& gamma, const Fr (&v)[kPerm3T
     return fr_add(fr_sub(v[1], p), fr_mul(gamma, fr_sub(dd, nn)));
 }
 
+// the wide Plonk gate (zk_gatew.hip, its transcript-driven form in zk_fs.hip): eq, qL, qR, qM, qO, qC, qH, a, b, c, in
+static constexpr int kGatewTabs = 11;
+static constexpr int kGatewEvals = 8;             // t = 0 .. 7: qH a^5 is degree 6, eq adds one
+static constexpr unsigned kGatewLocalMax = 256;  // 11 x 256 x 32 B = 88 KiB of the CU's 160 KiB (512 elements would be 176 KiB)
+
+// [ qL a + qR b + qM a b + qH a^5 - qO c + qC + in ] of one point, v in the table order above: nine multiplications (a^5 as a^2, a^4, a^4 a)
+__device__ __forceinline__ Fr gatew_inner(const Fr (&v)[kGatewTabs]) {
+    const Fr &a = v[7], &b = v[8];
+    const Fr a2 = fr_mul(a, a);
+    const Fr a5 = fr_mul(fr_mul(a2, a2), a);
+    const Fr lin = fr_add(fr_mul(v[1], a), fr_mul(v[2], b));
+    const Fr hi = fr_add(fr_mul(fr_mul(v[3], a), b), fr_mul(v[6], a5));
+    return fr_add(fr_add(fr_sub(fr_add(lin, hi), fr_mul(v[4], v[9])), v[5]), v[10]);
+}
+
 // One workgroup of kGateBlock lanes adds the nbw per-wave partials from slot `base` on and reduces W0 + W1 R + W2 R^2 (a sum of
 // integer products of Montgomery forms) to W0 R^-1 + W1 + W2 R mod r, canonical: the value is lane 0's (the other lanes get zero).
 // lds: (kGateBlock / 64) slots, free again after the call's barrier.

@@ -289,6 +289,18 @@ class Ctx {
         check(zk_sumcheck_perm3(h_, eq.get(), tree.get(), pn, pd, N, gamma.v, chal[0].v, r.sums[0].v, last[0].v));
         return r;
     }
+    // zk_sumcheck_gate_wide: tabs = eq, qL, qR, qM, qO, qC, qH, a, b, c, in -> r.sums = 8 Fr per round (t = 0 .. 7), `last` = the eleven remaining elements
+    ScResult sumcheck_gate_wide(const std::array<DevPtr, 11> &tabs, size_t len, const FrVec &chal, FrVec &last) {
+        size_t n = log2_exact(len);
+        need(n >= 1 && chal.size() >= n, "sumcheck_gate_wide: fewer challenges than rounds");
+        ScResult r;
+        r.sums.resize(8 * n);
+        last.assign(11, Fr::zero());
+        const void *p[11];
+        for (int k = 0; k < 11; k++) p[k] = tabs[k].get();
+        check(zk_sumcheck_gate_wide(h_, p, len, chal[0].v, r.sums[0].v, last[0].v));
+        return r;
+    }
     // zk_eq_table_acc: acc[x] += weight * eq(point, x), acc = 2^n Fr (asynchronous)
     void eq_table_acc(const FrVec &point, const Fr &weight, const DevPtr &acc) {
         check(zk_eq_table_acc(h_, point.empty() ? nullptr : point[0].v, point.size(), weight.v, acc.get()));
@@ -362,6 +374,18 @@ class Ctx {
         chal.assign(mu, Fr::zero());
         const void *pn[3] = {num[0].get(), num[1].get(), num[2].get()}, *pd[3] = {den[0].get(), den[1].get(), den[2].get()};
         check(zk_sumcheck_perm3_fs(h_, eq.get(), tree.get(), pn, pd, N, gamma.v, t.h, r.sums[0].v, last[0].v, chal[0].v));
+        return r;
+    }
+    ScResult sumcheck_gate_wide_fs(const std::array<DevPtr, 11> &tabs, size_t len, DeviceTranscript &t, FrVec &last, FrVec &chal) {
+        size_t n = log2_exact(len);
+        need(n >= 1, "sumcheck_gate_wide_fs: at least one round");
+        ScResult r;
+        r.sums.resize(8 * n);
+        last.assign(11, Fr::zero());
+        chal.assign(n, Fr::zero());
+        const void *p[11];
+        for (int k = 0; k < 11; k++) p[k] = tabs[k].get();
+        check(zk_sumcheck_gate_wide_fs(h_, p, len, t.h, r.sums[0].v, last[0].v, chal[0].v));
         return r;
     }
     ScResult sumcheck_multi_fs(const std::vector<DevPtr> &es, const std::vector<DevPtr> &fs, size_t len, DeviceTranscript &t, FrVec &last_e, FrVec &last_f,

@@ -15,35 +15,93 @@
 //   7. the mu-variate batch instance (eleven claims on q1, q2, a, b, c, ssigma_0..2), then the (mu + 1)-variate one (five claims on the
 //      tree): per round absorb (t0, t1, t2), rho[i] <- challenge.  Two opening proofs.
 // The SRS has mu + 1 variables; the mu-variate tables use the last mu of them.  Single party only.
+//
+// A SECOND arithmetisation beside this one (GateKind::wide): the selectors qL, qR, qM, qO, qC, qH in the place of q1, q2 and the gate
+//     qL a + qR b + qM a b + qH a^5 - qO c + qC + in = 0
+// under the label "plonk-wide": nine vk commitments, zk_sumcheck_gate_wide_fs with EIGHT evaluations per round, nine values at r_g, a
+// mu-variate batch instance of twelve tables and fifteen claims.  The schedule, the permutation half and the (mu + 1)-variate instance are
+// the same code: a gate kind is described by gate_desc (label, selector count, evaluations per round), gate_sumcheck_fs (the device
+// sumcheck) and gate_closed_form (the verifier's closed form).  GateKind::basic behaves exactly as before.
 #pragma once
 #include "nizk.hpp"
 
 namespace zkhost {
 
+enum class GateKind { basic, wide };
+struct GateDesc {
+    const char *label;
+    size_t selectors;  // basic: q1, q2;  wide: qL, qR, qM, qO, qC, qH
+    size_t evals;      // evaluations per round of the gate sumcheck
+};
+inline const GateDesc &gate_desc(GateKind k) {
+    static const GateDesc d[2] = {{"plonk", 2, 5}, {"plonk-wide", 6, 8}};
+    return d[k == GateKind::wide ? 1 : 0];
+}
+
 struct PlonkCircuit {
+    GateKind gate = GateKind::basic;
     size_t mu = 0, l = 0;
-    FrVec q1, q2, a, b, c, public_inputs, s;  // s: the SRS trapdoor, mu + 1 elements
-    std::vector<uint64_t> sigma;              // 3N slot numbers
+    std::vector<FrVec> sel;             // the selectors in the order of gate_desc
+    FrVec a, b, c, public_inputs, s;    // s: the SRS trapdoor, mu + 1 elements
+    std::vector<uint64_t> sigma;        // 3N slot numbers
 };
 struct PlonkVk {
+    GateKind gate = GateKind::basic;
     size_t mu = 0, l = 0;
-    G1Vec commitments;  // q1, q2, ssigma_0, ssigma_1, ssigma_2
+    G1Vec commitments;  // the selectors, ssigma_0, ssigma_1, ssigma_2
 };
 struct PlonkPk {
+    GateKind gate = GateKind::basic;
     size_t mu = 0, l = 0;
-    DevPtr q1, q2;
+    std::vector<DevPtr> sel;
     std::array<DevPtr, 3> ssigma;
     G1Vec commitments;
 };
 struct PlonkProof {
+    GateKind gate = GateKind::basic;
     size_t mu = 0, l = 0;
     G1Vec commitments;  // a, b, c
     G1 v_commitment;
     std::vector<std::array<Fr, 6>> p_rounds;
-    std::vector<std::array<Fr, 5>> g_rounds;
-    FrVec g_values, p_values, v_values;  // 5, 6, 5
+    std::vector<FrVec> g_rounds;         // gate_desc(gate).evals per round
+    FrVec g_values, p_values, v_values;  // selectors + 3, 6, 5
     BatchOpenProof batch, v_batch;
 };
+
+// the device sumcheck of a gate kind; tabs: eq, the selectors, a, b, c, in
+inline ScResult gate_sumcheck_fs(Ctx &be, GateKind k, const std::vector<DevPtr> &tabs, size_t N, DeviceTranscript &tr, FrVec &last, FrVec &chal) {
+    if (tabs.size() != gate_desc(k).selectors + 5) throw ZkError(ZK_ERR_INVALID, "gate_sumcheck_fs: eq, the selectors, a, b, c, in are needed");
+    if (k == GateKind::wide) {
+        std::array<DevPtr, 11> t;
+        for (size_t i = 0; i < 11; ++i) t[i] = tabs[i];
+        return be.sumcheck_gate_wide_fs(t, N, tr, last, chal);
+    }
+    std::array<DevPtr, 7> t;
+    for (size_t i = 0; i < 7; ++i) t[i] = tabs[i];
+    return be.sumcheck_gate_fs(t, N, tr, last, chal);
+}
+// the verifier's closed form of a gate kind; g: the selectors, a, b, c at r_g
+inline Fr gate_closed_form(GateKind k, const Fr &eq, const FrVec &g, const Fr &in) {
+    if (k == GateKind::wide) return wide_gate_value(eq, g[0], g[1], g[2], g[3], g[4], g[5], g[6], g[7], g[8], in);
+    return eq * (g[0] * (g[2] + g[3]) + g[1] * g[2] * g[3] - g[4] + in);
+}
+
+namespace detail {
+// sigma: one cycle per value -- the c slot of row y, then the a / b slots that copy it in ascending slot order
+inline std::vector<uint64_t> copy_sigma(const std::vector<size_t> &ia, const std::vector<size_t> &ib, size_t l, size_t N) {
+    std::vector<std::vector<uint64_t>> users(N);
+    for (size_t x = l; x < N; ++x) users[ia[x]].push_back(x);
+    for (size_t x = l; x < N; ++x) users[ib[x]].push_back(N + x);
+    std::vector<uint64_t> sigma(3 * N);
+    for (size_t i = 0; i < 3 * N; ++i) sigma[i] = i;
+    for (size_t y = 0; y < N; ++y) {
+        uint64_t prev = 2 * N + y;
+        for (uint64_t u : users[y]) sigma[prev] = u, prev = u;
+        sigma[prev] = 2 * N + y;
+    }
+    return sigma;
+}
+}  // namespace detail
 struct PlonkChallenges {
     Fr alpha, beta, gamma, b_alpha;
     FrVec tau_p, r_p, tau_g, r_g, rho_mu, rho_mu1;
@@ -58,12 +116,13 @@ inline PlonkCircuit sample_circuit(size_t mu, uint64_t seed, long long break_gat
     const uint64_t base = 0x91A70000ull + 1000 * seed;
     c.mu = mu, c.l = l;
     c.public_inputs = SplitMix64(base + 1).fr_vec(l);
-    c.q1 = SplitMix64(base + 2).fr_vec(N), c.q2 = SplitMix64(base + 3).fr_vec(N);
+    c.sel = {SplitMix64(base + 2).fr_vec(N), SplitMix64(base + 3).fr_vec(N)};
+    FrVec &q1 = c.sel[0], &q2 = c.sel[1];
     const FrVec pick = SplitMix64(base + 4).fr_vec(N);
     c.a.assign(N, Fr::zero()), c.b.assign(N, Fr::zero()), c.c.assign(N, Fr::zero());
-    for (size_t x = 0; x < l; ++x) c.q1[x] = Fr::zero(), c.q2[x] = Fr::zero(), c.c[x] = c.public_inputs[x];
+    for (size_t x = 0; x < l; ++x) q1[x] = Fr::zero(), q2[x] = Fr::zero(), c.c[x] = c.public_inputs[x];
     std::vector<size_t> ia(N, 0), ib(N, 0);
-    auto gate = [&](size_t x) { return c.q1[x] * (c.a[x] + c.b[x]) + c.q2[x] * c.a[x] * c.b[x]; };
+    auto gate = [&](size_t x) { return q1[x] * (c.a[x] + c.b[x]) + q2[x] * c.a[x] * c.b[x]; };
     for (size_t x = l; x < N; ++x) {
         ia[x] = pick[x].v[0] % x, ib[x] = pick[x].v[1] % x;
         c.a[x] = c.c[ia[x]], c.b[x] = c.c[ib[x]];
@@ -75,24 +134,60 @@ inline PlonkCircuit sample_circuit(size_t mu, uint64_t seed, long long break_gat
         c.c[break_wire] = gate(break_wire);
     }
     if (break_gate >= 0) c.c[break_gate] += Fr::one();
-    // sigma: one cycle per value -- the c slot of row y, then the a / b slots that copy it in ascending slot order
-    std::vector<std::vector<uint64_t>> users(N);
-    for (size_t x = l; x < N; ++x) users[ia[x]].push_back(x);
-    for (size_t x = l; x < N; ++x) users[ib[x]].push_back(N + x);
-    c.sigma.resize(3 * N);
-    for (size_t i = 0; i < 3 * N; ++i) c.sigma[i] = i;
-    for (size_t y = 0; y < N; ++y) {
-        uint64_t prev = 2 * N + y;
-        for (uint64_t u : users[y]) c.sigma[prev] = u, prev = u;
-        c.sigma[prev] = 2 * N + y;
+    c.sigma = detail::copy_sigma(ia, ib, l, N);
+    c.s = SplitMix64(base + 5).fr_vec(mu + 1);
+    return c;
+}
+
+// The test circuit of zkhip.plonk.sample_circuit_wide, bit for bit: streams 1 public inputs, 4 picks, 5 trapdoor as above and 6 .. 11 =
+// qL, qR, qM, qO, qC, qH.  Input rows: qO = 1, every other selector 0, c = the public input.  Row x >= l copies a, b from earlier c
+// values; its kind is limb 2 of pick x mod 4: 0 linear (qL, qR, qC drawn, qO = 1), 1 product (qM, qC drawn, qO = 1), 2 S-box (qH = 1, qC
+// drawn, qO = 1), 3 full (all six drawn; a zero qO is replaced by 1); a selector the kind does not name is 0 and
+// c = (qL a + qR b + qM a b + qH a^5 + qC) / qO.  break_gate / break_wire as in sample_circuit.
+inline PlonkCircuit sample_circuit_wide(size_t mu, uint64_t seed, long long break_gate = -1, long long break_wire = -1) {
+    if (mu < 2) throw ZkError(ZK_ERR_INVALID, "sample_circuit_wide: mu >= 2");
+    PlonkCircuit c;
+    const size_t N = size_t(1) << mu, l = N / 2 < 4 ? N / 2 : 4;
+    const uint64_t base = 0x91A70000ull + 1000 * seed;
+    enum { qL, qR, qM, qO, qC, qH };
+    c.gate = GateKind::wide, c.mu = mu, c.l = l;
+    c.public_inputs = SplitMix64(base + 1).fr_vec(l);
+    const FrVec pick = SplitMix64(base + 4).fr_vec(N);
+    std::vector<FrVec> drawn;
+    for (uint64_t k = 0; k < 6; ++k) drawn.push_back(SplitMix64(base + 6 + k).fr_vec(N));
+    c.sel.assign(6, FrVec(N, Fr::zero()));
+    c.sel[qO].assign(N, Fr::one());
+    c.a.assign(N, Fr::zero()), c.b.assign(N, Fr::zero()), c.c.assign(N, Fr::zero());
+    for (size_t x = 0; x < l; ++x) c.c[x] = c.public_inputs[x];
+    static const std::vector<std::vector<int>> named = {{qL, qR, qC}, {qM, qC}, {qC}, {qL, qR, qM, qO, qC, qH}};
+    std::vector<size_t> ia(N, 0), ib(N, 0);
+    auto out = [&](size_t x) {  // the c that satisfies row x
+        const Fr &a = c.a[x], a2 = a * a;
+        const Fr s = c.sel[qL][x] * a + c.sel[qR][x] * c.b[x] + c.sel[qM][x] * a * c.b[x] + c.sel[qH][x] * a2 * a2 * a + c.sel[qC][x];
+        return c.sel[qO][x] == Fr::one() ? s : s * c.sel[qO][x].inverse();
+    };
+    for (size_t x = l; x < N; ++x) {
+        const unsigned kind = pick[x].v[2] % 4;
+        for (int k : named[kind]) c.sel[k][x] = drawn[k][x];
+        if (kind == 2) c.sel[qH][x] = Fr::one();
+        if (kind == 3 && c.sel[qO][x].is_zero()) c.sel[qO][x] = Fr::one();
+        ia[x] = pick[x].v[0] % x, ib[x] = pick[x].v[1] % x;
+        c.a[x] = c.c[ia[x]], c.b[x] = c.c[ib[x]];
+        c.c[x] = out(x);
     }
+    if (break_wire >= 0) {
+        if ((size_t)break_wire < l || (size_t)break_wire >= N) throw ZkError(ZK_ERR_INVALID, "sample_circuit_wide: break_wire must name a row past the input rows");
+        c.a[break_wire] += Fr::one();
+        c.c[break_wire] = out(break_wire);
+    }
+    if (break_gate >= 0) c.c[break_gate] += Fr::one();
+    c.sigma = detail::copy_sigma(ia, ib, l, N);
     c.s = SplitMix64(base + 5).fr_vec(mu + 1);
     return c;
 }
 
 // ---- the verifier's closed forms ----
-template <size_t K>
-inline Fr round_poly_nodes(const std::array<Fr, K> &e, const Fr &x) {  // the polynomial of degree K - 1 through (k, e[k]) at x
+inline Fr round_poly_nodes(const Fr *e, size_t K, const Fr &x) {  // the polynomial of degree K - 1 through (k, e[k]) at x
     Fr acc = Fr::zero();
     for (size_t k = 0; k < K; ++k) {
         Fr num = Fr::one(), den = Fr::one();
@@ -101,6 +196,10 @@ inline Fr round_poly_nodes(const std::array<Fr, K> &e, const Fr &x) {  // the po
         acc += e[k] * num * den.inverse();
     }
     return acc;
+}
+template <size_t K>
+inline Fr round_poly_nodes(const std::array<Fr, K> &e, const Fr &x) {
+    return round_poly_nodes(e.data(), K, x);
 }
 // in(r): prod_{i < mu - k} (1 - r_i) * sum_y pi[y] eq(y, r_{mu-k..}), index bit 0 the TOP bit
 inline Fr in_eval(const FrVec &pi, const FrVec &r) {
@@ -128,28 +227,37 @@ inline Fr slot_eval(const FrVec &r) {
 // ---- keys ----
 inline PlonkPk preprocess(Ctx &be, const PowersOfG &pg, const PlonkCircuit &c, PlonkVk &vk) {
     const size_t N = size_t(1) << c.mu;
-    if (c.mu < 1 || c.l < 1 || (c.l & (c.l - 1)) || 2 * c.l > N || c.sigma.size() != 3 * N || c.q1.size() != N || c.q2.size() != N)
-        throw ZkError(ZK_ERR_INVALID, "preprocess: mu >= 1, l = 2^k <= N / 2, q1, q2 of N and sigma of 3N elements are needed");
+    bool ok = c.mu >= 1 && c.l >= 1 && !(c.l & (c.l - 1)) && 2 * c.l <= N && c.sigma.size() == 3 * N && c.sel.size() == gate_desc(c.gate).selectors;
+    for (const FrVec &q : c.sel) ok = ok && q.size() == N;
+    if (!ok) throw ZkError(ZK_ERR_INVALID, "preprocess: mu >= 1, l = 2^k <= N / 2, the gate kind's selectors of N and sigma of 3N elements are needed");
     PlonkPk pk;
+    pk.gate = vk.gate = c.gate;
     pk.mu = vk.mu = c.mu, pk.l = vk.l = c.l;
-    pk.q1 = be.to_device(c.q1), pk.q2 = be.to_device(c.q2);
+    for (const FrVec &q : c.sel) pk.sel.push_back(be.to_device(q));
     for (size_t j = 0; j < 3; ++j) {
         FrVec col(N);
         for (size_t x = 0; x < N; ++x) col[x] = Fr::from_u64(c.sigma[j * N + x]);
         pk.ssigma[j] = be.to_device(col);
     }
-    for (const DevPtr &t : {pk.q1, pk.q2, pk.ssigma[0], pk.ssigma[1], pk.ssigma[2]}) pk.commitments.push_back(commit(be, pg, t, N));
+    for (const DevPtr &t : pk.sel) pk.commitments.push_back(commit(be, pg, t, N));
+    for (const DevPtr &t : pk.ssigma) pk.commitments.push_back(commit(be, pg, t, N));
     vk.commitments = pk.commitments;
     return pk;
 }
 
 namespace detail {
 inline void plonk_claims(const PlonkProof &p, const FrVec &r_g, const FrVec &r_p, std::vector<Claim> &claims, std::vector<Claim> &v_claims) {
-    // tables of the mu-variate instance: q1, q2, a, b, c, ssigma_0..2
-    for (size_t k = 0; k < 5; ++k) claims.push_back(Claim{k, r_g, p.g_values[k]});
-    for (size_t k = 0; k < 6; ++k) claims.push_back(Claim{2 + k, r_p, p.p_values[k]});
+    // tables of the mu-variate instance: the selectors, a, b, c, ssigma_0..2
+    const size_t ns = gate_desc(p.gate).selectors;
+    for (size_t k = 0; k < ns + 3; ++k) claims.push_back(Claim{k, r_g, p.g_values[k]});
+    for (size_t k = 0; k < 6; ++k) claims.push_back(Claim{ns + k, r_p, p.p_values[k]});
     const std::vector<FrVec> vp = v_points(r_p);
     for (size_t k = 0; k < 5; ++k) v_claims.push_back(Claim{0, vp[k], p.v_values[k]});
+}
+inline FrVec replay_rounds(HostTranscript &tr, const std::vector<FrVec> &rounds) {
+    FrVec out;
+    for (const FrVec &r : rounds) out.push_back(tr.absorb(r).challenge());
+    return out;
 }
 }  // namespace detail
 
@@ -157,15 +265,17 @@ inline void plonk_claims(const PlonkProof &p, const FrVec &r_g, const FrVec &r_p
 inline PlonkProof plonk_prove(Ctx &be, const PowersOfG &pg, const PlonkPk &pk, const DevPtr &a, const DevPtr &b, const DevPtr &c, const FrVec &public_inputs) {
     const size_t mu = pk.mu, l = pk.l, N = size_t(1) << mu;
     if (public_inputs.size() != l) throw ZkError(ZK_ERR_INVALID, "plonk_prove: l public inputs are needed");
+    const GateDesc &gd = gate_desc(pk.gate);
+    const size_t ns = gd.selectors;
     PlonkProof p;
-    p.mu = mu, p.l = l;
+    p.gate = pk.gate, p.mu = mu, p.l = l;
     const std::array<DevPtr, 3> w = {a, b, c};
     for (const DevPtr &t : w) p.commitments.push_back(commit(be, pg, t, N));
-    std::shared_ptr<DeviceTranscript> tr = be.transcript("plonk");
+    std::shared_ptr<DeviceTranscript> tr = be.transcript(gd.label);
     const uint64_t mu64 = mu, l64 = l;
     be.absorb(*tr, &mu64, 8);
     be.absorb(*tr, &l64, 8);
-    be.absorb(*tr, pk.commitments.data(), 144 * 5);
+    be.absorb(*tr, pk.commitments.data(), 144 * (ns + 3));
     be.absorb(*tr, public_inputs.data(), 32 * l);
     be.absorb(*tr, p.commitments.data(), 144 * 3);
     const FrVec ab = be.challenges(*tr, 2);
@@ -188,12 +298,13 @@ inline PlonkProof plonk_prove(Ctx &be, const PowersOfG &pg, const PlonkPk &pk, c
         DevPtr eq = be.eq_table(be.challenges(*tr, mu));
         FrVec inp(N, Fr::zero());
         for (size_t y = 0; y < l; ++y) inp[y] = public_inputs[y];
-        ScResult sc = be.sumcheck_gate_fs({eq, pk.q1, pk.q2, a, b, c, be.to_device(inp)}, N, *tr, g_last, r_g);
-        p.g_rounds.resize(mu);
-        for (size_t i = 0; i < mu; ++i)
-            for (int k = 0; k < 5; ++k) p.g_rounds[i][k] = sc.sums[5 * i + k];
+        std::vector<DevPtr> tabs = {eq};
+        tabs.insert(tabs.end(), pk.sel.begin(), pk.sel.end());
+        tabs.insert(tabs.end(), {a, b, c, be.to_device(inp)});
+        ScResult sc = gate_sumcheck_fs(be, pk.gate, tabs, N, *tr, g_last, r_g);
+        for (size_t i = 0; i < mu; ++i) p.g_rounds.emplace_back(sc.sums.begin() + gd.evals * i, sc.sums.begin() + gd.evals * (i + 1));
     }
-    p.g_values = {g_last[1], g_last[2], g_last[3], g_last[4], g_last[5]};  // the folded-out values ARE q1, q2, a, b, c at r_g
+    p.g_values.assign(g_last.begin() + 1, g_last.begin() + 1 + ns + 3);  // the folded-out values ARE the selectors and a, b, c at r_g
     // the folded-out n_j, d_j at r_p give the wires and the permutation columns there: both are linear in them
     const Fr ids = slot_eval(r_p), ainv = alpha.inverse();
     FrVec w_r(3), s_r(3);
@@ -205,27 +316,33 @@ inline PlonkProof plonk_prove(Ctx &be, const PowersOfG &pg, const PlonkPk &pk, c
     Fr prod;  // the tree at (0,r) = h, (1,r) = v1x, (r,0) = vx0, (r,1) = vx1 are folded-out values too; (1,..,1,0) is tree[2N - 2]
     be.check(zk_memcpy_d2h(be.handle(), prod.v, (const char *)tree.get() + 32 * (2 * N - 2), 32));
     p.v_values = {p_last[4], p_last[1], p_last[2], p_last[3], prod};
-    be.absorb(*tr, p.g_values.data(), 32 * 5);
+    be.absorb(*tr, p.g_values.data(), 32 * (ns + 3));
     be.absorb(*tr, p.p_values.data(), 32 * 6);
     be.absorb(*tr, p.v_values.data(), 32 * 5);
     const Fr b_alpha = be.challenges(*tr, 1)[0];
     std::vector<Claim> claims, v_claims;
     detail::plonk_claims(p, r_g, r_p, claims, v_claims);
-    p.batch = detail::batch_prove_ni(be, pg, {pk.q1, pk.q2, a, b, c, pk.ssigma[0], pk.ssigma[1], pk.ssigma[2]}, N, claims, b_alpha, *tr);
+    std::vector<DevPtr> batch_tables = pk.sel;
+    batch_tables.insert(batch_tables.end(), {a, b, c, pk.ssigma[0], pk.ssigma[1], pk.ssigma[2]});
+    p.batch = detail::batch_prove_ni(be, pg, batch_tables, N, claims, b_alpha, *tr);
     p.v_batch = detail::batch_prove_ni(be, pg, {tree}, 2 * N, v_claims, b_alpha, *tr);
     return p;
 }
 
 // ---- verifier ----
-// the replay of the schedule on the host transcript; false on a malformed record or statement
+// the replay of the schedule on the host transcript; false on a malformed record or statement (a record of another gate kind than the key's among them)
 inline bool plonk_challenges(const PlonkVk &vk, const FrVec &pi, const PlonkProof &p, PlonkChallenges &c) {
     const size_t mu = vk.mu;
-    if (mu < 1 || p.mu != mu || p.l != vk.l || pi.size() != vk.l || vk.commitments.size() != 5 || p.commitments.size() != 3 || p.p_rounds.size() != mu ||
-        p.g_rounds.size() != mu || p.batch.rounds.size() != mu || p.v_batch.rounds.size() != mu + 1 || p.g_values.size() != 5 || p.p_values.size() != 6 ||
-        p.v_values.size() != 5)
+    const GateDesc &gd = gate_desc(vk.gate);
+    const size_t ns = gd.selectors;
+    if (p.gate != vk.gate || mu < 1 || p.mu != mu || p.l != vk.l || pi.size() != vk.l || vk.commitments.size() != ns + 3 || p.commitments.size() != 3 ||
+        p.p_rounds.size() != mu || p.g_rounds.size() != mu || p.batch.rounds.size() != mu || p.v_batch.rounds.size() != mu + 1 || p.g_values.size() != ns + 3 ||
+        p.p_values.size() != 6 || p.v_values.size() != 5)
         return false;
-    HostTranscript tr("plonk");
-    tr.absorb_u64(mu).absorb_u64(vk.l).absorb(vk.commitments.data(), 144 * 5).absorb(pi);
+    for (const FrVec &r : p.g_rounds)
+        if (r.size() != gd.evals) return false;
+    HostTranscript tr(gd.label);
+    tr.absorb_u64(mu).absorb_u64(vk.l).absorb(vk.commitments.data(), 144 * (ns + 3)).absorb(pi);
     tr.absorb(p.commitments.data(), 144 * 3);
     c.alpha = tr.challenge(), c.beta = tr.challenge();
     c.gamma = tr.absorb(p.v_commitment.data(), 144).challenge();
@@ -240,10 +357,11 @@ inline bool plonk_challenges(const PlonkVk &vk, const FrVec &pi, const PlonkProo
 }
 
 // The verifier's field arithmetic (no GPU, no pairing) -> a bit per failed check (0: all hold; bit 0: malformed): 1 the wiring chain,
-// 2 the gate chain, 3 the gate's last value with in(r_g) formed here, 4 the wiring's last value with n_j formed here, 5 v(1,..,1,0) == 1,
+// 2 the gate chain (on the gate kind's nodes), 3 the gate's last value (gate_closed_form) with in(r_g) formed here, 4 the wiring's last value with n_j formed here, 5 v(1,..,1,0) == 1,
 // 6 the chains of the two batch instances (zkhip.plonk.failed_checks).
 inline unsigned plonk_failed_checks(const PlonkVk &vk, const FrVec &pi, const PlonkProof &p, const PlonkChallenges &c) {
-    const size_t mu = vk.mu, N = size_t(1) << mu;
+    const size_t mu = vk.mu, N = size_t(1) << mu, ns = gate_desc(vk.gate).selectors;
+    if (p.gate != vk.gate) return 1u;
     unsigned bad = 0;
     Fr p_target = Fr::zero(), g_target = Fr::zero();
     for (size_t i = 0; i < mu; ++i) {
@@ -258,10 +376,10 @@ inline unsigned plonk_failed_checks(const PlonkVk &vk, const FrVec &pi, const Pl
             bad |= 1u << 2;
             break;
         }
-        g_target = round_poly_nodes(p.g_rounds[i], c.r_g[i]);
+        g_target = round_poly_nodes(p.g_rounds[i].data(), p.g_rounds[i].size(), c.r_g[i]);
     }
-    const FrVec &g = p.g_values, &v = p.p_values, &t = p.v_values;  // g: q1, q2, a, b, c;  t: v(0,r), v(1,r), v(r,0), v(r,1), v(1,..,1,0)
-    if (!(bad & (1u << 2)) && g_target != eq_eval(c.tau_g, c.r_g) * (g[0] * (g[2] + g[3]) + g[1] * g[2] * g[3] - g[4] + in_eval(pi, c.r_g))) bad |= 1u << 3;
+    const FrVec &g = p.g_values, &v = p.p_values, &t = p.v_values;  // g: the selectors, a, b, c;  t: v(0,r), v(1,r), v(r,0), v(r,1), v(1,..,1,0)
+    if (!(bad & (1u << 2)) && g_target != gate_closed_form(vk.gate, eq_eval(c.tau_g, c.r_g), g, in_eval(pi, c.r_g))) bad |= 1u << 3;
     const Fr ids = slot_eval(c.r_p);
     Fr nn = Fr::one(), dd = Fr::one();
     for (size_t j = 0; j < 3; ++j) {
@@ -272,7 +390,7 @@ inline unsigned plonk_failed_checks(const PlonkVk &vk, const FrVec &pi, const Pl
     if (t[4] != Fr::one()) bad |= 1u << 5;
     std::vector<Claim> claims, v_claims;
     detail::plonk_claims(p, c.r_g, c.r_p, claims, v_claims);
-    if (failed_checks(8, claims, p.batch, c.b_alpha, c.rho_mu) || failed_checks(1, v_claims, p.v_batch, c.b_alpha, c.rho_mu1)) bad |= 1u << 6;
+    if (failed_checks(ns + 6, claims, p.batch, c.b_alpha, c.rho_mu) || failed_checks(1, v_claims, p.v_batch, c.b_alpha, c.rho_mu1)) bad |= 1u << 6;
     return bad;
 }
 
@@ -281,8 +399,10 @@ inline bool plonk_verify(Ctx &be, const PcsVk &vk_mu, const PcsVk &vk_mu1, const
     if (!plonk_challenges(vk, pi, p, c) || plonk_failed_checks(vk, pi, p, c)) return false;
     std::vector<Claim> claims, v_claims;
     detail::plonk_claims(p, c.r_g, c.r_p, claims, v_claims);
-    const G1Vec comms = {vk.commitments[0], vk.commitments[1], p.commitments[0], p.commitments[1], p.commitments[2], vk.commitments[2], vk.commitments[3],
-                         vk.commitments[4]};
+    const size_t ns = gate_desc(vk.gate).selectors;  // the tables of the mu-variate instance: the selectors, a, b, c, ssigma_0..2
+    G1Vec comms(vk.commitments.begin(), vk.commitments.begin() + ns);
+    comms.insert(comms.end(), p.commitments.begin(), p.commitments.end());
+    comms.insert(comms.end(), vk.commitments.begin() + ns, vk.commitments.end());
     return batch_open_verify(be, vk_mu, comms, claims, p.batch, c.b_alpha, c.rho_mu) &&
            batch_open_verify(be, vk_mu1, G1Vec{p.v_commitment}, v_claims, p.v_batch, c.b_alpha, c.rho_mu1);
 }
@@ -296,7 +416,7 @@ inline std::string proof_digest(const PlonkProof &p) {
     h.update(p.commitments.data(), 144 * p.commitments.size());
     h.update(p.v_commitment.data(), 144);
     for (auto &r : p.p_rounds) h.update(r.data(), 6 * 32);
-    for (auto &r : p.g_rounds) h.update(r.data(), 5 * 32);
+    for (auto &r : p.g_rounds) h.update(r.data(), 32 * r.size());
     h.update(p.g_values.data(), 32 * p.g_values.size());
     h.update(p.p_values.data(), 32 * p.p_values.size());
     h.update(p.v_values.data(), 32 * p.v_values.size());

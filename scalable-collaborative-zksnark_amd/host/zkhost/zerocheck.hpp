@@ -55,6 +55,13 @@ inline Fr round_poly_at(const std::array<Fr, 5> &e, const Fr &x) {
     return acc;
 }
 
+// the wide Plonk gate (zk_sumcheck_gate_wide) at one point: eq [ qL a + qR b + qM a b + qH a^5 - qO c + qC + in ]
+inline Fr wide_gate_value(const Fr &eq, const Fr &qL, const Fr &qR, const Fr &qM, const Fr &qO, const Fr &qC, const Fr &qH, const Fr &a, const Fr &b, const Fr &c,
+                          const Fr &in) {
+    const Fr a2 = a * a;
+    return eq * (qL * a + qR * b + qM * a * b + qH * a2 * a2 * a - qO * c + qC + in);
+}
+
 // The verifier's field arithmetic (no GPU): p_0(0) + p_0(1) == 0; p_i(0) + p_i(1) == p_{i-1}(r_{i-1}); and
 // p_{n-1}(r_{n-1}) == eq(tau, r) [q1 (a + b) + q2 a b - c + in] on the six opened values.
 inline bool verify_rounds(const GateProof &proof, const FrVec &tau, const FrVec &chal) {

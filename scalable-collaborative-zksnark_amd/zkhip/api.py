@@ -532,6 +532,20 @@ class Ctx:
         self._check(self.lib.zk_sumcheck_perm3(self.h, _ptr(eq), _ptr(tree), self._ptr_array(nums), self._ptr_array(dens), N, _h(gamma), _h(chal), _h(out), _h(last)))
         return out, last
 
+    def sumcheck_gate_wide(self, tabs, length: int, chal: np.ndarray):
+        """the wide gate identity eq [qL a + qR b + qM a b + qH a^5 - qO c + qC + in] as one degree-7 sumcheck; tabs: the eleven device
+        buffers eq, qL, qR, qM, qO, qC, qH, a, b, c, in of `length` Fr -> (evals [n,8,4], last [11,4] in that order)"""
+        if len(tabs) != 11:
+            raise ValueError("eleven tables are needed: eq, qL, qR, qM, qO, qC, qH, a, b, c, in")
+        n = max(length.bit_length() - 1, 0)
+        chal = np.ascontiguousarray(chal, dtype=np.uint64).reshape(-1, 4)
+        if len(chal) < n:
+            raise ValueError(f"{n} challenges needed, {len(chal)} given")
+        out = np.zeros((n, 8, 4), dtype=np.uint64)
+        last = np.zeros((11, 4), dtype=np.uint64)
+        self._check(self.lib.zk_sumcheck_gate_wide(self.h, self._ptr_array(tabs), length, _h(chal), _h(out), _h(last)))
+        return out, last
+
     def eq_table_acc(self, point: np.ndarray, weight: np.ndarray, acc):
         """acc[x] += weight * eq(point, x), acc a device buffer of 2^n Fr (zk_eq_table_acc; asynchronous) -> acc"""
         point = np.ascontiguousarray(point, dtype=np.uint64).reshape(-1, 4)
@@ -592,6 +606,15 @@ class Ctx:
         out, last, chal = np.zeros((mu, 6, 4), dtype=np.uint64), np.zeros((11, 4), dtype=np.uint64), np.zeros((mu, 4), dtype=np.uint64)
         self._check(self.lib.zk_sumcheck_perm3_fs(self.h, _ptr(eq), _ptr(tree), self._ptr_array(nums), self._ptr_array(dens), N, _h(gamma), self._tr(transcript),
                                                   _h(out), _h(last), _h(chal)))
+        return out, last, chal
+
+    def sumcheck_gate_wide_fs(self, tabs, length: int, transcript):
+        """sumcheck_gate_wide with derived challenges -> (evals [n,8,4], last [11,4], chal [n,4])"""
+        if len(tabs) != 11:
+            raise ValueError("eleven tables are needed: eq, qL, qR, qM, qO, qC, qH, a, b, c, in")
+        n = max(length.bit_length() - 1, 0)
+        out, last, chal = np.zeros((n, 8, 4), dtype=np.uint64), np.zeros((11, 4), dtype=np.uint64), np.zeros((n, 4), dtype=np.uint64)
+        self._check(self.lib.zk_sumcheck_gate_wide_fs(self.h, self._ptr_array(tabs), length, self._tr(transcript), _h(out), _h(last), _h(chal)))
         return out, last, chal
 
     def sumcheck_multi_fs(self, es, fs, length: int, transcript):

@@ -59,6 +59,11 @@ def gate_value(eq: int, q1: int, q2: int, a: int, b: int, c: int, inp: int) -> i
     return eq * (q1 * (a + b) + q2 * a * b - c + inp) % R_MOD
 
 
+def wide_gate_value(eq: int, qL: int, qR: int, qM: int, qO: int, qC: int, qH: int, a: int, b: int, c: int, inp: int) -> int:
+    """the wide Plonk gate (zk_sumcheck_gate_wide) at one point, on python ints"""
+    return eq * (qL * a + qR * b + qM * a * b + qH * pow(a, 5, R_MOD) - qO * c + qC + inp) % R_MOD
+
+
 def verify_rounds(proof: dict, tau, chal) -> bool:
     """
     The verifier's field arithmetic (no GPU, no pairing):

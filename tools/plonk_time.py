@@ -11,6 +11,14 @@ median of --reps:
 
 --trace-mu M runs five zk_sumcheck_perm3 calls at 2^M and nothing else (the subject of a kernel trace).  One JSON line per result goes
 to stdout and to --out (default profiles/plonk_time.txt; '-' for stdout only).
+
+--gate wide measures the wide Plonk gate instead (default --out profiles/widegate_time.txt):
+
+  sumcheck  zk_sumcheck_gate_wide and zk_sumcheck_gate_wide_fs against zk_sumcheck_gate on tables of the same 2^mu rows, with the ratio
+            the multiplication counts predict (91 / 27 per index pair);
+  proof     plonk.prove / plonk.verify of the wide kind with the four phase times, and the basic kind's prove of the same run beside them.
+
+With --gate wide, --trace-mu M runs five zk_sumcheck_gate_wide calls at 2^M.
 """
 import argparse
 import json
@@ -47,8 +55,11 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--seed", type=int, default=7)
     ap.add_argument("--trace-mu", type=int, default=0)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "plonk_time.txt"), help="file the JSON lines are written to ('-': stdout only)")
+    ap.add_argument("--gate", choices=["wide"], default=None, help="measure the wide gate against the basic one instead")
+    ap.add_argument("--out", default=None, help="file the JSON lines are written to ('-': stdout only; default profiles/plonk_time.txt, with --gate wide profiles/widegate_time.txt)")
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "widegate_time.txt" if a.gate else "plonk_time.txt")
     import zkhip
     from zkhip import dist_primitive as dp
     from zkhip import nizk, plonk
@@ -82,6 +93,57 @@ def main():
         N = 1 << mu
         return filler(N, 0), filler(2 * N, 1), [filler(N, 2 + j) for j in range(3)], [filler(N, 5 + j) for j in range(3)]
 
+    ints = lambda s: [fr_from_mont(x) for x in s]
+
+    def wide_gate():
+        if a.trace_mu:
+            mu = a.trace_mu
+            tabs, chal = [filler(1 << mu, k) for k in range(11)], splitmix_fr(mu, 4)
+            for _ in range(5):
+                be.sumcheck_gate_wide(tabs, 1 << mu, chal)
+            return
+        free = be.mem_info()[0]
+        for mu in [int(x) for x in a.mu.split(",") if x]:
+            N = 1 << mu
+            need = 32 * (11 * N + 11 * 3 * N // 4)  # eleven tables and the ping-pong scratch of 11 x (N/2 + N/4)
+            if need > 0.8 * free:
+                emit({"sumcheck_mu": mu, "skipped": "needs %.1f GiB of %.1f GiB free" % (need / 2**30, free / 2**30)})
+                continue
+            tabs, chal = [filler(N, k) for k in range(11)], splitmix_fr(mu, 4)
+            wide = timed(lambda: be.sumcheck_gate_wide(tabs, N, chal), 3, a.reps)
+            tr = Transcript(be, b"time")
+            wide_fs = timed(lambda: be.sumcheck_gate_wide_fs(tabs, N, tr), 3, a.reps)
+            basic = timed(lambda: be.sumcheck_gate(*tabs[:7], N, chal), 3, a.reps)
+            basic_fs = timed(lambda: be.sumcheck_gate_fs(*tabs[:7], N, tr), 3, a.reps)
+            tr.free()
+            del tabs
+            emit({"sumcheck_mu": mu, "gate_wide_ms": wide, "gate_wide_fs_ms": wide_fs, "gate_ms": basic, "gate_fs_ms": basic_fs, "wide_over_gate": wide / basic,
+                  "wide_fs_over_gate_fs": wide_fs / basic_fs, "predicted_by_multiplications": 91 / 27})
+        for mu in [int(x) for x in a.proof_mu.split(",") if x]:
+            g = {"proof_mu": mu}
+            for kind, sample in (("wide", plonk.sample_circuit_wide), ("basic", plonk.sample_circuit)):
+                c = sample(mu, a.seed)
+                pcs = dp.PolynomialCommitmentCub.new(be, c["s"]).mature()
+                pk, vk = plonk.preprocess(be, pcs, c, pr.powers_of_g2(ints(c["s"])))
+                wires = [be.to_device(c[k]) for k in ("a", "b", "c")]
+                for rep in range(3):  # the last of three runs is reported (the first ones grow the arenas)
+                    tb = {}
+                    proof, g[kind + "_prove_ms"] = once(lambda: plonk.prove(be, pk, *wires, c["public_inputs"], timing=tb))
+                    g.update({kind + "_prove_" + k.replace("_s", "_ms"): v * 1e3 for k, v in tb.items()})
+                for rep in range(2):
+                    ok, g[kind + "_verify_ms"] = once(lambda: plonk.verify(be, vk, c["public_inputs"], proof))
+                g[kind + "_verdict"] = bool(ok)
+                del pk, vk, pcs, wires, proof
+            g["wide_prove_over_basic"] = g["wide_prove_ms"] / g["basic_prove_ms"]
+            emit(g)
+
+    if a.gate == "wide":
+        wide_gate()
+        if out:
+            out.close()
+        be.close()
+        return 0
+
     if a.trace_mu:
         mu = a.trace_mu
         eq, tree, nums, dens = perm3_tables(mu)
@@ -113,7 +175,6 @@ def main():
         emit({"sumcheck_mu": mu, "perm3_ms": perm3, "perm3_fs_ms": perm3_fs, "wiring_4N_ms": wiring, "perm3_over_wiring_4N": perm3 / wiring,
               "predicted_by_multiplications": 59 / 92})
 
-    ints = lambda s: [fr_from_mont(x) for x in s]
     for mu in [int(x) for x in a.proof_mu.split(",") if x]:
         N = 1 << mu
         c = plonk.sample_circuit(mu, a.seed)
