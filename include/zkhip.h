@@ -194,6 +194,25 @@ int zk_sumcheck_perm3(zk_ctx *ctx, const void *d_eq, const void *d_tree, const v
  * power of two in [1, 256]: ZK_ERR_INVALID; nothing is launched or written on error. */
 int zk_sumcheck_gate_wide(zk_ctx *ctx, const void *const d_tabs[11], size_t len, const uint64_t *h_chal,
                           uint64_t *h_out_evals, uint64_t *h_last);
+/* ---- the lookup argument (LogUp): every value of a column f lies in a table t, both of N = 2^n Fr ----
+ * The multiplicities m[y] = #{x : idx[x] = y} of the caller's row-to-table indices (idx: N u32 on the device, f[x] = t[idx[x]]) as
+ * N Fr in Montgomery form.  One pass checks idx[x] < N BEFORE anything is read through it, compares the four limbs of f[x] and
+ * t[idx[x]] and counts on u32 counters; a second pass writes the counters as field elements.  Blocking (a status word is read back).
+ * An index >= N or a row whose value is not the table's entry: ZK_ERR_INVALID, zk_last_error gives the number of such rows, d_m is
+ * unspecified, nothing is read out of bounds.  N < 2, not a power of two or > 2^32, or a null pointer: ZK_ERR_INVALID, nothing is
+ * launched.  The inputs are not modified. */
+int zk_lookup_multiplicities(zk_ctx *ctx, const void *d_f, const void *d_t, const uint32_t *d_idx, size_t N, void *d_m);
+/* The sum identity of LogUp and the definitions of its two helper columns as ONE sumcheck: with df = beta + f, dt = beta + t,
+ * hf = 1 / df, ht = m / dt the prover's rounds for
+ *     L(x) = hf(x) - ht(x) + E(x) [ hf(x) df(x) - 1 + gamma ( ht(x) dt(x) - m(x) ) ],        E = lambda eq(tau, .)
+ * over the six tables d_tabs = E, df, dt, m, hf, ht of len = 2^n Fr each (not modified; lambda is folded into E with
+ * zk_eq_table_acc, beta into df and dt).  The first two terms are NOT multiplied by E.  Round i writes four Fr to h_out_evals: the
+ * round polynomial (degree 3) at t = 0, 1, 2, 3, every table extended as (1 - t) lo + t hi, then folds the six tables with h_chal[i].
+ * h_out_evals: 4 n Fr; h_last: the six remaining elements in the order of d_tabs, 6 Fr.  Blocking: the results are on the host when
+ * it returns.  len < 2, not a power of two or > 2^35, a null pointer, or the knob lookup_local_e not a power of two in [1, 512]:
+ * ZK_ERR_INVALID; nothing is launched or written on error. */
+int zk_sumcheck_lookup(zk_ctx *ctx, const void *const d_tabs[6], size_t len, const uint64_t h_gamma[4],
+                       const uint64_t *h_chal, uint64_t *h_out_evals, uint64_t *h_last);
 /* ---- batch opening: K claims f_{j_k}(z_k) = v_k on J tables of one size -> one degree-2 sumcheck and one opening ---- */
 /* d_acc[x] += weight * eq(point, x) over the cube of n variables (x_0 the TOP index bit), d_acc: 2^n Fr, read and written.  The
  * doubling scheme of zk_eq_table seeded with the weight; the last level is added into d_acc instead of stored, so a claim costs
@@ -248,6 +267,9 @@ int zk_sumcheck_perm3_fs(zk_ctx *ctx, const void *d_eq, const void *d_tree, cons
                          uint64_t *h_out_evals, uint64_t *h_last, uint64_t *h_chal_out);
 int zk_sumcheck_gate_wide_fs(zk_ctx *ctx, const void *const d_tabs[11], size_t len, zk_transcript *t,
                              uint64_t *h_out_evals, uint64_t *h_last, uint64_t *h_chal_out);
+/* zk_sumcheck_lookup in the same form (4 Fr absorbed per round) */
+int zk_sumcheck_lookup_fs(zk_ctx *ctx, const void *const d_tabs[6], size_t len, const uint64_t h_gamma[4],
+                          zk_transcript *t, uint64_t *h_out_evals, uint64_t *h_last, uint64_t *h_chal_out);
 int zk_sumcheck_multi_fs(zk_ctx *ctx, size_t count, const void *const *d_e, const void *const *d_f, size_t len,
                          zk_transcript *t, uint64_t *h_out_triples, uint64_t *h_last_e, uint64_t *h_last_f,
                          uint64_t *h_chal_out);

@@ -73,9 +73,10 @@ struct zk_ctx {
     bool gate_lds_raised = false;  // zk_gate.hip: k_gate_local's dynamic LDS limit has been raised on this ctx's device
     bool wiring_lds_raised = false;  // zk_wiring.hip: the same for k_wiring_local
     bool multi_lds_raised = false;   // zk_batchopen.hip: the same for k_multi_local
-    bool fs_lds_raised[5] = {false, false, false, false, false};  // zk_fs.hip: the same for its five local kernels (gate, wiring, multi, perm3, wide gate)
+    bool fs_lds_raised[6] = {false, false, false, false, false, false};  // zk_fs.hip: the same for its six local kernels (gate, wiring, multi, perm3, wide gate, lookup)
     bool perm3_lds_raised = false;   // zk_perm3.hip: the same for k_perm3_local
     bool gatew_lds_raised = false;   // zk_gatew.hip: the same for k_gatew_local
+    bool lookup_lds_raised = false;  // zk_lookup.hip: the same for k_lookup_local
     // party exchanges (zk_comm.cpp): an RCCL communicator bound to this ctx's GPU
     void* comm = nullptr;
     int comm_rank = 0, comm_world = 1;
@@ -130,6 +131,8 @@ struct Tuning {
     long perm3_local_e = 256;   // longest table (elements, a power of two <= 256: eleven tables of 512 would be 176 KiB of LDS) the single-workgroup LDS stage takes over; 1: HBM passes down to the last element
     // wide gate sumcheck (zk_gatew.hip)
     long gatew_local_e = 256;   // longest table (elements, a power of two <= 256: eleven tables of 512 would be 176 KiB of LDS) the single-workgroup LDS stage takes over; 1: HBM passes down to the last element
+    // lookup sumcheck (zk_lookup.hip)
+    long lookup_local_e = 512;  // longest table (elements, a power of two <= 512) the single-workgroup LDS stage takes over; 1: HBM passes down to the last element
     // MSM (zk_msm.hip)
     long msm_table_dc = 0;    // window-table width delta (sweeps)
     long msm_qstep = 2;       // window-class quantisation step of batches
@@ -216,6 +219,11 @@ int sumcheck_perm3(zk_ctx* ctx, const void* d_eq, const void* d_tree, const void
 // d_tabs: eq, qL, qR, qM, qO, qC, qH, a, b, c, in; h_out_evals: rounds x 8 Fr; h_last: the eleven remaining elements in that order
 int sumcheck_gate_wide(zk_ctx* ctx, const void* const* d_tabs, size_t len, const uint64_t* h_chal, uint64_t* h_out_evals, uint64_t* h_last);
 
+// ---- zk_lookup.hip ----
+int lookup_multiplicities(zk_ctx* ctx, const void* d_f, const void* d_t, const uint32_t* d_idx, size_t N, void* d_m);
+// d_tabs, h_last: E, df, dt, m, hf, ht; h_out_evals: rounds x 4 Fr
+int sumcheck_lookup(zk_ctx* ctx, const void* const* d_tabs, size_t len, const uint64_t* h_gamma, const uint64_t* h_chal, uint64_t* h_out_evals, uint64_t* h_last);
+
 // ---- zk_batchopen.hip ----
 int eq_table_acc(zk_ctx* ctx, const uint64_t* h_point, size_t n, const uint64_t* h_weight, void* d_acc);
 int fr_lincomb(zk_ctx* ctx, size_t count, const void* const* d_tabs, const uint64_t* h_coeffs, size_t len, void* d_out);
@@ -240,6 +248,8 @@ int sumcheck_multi_fs(zk_ctx* ctx, size_t count, const void* const* d_e, const v
 int sumcheck_perm3_fs(zk_ctx* ctx, const void* d_eq, const void* d_tree, const void* const* d_num, const void* const* d_den, size_t N, const uint64_t* h_gamma,
                       zk_transcript* t, uint64_t* h_out_evals, uint64_t* h_last, uint64_t* h_chal_out);
 int sumcheck_gate_wide_fs(zk_ctx* ctx, const void* const* d_tabs, size_t len, zk_transcript* t, uint64_t* h_out_evals, uint64_t* h_last, uint64_t* h_chal_out);
+int sumcheck_lookup_fs(zk_ctx* ctx, const void* const* d_tabs, size_t len, const uint64_t* h_gamma, zk_transcript* t, uint64_t* h_out_evals, uint64_t* h_last,
+                       uint64_t* h_chal_out);
 
 // ---- zk_msm.hip ----
 struct MsmItem {

@@ -1,4 +1,4 @@
-// zk_fs.hip -- the five fused sumchecks (zk_gate.hip, zk_wiring.hip, zk_perm3.hip, zk_gatew.hip, zk_batchopen.hip) with their challenges drawn from a
+// zk_fs.hip -- the six fused sumchecks (zk_gate.hip, zk_wiring.hip, zk_perm3.hip, zk_gatew.hip, zk_lookup.hip, zk_batchopen.hip) with their challenges drawn from a
 // Fiat-Shamir transcript ON THE DEVICE (zk_transcript.hip, sha256.cuh): challenge r_p is a hash of round p's evaluations, so the
 // fold by r_p cannot share a sweep with round p's sums as it does in the preset-challenge kernels.  The shape here:
 //   pass 0            evaluate only: the sums of round 0 over the caller's tables (nothing is written but the partials),
@@ -23,13 +23,15 @@ namespace zk {
 
 // An identity eq(x) [ inner(tables 1 .. kTabs - 1) ]: its table count, the evaluations of a round (degree + 1), the longest table of
 // the local stage (kTabs tables of kLocalMax elements fit the CU's LDS), its slot of zk_ctx::fs_lds_raised, the waves per SIMD its pass is
-// compiled for, and the bracket.
+// compiled for, and the bracket.  kFree: the identity has a term free(tables), LINEAR in the
+// tables, that eq does not multiply; a lane sums it apart from the products (k_lookup_pass, zk_lookup.hip, says why).
 struct GateKind {  // eq, q1, q2, a, b, c, in
     static constexpr int kTabs = 7;
     static constexpr int kEvals = 5;
     static constexpr int kSlot = 0;
     static constexpr unsigned kLocalMax = kGateLocalMax;
     static constexpr int kWaves = 2;
+    static constexpr bool kFree = false;
     __device__ static __forceinline__ Fr inner(const Fr&, const Fr (&v)[kTabs]) { return gate_inner(v[1], v[2], v[3], v[4], v[5], v[6]); }
 };
 struct WireKind {  // eq, v1x, vx0, vx1, h, num, den
@@ -38,6 +40,7 @@ struct WireKind {  // eq, v1x, vx0, vx1, h, num, den
     static constexpr int kSlot = 1;
     static constexpr unsigned kLocalMax = kGateLocalMax;
     static constexpr int kWaves = 2;
+    static constexpr bool kFree = false;
     __device__ static __forceinline__ Fr inner(const Fr& gamma, const Fr (&v)[kTabs]) { return wiring_inner(gamma, v[1], v[2], v[3], v[4], v[5], v[6]); }
 };
 struct Perm3Kind {  // eq, v1x, vx0, vx1, h, n_0, n_1, n_2, d_0, d_1, d_2
@@ -46,6 +49,7 @@ struct Perm3Kind {  // eq, v1x, vx0, vx1, h, n_0, n_1, n_2, d_0, d_1, d_2
     static constexpr int kSlot = 3;
     static constexpr unsigned kLocalMax = kPerm3LocalMax;
     static constexpr int kWaves = 1;  // 22 table registers of 8 limbs and six 17-limb sums: the 264 .. 512 register bracket
+    static constexpr bool kFree = false;
     __device__ static __forceinline__ Fr inner(const Fr& gamma, const Fr (&v)[kTabs]) { return perm3_inner(gamma, v); }
 };
 struct GatewKind {  // eq, qL, qR, qM, qO, qC, qH, a, b, c, in
@@ -54,7 +58,18 @@ struct GatewKind {  // eq, qL, qR, qM, qO, qC, qH, a, b, c, in
     static constexpr int kSlot = 4;
     static constexpr unsigned kLocalMax = kGatewLocalMax;
     static constexpr int kWaves = 1;  // 22 table registers of 8 limbs and eight 17-limb sums: the 264 .. 512 register bracket
+    static constexpr bool kFree = false;
     __device__ static __forceinline__ Fr inner(const Fr&, const Fr (&v)[kTabs]) { return gatew_inner(v); }
+};
+struct LookupKind {  // E, df, dt, m, hf, ht
+    static constexpr int kTabs = kLookupTabs;
+    static constexpr int kEvals = kLookupEvals;
+    static constexpr int kSlot = 5;
+    static constexpr unsigned kLocalMax = kGateLocalMax;
+    static constexpr int kWaves = 2;
+    static constexpr bool kFree = true;  // hf - ht
+    __device__ static __forceinline__ Fr inner(const Fr& gamma, const Fr (&v)[kTabs]) { return lookup_inner(gamma, v[1], v[2], v[3], v[4], v[5]); }
+    __device__ static __forceinline__ Fr free(const Fr (&v)[kTabs]) { return fr_sub(v[4], v[5]); }
 };
 
 // ---------------------------------------------------------------------------------------
@@ -72,6 +87,7 @@ k_fs_pass(FsIn<K::kTabs> in, FsOut<K::kTabs> out, size_t half, const void* __res
         for (int i = 0; i < 17; i++) w[t][i] = 0;
     Fr r = fp_zero<FrCfg>();
     if (FOLD) r = fr_load(d_chal, 0);
+    Fr g0 = fp_zero<FrCfg>(), gd = fp_zero<FrCfg>();  // kFree: the lane's sums of free(lo) and free(hi - lo)
     for (size_t j = (size_t)blockIdx.x * kGateBlock + threadIdx.x; j < half; j += (size_t)gridDim.x * kGateBlock) {
         Fr v[K::kTabs], d[K::kTabs];
 #pragma unroll
@@ -90,6 +106,7 @@ k_fs_pass(FsIn<K::kTabs> in, FsOut<K::kTabs> out, size_t half, const void* __res
                 d[k] = fr_sub(fr_load(in.t[k], (j + half) << sh), v[k]);
             }
         }
+        if constexpr (K::kFree) g0 = fr_add(g0, K::free(v)), gd = fr_add(gd, K::free(d));
 #pragma unroll
         for (int t = 0; t < K::kEvals; t++) {
             fp_mac_wide(w[t], v[0], K::inner(gamma.r, v));
@@ -97,6 +114,13 @@ k_fs_pass(FsIn<K::kTabs> in, FsOut<K::kTabs> out, size_t half, const void* __res
 #pragma unroll
                 for (int k = 0; k < K::kTabs; k++) v[k] = fr_add(v[k], d[k]);
             }
+        }
+    }
+    if constexpr (K::kFree) {
+#pragma unroll
+        for (int t = 0; t < K::kEvals; t++) {  // free at t = g0 + t gd
+            gate_wide_add_hi(w[t], g0);
+            g0 = fr_add(g0, gd);
         }
     }
     const unsigned wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -182,6 +206,7 @@ __global__ void __launch_bounds__(kGateBlock) k_fs_local(FsIn<K::kTabs> in, unsi
 #pragma unroll
             for (int t = 0; t < K::kEvals; t++) {
                 acc[t] = fr_add(acc[t], fr_mul(v[0], K::inner(gamma.r, v)));
+                if constexpr (K::kFree) acc[t] = fr_add(acc[t], K::free(v));
                 if (t + 1 < K::kEvals) {
 #pragma unroll
                     for (int k = 0; k < K::kTabs; k++) v[k] = fr_add(v[k], d[k]);
@@ -513,6 +538,18 @@ int sumcheck_gate_wide_fs(zk_ctx* ctx, const void* const* d_tabs, size_t len, zk
     GateChal none;
     std::memset(&none, 0, sizeof(none));
     return run_fs<GatewKind>(ctx, "zk_sumcheck_gate_wide_fs", first, len, emax, 1, none, t, h_out_evals, h_last, h_chal_out);
+}
+
+int sumcheck_lookup_fs(zk_ctx* ctx, const void* const* d_tabs, size_t len, const uint64_t* h_gamma, zk_transcript* t, uint64_t* h_out_evals, uint64_t* h_last,
+                       uint64_t* h_chal_out) {
+    size_t emax;
+    const int rc = local_e(ctx, tuning().lookup_local_e, "lookup_local_e", emax);
+    if (rc) return rc;
+    FsIn<kLookupTabs> first;
+    for (int k = 0; k < kLookupTabs; k++) first.t[k] = d_tabs[k], first.sh[k] = 0;
+    GateChal gamma;
+    std::memcpy(&gamma.r, h_gamma, 32);
+    return run_fs<LookupKind>(ctx, "zk_sumcheck_lookup_fs", first, len, emax, 2, gamma, t, h_out_evals, h_last, h_chal_out);
 }
 
 int sumcheck_multi_fs(zk_ctx* ctx, size_t count, const void* const* d_e, const void* const* d_f, size_t len, zk_transcript* t, uint64_t* h_out_triples,

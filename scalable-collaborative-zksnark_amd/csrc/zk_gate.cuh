@@ -1,4 +1,4 @@
-// zk_gate.cuh -- what the fused sumchecks (zk_gate.hip: gate identity, zk_wiring.hip: wiring identity, zk_batchopen.hip, zk_perm3.hip, zk_fs.hip) share: launch geometry, the
+// zk_gate.cuh -- what the fused sumchecks (zk_gate.hip: gate identity, zk_wiring.hip: wiring identity, zk_batchopen.hip, zk_perm3.hip, zk_lookup.hip, zk_fs.hip) share: launch geometry, the
 // argument blocks of their kernels and the 544-bit lazily reduced sums (one 80-byte slot per wave, evaluation and pass).
 #pragma once
 #include "fp.cuh"
@@ -115,6 +115,25 @@ __device__ __forceinline__ Fr gatew_inner(const Fr (&v)[kGatewTabs]) {
     const Fr lin = fr_add(fr_mul(v[1], a), fr_mul(v[2], b));
     const Fr hi = fr_add(fr_mul(fr_mul(v[3], a), b), fr_mul(v[6], a5));
     return fr_add(fr_add(fr_sub(fr_add(lin, hi), fr_mul(v[4], v[9])), v[5]), v[10]);
+}
+
+// the lookup identity (zk_lookup.hip, its transcript-driven form in zk_fs.hip): E, df, dt, m, hf, ht
+static constexpr int kLookupTabs = 6;
+static constexpr int kLookupEvals = 4;  // t = 0 .. 3
+
+// [ hf df - 1 + gamma ( ht dt - m ) ] of one point: three multiplications
+__device__ __forceinline__ Fr lookup_inner(const Fr& gamma, const Fr& df, const Fr& dt, const Fr& m, const Fr& hf, const Fr& ht) {
+    const Fr p = fr_sub(fr_mul(hf, df), fp_one<FrCfg>());
+    const Fr q = fr_mul(gamma, fr_sub(fr_mul(ht, dt), m));
+    return fr_add(p, q);
+}
+// A sum of the term of an identity that eq does not multiply (the lookup's hf - ht), a canonical g < r, enters a lazily reduced sum
+// as g 2^256: its eight limbs are added from limb 8 on, and the one reduction W0 R^-1 + W1 + W2 R of gate_reduce_value gives it back.
+__device__ __forceinline__ void gate_wide_add_hi(u32 (&a)[17], const Fr& g) {
+    u32 c = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) a[8 + i] = addc(a[8 + i], g.l[i], c);
+    a[16] += c;
 }
 
 // One workgroup of kGateBlock lanes adds the nbw per-wave partials from slot `base` on and reduces W0 + W1 R + W2 R^2 (a sum of

@@ -301,6 +301,24 @@ class Ctx {
         check(zk_sumcheck_gate_wide(h_, p, len, chal[0].v, r.sums[0].v, last[0].v));
         return r;
     }
+    // zk_lookup_multiplicities: m[y] = #{x : idx[x] = y} as N Fr; idx = N u32 on the device.  A row that is not in the table: ZkError(ZK_ERR_INVALID)
+    DevPtr lookup_multiplicities(const DevPtr &f, const DevPtr &t, const DevPtr &idx, size_t N) {
+        DevPtr m = alloc_fr(N);
+        check(zk_lookup_multiplicities(h_, f.get(), t.get(), (const uint32_t *)idx.get(), N, m.get()));
+        return m;
+    }
+    // zk_sumcheck_lookup: tabs = E, df, dt, m, hf, ht -> r.sums = 4 Fr per round (t = 0 .. 3), `last` = the six remaining elements
+    ScResult sumcheck_lookup(const std::array<DevPtr, 6> &tabs, size_t len, const Fr &gamma, const FrVec &chal, FrVec &last) {
+        size_t n = log2_exact(len);
+        need(n >= 1 && chal.size() >= n, "sumcheck_lookup: fewer challenges than rounds");
+        ScResult r;
+        r.sums.resize(4 * n);
+        last.assign(6, Fr::zero());
+        const void *p[6];
+        for (int k = 0; k < 6; k++) p[k] = tabs[k].get();
+        check(zk_sumcheck_lookup(h_, p, len, gamma.v, chal[0].v, r.sums[0].v, last[0].v));
+        return r;
+    }
     // zk_eq_table_acc: acc[x] += weight * eq(point, x), acc = 2^n Fr (asynchronous)
     void eq_table_acc(const FrVec &point, const Fr &weight, const DevPtr &acc) {
         check(zk_eq_table_acc(h_, point.empty() ? nullptr : point[0].v, point.size(), weight.v, acc.get()));
@@ -386,6 +404,18 @@ class Ctx {
         const void *p[11];
         for (int k = 0; k < 11; k++) p[k] = tabs[k].get();
         check(zk_sumcheck_gate_wide_fs(h_, p, len, t.h, r.sums[0].v, last[0].v, chal[0].v));
+        return r;
+    }
+    ScResult sumcheck_lookup_fs(const std::array<DevPtr, 6> &tabs, size_t len, const Fr &gamma, DeviceTranscript &t, FrVec &last, FrVec &chal) {
+        size_t n = log2_exact(len);
+        need(n >= 1, "sumcheck_lookup_fs: at least one round");
+        ScResult r;
+        r.sums.resize(4 * n);
+        last.assign(6, Fr::zero());
+        chal.assign(n, Fr::zero());
+        const void *p[6];
+        for (int k = 0; k < 6; k++) p[k] = tabs[k].get();
+        check(zk_sumcheck_lookup_fs(h_, p, len, gamma.v, t.h, r.sums[0].v, last[0].v, chal[0].v));
         return r;
     }
     ScResult sumcheck_multi_fs(const std::vector<DevPtr> &es, const std::vector<DevPtr> &fs, size_t len, DeviceTranscript &t, FrVec &last_e, FrVec &last_f,

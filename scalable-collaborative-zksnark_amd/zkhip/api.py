@@ -11,7 +11,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import ZK_ERR_DIV_ZERO, ZK_ERR_LENGTH, test_hooks
+from ._lib import ZK_ERR_DIV_ZERO, ZK_ERR_INVALID, ZK_ERR_LENGTH, test_hooks
 
 
 _TRACE_MSM = bool(os.environ.get("ZKHIP_TRACE_MSM"))
@@ -546,6 +546,32 @@ class Ctx:
         self._check(self.lib.zk_sumcheck_gate_wide(self.h, self._ptr_array(tabs), length, _h(chal), _h(out), _h(last)))
         return out, last
 
+    def lookup_multiplicities(self, f, t, idx, N: int, out=None):
+        """m[y] = #{x : idx[x] = y} as N Fr for the lookup argument (zk_lookup_multiplicities; blocking): f, t device buffers of N Fr, idx one
+        of N u32 with f[x] = t[idx[x]].  An index out of range or a row whose value is not the table's entry: ValueError -- as is every other ZK_ERR_INVALID of the call
+        (N < 2, not a power of two or > 2^32, a null pointer), with the library's message."""
+        out = out or self.alloc(max(32 * N, 1))
+        rc = self.lib.zk_lookup_multiplicities(self.h, _ptr(f), _ptr(t), _ptr(idx), N, _ptr(out))
+        if rc == ZK_ERR_INVALID:
+            raise ValueError((self.lib.zk_last_error(self.h) or b"").decode())
+        self._check(rc)
+        return out
+
+    def sumcheck_lookup(self, tabs, length: int, gamma: np.ndarray, chal: np.ndarray):
+        """the lookup identity hf - ht + E [hf df - 1 + gamma (ht dt - m)] as one degree-3 sumcheck; tabs: the six device buffers
+        E, df, dt, m, hf, ht of `length` Fr -> (evals [n,4,4], last [6,4] in that order)"""
+        if len(tabs) != 6:
+            raise ValueError("six tables are needed: E, df, dt, m, hf, ht")
+        n = max(length.bit_length() - 1, 0)
+        gamma = np.ascontiguousarray(gamma, dtype=np.uint64).reshape(4)
+        chal = np.ascontiguousarray(chal, dtype=np.uint64).reshape(-1, 4)
+        if len(chal) < n:
+            raise ValueError(f"{n} challenges needed, {len(chal)} given")
+        out = np.zeros((n, 4, 4), dtype=np.uint64)
+        last = np.zeros((6, 4), dtype=np.uint64)
+        self._check(self.lib.zk_sumcheck_lookup(self.h, self._ptr_array(tabs), length, _h(gamma), _h(chal), _h(out), _h(last)))
+        return out, last
+
     def eq_table_acc(self, point: np.ndarray, weight: np.ndarray, acc):
         """acc[x] += weight * eq(point, x), acc a device buffer of 2^n Fr (zk_eq_table_acc; asynchronous) -> acc"""
         point = np.ascontiguousarray(point, dtype=np.uint64).reshape(-1, 4)
@@ -615,6 +641,16 @@ class Ctx:
         n = max(length.bit_length() - 1, 0)
         out, last, chal = np.zeros((n, 8, 4), dtype=np.uint64), np.zeros((11, 4), dtype=np.uint64), np.zeros((n, 4), dtype=np.uint64)
         self._check(self.lib.zk_sumcheck_gate_wide_fs(self.h, self._ptr_array(tabs), length, self._tr(transcript), _h(out), _h(last), _h(chal)))
+        return out, last, chal
+
+    def sumcheck_lookup_fs(self, tabs, length: int, gamma: np.ndarray, transcript):
+        """sumcheck_lookup with derived challenges -> (evals [n,4,4], last [6,4], chal [n,4])"""
+        if len(tabs) != 6:
+            raise ValueError("six tables are needed: E, df, dt, m, hf, ht")
+        n = max(length.bit_length() - 1, 0)
+        gamma = np.ascontiguousarray(gamma, dtype=np.uint64).reshape(4)
+        out, last, chal = np.zeros((n, 4, 4), dtype=np.uint64), np.zeros((6, 4), dtype=np.uint64), np.zeros((n, 4), dtype=np.uint64)
+        self._check(self.lib.zk_sumcheck_lookup_fs(self.h, self._ptr_array(tabs), length, _h(gamma), self._tr(transcript), _h(out), _h(last), _h(chal)))
         return out, last, chal
 
     def sumcheck_multi_fs(self, es, fs, length: int, transcript):
