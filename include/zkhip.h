@@ -213,6 +213,30 @@ int zk_lookup_multiplicities(zk_ctx *ctx, const void *d_f, const void *d_t, cons
  * ZK_ERR_INVALID; nothing is launched or written on error. */
 int zk_sumcheck_lookup(zk_ctx *ctx, const void *const d_tabs[6], size_t len, const uint64_t h_gamma[4],
                        const uint64_t *h_chal, uint64_t *h_out_evals, uint64_t *h_last);
+/* ---- the lookup argument as a path of a Plonk circuit: selector-gated, over the three wire columns ----
+ * Row x of N = 2^n with qk(x) = 1 claims (a, b, c)(x) = (t0, t1, t2)(idx[x]); a row with qk(x) = 0 claims nothing.  qk entries are 0 or
+ * the Montgomery form of 1.  zk_lookup3_multiplicities writes m[y] = #{x : qk(x) = 1, idx[x] = y} as N Fr in Montgomery form (d_w: a, b,
+ * c; d_t: t0, t1, t2; d_idx: N u32).  A row with qk = 0 is skipped and its index is never read through.  A row with qk = 1 is good when
+ * idx[x] < N -- checked BEFORE anything is read through it -- and all twelve limbs of the two triples agree.  Any other row, a qk that is
+ * neither 0 nor 1 among them, is a bad row: ZK_ERR_INVALID, zk_last_error gives the number of such rows ("K of N rows ..."), d_m is
+ * unspecified, nothing is read out of bounds.  Blocking.  N < 2, not a power of two or > 2^32, or a null pointer: ZK_ERR_INVALID,
+ * nothing is launched.  The inputs are not modified. */
+int zk_lookup3_multiplicities(zk_ctx *ctx, const void *const d_w[3], const void *const d_t[3], const void *d_qk,
+                              const uint32_t *d_idx, size_t N, void *d_m);
+/* df = beta + a + zeta b + zeta^2 c and dt = beta + t0 + zeta t1 + zeta^2 t2 in ONE pass (N Fr each).  The inputs are not modified; an
+ * output may not alias an input.  ASYNCHRONOUS on the ctx stream like zk_perm3_terms.  N < 2, not a power of two or > 2^35, or a null
+ * pointer: ZK_ERR_INVALID, nothing is launched. */
+int zk_lookup3_terms(zk_ctx *ctx, const void *const d_w[3], const void *const d_t[3], size_t N, const uint64_t h_zeta[4],
+                     const uint64_t h_beta[4], void *d_df, void *d_dt);
+/* zk_sumcheck_lookup with a selector: with hf = qk / df and ht = m / dt the prover's rounds for
+ *     L(x) = hf(x) - ht(x) + E(x) [ hf(x) df(x) - qk(x) + gamma ( ht(x) dt(x) - m(x) ) ],        E = lambda eq(tau, .)
+ * over the SEVEN tables d_tabs = E, df, dt, m, hf, ht, qk of len = 2^n Fr each (not modified).  Round i writes four Fr to h_out_evals: the
+ * round polynomial (degree 3) at t = 0, 1, 2, 3, then folds the seven tables with h_chal[i].  h_out_evals: 4 n Fr; h_last: the seven
+ * remaining elements in the order of d_tabs, 7 Fr.  With qk = 1 everywhere the rounds and the first six last values are those of
+ * zk_sumcheck_lookup, bit for bit.  Blocking.  len < 2, not a power of two or > 2^35, a null pointer, or the knob lookupsel_local_e not
+ * a power of two in [1, 512]: ZK_ERR_INVALID; nothing is launched or written on error. */
+int zk_sumcheck_lookup_sel(zk_ctx *ctx, const void *const d_tabs[7], size_t len, const uint64_t h_gamma[4],
+                           const uint64_t *h_chal, uint64_t *h_out_evals, uint64_t *h_last);
 /* ---- batch opening: K claims f_{j_k}(z_k) = v_k on J tables of one size -> one degree-2 sumcheck and one opening ---- */
 /* d_acc[x] += weight * eq(point, x) over the cube of n variables (x_0 the TOP index bit), d_acc: 2^n Fr, read and written.  The
  * doubling scheme of zk_eq_table seeded with the weight; the last level is added into d_acc instead of stored, so a claim costs
@@ -270,6 +294,9 @@ int zk_sumcheck_gate_wide_fs(zk_ctx *ctx, const void *const d_tabs[11], size_t l
 /* zk_sumcheck_lookup in the same form (4 Fr absorbed per round) */
 int zk_sumcheck_lookup_fs(zk_ctx *ctx, const void *const d_tabs[6], size_t len, const uint64_t h_gamma[4],
                           zk_transcript *t, uint64_t *h_out_evals, uint64_t *h_last, uint64_t *h_chal_out);
+/* zk_sumcheck_lookup_sel in the same form (4 Fr absorbed per round) */
+int zk_sumcheck_lookup_sel_fs(zk_ctx *ctx, const void *const d_tabs[7], size_t len, const uint64_t h_gamma[4],
+                              zk_transcript *t, uint64_t *h_out_evals, uint64_t *h_last, uint64_t *h_chal_out);
 int zk_sumcheck_multi_fs(zk_ctx *ctx, size_t count, const void *const *d_e, const void *const *d_f, size_t len,
                          zk_transcript *t, uint64_t *h_out_triples, uint64_t *h_last_e, uint64_t *h_last_f,
                          uint64_t *h_chal_out);

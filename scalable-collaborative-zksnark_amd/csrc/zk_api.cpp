@@ -24,7 +24,7 @@ static const TuneKey kTuneKeys[] = {
     {"wiring_local_e", &Tuning::wiring_local_e}, {"wiring_pass_wg", &Tuning::wiring_pass_wg},
     {"multi_local_e", &Tuning::multi_local_e}, {"multi_pass_wg", &Tuning::multi_pass_wg},
     {"perm3_local_e", &Tuning::perm3_local_e}, {"gatew_local_e", &Tuning::gatew_local_e},
-    {"lookup_local_e", &Tuning::lookup_local_e},
+    {"lookup_local_e", &Tuning::lookup_local_e}, {"lookupsel_local_e", &Tuning::lookupsel_local_e},
     {"msm_table_dc", &Tuning::msm_table_dc}, {"msm_qstep", &Tuning::msm_qstep}, {"msm_tile", &Tuning::msm_tile}, {"msm_pair", &Tuning::msm_pair},
     {"msm_fixq", &Tuning::msm_fixq}, {"msm_quad", &Tuning::msm_quad}, {"msm_stage", &Tuning::msm_stage}, {"msm_split", &Tuning::msm_split},
     {"msm_np", &Tuning::msm_np}, {"msm_fused_min", &Tuning::msm_fused_min}, {"msm_l2_tiled", &Tuning::msm_l2_tiled}, {"msm_tab_spt", &Tuning::msm_tab_spt}, {"msm_idx_ahead", &Tuning::msm_idx_ahead}, {"msm_share_l1", &Tuning::msm_share_l1}, {"srs_table_batched", &Tuning::srs_table_batched}, {"msm_debug", &Tuning::msm_debug}, {"msm_serial", &Tuning::msm_serial}, {"msm_size_classes", &Tuning::msm_size_classes},
@@ -448,6 +448,21 @@ int zk_sumcheck_lookup(zk_ctx* ctx, const void* const d_tabs[6], size_t len, con
     for (int k = 0; k < 6; k++) NEED(ctx, d_tabs[k]);
     return sumcheck_lookup(ctx, d_tabs, len, h_gamma, h_chal, h_out_evals, h_last);
 }
+int zk_lookup3_multiplicities(zk_ctx* ctx, const void* const d_w[3], const void* const d_t[3], const void* d_qk, const uint32_t* d_idx, size_t N, void* d_m) {
+    NEED(ctx, d_w && d_t && d_qk && d_idx && d_m);
+    for (int j = 0; j < 3; j++) NEED(ctx, d_w[j] && d_t[j]);
+    return lookup3_multiplicities(ctx, d_w, d_t, d_qk, d_idx, N, d_m);
+}
+int zk_lookup3_terms(zk_ctx* ctx, const void* const d_w[3], const void* const d_t[3], size_t N, const uint64_t h_zeta[4], const uint64_t h_beta[4], void* d_df, void* d_dt) {
+    NEED(ctx, d_w && d_t && h_zeta && h_beta && d_df && d_dt);
+    for (int j = 0; j < 3; j++) NEED(ctx, d_w[j] && d_t[j]);
+    return lookup3_terms(ctx, d_w, d_t, N, h_zeta, h_beta, d_df, d_dt);
+}
+int zk_sumcheck_lookup_sel(zk_ctx* ctx, const void* const d_tabs[7], size_t len, const uint64_t h_gamma[4], const uint64_t* h_chal, uint64_t* h_out_evals, uint64_t* h_last) {
+    NEED(ctx, d_tabs && h_gamma && h_chal && h_out_evals && h_last);
+    for (int k = 0; k < 7; k++) NEED(ctx, d_tabs[k]);
+    return sumcheck_lookup_sel(ctx, d_tabs, len, h_gamma, h_chal, h_out_evals, h_last);
+}
 int zk_eq_table_acc(zk_ctx* ctx, const uint64_t* h_point, size_t n, const uint64_t h_weight[4], void* d_acc) {
     NEED(ctx, d_acc && h_weight && (n == 0 || h_point));
     return eq_table_acc(ctx, h_point, n, h_weight, d_acc);
@@ -509,6 +524,12 @@ int zk_sumcheck_lookup_fs(zk_ctx* ctx, const void* const d_tabs[6], size_t len, 
     NEED(ctx, d_tabs && h_gamma && h_out_evals && h_last && h_chal_out);
     for (int k = 0; k < 6; k++) NEED(ctx, d_tabs[k]);
     return sumcheck_lookup_fs(ctx, d_tabs, len, h_gamma, t, h_out_evals, h_last, h_chal_out);
+}
+int zk_sumcheck_lookup_sel_fs(zk_ctx* ctx, const void* const d_tabs[7], size_t len, const uint64_t h_gamma[4], zk_transcript* t, uint64_t* h_out_evals, uint64_t* h_last,
+                              uint64_t* h_chal_out) {
+    NEED(ctx, d_tabs && h_gamma && h_out_evals && h_last && h_chal_out);
+    for (int k = 0; k < 7; k++) NEED(ctx, d_tabs[k]);
+    return sumcheck_lookup_sel_fs(ctx, d_tabs, len, h_gamma, t, h_out_evals, h_last, h_chal_out);
 }
 int zk_sumcheck_multi_fs(zk_ctx* ctx, size_t count, const void* const* d_e, const void* const* d_f, size_t len, zk_transcript* t,
                          uint64_t* h_out_triples, uint64_t* h_last_e, uint64_t* h_last_f, uint64_t* h_chal_out) {

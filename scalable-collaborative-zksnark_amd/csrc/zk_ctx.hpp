@@ -73,10 +73,11 @@ struct zk_ctx {
     bool gate_lds_raised = false;  // zk_gate.hip: k_gate_local's dynamic LDS limit has been raised on this ctx's device
     bool wiring_lds_raised = false;  // zk_wiring.hip: the same for k_wiring_local
     bool multi_lds_raised = false;   // zk_batchopen.hip: the same for k_multi_local
-    bool fs_lds_raised[6] = {false, false, false, false, false, false};  // zk_fs.hip: the same for its six local kernels (gate, wiring, multi, perm3, wide gate, lookup)
+    bool fs_lds_raised[7] = {false, false, false, false, false, false, false};  // zk_fs.hip: the same for its seven local kernels (gate, wiring, multi, perm3, wide gate, lookup, selector-gated lookup)
     bool perm3_lds_raised = false;   // zk_perm3.hip: the same for k_perm3_local
     bool gatew_lds_raised = false;   // zk_gatew.hip: the same for k_gatew_local
     bool lookup_lds_raised = false;  // zk_lookup.hip: the same for k_lookup_local
+    bool lookupsel_lds_raised = false;  // zk_lookup3.hip: the same for k_lookupsel_local
     // party exchanges (zk_comm.cpp): an RCCL communicator bound to this ctx's GPU
     void* comm = nullptr;
     int comm_rank = 0, comm_world = 1;
@@ -133,6 +134,8 @@ struct Tuning {
     long gatew_local_e = 256;   // longest table (elements, a power of two <= 256: eleven tables of 512 would be 176 KiB of LDS) the single-workgroup LDS stage takes over; 1: HBM passes down to the last element
     // lookup sumcheck (zk_lookup.hip)
     long lookup_local_e = 512;  // longest table (elements, a power of two <= 512) the single-workgroup LDS stage takes over; 1: HBM passes down to the last element
+    // selector-gated lookup sumcheck (zk_lookup3.hip)
+    long lookupsel_local_e = 512;  // longest table (elements, a power of two <= 512: seven tables are 112 KiB of LDS) the single-workgroup LDS stage takes over; 1: HBM passes down to the last element
     // MSM (zk_msm.hip)
     long msm_table_dc = 0;    // window-table width delta (sweeps)
     long msm_qstep = 2;       // window-class quantisation step of batches
@@ -224,6 +227,13 @@ int lookup_multiplicities(zk_ctx* ctx, const void* d_f, const void* d_t, const u
 // d_tabs, h_last: E, df, dt, m, hf, ht; h_out_evals: rounds x 4 Fr
 int sumcheck_lookup(zk_ctx* ctx, const void* const* d_tabs, size_t len, const uint64_t* h_gamma, const uint64_t* h_chal, uint64_t* h_out_evals, uint64_t* h_last);
 
+// ---- zk_lookup3.hip ----
+// d_w: a, b, c; d_t: t0, t1, t2 (N Fr each); d_qk: the selector; m[y] = #{x : qk(x) = 1, idx[x] = y}
+int lookup3_multiplicities(zk_ctx* ctx, const void* const* d_w, const void* const* d_t, const void* d_qk, const uint32_t* d_idx, size_t N, void* d_m);
+int lookup3_terms(zk_ctx* ctx, const void* const* d_w, const void* const* d_t, size_t N, const uint64_t* h_zeta, const uint64_t* h_beta, void* d_df, void* d_dt);
+// d_tabs, h_last: E, df, dt, m, hf, ht, qk; h_out_evals: rounds x 4 Fr
+int sumcheck_lookup_sel(zk_ctx* ctx, const void* const* d_tabs, size_t len, const uint64_t* h_gamma, const uint64_t* h_chal, uint64_t* h_out_evals, uint64_t* h_last);
+
 // ---- zk_batchopen.hip ----
 int eq_table_acc(zk_ctx* ctx, const uint64_t* h_point, size_t n, const uint64_t* h_weight, void* d_acc);
 int fr_lincomb(zk_ctx* ctx, size_t count, const void* const* d_tabs, const uint64_t* h_coeffs, size_t len, void* d_out);
@@ -250,6 +260,8 @@ int sumcheck_perm3_fs(zk_ctx* ctx, const void* d_eq, const void* d_tree, const v
 int sumcheck_gate_wide_fs(zk_ctx* ctx, const void* const* d_tabs, size_t len, zk_transcript* t, uint64_t* h_out_evals, uint64_t* h_last, uint64_t* h_chal_out);
 int sumcheck_lookup_fs(zk_ctx* ctx, const void* const* d_tabs, size_t len, const uint64_t* h_gamma, zk_transcript* t, uint64_t* h_out_evals, uint64_t* h_last,
                        uint64_t* h_chal_out);
+int sumcheck_lookup_sel_fs(zk_ctx* ctx, const void* const* d_tabs, size_t len, const uint64_t* h_gamma, zk_transcript* t, uint64_t* h_out_evals, uint64_t* h_last,
+                           uint64_t* h_chal_out);
 
 // ---- zk_msm.hip ----
 struct MsmItem {

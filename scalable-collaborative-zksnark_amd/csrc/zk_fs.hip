@@ -1,4 +1,4 @@
-// zk_fs.hip -- the six fused sumchecks (zk_gate.hip, zk_wiring.hip, zk_perm3.hip, zk_gatew.hip, zk_lookup.hip, zk_batchopen.hip) with their challenges drawn from a
+// zk_fs.hip -- the seven fused sumchecks (zk_gate.hip, zk_wiring.hip, zk_perm3.hip, zk_gatew.hip, zk_lookup.hip, zk_lookup3.hip, zk_batchopen.hip) with their challenges drawn from a
 // Fiat-Shamir transcript ON THE DEVICE (zk_transcript.hip, sha256.cuh): challenge r_p is a hash of round p's evaluations, so the
 // fold by r_p cannot share a sweep with round p's sums as it does in the preset-challenge kernels.  The shape here:
 //   pass 0            evaluate only: the sums of round 0 over the caller's tables (nothing is written but the partials),
@@ -69,6 +69,17 @@ struct LookupKind {  // E, df, dt, m, hf, ht
     static constexpr int kWaves = 2;
     static constexpr bool kFree = true;  // hf - ht
     __device__ static __forceinline__ Fr inner(const Fr& gamma, const Fr (&v)[kTabs]) { return lookup_inner(gamma, v[1], v[2], v[3], v[4], v[5]); }
+    __device__ static __forceinline__ Fr free(const Fr (&v)[kTabs]) { return fr_sub(v[4], v[5]); }
+};
+
+struct LookupSelKind {  // E, df, dt, m, hf, ht, qk
+    static constexpr int kTabs = kLookupSelTabs;
+    static constexpr int kEvals = kLookupEvals;
+    static constexpr int kSlot = 6;
+    static constexpr unsigned kLocalMax = kGateLocalMax;
+    static constexpr int kWaves = 1;  // 28 table registers of 8 limbs (the fold reads four elements per table) and four 17-limb sums: the 264 .. 512 register bracket
+    static constexpr bool kFree = true;  // hf - ht
+    __device__ static __forceinline__ Fr inner(const Fr& gamma, const Fr (&v)[kTabs]) { return lookupsel_inner(gamma, v[1], v[2], v[3], v[4], v[5], v[6]); }
     __device__ static __forceinline__ Fr free(const Fr (&v)[kTabs]) { return fr_sub(v[4], v[5]); }
 };
 
@@ -550,6 +561,18 @@ int sumcheck_lookup_fs(zk_ctx* ctx, const void* const* d_tabs, size_t len, const
     GateChal gamma;
     std::memcpy(&gamma.r, h_gamma, 32);
     return run_fs<LookupKind>(ctx, "zk_sumcheck_lookup_fs", first, len, emax, 2, gamma, t, h_out_evals, h_last, h_chal_out);
+}
+
+int sumcheck_lookup_sel_fs(zk_ctx* ctx, const void* const* d_tabs, size_t len, const uint64_t* h_gamma, zk_transcript* t, uint64_t* h_out_evals, uint64_t* h_last,
+                           uint64_t* h_chal_out) {
+    size_t emax;
+    const int rc = local_e(ctx, tuning().lookupsel_local_e, "lookupsel_local_e", emax);
+    if (rc) return rc;
+    FsIn<kLookupSelTabs> first;
+    for (int k = 0; k < kLookupSelTabs; k++) first.t[k] = d_tabs[k], first.sh[k] = 0;
+    GateChal gamma;
+    std::memcpy(&gamma.r, h_gamma, 32);
+    return run_fs<LookupSelKind>(ctx, "zk_sumcheck_lookup_sel_fs", first, len, emax, 1, gamma, t, h_out_evals, h_last, h_chal_out);
 }
 
 int sumcheck_multi_fs(zk_ctx* ctx, size_t count, const void* const* d_e, const void* const* d_f, size_t len, zk_transcript* t, uint64_t* h_out_triples,

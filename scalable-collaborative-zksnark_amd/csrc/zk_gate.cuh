@@ -127,6 +127,15 @@ __device__ __forceinline__ Fr lookup_inner(const Fr& gamma, const Fr& df, const 
     const Fr q = fr_mul(gamma, fr_sub(fr_mul(ht, dt), m));
     return fr_add(p, q);
 }
+// the selector-gated lookup identity of a Plonk circuit (zk_lookup3.hip, its transcript-driven form in zk_fs.hip): the six tables above, then qk
+static constexpr int kLookupSelTabs = 7;
+
+// [ hf df - qk + gamma ( ht dt - m ) ] of one point: three multiplications, qk subtracted as a reduced value
+__device__ __forceinline__ Fr lookupsel_inner(const Fr& gamma, const Fr& df, const Fr& dt, const Fr& m, const Fr& hf, const Fr& ht, const Fr& qk) {
+    const Fr p = fr_sub(fr_mul(hf, df), qk);
+    const Fr q = fr_mul(gamma, fr_sub(fr_mul(ht, dt), m));
+    return fr_add(p, q);
+}
 // A sum of the term of an identity that eq does not multiply (the lookup's hf - ht), a canonical g < r, enters a lazily reduced sum
 // as g 2^256: its eight limbs are added from limb 8 on, and the one reduction W0 R^-1 + W1 + W2 R of gate_reduce_value gives it back.
 __device__ __forceinline__ void gate_wide_add_hi(u32 (&a)[17], const Fr& g) {

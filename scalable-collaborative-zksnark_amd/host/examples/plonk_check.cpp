@@ -3,14 +3,24 @@
 // drawn from the device transcript and verified by replaying the schedule on the host transcript.  One digest for one seed across the
 // two hosts (zkhip.plonk.proof_digest).
 //
-//     bin/plonk_check --mu M [--seed S] [--gate wide] [--break-gate K | --break-wire K | --bad-input] [--circuit-only]
+//     bin/plonk_check --mu M [--seed S] [--gate wide] [--lookup [--break-lookup K]] [--break-gate K | --break-wire K | --bad-input | --break K|all]
+//                     [--circuit-only | --sample-only]
+//
+// --lookup proves the test circuit with lookup rows (zkhip.plonk.sample_circuit_lookup, mu >= 3) under the label + "-lookup": three opening
+// proofs.  --break-lookup K moves the triple of lookup row K out of the table with gate and wiring intact: the prover refuses (exit 3, the
+// device's "K of N rows" message on stderr).  --break K flips one bit of part K of the honest record before it is verified; the parts, in the
+// order of the digest: 0 commitments, 1 v_commitment, 2 p_rounds, 3 g_rounds, 4 g_values, 5 p_values, 6 v_values, 7 batch.rounds,
+// 8 batch.opening, 9 v_batch.rounds, 10 v_batch.opening and, with --lookup, 11 lookup.commitments, 12 lookup.rounds, 13 lookup.values,
+// 14 lookup.batch.rounds, 15 lookup.batch.opening.  --break all proves once and verifies one tampered copy per part: one line each, exit 1 when
+// every copy is rejected and 0 when one is accepted.
 //
 // --gate wide proves the test circuit of the wide gate (zkhip.plonk.sample_circuit_wide: six selectors and a fifth-power term) instead.
 // --break-gate K adds 1 to c[K]; --break-wire K (K past the input rows) changes a[K] and recomputes c[K], so that only the copy
 // constraint fails; --bad-input hands the verifier a public input the prover did not use.  The verifier rejects each.  Prints the proof
 // digest and accept / reject; exit 0 on accept, 1 on reject, 2 on error (arguments are checked before any device is touched).
-// Without a GPU it refuses (no CPU fallback) -- but for --circuit-only, which builds the test circuit, prints the SHA-256 of its tables (the
-// selectors, a, b, c, the public inputs, the trapdoor, sigma: little-endian words in that order) and exits 0 without touching a device.
+// Without a GPU it refuses (no CPU fallback) -- but for --circuit-only (--sample-only is the same mode), which builds the test circuit, prints
+// the SHA-256 of its tables (the selectors, a, b, c, the public inputs, the trapdoor, sigma and, with --lookup, qk, t0, t1, t2, idx:
+// little-endian words in that order, zkhip.plonk.circuit_digest) and exits 0 without touching a device.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -28,42 +38,95 @@ static bool number(const char *s, long long &out) {
     return *s && end && !*end && out >= 0;
 }
 
-static int circuit_only(size_t mu, uint64_t seed, bool wide, long long break_gate, long long break_wire) {
-    const PlonkCircuit c = (wide ? sample_circuit_wide : sample_circuit)(mu, seed, break_gate, break_wire);
-    Sha256 h;
-    for (const FrVec &q : c.sel) h.update(q.data(), 32 * q.size());
-    for (const FrVec *t : {&c.a, &c.b, &c.c, &c.public_inputs, &c.s}) h.update(t->data(), 32 * t->size());
-    h.update(c.sigma.data(), 8 * c.sigma.size());
-    std::printf("circuit sha256 %s\n", h.hex().c_str());
+struct Options {
+    long long mu = -1, seed = 7, break_gate = -1, break_wire = -1, break_lookup = -1, break_part = -1;
+    bool bad_input = false, wide = false, lookup = false, break_all = false;
+};
+
+static PlonkCircuit sample(const Options &o, bool broken) {
+    if (o.lookup) return sample_circuit_lookup((size_t)o.mu, (uint64_t)o.seed, o.wide, broken ? o.break_lookup : -1);
+    return (o.wide ? sample_circuit_wide : sample_circuit)((size_t)o.mu, (uint64_t)o.seed, broken ? o.break_gate : -1, broken ? o.break_wire : -1, nullptr);
+}
+
+static int circuit_only(const Options &o) {
+    std::printf("circuit sha256 %s\n", circuit_digest(sample(o, true)).c_str());
     return 0;
 }
 
-static int run(size_t mu, uint64_t seed, bool wide, long long break_gate, long long break_wire, bool bad_input) {
+static const char *const kParts[16] = {"commitments", "v_commitment", "p_rounds", "g_rounds", "g_values", "p_values", "v_values", "batch.rounds", "batch.opening",
+                                       "v_batch.rounds", "v_batch.opening", "lookup.commitments", "lookup.rounds", "lookup.values", "lookup.batch.rounds",
+                                       "lookup.batch.opening"};
+// one bit of the first word of part k of the record
+static void flip(PlonkProof &p, int k) {
+    uint64_t *w[16] = {p.commitments[0].data(), p.v_commitment.data(), p.p_rounds[0][0].v, p.g_rounds[0][0].v, p.g_values[0].v, p.p_values[0].v, p.v_values[0].v,
+                       p.batch.rounds[0][0].v, p.batch.opening[0].data(), p.v_batch.rounds[0][0].v, p.v_batch.opening[0].data()};
+    if (p.lookup) {
+        uint64_t *l[5] = {p.l_commitments[0].data(), p.l_rounds[0][0].v, p.l_values[0].v, p.l_batch.rounds[0][0].v, p.l_batch.opening[0].data()};
+        for (int j = 0; j < 5; ++j) w[11 + j] = l[j];
+    }
+    w[k][0] ^= 1;
+}
+
+static int run(const Options &o) {
     Ctx be(0);
-    const size_t N = size_t(1) << mu;
-    const auto sample = wide ? sample_circuit_wide : sample_circuit;
-    const PlonkCircuit good = sample(mu, seed, -1, -1), c = sample(mu, seed, break_gate, break_wire);
+    const size_t mu = (size_t)o.mu, N = size_t(1) << mu;
+    const uint64_t seed = (uint64_t)o.seed;
+    const bool wide = o.wide, bad_input = o.bad_input;
+    const PlonkCircuit good = sample(o, false), c = sample(o, true);
     PolynomialCommitmentCub cub = PolynomialCommitmentCub::make(be, good.s);
     // level mu of the parameter set uses s_1 .. s_mu: its openings verify against [g2, s_1 g2, .., s_mu g2]
     std::shared_ptr<PcsVk> vk_mu1 = make_pcs_vk(be, good.s), vk_mu = make_pcs_vk(be, FrVec(good.s.begin() + 1, good.s.end()));
     PlonkVk vk;
     const PlonkPk pk = preprocess(be, cub.mature(), good, vk);
-    const PlonkProof proof = plonk_prove(be, cub.mature(), pk, be.to_device(c.a), be.to_device(c.b), be.to_device(c.c), good.public_inputs);
+    DevPtr idx;
+    if (o.lookup) {
+        idx = be.alloc(4 * N);
+        be.upload(idx, c.idx.data(), 4 * N);
+    }
+    PlonkProof proof;
+    try {
+        proof = plonk_prove(be, cub.mature(), pk, be.to_device(c.a), be.to_device(c.b), be.to_device(c.c), good.public_inputs, idx);
+    } catch (const ZkError &e) {
+        if (o.break_lookup < 0 || e.status != ZK_ERR_INVALID) throw;
+        std::fprintf(stderr, "plonk_check: the prover refused: %s\n", e.what());
+        return 3;
+    }
     FrVec pi = good.public_inputs;
     if (bad_input) pi[1] += Fr::one();
-    const bool ok = plonk_verify(be, *vk_mu, *vk_mu1, vk, pi, proof);
     std::printf("proof sha256 %s\n", proof_digest(proof).c_str());
-    std::printf("plonk_check mu=%zu N=%zu l=%zu seed=%llu%s: %s\n", mu, N, good.l, (unsigned long long)seed, wide ? " gate=wide" : "", ok ? "accept" : "reject");
+    bool ok = true;
+    if (o.break_all) {
+        const int parts = o.lookup ? 16 : 11;
+        bool any = false;
+        for (int k = 0; k < parts; ++k) {
+            PlonkProof t = proof;
+            flip(t, k);
+            const bool acc = plonk_verify(be, *vk_mu, *vk_mu1, vk, pi, t);
+            std::printf("break %d %s: %s\n", k, kParts[k], acc ? "accept" : "reject");
+            any = any || acc;
+        }
+        ok = any;
+    } else {
+        if (o.break_part >= 0) flip(proof, (int)o.break_part);
+        ok = plonk_verify(be, *vk_mu, *vk_mu1, vk, pi, proof);
+    }
+    std::printf("plonk_check mu=%zu N=%zu l=%zu seed=%llu%s%s: %s\n", mu, N, good.l, (unsigned long long)seed, wide ? " gate=wide" : "", o.lookup ? " lookup" : "",
+                ok ? "accept" : "reject");
     return ok ? 0 : 1;
 }
 
 int main(int argc, char **argv) {
-    long long mu = -1, seed = 7, break_gate = -1, break_wire = -1;
-    bool bad_input = false, wide = false, only_circuit = false, usage = argc < 2;
+    Options o;
+    long long &mu = o.mu, &seed = o.seed, &break_gate = o.break_gate, &break_wire = o.break_wire;
+    bool &bad_input = o.bad_input, &wide = o.wide, only_circuit = false, usage = argc < 2;
     for (int i = 1; i < argc && !usage; ++i) {
         const std::string k = argv[i];
         if (k == "--bad-input") bad_input = true;
-        else if (k == "--circuit-only") only_circuit = true;
+        else if (k == "--circuit-only" || k == "--sample-only") only_circuit = true;
+        else if (k == "--lookup") o.lookup = true;
+        else if (i + 1 < argc && k == "--break-lookup") usage = !number(argv[++i], o.break_lookup);
+        else if (i + 1 < argc && k == "--break" && !std::strcmp(argv[i + 1], "all")) o.break_all = true, ++i;
+        else if (i + 1 < argc && k == "--break") usage = !number(argv[++i], o.break_part);
         else if (i + 1 < argc && k == "--gate") usage = std::strcmp(argv[++i], "wide") != 0, wide = true;
         else if (i + 1 < argc && k == "--mu") usage = !number(argv[++i], mu);
         else if (i + 1 < argc && k == "--seed") usage = !number(argv[++i], seed);
@@ -71,8 +134,10 @@ int main(int argc, char **argv) {
         else if (i + 1 < argc && k == "--break-wire") usage = !number(argv[++i], break_wire);
         else usage = true;
     }
-    if (usage || mu < 0 || (break_gate >= 0) + (break_wire >= 0) + (bad_input ? 1 : 0) > 1) {
-        std::fprintf(stderr, "usage: plonk_check --mu M [--seed S] [--gate wide] [--break-gate K | --break-wire K | --bad-input] [--circuit-only]\n");
+    const bool tamper = o.break_all || o.break_part >= 0;
+    if (usage || mu < 0 || (break_gate >= 0) + (break_wire >= 0) + (bad_input ? 1 : 0) + (o.break_lookup >= 0) + (tamper ? 1 : 0) > 1 ||
+        (o.break_all && o.break_part >= 0) || (o.break_lookup >= 0 && !o.lookup) || (o.lookup && (break_gate >= 0 || break_wire >= 0))) {
+        std::fprintf(stderr, "usage: plonk_check --mu M [--seed S] [--gate wide] [--lookup [--break-lookup K]] [--break-gate K | --break-wire K | --bad-input | --break K|all] [--circuit-only | --sample-only]\n");
         return 2;
     }
     if (mu < 2 || mu > 24) {
@@ -84,14 +149,27 @@ int main(int argc, char **argv) {
         std::fprintf(stderr, "plonk_check: --break-gate must be below 2^mu, --break-wire in [l, 2^mu) with l = %lld input rows\n", l);
         return 2;
     }
-    if (only_circuit) return circuit_only((size_t)mu, (uint64_t)seed, wide, break_gate, break_wire);
+    if (o.lookup && mu < 3) {
+        std::fprintf(stderr, "plonk_check: --lookup needs --mu >= 3\n");
+        return 2;
+    }
+    if (o.break_part >= (o.lookup ? 16 : 11) || o.break_lookup >= N) {
+        std::fprintf(stderr, "plonk_check: --break names one of the record's %d parts, --break-lookup a row below 2^mu\n", o.lookup ? 16 : 11);
+        return 2;
+    }
+    try {
+        if (only_circuit) return circuit_only(o);
+    } catch (const std::exception &e) {  // --break-lookup on a row that is no lookup row
+        std::fprintf(stderr, "plonk_check: %s\n", e.what());
+        return 2;
+    }
     int ngpu = zk_device_count();
     if (ngpu <= 0) {
         std::fprintf(stderr, "plonk_check: no GPU visible -- this host has no CPU fallback (zk_device_count = %d)\n", ngpu);
         return 2;
     }
     try {
-        return run((size_t)mu, (uint64_t)seed, wide, break_gate, break_wire, bad_input);
+        return run(o);
     } catch (const std::exception &e) {
         std::fprintf(stderr, "plonk_check: %s\n", e.what());
         return 2;

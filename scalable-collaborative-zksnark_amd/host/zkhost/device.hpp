@@ -319,6 +319,33 @@ class Ctx {
         check(zk_sumcheck_lookup(h_, p, len, gamma.v, chal[0].v, r.sums[0].v, last[0].v));
         return r;
     }
+    // zk_lookup3_multiplicities: m[y] = #{x : qk(x) = 1, idx[x] = y} as N Fr; w = a, b, c; t = t0, t1, t2; idx = N u32 on the device.  A selected
+    // row whose triple is not the table entry it names, or a qk that is neither 0 nor 1: ZkError(ZK_ERR_INVALID)
+    DevPtr lookup3_multiplicities(const std::array<DevPtr, 3> &w, const std::array<DevPtr, 3> &t, const DevPtr &qk, const DevPtr &idx, size_t N) {
+        DevPtr m = alloc_fr(N);
+        const void *pw[3] = {w[0].get(), w[1].get(), w[2].get()}, *pt[3] = {t[0].get(), t[1].get(), t[2].get()};
+        check(zk_lookup3_multiplicities(h_, pw, pt, qk.get(), (const uint32_t *)idx.get(), N, m.get()));
+        return m;
+    }
+    // zk_lookup3_terms: df = beta + a + zeta b + zeta^2 c, dt = beta + t0 + zeta t1 + zeta^2 t2 in one pass (asynchronous)
+    std::pair<DevPtr, DevPtr> lookup3_terms(const std::array<DevPtr, 3> &w, const std::array<DevPtr, 3> &t, size_t N, const Fr &zeta, const Fr &beta) {
+        DevPtr df = alloc_fr(N), dt = alloc_fr(N);
+        const void *pw[3] = {w[0].get(), w[1].get(), w[2].get()}, *pt[3] = {t[0].get(), t[1].get(), t[2].get()};
+        check(zk_lookup3_terms(h_, pw, pt, N, zeta.v, beta.v, df.get(), dt.get()));
+        return {df, dt};
+    }
+    // zk_sumcheck_lookup_sel: tabs = E, df, dt, m, hf, ht, qk -> r.sums = 4 Fr per round (t = 0 .. 3), `last` = the seven remaining elements
+    ScResult sumcheck_lookup_sel(const std::array<DevPtr, 7> &tabs, size_t len, const Fr &gamma, const FrVec &chal, FrVec &last) {
+        size_t n = log2_exact(len);
+        need(n >= 1 && chal.size() >= n, "sumcheck_lookup_sel: fewer challenges than rounds");
+        ScResult r;
+        r.sums.resize(4 * n);
+        last.assign(7, Fr::zero());
+        const void *p[7];
+        for (int k = 0; k < 7; k++) p[k] = tabs[k].get();
+        check(zk_sumcheck_lookup_sel(h_, p, len, gamma.v, chal[0].v, r.sums[0].v, last[0].v));
+        return r;
+    }
     // zk_eq_table_acc: acc[x] += weight * eq(point, x), acc = 2^n Fr (asynchronous)
     void eq_table_acc(const FrVec &point, const Fr &weight, const DevPtr &acc) {
         check(zk_eq_table_acc(h_, point.empty() ? nullptr : point[0].v, point.size(), weight.v, acc.get()));
@@ -416,6 +443,18 @@ class Ctx {
         const void *p[6];
         for (int k = 0; k < 6; k++) p[k] = tabs[k].get();
         check(zk_sumcheck_lookup_fs(h_, p, len, gamma.v, t.h, r.sums[0].v, last[0].v, chal[0].v));
+        return r;
+    }
+    ScResult sumcheck_lookup_sel_fs(const std::array<DevPtr, 7> &tabs, size_t len, const Fr &gamma, DeviceTranscript &t, FrVec &last, FrVec &chal) {
+        size_t n = log2_exact(len);
+        need(n >= 1, "sumcheck_lookup_sel_fs: at least one round");
+        ScResult r;
+        r.sums.resize(4 * n);
+        last.assign(7, Fr::zero());
+        chal.assign(n, Fr::zero());
+        const void *p[7];
+        for (int k = 0; k < 7; k++) p[k] = tabs[k].get();
+        check(zk_sumcheck_lookup_sel_fs(h_, p, len, gamma.v, t.h, r.sums[0].v, last[0].v, chal[0].v));
         return r;
     }
     ScResult sumcheck_multi_fs(const std::vector<DevPtr> &es, const std::vector<DevPtr> &fs, size_t len, DeviceTranscript &t, FrVec &last_e, FrVec &last_f,

@@ -22,6 +22,19 @@
 // mu-variate batch instance of twelve tables and fifteen claims.  The schedule, the permutation half and the (mu + 1)-variate instance are
 // the same code: a gate kind is described by gate_desc (label, selector count, evaluations per round), gate_sumcheck_fs (the device
 // sumcheck) and gate_closed_form (the verifier's closed form).  GateKind::basic behaves exactly as before.
+//
+// LOOKUPS (zkhip/plonk.py, module text): a circuit may carry a selector qk (0 or 1) and a table of N triples (t0, t1, t2); row x with
+// qk(x) = 1 claims (a, b, c)(x) = (t0, t1, t2)(idx[x]).  With f = a + zeta b + zeta^2 c, t = t0 + zeta t1 + zeta^2 t2, df = beta_l + f,
+// dt = beta_l + t, hf = qk / df, ht = m / dt one degree-3 sumcheck over E, df, dt, m, hf, ht, qk (zk_sumcheck_lookup_sel_fs) proves
+//     sum_x hf - ht + E [ hf df - qk + gamma_l ( ht dt - m ) ] = 0,      E = lambda eq(tau_l, .)
+// The label is the gate's + "-lookup"; the vk commitments are the gate's followed by qk, t0, t1, t2.  Insertions into the schedule:
+//   2L. after alpha, beta: m; absorb its commitment;  zeta, beta_l <- challenges;
+//   3L. after gamma: df, dt, hf, ht; absorb the commitments of hf, ht;  gamma_l, lambda <- challenges;
+//   5L. after the gate sumcheck: tau_l <- mu challenges; the lookup sumcheck: per round absorb four evaluations, r_l[i] <- challenge;
+//   6.  after v_values absorb l_values = a, b, c, qk, t0, t1, t2, m, hf, ht at r_l;
+//   7.  the mu-variate instance gains three claims (a, b, c at r_l); after the (mu + 1)-variate instance a THIRD one: qk, t0, t1, t2, m,
+//       hf, ht with seven claims at r_l.  Three opening proofs.
+// A circuit, key or record without a lookup behaves exactly as before.
 #pragma once
 #include "nizk.hpp"
 
@@ -44,11 +57,15 @@ struct PlonkCircuit {
     std::vector<FrVec> sel;             // the selectors in the order of gate_desc
     FrVec a, b, c, public_inputs, s;    // s: the SRS trapdoor, mu + 1 elements
     std::vector<uint64_t> sigma;        // 3N slot numbers
+    bool lookup = false;
+    FrVec qk, t0, t1, t2;               // with a lookup: the selector and the table, N elements each
+    std::vector<uint32_t> idx;          // with a lookup: the prover's row-to-table indices
 };
 struct PlonkVk {
     GateKind gate = GateKind::basic;
     size_t mu = 0, l = 0;
-    G1Vec commitments;  // the selectors, ssigma_0, ssigma_1, ssigma_2
+    G1Vec commitments;  // the selectors, ssigma_0, ssigma_1, ssigma_2; with a lookup then qk, t0, t1, t2
+    bool lookup = false;
 };
 struct PlonkPk {
     GateKind gate = GateKind::basic;
@@ -56,6 +73,9 @@ struct PlonkPk {
     std::vector<DevPtr> sel;
     std::array<DevPtr, 3> ssigma;
     G1Vec commitments;
+    bool lookup = false;
+    DevPtr qk;
+    std::array<DevPtr, 3> table;  // t0, t1, t2
 };
 struct PlonkProof {
     GateKind gate = GateKind::basic;
@@ -66,7 +86,18 @@ struct PlonkProof {
     std::vector<FrVec> g_rounds;         // gate_desc(gate).evals per round
     FrVec g_values, p_values, v_values;  // selectors + 3, 6, 5
     BatchOpenProof batch, v_batch;
+    bool lookup = false;
+    G1Vec l_commitments;                     // m, hf, ht
+    std::vector<std::array<Fr, 4>> l_rounds;
+    FrVec l_values;                          // a, b, c, qk, t0, t1, t2, m, hf, ht at r_l
+    BatchOpenProof l_batch;
 };
+inline std::string plonk_label(GateKind k, bool lookup) { return std::string(gate_desc(k).label) + (lookup ? "-lookup" : ""); }
+// hf - ht + E [ hf (beta + a + zeta b + zeta^2 c) - qk + gamma ( ht (beta + t0 + zeta t1 + zeta^2 t2) - m ) ];  v: the ten l_values
+inline Fr lookup3_value(const Fr &E, const FrVec &v, const Fr &zeta, const Fr &beta, const Fr &gamma) {
+    const Fr df = beta + v[0] + zeta * v[1] + zeta * zeta * v[2], dt = beta + v[4] + zeta * v[5] + zeta * zeta * v[6];
+    return v[8] - v[9] + E * (v[8] * df - v[3] + gamma * (v[9] * dt - v[7]));
+}
 
 // the device sumcheck of a gate kind; tabs: eq, the selectors, a, b, c, in
 inline ScResult gate_sumcheck_fs(Ctx &be, GateKind k, const std::vector<DevPtr> &tabs, size_t N, DeviceTranscript &tr, FrVec &last, FrVec &chal) {
@@ -88,10 +119,13 @@ inline Fr gate_closed_form(GateKind k, const Fr &eq, const FrVec &g, const Fr &i
 
 namespace detail {
 // sigma: one cycle per value -- the c slot of row y, then the a / b slots that copy it in ascending slot order
-inline std::vector<uint64_t> copy_sigma(const std::vector<size_t> &ia, const std::vector<size_t> &ib, size_t l, size_t N) {
+// fixed (optional, N flags): rows whose a and b slots copy nothing and stay fixed points (the lookup rows)
+inline std::vector<uint64_t> copy_sigma(const std::vector<size_t> &ia, const std::vector<size_t> &ib, size_t l, size_t N, const std::vector<char> *fixed = nullptr) {
     std::vector<std::vector<uint64_t>> users(N);
-    for (size_t x = l; x < N; ++x) users[ia[x]].push_back(x);
-    for (size_t x = l; x < N; ++x) users[ib[x]].push_back(N + x);
+    for (size_t x = l; x < N; ++x)
+        if (!fixed || !(*fixed)[x]) users[ia[x]].push_back(x);
+    for (size_t x = l; x < N; ++x)
+        if (!fixed || !(*fixed)[x]) users[ib[x]].push_back(N + x);
     std::vector<uint64_t> sigma(3 * N);
     for (size_t i = 0; i < 3 * N; ++i) sigma[i] = i;
     for (size_t y = 0; y < N; ++y) {
@@ -102,14 +136,25 @@ inline std::vector<uint64_t> copy_sigma(const std::vector<size_t> &ia, const std
     return sigma;
 }
 }  // namespace detail
+// the lookup rows that sample_circuit_lookup hands to the two generators: row x with mask[x] takes a = u[y[x]], b = v[y[x]] in the place
+// of copies and a product gate (c = a b); row brk (-1: none) gets a + 1 before its c is computed
+// (u, v are Fr here for both gate kinds; Python's _lookup_rows carries them as integers in the domain its generator builds rows in)
+struct LookupRows {
+    std::vector<char> mask;
+    std::vector<size_t> y;
+    FrVec u, v;
+    long long brk = -1;
+};
 struct PlonkChallenges {
     Fr alpha, beta, gamma, b_alpha;
     FrVec tau_p, r_p, tau_g, r_g, rho_mu, rho_mu1;
+    Fr zeta, beta_l, gamma_l, lambda;  // with a lookup
+    FrVec tau_l, r_l, rho_l;
 };
 
 // The test circuit of zkhip.plonk.sample_circuit (the same SplitMix64 streams: 1 public inputs, 2 q1, 3 q2, 4 picks, 5 trapdoor).
 // break_gate K adds 1 to c[K] after the fact; break_wire K (K >= l) adds 1 to a[K] and recomputes c[K].  -1: none.
-inline PlonkCircuit sample_circuit(size_t mu, uint64_t seed, long long break_gate = -1, long long break_wire = -1) {
+inline PlonkCircuit sample_circuit(size_t mu, uint64_t seed, long long break_gate = -1, long long break_wire = -1, const LookupRows *lk = nullptr) {
     if (mu < 2) throw ZkError(ZK_ERR_INVALID, "sample_circuit: mu >= 2");
     PlonkCircuit c;
     const size_t N = size_t(1) << mu, l = N / 2 < 4 ? N / 2 : 4;
@@ -121,11 +166,18 @@ inline PlonkCircuit sample_circuit(size_t mu, uint64_t seed, long long break_gat
     const FrVec pick = SplitMix64(base + 4).fr_vec(N);
     c.a.assign(N, Fr::zero()), c.b.assign(N, Fr::zero()), c.c.assign(N, Fr::zero());
     for (size_t x = 0; x < l; ++x) q1[x] = Fr::zero(), q2[x] = Fr::zero(), c.c[x] = c.public_inputs[x];
+    for (size_t x = l; lk && x < N; ++x)  // a lookup row is a product row: q1 = 0, q2 = 1
+        if (lk->mask[x]) q1[x] = Fr::zero(), q2[x] = Fr::one();
     std::vector<size_t> ia(N, 0), ib(N, 0);
     auto gate = [&](size_t x) { return q1[x] * (c.a[x] + c.b[x]) + q2[x] * c.a[x] * c.b[x]; };
     for (size_t x = l; x < N; ++x) {
         ia[x] = pick[x].v[0] % x, ib[x] = pick[x].v[1] % x;
-        c.a[x] = c.c[ia[x]], c.b[x] = c.c[ib[x]];
+        if (lk && lk->mask[x]) {
+            c.a[x] = lk->u[lk->y[x]], c.b[x] = lk->v[lk->y[x]];
+            if ((long long)x == lk->brk) c.a[x] += Fr::one();
+        } else {
+            c.a[x] = c.c[ia[x]], c.b[x] = c.c[ib[x]];
+        }
         c.c[x] = gate(x);
     }
     if (break_wire >= 0) {
@@ -134,7 +186,7 @@ inline PlonkCircuit sample_circuit(size_t mu, uint64_t seed, long long break_gat
         c.c[break_wire] = gate(break_wire);
     }
     if (break_gate >= 0) c.c[break_gate] += Fr::one();
-    c.sigma = detail::copy_sigma(ia, ib, l, N);
+    c.sigma = detail::copy_sigma(ia, ib, l, N, lk ? &lk->mask : nullptr);
     c.s = SplitMix64(base + 5).fr_vec(mu + 1);
     return c;
 }
@@ -144,7 +196,7 @@ inline PlonkCircuit sample_circuit(size_t mu, uint64_t seed, long long break_gat
 // values; its kind is limb 2 of pick x mod 4: 0 linear (qL, qR, qC drawn, qO = 1), 1 product (qM, qC drawn, qO = 1), 2 S-box (qH = 1, qC
 // drawn, qO = 1), 3 full (all six drawn; a zero qO is replaced by 1); a selector the kind does not name is 0 and
 // c = (qL a + qR b + qM a b + qH a^5 + qC) / qO.  break_gate / break_wire as in sample_circuit.
-inline PlonkCircuit sample_circuit_wide(size_t mu, uint64_t seed, long long break_gate = -1, long long break_wire = -1) {
+inline PlonkCircuit sample_circuit_wide(size_t mu, uint64_t seed, long long break_gate = -1, long long break_wire = -1, const LookupRows *lk = nullptr) {
     if (mu < 2) throw ZkError(ZK_ERR_INVALID, "sample_circuit_wide: mu >= 2");
     PlonkCircuit c;
     const size_t N = size_t(1) << mu, l = N / 2 < 4 ? N / 2 : 4;
@@ -172,7 +224,13 @@ inline PlonkCircuit sample_circuit_wide(size_t mu, uint64_t seed, long long brea
         if (kind == 2) c.sel[qH][x] = Fr::one();
         if (kind == 3 && c.sel[qO][x].is_zero()) c.sel[qO][x] = Fr::one();
         ia[x] = pick[x].v[0] % x, ib[x] = pick[x].v[1] % x;
-        c.a[x] = c.c[ia[x]], c.b[x] = c.c[ib[x]];
+        if (lk && lk->mask[x]) {  // a lookup row is a pure product row: qM = qO = 1, every other selector 0
+            for (int k = 0; k < 6; ++k) c.sel[k][x] = (k == qM || k == qO) ? Fr::one() : Fr::zero();
+            c.a[x] = lk->u[lk->y[x]], c.b[x] = lk->v[lk->y[x]];
+            if ((long long)x == lk->brk) c.a[x] += Fr::one();
+        } else {
+            c.a[x] = c.c[ia[x]], c.b[x] = c.c[ib[x]];
+        }
         c.c[x] = out(x);
     }
     if (break_wire >= 0) {
@@ -181,9 +239,48 @@ inline PlonkCircuit sample_circuit_wide(size_t mu, uint64_t seed, long long brea
         c.c[break_wire] = out(break_wire);
     }
     if (break_gate >= 0) c.c[break_gate] += Fr::one();
-    c.sigma = detail::copy_sigma(ia, ib, l, N);
+    c.sigma = detail::copy_sigma(ia, ib, l, N, lk ? &lk->mask : nullptr);
     c.s = SplitMix64(base + 5).fr_vec(mu + 1);
     return c;
+}
+
+// The test circuit of zkhip.plonk.sample_circuit_lookup, bit for bit: sample_circuit (wide: sample_circuit_wide) plus lookup rows against
+// a fixed multiplication table.  mu >= 3; streams 12 = u, 13 = v (D = N / 4 elements each); entry y < D is (u_y, v_y, u_y v_y), padded to
+// N by repeating entry D - 1.  Row x >= l whose pick (stream 4) has an odd limb 3 is a lookup row: y = (limb 3 >> 1) mod D, a = u_y,
+// b = v_y, c = a b, qk = 1, idx = y; its a and b slots are fixed points of sigma.  Every other row: qk = 0, idx = 0.  break_lookup K (a
+// lookup row): a[K] + 1 and c[K] recomputed -- gate and wiring still hold and the triple is outside the table.
+inline PlonkCircuit sample_circuit_lookup(size_t mu, uint64_t seed, bool wide = false, long long break_lookup = -1) {
+    if (mu < 3) throw ZkError(ZK_ERR_INVALID, "sample_circuit_lookup: mu >= 3");
+    const size_t N = size_t(1) << mu, l = 4, D = N / 4;
+    const uint64_t base = 0x91A70000ull + 1000 * seed;
+    const FrVec pick = SplitMix64(base + 4).fr_vec(N);
+    LookupRows lk;
+    lk.mask.assign(N, 0), lk.y.assign(N, 0), lk.brk = break_lookup;
+    for (size_t x = 0; x < N; ++x) lk.mask[x] = x >= l && (pick[x].v[3] & 1), lk.y[x] = (pick[x].v[3] >> 1) % D;
+    if (break_lookup >= 0 && !((size_t)break_lookup < N && lk.mask[break_lookup])) throw ZkError(ZK_ERR_INVALID, "sample_circuit_lookup: break_lookup must name a lookup row");
+    lk.u = SplitMix64(base + 12).fr_vec(D), lk.v = SplitMix64(base + 13).fr_vec(D);
+    PlonkCircuit c = (wide ? sample_circuit_wide : sample_circuit)(mu, seed, -1, -1, &lk);
+    c.lookup = true;
+    c.t0 = lk.u, c.t1 = lk.v, c.t2.resize(D);
+    for (size_t y = 0; y < D; ++y) c.t2[y] = lk.u[y] * lk.v[y];
+    for (FrVec *t : {&c.t0, &c.t1, &c.t2}) t->resize(N, (*t)[D - 1]);
+    c.qk.assign(N, Fr::zero()), c.idx.assign(N, 0);
+    for (size_t x = 0; x < N; ++x)
+        if (lk.mask[x]) c.qk[x] = Fr::one(), c.idx[x] = (uint32_t)lk.y[x];
+    return c;
+}
+// SHA-256 of a sampled circuit's tables: the selectors, a, b, c, the public inputs, the trapdoor, sigma (u64) and, with a lookup, qk, t0,
+// t1, t2 and idx (u32), little-endian in that order (zkhip.plonk.circuit_digest)
+inline std::string circuit_digest(const PlonkCircuit &c) {
+    Sha256 h;
+    for (const FrVec &q : c.sel) h.update(q.data(), 32 * q.size());
+    for (const FrVec *t : {&c.a, &c.b, &c.c, &c.public_inputs, &c.s}) h.update(t->data(), 32 * t->size());
+    h.update(c.sigma.data(), 8 * c.sigma.size());
+    if (c.lookup) {
+        for (const FrVec *t : {&c.qk, &c.t0, &c.t1, &c.t2}) h.update(t->data(), 32 * t->size());
+        h.update(c.idx.data(), 4 * c.idx.size());
+    }
+    return h.hex();
 }
 
 // ---- the verifier's closed forms ----
@@ -241,6 +338,15 @@ inline PlonkPk preprocess(Ctx &be, const PowersOfG &pg, const PlonkCircuit &c, P
     }
     for (const DevPtr &t : pk.sel) pk.commitments.push_back(commit(be, pg, t, N));
     for (const DevPtr &t : pk.ssigma) pk.commitments.push_back(commit(be, pg, t, N));
+    pk.lookup = vk.lookup = c.lookup;
+    if (c.lookup) {
+        bool lok = c.qk.size() == N && c.t0.size() == N && c.t1.size() == N && c.t2.size() == N;
+        for (size_t x = 0; lok && x < N; ++x) lok = c.qk[x].is_zero() || c.qk[x] == Fr::one();
+        if (!lok) throw ZkError(ZK_ERR_INVALID, "preprocess: the lookup needs qk, t0, t1, t2 of N elements and every entry of qk 0 or 1");
+        pk.qk = be.to_device(c.qk), pk.table = {be.to_device(c.t0), be.to_device(c.t1), be.to_device(c.t2)};
+        pk.commitments.push_back(commit(be, pg, pk.qk, N));
+        for (const DevPtr &t : pk.table) pk.commitments.push_back(commit(be, pg, t, N));
+    }
     vk.commitments = pk.commitments;
     return pk;
 }
@@ -254,6 +360,12 @@ inline void plonk_claims(const PlonkProof &p, const FrVec &r_g, const FrVec &r_p
     const std::vector<FrVec> vp = v_points(r_p);
     for (size_t k = 0; k < 5; ++k) v_claims.push_back(Claim{0, vp[k], p.v_values[k]});
 }
+// with a lookup: the three claims a, b, c at r_l that the mu-variate instance gains, and the seven of the third instance (qk, t0, t1, t2, m, hf, ht)
+inline void lookup_claims(const PlonkProof &p, const FrVec &r_l, std::vector<Claim> &claims, std::vector<Claim> &l_claims) {
+    const size_t ns = gate_desc(p.gate).selectors;
+    for (size_t k = 0; k < 3; ++k) claims.push_back(Claim{ns + k, r_l, p.l_values[k]});
+    for (size_t j = 0; j < 7; ++j) l_claims.push_back(Claim{j, r_l, p.l_values[3 + j]});
+}
 inline FrVec replay_rounds(HostTranscript &tr, const std::vector<FrVec> &rounds) {
     FrVec out;
     for (const FrVec &r : rounds) out.push_back(tr.absorb(r).challenge());
@@ -262,31 +374,52 @@ inline FrVec replay_rounds(HostTranscript &tr, const std::vector<FrVec> &rounds)
 }  // namespace detail
 
 // ---- prover ----  (pg: the levels of a PolynomialCommitment over mu + 1 variables; a zero alpha, of probability 2^-254, is refused)
-inline PlonkProof plonk_prove(Ctx &be, const PowersOfG &pg, const PlonkPk &pk, const DevPtr &a, const DevPtr &b, const DevPtr &c, const FrVec &public_inputs) {
+// idx: the N row-to-table indices (u32 on the device), needed exactly when the key has a lookup; a selected row whose triple is not the table
+// entry it names: ZkError(ZK_ERR_INVALID)
+inline PlonkProof plonk_prove(Ctx &be, const PowersOfG &pg, const PlonkPk &pk, const DevPtr &a, const DevPtr &b, const DevPtr &c, const FrVec &public_inputs,
+                              const DevPtr &idx = DevPtr()) {
     const size_t mu = pk.mu, l = pk.l, N = size_t(1) << mu;
     if (public_inputs.size() != l) throw ZkError(ZK_ERR_INVALID, "plonk_prove: l public inputs are needed");
+    if (pk.lookup != (idx.get() != nullptr)) throw ZkError(ZK_ERR_INVALID, "plonk_prove: idx is needed exactly when the key has a lookup");
     const GateDesc &gd = gate_desc(pk.gate);
     const size_t ns = gd.selectors;
     PlonkProof p;
-    p.gate = pk.gate, p.mu = mu, p.l = l;
+    p.gate = pk.gate, p.mu = mu, p.l = l, p.lookup = pk.lookup;
     const std::array<DevPtr, 3> w = {a, b, c};
     for (const DevPtr &t : w) p.commitments.push_back(commit(be, pg, t, N));
-    std::shared_ptr<DeviceTranscript> tr = be.transcript(gd.label);
+    std::shared_ptr<DeviceTranscript> tr = be.transcript(plonk_label(pk.gate, pk.lookup));
     const uint64_t mu64 = mu, l64 = l;
     be.absorb(*tr, &mu64, 8);
     be.absorb(*tr, &l64, 8);
-    be.absorb(*tr, pk.commitments.data(), 144 * (ns + 3));
+    be.absorb(*tr, pk.commitments.data(), 144 * pk.commitments.size());
     be.absorb(*tr, public_inputs.data(), 32 * l);
     be.absorb(*tr, p.commitments.data(), 144 * 3);
     const FrVec ab = be.challenges(*tr, 2);
     const Fr alpha = ab[0], beta = ab[1];
     if (alpha.is_zero()) throw ZkError(ZK_ERR_INVALID, "plonk_prove: the challenge alpha is zero");
+    DevPtr m, df, dt, hf, ht;
+    Fr zeta, beta_l, gamma_l, lambda;
+    if (pk.lookup) {  // 2L
+        m = be.lookup3_multiplicities(w, pk.table, pk.qk, idx, N);
+        p.l_commitments.push_back(commit(be, pg, m, N));
+        be.absorb(*tr, p.l_commitments.data(), 144);
+        const FrVec zb = be.challenges(*tr, 2);
+        zeta = zb[0], beta_l = zb[1];
+    }
     Ctx::Perm3Terms t = be.perm3_terms(w, pk.ssigma, N, alpha, beta);
     DevPtr tree = be.product_tree(be.fr_batch_div(t.P, t.Q, N), N);
     p.v_commitment = commit(be, pg, tree, 2 * N);
     be.absorb(*tr, p.v_commitment.data(), 144);
     const Fr gamma = be.challenges(*tr, 1)[0];
-    FrVec p_last, r_p, g_last, r_g;
+    if (pk.lookup) {  // 3L
+        std::tie(df, dt) = be.lookup3_terms(w, pk.table, N, zeta, beta_l);
+        hf = be.fr_batch_div(pk.qk, df, N), ht = be.fr_batch_div(m, dt, N);
+        p.l_commitments.push_back(commit(be, pg, hf, N)), p.l_commitments.push_back(commit(be, pg, ht, N));
+        be.absorb(*tr, p.l_commitments.data() + 1, 144 * 2);
+        const FrVec gl = be.challenges(*tr, 2);
+        gamma_l = gl[0], lambda = gl[1];
+    }
+    FrVec p_last, r_p, g_last, r_g, r_l;
     {
         DevPtr eq = be.eq_table(be.challenges(*tr, mu));
         ScResult sc = be.sumcheck_perm3_fs(eq, tree, t.num, t.den, N, gamma, *tr, p_last, r_p);
@@ -304,6 +437,22 @@ inline PlonkProof plonk_prove(Ctx &be, const PowersOfG &pg, const PlonkPk &pk, c
         ScResult sc = gate_sumcheck_fs(be, pk.gate, tabs, N, *tr, g_last, r_g);
         for (size_t i = 0; i < mu; ++i) p.g_rounds.emplace_back(sc.sums.begin() + gd.evals * i, sc.sums.begin() + gd.evals * (i + 1));
     }
+    if (pk.lookup) {  // 5L
+        DevPtr E = be.fr_scale(be.eq_table(be.challenges(*tr, mu)), lambda, N);
+        FrVec l_last;
+        ScResult sc = be.sumcheck_lookup_sel_fs({E, df, dt, m, hf, ht, pk.qk}, N, gamma_l, *tr, l_last, r_l);
+        p.l_rounds.resize(mu);
+        for (size_t i = 0; i < mu; ++i)
+            for (int k = 0; k < 4; ++k) p.l_rounds[i][k] = sc.sums[4 * i + k];
+        // a, b, c, t0, t1, t2 at r_l: six folds in one batch, into one buffer; qk, m, hf, ht are the folded-out last values
+        DevPtr at = be.alloc_fr(6);
+        std::vector<ScRequest> folds;
+        const DevPtr six[6] = {a, b, c, pk.table[0], pk.table[1], pk.table[2]};
+        for (size_t j = 0; j < 6; ++j) folds.push_back(ScRequest{ScRequest::Fold, six[j], DevPtr(), N, r_l, at.fr(j)});
+        be.sumcheck_batch(folds);
+        const FrVec v = be.to_host(at, 6);
+        p.l_values = {v[0], v[1], v[2], l_last[6], v[3], v[4], v[5], l_last[3], l_last[4], l_last[5]};
+    }
     p.g_values.assign(g_last.begin() + 1, g_last.begin() + 1 + ns + 3);  // the folded-out values ARE the selectors and a, b, c at r_g
     // the folded-out n_j, d_j at r_p give the wires and the permutation columns there: both are linear in them
     const Fr ids = slot_eval(r_p), ainv = alpha.inverse();
@@ -319,13 +468,16 @@ inline PlonkProof plonk_prove(Ctx &be, const PowersOfG &pg, const PlonkPk &pk, c
     be.absorb(*tr, p.g_values.data(), 32 * (ns + 3));
     be.absorb(*tr, p.p_values.data(), 32 * 6);
     be.absorb(*tr, p.v_values.data(), 32 * 5);
+    if (pk.lookup) be.absorb(*tr, p.l_values.data(), 32 * 10);
     const Fr b_alpha = be.challenges(*tr, 1)[0];
-    std::vector<Claim> claims, v_claims;
+    std::vector<Claim> claims, v_claims, l_claims;
     detail::plonk_claims(p, r_g, r_p, claims, v_claims);
+    if (pk.lookup) detail::lookup_claims(p, r_l, claims, l_claims);
     std::vector<DevPtr> batch_tables = pk.sel;
     batch_tables.insert(batch_tables.end(), {a, b, c, pk.ssigma[0], pk.ssigma[1], pk.ssigma[2]});
     p.batch = detail::batch_prove_ni(be, pg, batch_tables, N, claims, b_alpha, *tr);
     p.v_batch = detail::batch_prove_ni(be, pg, {tree}, 2 * N, v_claims, b_alpha, *tr);
+    if (pk.lookup) p.l_batch = detail::batch_prove_ni(be, pg, {pk.qk, pk.table[0], pk.table[1], pk.table[2], m, hf, ht}, N, l_claims, b_alpha, *tr);
     return p;
 }
 
@@ -335,33 +487,47 @@ inline bool plonk_challenges(const PlonkVk &vk, const FrVec &pi, const PlonkProo
     const size_t mu = vk.mu;
     const GateDesc &gd = gate_desc(vk.gate);
     const size_t ns = gd.selectors;
-    if (p.gate != vk.gate || mu < 1 || p.mu != mu || p.l != vk.l || pi.size() != vk.l || vk.commitments.size() != ns + 3 || p.commitments.size() != 3 ||
+    const bool lk = vk.lookup;
+    if (p.lookup != lk) return false;  // a record / key pair that disagrees on having a lookup is malformed
+    if (lk && (p.l_commitments.size() != 3 || p.l_rounds.size() != mu || p.l_values.size() != 10 || p.l_batch.rounds.size() != mu || p.l_batch.opening.size() != mu))
+        return false;
+    if (p.gate != vk.gate || mu < 1 || p.mu != mu || p.l != vk.l || pi.size() != vk.l || vk.commitments.size() != ns + 3 + (lk ? 4 : 0) || p.commitments.size() != 3 ||
         p.p_rounds.size() != mu || p.g_rounds.size() != mu || p.batch.rounds.size() != mu || p.v_batch.rounds.size() != mu + 1 || p.g_values.size() != ns + 3 ||
         p.p_values.size() != 6 || p.v_values.size() != 5)
         return false;
     for (const FrVec &r : p.g_rounds)
         if (r.size() != gd.evals) return false;
-    HostTranscript tr(gd.label);
-    tr.absorb_u64(mu).absorb_u64(vk.l).absorb(vk.commitments.data(), 144 * (ns + 3)).absorb(pi);
+    HostTranscript tr(plonk_label(vk.gate, lk));
+    tr.absorb_u64(mu).absorb_u64(vk.l).absorb(vk.commitments.data(), 144 * vk.commitments.size()).absorb(pi);
     tr.absorb(p.commitments.data(), 144 * 3);
     c.alpha = tr.challenge(), c.beta = tr.challenge();
+    if (lk) tr.absorb(p.l_commitments.data(), 144), c.zeta = tr.challenge(), c.beta_l = tr.challenge();
     c.gamma = tr.absorb(p.v_commitment.data(), 144).challenge();
+    if (lk) tr.absorb(p.l_commitments.data() + 1, 144 * 2), c.gamma_l = tr.challenge(), c.lambda = tr.challenge();
     c.tau_p = tr.challenges(mu);
     c.r_p = detail::replay_rounds(tr, p.p_rounds);
     c.tau_g = tr.challenges(mu);
     c.r_g = detail::replay_rounds(tr, p.g_rounds);
-    c.b_alpha = tr.absorb(p.g_values).absorb(p.p_values).absorb(p.v_values).challenge();
+    if (lk) {
+        c.tau_l = tr.challenges(mu);
+        for (const std::array<Fr, 4> &r : p.l_rounds) c.r_l.push_back(tr.absorb(r.data(), 32 * 4).challenge());
+    }
+    tr.absorb(p.g_values).absorb(p.p_values).absorb(p.v_values);
+    if (lk) tr.absorb(p.l_values);
+    c.b_alpha = tr.challenge();
     c.rho_mu = detail::replay_rounds(tr, p.batch.rounds);
     c.rho_mu1 = detail::replay_rounds(tr, p.v_batch.rounds);
+    if (lk) c.rho_l = detail::replay_rounds(tr, p.l_batch.rounds);
     return true;
 }
 
 // The verifier's field arithmetic (no GPU, no pairing) -> a bit per failed check (0: all hold; bit 0: malformed): 1 the wiring chain,
 // 2 the gate chain (on the gate kind's nodes), 3 the gate's last value (gate_closed_form) with in(r_g) formed here, 4 the wiring's last value with n_j formed here, 5 v(1,..,1,0) == 1,
-// 6 the chains of the two batch instances (zkhip.plonk.failed_checks).
+// 6 the chains of the two batch instances; with a lookup 7 the lookup chain (nodes 0 .. 3), 8 its last value (lookup3_value on the ten l_values with
+// E = lambda eq(tau_l, r_l)), 9 the third batch instance's chain (zkhip.plonk.failed_checks).
 inline unsigned plonk_failed_checks(const PlonkVk &vk, const FrVec &pi, const PlonkProof &p, const PlonkChallenges &c) {
     const size_t mu = vk.mu, N = size_t(1) << mu, ns = gate_desc(vk.gate).selectors;
-    if (p.gate != vk.gate) return 1u;
+    if (p.gate != vk.gate || p.lookup != vk.lookup) return 1u;
     unsigned bad = 0;
     Fr p_target = Fr::zero(), g_target = Fr::zero();
     for (size_t i = 0; i < mu; ++i) {
@@ -388,23 +554,47 @@ inline unsigned plonk_failed_checks(const PlonkVk &vk, const FrVec &pi, const Pl
     }
     if (!(bad & (1u << 1)) && p_target != eq_eval(c.tau_p, c.r_p) * (t[1] - t[2] * t[3] + c.gamma * (t[0] * dd - nn))) bad |= 1u << 4;
     if (t[4] != Fr::one()) bad |= 1u << 5;
-    std::vector<Claim> claims, v_claims;
+    std::vector<Claim> claims, v_claims, l_claims;
     detail::plonk_claims(p, c.r_g, c.r_p, claims, v_claims);
+    if (vk.lookup) detail::lookup_claims(p, c.r_l, claims, l_claims);
     if (failed_checks(ns + 6, claims, p.batch, c.b_alpha, c.rho_mu) || failed_checks(1, v_claims, p.v_batch, c.b_alpha, c.rho_mu1)) bad |= 1u << 6;
+    if (vk.lookup) {
+        Fr target = Fr::zero();
+        for (size_t i = 0; i < mu; ++i) {
+            if (p.l_rounds[i][0] + p.l_rounds[i][1] != target) {
+                bad |= 1u << 7;
+                break;
+            }
+            target = round_poly_nodes(p.l_rounds[i], c.r_l[i]);
+        }
+        if (!(bad & (1u << 7)) && target != lookup3_value(c.lambda * eq_eval(c.tau_l, c.r_l), p.l_values, c.zeta, c.beta_l, c.gamma_l)) bad |= 1u << 8;
+        if (failed_checks(7, l_claims, p.l_batch, c.b_alpha, c.rho_l)) bad |= 1u << 9;
+    }
     return bad;
 }
 
 inline bool plonk_verify(Ctx &be, const PcsVk &vk_mu, const PcsVk &vk_mu1, const PlonkVk &vk, const FrVec &pi, const PlonkProof &p) {
     PlonkChallenges c;
     if (!plonk_challenges(vk, pi, p, c) || plonk_failed_checks(vk, pi, p, c)) return false;
-    std::vector<Claim> claims, v_claims;
+    std::vector<Claim> claims, v_claims, l_claims;
     detail::plonk_claims(p, c.r_g, c.r_p, claims, v_claims);
+    if (vk.lookup) detail::lookup_claims(p, c.r_l, claims, l_claims);
     const size_t ns = gate_desc(vk.gate).selectors;  // the tables of the mu-variate instance: the selectors, a, b, c, ssigma_0..2
     G1Vec comms(vk.commitments.begin(), vk.commitments.begin() + ns);
     comms.insert(comms.end(), p.commitments.begin(), p.commitments.end());
-    comms.insert(comms.end(), vk.commitments.begin() + ns, vk.commitments.end());
-    return batch_open_verify(be, vk_mu, comms, claims, p.batch, c.b_alpha, c.rho_mu) &&
-           batch_open_verify(be, vk_mu1, G1Vec{p.v_commitment}, v_claims, p.v_batch, c.b_alpha, c.rho_mu1);
+    comms.insert(comms.end(), vk.commitments.begin() + ns, vk.commitments.begin() + ns + 3);
+    try {
+        if (!batch_open_verify(be, vk_mu, comms, claims, p.batch, c.b_alpha, c.rho_mu) ||
+            !batch_open_verify(be, vk_mu1, G1Vec{p.v_commitment}, v_claims, p.v_batch, c.b_alpha, c.rho_mu1))
+            return false;
+        if (!vk.lookup) return true;
+        G1Vec l_comms(vk.commitments.begin() + ns + 3, vk.commitments.end());  // the third instance: qk, t0, t1, t2, m, hf, ht
+        l_comms.insert(l_comms.end(), p.l_commitments.begin(), p.l_commitments.end());
+        return batch_open_verify(be, vk_mu, l_comms, l_claims, p.l_batch, c.b_alpha, c.rho_l);
+    } catch (const ZkError &e) {  // a point of the record that is not on the curve is refused by the pairing call: a record to reject
+        if (e.status != ZK_ERR_INVALID) throw;
+        return false;
+    }
 }
 
 // zkhip.plonk.proof_digest: the record's words in the order of the schedule
@@ -422,6 +612,12 @@ inline std::string proof_digest(const PlonkProof &p) {
     h.update(p.v_values.data(), 32 * p.v_values.size());
     detail::digest_batch(h, p.batch);
     detail::digest_batch(h, p.v_batch);
+    if (p.lookup) {
+        h.update(p.l_commitments.data(), 144 * p.l_commitments.size());
+        for (auto &r : p.l_rounds) h.update(r.data(), 4 * 32);
+        h.update(p.l_values.data(), 32 * p.l_values.size());
+        detail::digest_batch(h, p.l_batch);
+    }
     return h.hex();
 }
 

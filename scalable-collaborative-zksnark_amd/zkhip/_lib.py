@@ -50,6 +50,9 @@ SYMBOLS = [
     ("zk_sumcheck_gate_wide", _i, [_vp, _vp, _sz, _vp, _vp, _vp]),
     ("zk_lookup_multiplicities", _i, [_vp, _vp, _vp, _vp, _sz, _vp]),
     ("zk_sumcheck_lookup", _i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp]),
+    ("zk_lookup3_multiplicities", _i, [_vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    ("zk_lookup3_terms", _i, [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
+    ("zk_sumcheck_lookup_sel", _i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp]),
     ("zk_eq_table_acc", _i, [_vp, _vp, _sz, _vp, _vp]),
     ("zk_fr_lincomb", _i, [_vp, _sz, _vp, _vp, _sz, _vp]),
     ("zk_sumcheck_multi", _i, [_vp, _sz, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
@@ -64,6 +67,7 @@ SYMBOLS = [
     ("zk_sumcheck_perm3_fs", _i, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
     ("zk_sumcheck_gate_wide_fs", _i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp]),
     ("zk_sumcheck_lookup_fs", _i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
+    ("zk_sumcheck_lookup_sel_fs", _i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
     ("zk_sumcheck_multi_fs", _i, [_vp, _sz, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
     ("zk_open_rounds", _i, [_vp, _vp, _sz, _vp, _vp, _vp]),
     ("zk_sumcheck_batch", _i, [_vp, _sz, _vp]),

@@ -572,6 +572,44 @@ class Ctx:
         self._check(self.lib.zk_sumcheck_lookup(self.h, self._ptr_array(tabs), length, _h(gamma), _h(chal), _h(out), _h(last)))
         return out, last
 
+    def lookup3_multiplicities(self, ws, ts, qk, idx, N: int, out=None):
+        """m[y] = #{x : qk(x) = 1, idx[x] = y} as N Fr for the lookup of a Plonk circuit (zk_lookup3_multiplicities; blocking): ws = (a, b, c),
+        ts = (t0, t1, t2), qk device buffers of N Fr, idx one of N u32.  A selected row whose index is out of range or whose triple is not the
+        table's entry, or a qk that is neither 0 nor 1: ValueError -- as is every other ZK_ERR_INVALID of the call, with the library's message."""
+        if len(ws) != 3 or len(ts) != 3:
+            raise ValueError("three wire columns and three table columns are needed")
+        out = out or self.alloc(max(32 * N, 1))
+        rc = self.lib.zk_lookup3_multiplicities(self.h, self._ptr_array(ws), self._ptr_array(ts), _ptr(qk), _ptr(idx), N, _ptr(out))
+        if rc == ZK_ERR_INVALID:
+            raise ValueError((self.lib.zk_last_error(self.h) or b"").decode())
+        self._check(rc)
+        return out
+
+    def lookup3_terms(self, ws, ts, N: int, zeta: np.ndarray, beta: np.ndarray):
+        """df = beta + a + zeta b + zeta^2 c, dt = beta + t0 + zeta t1 + zeta^2 t2 in one pass (zk_lookup3_terms; asynchronous) -> (df, dt),
+        device buffers of N Fr"""
+        if len(ws) != 3 or len(ts) != 3:
+            raise ValueError("three wire columns and three table columns are needed")
+        ze, be = np.ascontiguousarray(zeta, dtype=np.uint64).reshape(4), np.ascontiguousarray(beta, dtype=np.uint64).reshape(4)
+        df, dt = self.alloc(max(32 * N, 1)), self.alloc(max(32 * N, 1))
+        self._check(self.lib.zk_lookup3_terms(self.h, self._ptr_array(ws), self._ptr_array(ts), N, _h(ze), _h(be), _ptr(df), _ptr(dt)))
+        return df, dt
+
+    def sumcheck_lookup_sel(self, tabs, length: int, gamma: np.ndarray, chal: np.ndarray):
+        """the selector-gated lookup identity hf - ht + E [hf df - qk + gamma (ht dt - m)] as one degree-3 sumcheck; tabs: the seven device
+        buffers E, df, dt, m, hf, ht, qk of `length` Fr -> (evals [n,4,4], last [7,4] in that order)"""
+        if len(tabs) != 7:
+            raise ValueError("seven tables are needed: E, df, dt, m, hf, ht, qk")
+        n = max(length.bit_length() - 1, 0)
+        gamma = np.ascontiguousarray(gamma, dtype=np.uint64).reshape(4)
+        chal = np.ascontiguousarray(chal, dtype=np.uint64).reshape(-1, 4)
+        if len(chal) != n:
+            raise ValueError(f"{n} challenges needed, {len(chal)} given")
+        out = np.zeros((n, 4, 4), dtype=np.uint64)
+        last = np.zeros((7, 4), dtype=np.uint64)
+        self._check(self.lib.zk_sumcheck_lookup_sel(self.h, self._ptr_array(tabs), length, _h(gamma), _h(chal), _h(out), _h(last)))
+        return out, last
+
     def eq_table_acc(self, point: np.ndarray, weight: np.ndarray, acc):
         """acc[x] += weight * eq(point, x), acc a device buffer of 2^n Fr (zk_eq_table_acc; asynchronous) -> acc"""
         point = np.ascontiguousarray(point, dtype=np.uint64).reshape(-1, 4)
@@ -651,6 +689,16 @@ class Ctx:
         gamma = np.ascontiguousarray(gamma, dtype=np.uint64).reshape(4)
         out, last, chal = np.zeros((n, 4, 4), dtype=np.uint64), np.zeros((6, 4), dtype=np.uint64), np.zeros((n, 4), dtype=np.uint64)
         self._check(self.lib.zk_sumcheck_lookup_fs(self.h, self._ptr_array(tabs), length, _h(gamma), self._tr(transcript), _h(out), _h(last), _h(chal)))
+        return out, last, chal
+
+    def sumcheck_lookup_sel_fs(self, tabs, length: int, gamma: np.ndarray, transcript):
+        """sumcheck_lookup_sel with derived challenges -> (evals [n,4,4], last [7,4], chal [n,4])"""
+        if len(tabs) != 7:
+            raise ValueError("seven tables are needed: E, df, dt, m, hf, ht, qk")
+        n = max(length.bit_length() - 1, 0)
+        gamma = np.ascontiguousarray(gamma, dtype=np.uint64).reshape(4)
+        out, last, chal = np.zeros((n, 4, 4), dtype=np.uint64), np.zeros((7, 4), dtype=np.uint64), np.zeros((n, 4), dtype=np.uint64)
+        self._check(self.lib.zk_sumcheck_lookup_sel_fs(self.h, self._ptr_array(tabs), length, _h(gamma), self._tr(transcript), _h(out), _h(last), _h(chal)))
         return out, last, chal
 
     def sumcheck_multi_fs(self, es, fs, length: int, transcript):

@@ -39,6 +39,27 @@ Everything else -- the schedule, the permutation half, the (mu + 1)-variate inst
 gate kind (label, selector names, evaluations per round, the device sumcheck, the verifier's closed form).  The wide record and vk carry
 "gate": "wide"; a circuit, key or record without the key is of the basic kind and behaves exactly as before.
 
+LOOKUPS.  A circuit may carry "lookup": {"qk", "t0", "t1", "t2": [N, 4]}: qk is a selector (0 or 1) and the table holds N triples (pad it by
+repeating an entry).  Row x with qk(x) = 1 claims (a, b, c)(x) = (t0, t1, t2)(idx[x]) for the prover's row-to-table indices idx (u32[N]); a
+row with qk(x) = 0 claims nothing.  With challenges zeta, beta_l, gamma_l, lambda and a point tau_l (LogUp with a selector):
+
+    f = a + zeta b + zeta^2 c,  t = t0 + zeta t1 + zeta^2 t2,  df = beta_l + f,  dt = beta_l + t,  hf = qk / df,  ht = m / dt,
+    m[y] = #{x : qk(x) = 1, idx[x] = y},
+    sum_x hf(x) - ht(x) + E(x) [ hf(x) df(x) - qk(x) + gamma_l ( ht(x) dt(x) - m(x) ) ] = 0,      E = lambda eq(tau_l, .)
+
+one degree-3 sumcheck over the seven tables E, df, dt, m, hf, ht, qk (zk_sumcheck_lookup_sel_fs).  f is not committed: df(r) is linear in
+a(r), b(r), c(r), which the wire commitments carry.  The lookup is orthogonal to the gate kind; the label is the gate's + "-lookup".  pk,
+vk and the record carry "lookup"; the vk commitments are the gate's followed by those of qk, t0, t1, t2.  Insertions into the schedule:
+  2L. after alpha, beta: m; absorb its commitment;  zeta, beta_l <- challenges;
+  3L. after gamma: df, dt, hf, ht; absorb the commitments of hf and ht;  gamma_l, lambda <- challenges;
+  5L. after the gate sumcheck: tau_l <- mu challenges; the lookup sumcheck: per round absorb its four evaluations, r_l[i] <- challenge;
+  6.  after v_values absorb "l_values": a, b, c, qk, t0, t1, t2, m, hf, ht at r_l;
+  7.  the mu-variate instance gains three claims (a, b, c at r_l) after the existing ones; after the (mu + 1)-variate instance comes a THIRD
+      one: the seven tables qk, t0, t1, t2, m, hf, ht with seven claims at r_l (zk_sumcheck_multi takes at most 16 tables: the wide kind's
+      twelve and these seven do not fit one instance).  Three opening proofs.
+The record gains "lookup": {"commitments": [3, 18] (m, hf, ht), "rounds": [mu, 4, 4], "values": [10, 4], "batch": {"rounds": [mu, 3, 4],
+"opening": [mu, 18]}}.  A circuit, key or record without "lookup" behaves exactly as before.
+
 Record: {"mu", "l", "commitments": [3, 18] (a, b, c), "v_commitment": [18], "p_rounds": [mu, 6, 4], "g_rounds": [mu, 5, 4],
          "g_values": [5, 4], "p_values": [6, 4], "v_values": [5, 4], "batch": {"rounds": [mu, 3, 4], "opening": [mu, 18]},
          "v_batch": {"rounds": [mu + 1, 3, 4], "opening": [mu + 1, 18]}}.
@@ -62,6 +83,11 @@ G_VALUES = ("q1", "q2", "a", "b", "c")                              # at r_g
 P_VALUES = ("a", "b", "c", "ssigma0", "ssigma1", "ssigma2")          # at r_p
 BATCH_TABLES = ("q1", "q2", "a", "b", "c", "ssigma0", "ssigma1", "ssigma2")  # the tables of the mu-variate batch instance
 _SSIGMA = ("ssigma0", "ssigma1", "ssigma2")
+LOOKUP_SUFFIX = b"-lookup"
+LOOKUP_VK_TABLES = ("qk", "t0", "t1", "t2")                          # preprocessed; their commitments follow the gate's in the vk
+LOOKUP_COMMITTED = ("m", "hf", "ht")                                  # the prover's commitments of the record's "lookup" part
+L_VALUES = ("a", "b", "c", "qk", "t0", "t1", "t2", "m", "hf", "ht")  # at r_l
+L_BATCH_TABLES = L_VALUES[3:]                                         # the tables of the third batch instance
 
 
 class Gate:
@@ -138,6 +164,21 @@ def slot_eval(r) -> int:
     return sum(x << (mu - 1 - i) for i, x in enumerate(r)) % R_MOD
 
 
+def lookup3_value(E: int, a: int, b: int, c: int, qk: int, t0: int, t1: int, t2: int, m: int, hf: int, ht: int, zeta: int, beta: int, gamma: int) -> int:
+    """hf - ht + E [ hf (beta + a + zeta b + zeta^2 c) - qk + gamma ( ht (beta + t0 + zeta t1 + zeta^2 t2) - m ) ]"""
+    df, dt = beta + a + zeta * b + zeta * zeta * c, beta + t0 + zeta * t1 + zeta * zeta * t2
+    return (hf - ht + E * (hf * df - qk + gamma * (ht * dt - m))) % R_MOD
+
+
+def has_lookup(d: dict) -> bool:
+    """whether a circuit, key or record carries the lookup part"""
+    return d.get("lookup") is not None and d.get("lookup") is not False
+
+
+def label_of(gate: Gate, lookup: bool) -> bytes:
+    return gate.label + LOOKUP_SUFFIX if lookup else gate.label
+
+
 def perm3_value(eq: int, v1x: int, vx0: int, vx1: int, h: int, n, d, gamma: int) -> int:
     return eq * (v1x - vx0 * vx1 + gamma * (h * d[0] * d[1] * d[2] - n[0] * n[1] * n[2])) % R_MOD
 
@@ -157,6 +198,8 @@ def preprocess(be, pcs, circuit: dict, powers_of_g2=None):
     qL, qR, qM, qO, qC, qH in the place of q1, q2 (the commitments then in GATES["wide"].vk_tables order, and pk, vk carry "gate"); pcs: the levels of a PolynomialCommitment
     over mu + 1 variables; powers_of_g2 (optional): the SRS's [g2, s_0 g2, .., s_mu g2], from which the pairing keys of `verify` are made.
     -> (pk, vk): vk = {"mu", "l", "commitments": [5, 18] in VK_TABLES order, "pcs": (vk_mu, vk_mu1) or None}; pk keeps the device tables.
+    A circuit with "lookup" (module text): qk is checked to hold only 0 and 1, qk, t0, t1, t2 are committed after the gate's tables, and pk, vk
+    carry "lookup": True.
     """
     from . import dist_primitive as dp
 
@@ -171,14 +214,24 @@ def preprocess(be, pcs, circuit: dict, powers_of_g2=None):
     tabs = {k: be.to_device(_u64(circuit[k], N, 4)) for k in gate.selectors}
     for j in range(3):
         tabs[f"ssigma{j}"] = slot_table(be, sigma[j * N:(j + 1) * N])
-    comms = np.stack([_u64(dp.commit(be, pcs, tabs[k], N), 18) for k in gate.vk_tables])
-    vk = {"mu": mu, "l": l, "commitments": comms, "pcs": wr.verifying_keys(be, powers_of_g2) if powers_of_g2 is not None else None, **gate.tag()}
-    return {"mu": mu, "l": l, "tables": tabs, "commitments": comms, "pcs": pcs, **gate.tag()}, vk
+    names, tag = gate.vk_tables, gate.tag()
+    if has_lookup(circuit):
+        lk = {k: _u64(circuit["lookup"][k], N, 4) for k in LOOKUP_VK_TABLES}
+        one = fr_mont(1)
+        if not ((lk["qk"] == 0).all(axis=1) | (lk["qk"] == one).all(axis=1)).all():
+            raise ValueError("every entry of the lookup selector qk must be 0 or 1")
+        tabs.update({k: be.to_device(v) for k, v in lk.items()})
+        names, tag = names + LOOKUP_VK_TABLES, dict(tag, lookup=True)
+    comms = np.stack([_u64(dp.commit(be, pcs, tabs[k], N), 18) for k in names])
+    vk = {"mu": mu, "l": l, "commitments": comms, "pcs": wr.verifying_keys(be, powers_of_g2) if powers_of_g2 is not None else None, **tag}
+    return {"mu": mu, "l": l, "tables": tabs, "commitments": comms, "pcs": pcs, **tag}, vk
 
 
 # ---- prover ----
-def prove(be, pk: dict, a, b, c, public_inputs, timing: dict | None = None) -> dict:
+def prove(be, pk: dict, a, b, c, public_inputs, idx=None, timing: dict | None = None) -> dict:
     """a, b, c: device buffers of N Fr (or [N, 4] arrays); public_inputs: [l, 4] Montgomery Fr -> the record of the module text.
+    idx: the N row-to-table indices (array or device buffer of u32), required exactly when the key has a lookup (else ValueError); a selected
+    row whose triple is not the table entry it names raises ValueError.
     A zero denominator raises ZeroDivisionError (ZK_ERR_DIV_ZERO); a zero challenge alpha (probability 2^-254), from which ssigma_j(r_p)
     cannot be recovered, ValueError.  timing (optional dict) receives the wall seconds of the phases."""
     import time
@@ -187,32 +240,61 @@ def prove(be, pk: dict, a, b, c, public_inputs, timing: dict | None = None) -> d
     from .nizk import _batch_prove
 
     gate = gate_of(pk)
+    lookup = has_lookup(pk)
     mu, l, pcs = pk["mu"], pk["l"], pk["pcs"]
     N = 1 << mu
     pi = _u64(public_inputs, -1, 4)
     if len(pi) != l:
         raise ValueError(f"{l} public inputs needed, {len(pi)} given")
+    if lookup != (idx is not None):
+        raise ValueError("idx is needed exactly when the key has a lookup")
+    if lookup and not (isinstance(idx, int) or hasattr(idx, "ptr") or hasattr(idx, "data_ptr")):  # not on the device: an array or a sequence
+        idx = np.asarray(idx)
+        if idx.size != N or idx.dtype.kind not in "ui":
+            raise ValueError(f"idx must hold {N} unsigned integers")
+        idx = be.to_device(np.ascontiguousarray(idx, dtype=np.uint32).reshape(N))
     wires = {k: (be.to_device(_u64(v, N, 4)) if isinstance(v, np.ndarray) else v) for k, v in (("a", a), ("b", b), ("c", c))}
     tabs = dict(pk["tables"], **wires)
     t0 = time.perf_counter()
     comms = np.stack([_u64(dp.commit(be, pcs, wires[k], N), 18) for k in ("a", "b", "c")])
-    tr = Transcript(be, gate.label)
+    tr = Transcript(be, label_of(gate, lookup))
+    lk_part = {}
     try:
         tr.absorb_u64(mu).absorb_u64(l).absorb(pk["commitments"]).absorb(pi)
         alpha, beta = tr.absorb(comms).challenges(2)
         if not fr_from_mont(alpha):
             raise ValueError("the challenge alpha is zero")
+        if lookup:  # 2L
+            w_cols, t_cols = [wires[k] for k in ("a", "b", "c")], [tabs[k] for k in ("t0", "t1", "t2")]
+            m = be.lookup3_multiplicities(w_cols, t_cols, tabs["qk"], idx, N)
+            c_m = _u64(dp.commit(be, pcs, m, N), 18)
+            zeta, beta_l = tr.absorb(c_m).challenges(2)
         nums, dens, P, Q = be.perm3_terms([wires[k] for k in ("a", "b", "c")], [tabs[f"ssigma{j}"] for j in range(3)], N, alpha, beta)
         tree = be.product_tree(be.fr_batch_div(P, Q, N), N)
         v_comm = _u64(dp.commit(be, pcs, tree, 2 * N), 18)
         t1 = time.perf_counter()
         gamma = tr.absorb(v_comm).challenge()
+        if lookup:  # 3L
+            df, dt = be.lookup3_terms(w_cols, t_cols, N, zeta, beta_l)
+            hf, ht = be.fr_batch_div(tabs["qk"], df, N), be.fr_batch_div(m, dt, N)
+            c_hf, c_ht = (_u64(dp.commit(be, pcs, x, N), 18) for x in (hf, ht))
+            gamma_l, lam = tr.absorb(np.stack([c_hf, c_ht])).challenges(2)
         p_rounds, p_last, r_p = be.sumcheck_perm3_fs(be.eq_table(tr.challenges(mu)), tree, nums, dens, N, gamma, tr)
         t2 = time.perf_counter()
         inp = np.zeros((N, 4), dtype=np.uint64)
         inp[:l] = pi
         g_rounds, g_last, r_g = gate.sumcheck(be, be.eq_table(tr.challenges(mu)), tabs, be.to_device(inp), N, tr)
         t3 = time.perf_counter()
+        if lookup:  # 5L
+            E = be.fr_scale(be.eq_table(tr.challenges(mu)), lam, N)
+            l_rounds, l_last, r_l = be.sumcheck_lookup_sel_fs([E, df, dt, m, hf, ht, tabs["qk"]], N, gamma_l, tr)
+            # a, b, c, t0, t1, t2 at r_l: six folds in one zk_sumcheck_batch, into one buffer, one download
+            six, at = ("a", "b", "c", "t0", "t1", "t2"), be.alloc(32 * 6)
+            be.sumcheck_batch([("fold", tabs[k], N, r_l, at.at(32 * j)) for j, k in enumerate(six)])
+            at_rl = dict(zip(six, at.download((6, 4))))
+            at_rl.update(qk=l_last[6], m=l_last[3], hf=l_last[4], ht=l_last[5])  # the folded-out last values
+            l_values = np.stack([at_rl[k] for k in L_VALUES])
+        t3l = time.perf_counter()
         g_values = g_last[1:1 + len(gate.g_values)]  # the folded-out values ARE the selectors and a, b, c at r_g
         # the folded-out n_j, d_j at r_p give the wires and the permutation columns there: both are linear in them
         al, bt, ids = fr_from_mont(alpha), fr_from_mont(beta), slot_eval(_ints(r_p))
@@ -222,29 +304,44 @@ def prove(be, pk: dict, a, b, c, public_inputs, timing: dict | None = None) -> d
         p_values = np.stack([fr_mont(x) for x in w_r + s_r])
         # the tree at (0,r) = h, (1,r) = v1x, (r,0) = vx0, (r,1) = vx1 are folded-out values too; (1,..,1,0) is tree[2N - 2]
         v_values = np.stack([p_last[4], p_last[1], p_last[2], p_last[3], tree.download((1, 4), offset=32 * (2 * N - 2))[0]])
-        b_alpha = tr.absorb(g_values).absorb(p_values).absorb(v_values).challenge()
+        tr.absorb(g_values).absorb(p_values).absorb(v_values)
+        if lookup:
+            tr.absorb(l_values)
+        b_alpha = tr.challenge()
         bt_names = gate.batch_tables
         claims = [(bt_names.index(k), r_g, v) for k, v in zip(gate.g_values, g_values)] + [(bt_names.index(k), r_p, v) for k, v in zip(P_VALUES, p_values)]
+        if lookup:
+            claims += [(bt_names.index(k), r_l, at_rl[k]) for k in ("a", "b", "c")]
         batch, _ = _batch_prove(be, pcs, [tabs[k] for k in bt_names], N, claims, b_alpha, tr)
         v_batch, _ = _batch_prove(be, pcs, [tree], 2 * N, [(0, z, v) for z, v in zip(wr.v_points(r_p), v_values)], b_alpha, tr)
+        if lookup:
+            l_tabs = dict(tabs, m=m, hf=hf, ht=ht)
+            l_batch, _ = _batch_prove(be, pcs, [l_tabs[k] for k in L_BATCH_TABLES], N, [(j, r_l, at_rl[k]) for j, k in enumerate(L_BATCH_TABLES)], b_alpha, tr)
+            lk_part = {"lookup": {"commitments": np.stack([c_m, c_hf, c_ht]), "rounds": l_rounds, "values": l_values, "batch": l_batch}}
     finally:
         tr.free()
     t4 = time.perf_counter()
     if timing is not None:
-        timing["commit_s"], timing["perm3_s"], timing["gate_s"], timing["opening_s"] = t1 - t0, t2 - t1, t3 - t2, t4 - t3
+        timing["commit_s"], timing["perm3_s"], timing["gate_s"], timing["opening_s"] = t1 - t0, t2 - t1, t3 - t2, t4 - t3l
+        if lookup:
+            timing["lookup_s"] = t3l - t3
     return {"mu": mu, "l": l, "commitments": comms, "v_commitment": v_comm, "p_rounds": p_rounds, "g_rounds": g_rounds, "g_values": np.array(g_values),
-            "p_values": p_values, "v_values": v_values, "batch": batch, "v_batch": v_batch, **gate.tag()}
+            "p_values": p_values, "v_values": v_values, "batch": batch, "v_batch": v_batch, **gate.tag(), **lk_part}
 
 
 # ---- verifier ----
 def challenges(vk: dict, public_inputs, proof: dict, label: bytes | None = None) -> dict:
     """the verifier's replay of the schedule on hashlib (label: the gate kind's, unless given) -> {"alpha", "beta", "gamma", "tau_p", "r_p",
-    "tau_g", "r_g", "b_alpha", "rho_mu", "rho_mu1"}; ValueError / KeyError on a malformed record or statement, a record of another gate
-    kind than the key's among them"""
+    "tau_g", "r_g", "b_alpha", "rho_mu", "rho_mu1"} and, with a lookup, {"zeta", "beta_l", "gamma_l", "lambda", "tau_l", "r_l", "rho_l"};
+    ValueError / KeyError on a malformed record or statement, a record of another gate kind than the key's or a record / key pair that
+    disagrees on having a lookup among them"""
     gate = gate_of(vk)
     if gate_of(proof) is not gate:
         raise ValueError("the record and the key are of different gate kinds")
-    label = gate.label if label is None else label
+    lookup = has_lookup(vk)
+    if has_lookup(proof) != lookup:
+        raise ValueError("the record and the key disagree on having a lookup")
+    label = label_of(gate, lookup) if label is None else label
     mu, l = int(vk["mu"]), int(vk["l"])
     pi = _u64(public_inputs, -1, 4)
     p_rounds, g_rounds = _u64(proof["p_rounds"], -1, 6, 4), _u64(proof["g_rounds"], -1, gate.evals, 4)
@@ -254,19 +351,38 @@ def challenges(vk: dict, public_inputs, proof: dict, label: bytes | None = None)
     if mu < 1 or len(p_rounds) != mu or len(g_rounds) != mu or len(b_rounds) != mu or len(v_rounds) != mu + 1:
         raise ValueError("the record does not hold mu / mu + 1 rounds")
     rr = lambda tr, rounds: np.stack([tr.absorb(r).challenge() for r in rounds])
+    c = {}
+    if lookup:
+        lp = proof["lookup"]
+        l_comms, l_rounds, lb_rounds = _u64(lp["commitments"], len(LOOKUP_COMMITTED), 18), _u64(lp["rounds"], -1, 4, 4), _u64(lp["batch"]["rounds"], -1, 3, 4)
+        l_values = _u64(lp["values"], len(L_VALUES), 4)
+        if len(l_rounds) != mu or len(lb_rounds) != mu:
+            raise ValueError("the lookup part does not hold mu rounds")
     tr = HostTranscript(label)
-    tr.absorb_u64(mu).absorb_u64(l).absorb(_u64(vk["commitments"], len(gate.vk_tables), 18)).absorb(pi)
+    tr.absorb_u64(mu).absorb_u64(l).absorb(_u64(vk["commitments"], len(gate.vk_tables) + (len(LOOKUP_VK_TABLES) if lookup else 0), 18)).absorb(pi)
     alpha, beta = tr.absorb(_u64(proof["commitments"], 3, 18)).challenges(2)
+    if lookup:
+        c["zeta"], c["beta_l"] = tr.absorb(l_comms[0]).challenges(2)
     gamma = tr.absorb(_u64(proof["v_commitment"], 18)).challenge()
+    if lookup:
+        c["gamma_l"], c["lambda"] = tr.absorb(l_comms[1:]).challenges(2)
     tau_p = tr.challenges(mu)
     r_p = rr(tr, p_rounds)
     tau_g = tr.challenges(mu)
     r_g = rr(tr, g_rounds)
+    if lookup:
+        c["tau_l"] = tr.challenges(mu)
+        c["r_l"] = rr(tr, l_rounds)
     tr.absorb(_u64(proof["g_values"], len(gate.g_values), 4)).absorb(_u64(proof["p_values"], len(P_VALUES), 4)).absorb(_u64(proof["v_values"], len(wr.V_POINTS), 4))
+    if lookup:
+        tr.absorb(l_values)
     b_alpha = tr.challenge()
     rho_mu = rr(tr, b_rounds)
-    return {"alpha": alpha, "beta": beta, "gamma": gamma, "tau_p": tau_p, "r_p": r_p, "tau_g": tau_g, "r_g": r_g, "b_alpha": b_alpha, "rho_mu": rho_mu,
-            "rho_mu1": rr(tr, v_rounds)}
+    c.update({"alpha": alpha, "beta": beta, "gamma": gamma, "tau_p": tau_p, "r_p": r_p, "tau_g": tau_g, "r_g": r_g, "b_alpha": b_alpha, "rho_mu": rho_mu,
+              "rho_mu1": rr(tr, v_rounds)})
+    if lookup:
+        c["rho_l"] = rr(tr, lb_rounds)
+    return c
 
 
 def _claims(c: dict, proof: dict):
@@ -275,10 +391,19 @@ def _claims(c: dict, proof: dict):
     v_values = _u64(proof["v_values"], len(wr.V_POINTS), 4)
     bt_names = gate.batch_tables
     claims = [(bt_names.index(k), c["r_g"], v) for k, v in zip(gate.g_values, g_values)] + [(bt_names.index(k), c["r_p"], v) for k, v in zip(P_VALUES, p_values)]
+    if has_lookup(proof):
+        l_values = _u64(proof["lookup"]["values"], len(L_VALUES), 4)
+        claims += [(bt_names.index(k), c["r_l"], l_values[j]) for j, k in enumerate(("a", "b", "c"))]
     return claims, [(0, z, v) for z, v in zip(wr.v_points(c["r_p"]), v_values)]
 
 
-def failed_checks(vk: dict, public_inputs, proof: dict, finals=None, v_finals=None, c: dict | None = None) -> list:
+def _lookup_claims(c: dict, proof: dict):
+    """the seven claims of the third batch instance: L_BATCH_TABLES at r_l"""
+    l_values = _u64(proof["lookup"]["values"], len(L_VALUES), 4)
+    return [(j, c["r_l"], l_values[3 + j]) for j in range(len(L_BATCH_TABLES))]
+
+
+def failed_checks(vk: dict, public_inputs, proof: dict, finals=None, v_finals=None, c: dict | None = None, l_finals=None) -> list:
     """
     The verifier's field arithmetic (no GPU, no pairing) -> the numbers of the checks that fail ([] = all hold; [0]: malformed):
       1. the wiring chain: p_0(0) + p_0(1) == 0, p_i(0) + p_i(1) == p_{i-1}(r_{i-1}) by interpolation on the nodes 0 .. 5;
@@ -289,7 +414,11 @@ def failed_checks(vk: dict, public_inputs, proof: dict, finals=None, v_finals=No
          n_j = a_j(r_p) + alpha (j N + slot_eval(r_p)) + beta and d_j = a_j(r_p) + alpha ssigma_j(r_p) + beta;
       5. v(1,..,1,0) == 1;
       6. the two batch instances' chains (and, given finals / v_finals = the tables at rho_mu / the tree at rho_mu1, their last values).
-    A record of another gate kind than the key's is malformed.
+    With a lookup:
+      7. the lookup chain: p_0(0) + p_0(1) == 0, then interpolation on the nodes 0 .. 3;
+      8. its last value == lookup3_value on the ten values of "lookup.values" with E = lambda eq(tau_l, r_l);
+      9. the third batch instance's chain (and, given l_finals = L_BATCH_TABLES at rho_l, its last value).
+    A record of another gate kind than the key's, or a record / key pair that disagrees on having a lookup, is malformed.
     """
     try:
         gate = gate_of(vk)
@@ -303,6 +432,12 @@ def failed_checks(vk: dict, public_inputs, proof: dict, finals=None, v_finals=No
         v0r, v1r, vr0, vr1, prod = _ints(_u64(proof["v_values"], len(wr.V_POINTS), 4))
         p_rounds, g_rounds = _u64(proof["p_rounds"], mu, 6, 4), _u64(proof["g_rounds"], mu, gate.evals, 4)
         claims, v_claims = _claims(c, proof)
+        lookup = has_lookup(vk)
+        if lookup:
+            l_rounds, lv = _u64(proof["lookup"]["rounds"], mu, 4, 4), _ints(_u64(proof["lookup"]["values"], len(L_VALUES), 4))
+            l_claims = _lookup_claims(c, proof)
+            if np.asarray(proof["lookup"]["batch"]["opening"], dtype=np.uint64).size != mu * 18:
+                return [0]
     except (KeyError, ValueError, TypeError):
         return [0]
     al, bt, gm = (fr_from_mont(c[k]) for k in ("alpha", "beta", "gamma"))
@@ -332,17 +467,31 @@ def failed_checks(vk: dict, public_inputs, proof: dict, finals=None, v_finals=No
     if bo.failed_checks(len(gate.batch_tables), claims, proof["batch"], c["b_alpha"], c["rho_mu"], finals) or \
             bo.failed_checks(1, v_claims, proof["v_batch"], c["b_alpha"], c["rho_mu1"], v_finals):
         bad.append(6)
+    if lookup:
+        r_l, target = _ints(c["r_l"]), 0
+        for i in range(mu):
+            p = _ints(l_rounds[i])
+            if (p[0] + p[1]) % R_MOD != target:
+                bad.append(7)
+                break
+            target = round_poly_at(p, r_l[i])
+        ze, bl, gl, lam = (fr_from_mont(c[k]) for k in ("zeta", "beta_l", "gamma_l", "lambda"))
+        if 7 not in bad and target != lookup3_value(lam * eq_eval(_ints(c["tau_l"]), r_l) % R_MOD, *lv, ze, bl, gl):
+            bad.append(8)
+        if bo.failed_checks(len(L_BATCH_TABLES), l_claims, proof["lookup"]["batch"], c["b_alpha"], c["rho_l"], l_finals):
+            bad.append(9)
     return sorted(bad)
 
 
-def field_checks(vk: dict, public_inputs, proof: dict, finals=None, v_finals=None) -> bool:
+def field_checks(vk: dict, public_inputs, proof: dict, finals=None, v_finals=None, l_finals=None) -> bool:
     """everything of `verify` but the pairings, without a GPU.  finals (tests that hold the tables): the gate kind's batch_tables at rho_mu;
     v_finals: [the tree at rho_mu1]; they stand in for the pairings' check of the values the batch chains end in"""
-    return not failed_checks(vk, public_inputs, proof, finals, v_finals)
+    return not failed_checks(vk, public_inputs, proof, finals, v_finals, l_finals=l_finals)
 
 
 def verify(be, vk: dict, public_inputs, proof: dict) -> bool:
-    """the replay, checks 1-6 of failed_checks, then one zk_pcs_verify_batch per batch instance (vk["pcs"]: wiring.verifying_keys)"""
+    """the replay, the checks of failed_checks, then one zk_pcs_verify_batch per batch instance: two, with a lookup three (vk["pcs"]:
+    wiring.verifying_keys)"""
     if vk.get("pcs") is None:
         raise ValueError("the verifying key holds no pairing keys (preprocess without powers_of_g2)")
     try:
@@ -351,12 +500,18 @@ def verify(be, vk: dict, public_inputs, proof: dict) -> bool:
             return False
         claims, v_claims = _claims(c, proof)
         ns = len(gate_of(vk).selectors)
-        vkc, pc = _u64(vk["commitments"], ns + 3, 18), _u64(proof["commitments"], 3, 18)
-        comms = np.concatenate([vkc[:ns], pc, vkc[ns:]])  # batch_tables order
+        lookup = has_lookup(vk)
+        vkc, pc = _u64(vk["commitments"], ns + 3 + (len(LOOKUP_VK_TABLES) if lookup else 0), 18), _u64(proof["commitments"], 3, 18)
+        comms = np.concatenate([vkc[:ns], pc, vkc[ns:ns + 3]])  # batch_tables order
         vk_mu, vk_mu1 = vk["pcs"]
         if not bo.batch_open_verify(be, vk_mu, comms, claims, proof["batch"], c["b_alpha"], c["rho_mu"]):
             return False
-        return bo.batch_open_verify(be, vk_mu1, _u64(proof["v_commitment"], 1, 18), v_claims, proof["v_batch"], c["b_alpha"], c["rho_mu1"])
+        if not bo.batch_open_verify(be, vk_mu1, _u64(proof["v_commitment"], 1, 18), v_claims, proof["v_batch"], c["b_alpha"], c["rho_mu1"]):
+            return False
+        if not lookup:
+            return True
+        l_comms = np.concatenate([vkc[ns + 3:], _u64(proof["lookup"]["commitments"], len(LOOKUP_COMMITTED), 18)])  # L_BATCH_TABLES order
+        return bo.batch_open_verify(be, vk_mu, l_comms, _lookup_claims(c, proof), proof["lookup"]["batch"], c["b_alpha"], c["rho_l"])
     except (KeyError, ValueError, TypeError):
         return False
 
@@ -370,6 +525,22 @@ def proof_digest(proof: dict) -> str:
         put(proof[k])
     for b in ("batch", "v_batch"):
         put(proof[b]["rounds"]), put(proof[b]["opening"])
+    if has_lookup(proof):
+        lp = proof["lookup"]
+        put(lp["commitments"]), put(lp["rounds"]), put(lp["values"]), put(lp["batch"]["rounds"]), put(lp["batch"]["opening"])
+    return h.hexdigest()
+
+
+def circuit_digest(circuit: dict) -> str:
+    """SHA-256 of a sampled circuit's tables: the selectors, a, b, c, the public inputs, the trapdoor, sigma (u64) and, with a lookup, qk, t0, t1,
+    t2 and idx (u32), little-endian in that order -- what host/bin/plonk_check --sample-only prints"""
+    h = hashlib.sha256()
+    for k in gate_of(circuit).selectors + ("a", "b", "c", "public_inputs", "s", "sigma"):
+        h.update(np.ascontiguousarray(circuit[k], dtype="<u8").tobytes())
+    if has_lookup(circuit):
+        for k in LOOKUP_VK_TABLES:
+            h.update(np.ascontiguousarray(circuit["lookup"][k], dtype="<u8").tobytes())
+        h.update(np.ascontiguousarray(circuit["idx"], dtype="<u4").tobytes())
     return h.hexdigest()
 
 
@@ -383,7 +554,7 @@ def _mont_ints(a) -> list:
     return [int.from_bytes(raw[i:i + 32], "little") for i in range(0, len(raw), 32)]
 
 
-def sample_circuit(mu: int, seed: int, break_gate: int | None = None, break_wire: int | None = None) -> dict:
+def sample_circuit(mu: int, seed: int, break_gate: int | None = None, break_wire: int | None = None, _lookup: dict | None = None) -> dict:
     """
     A satisfied circuit (numpy and python ints only; the same in host/zkhost/plonk.hpp): N = 2^mu rows, mu >= 2, l = min(4, N / 2).
     Streams of field.splitmix_fr: 1 = the l public inputs, 2 = q1, 3 = q2, 4 = the picks, 5 = the SRS trapdoor (mu + 1 elements).
@@ -392,7 +563,7 @@ def sample_circuit(mu: int, seed: int, break_gate: int | None = None, break_wire
                         c = q1 (a + b) + q2 a b, so in = 0 there.
     sigma: one cycle per value -- the c slot of row y, then the a / b slots that copy it in ascending slot order, back to the c slot;
     every other slot is a fixed point.  break_gate K adds 1 to c[K] after the fact; break_wire K (K >= l) adds 1 to a[K] and recomputes
-    c[K]: every gate still holds and only the copy constraint fails.
+    c[K]: every gate still holds and only the copy constraint fails.  (_lookup: the lookup rows of sample_circuit_lookup -- see _lookup_rows.)
     -> {"mu", "l", "q1", "q2", "a", "b", "c": [N, 4] Montgomery Fr, "sigma": [3N] u64, "public_inputs": [l, 4], "s": [mu + 1, 4]}
     """
     from .field import splitmix_fr
@@ -404,6 +575,9 @@ def sample_circuit(mu: int, seed: int, break_gate: int | None = None, break_wire
     pi = splitmix_fr(l, base + 1)
     q1, q2, pick = splitmix_fr(N, base + 2), splitmix_fr(N, base + 3), splitmix_fr(N, base + 4)
     q1[:l], q2[:l] = 0, 0
+    lk = _lookup
+    if lk:  # a lookup row is a product row: q1 = 0, q2 = 1
+        q1[lk["mask"]], q2[lk["mask"]] = 0, fr_mont(1)
     rows = np.arange(N, dtype=np.uint64)
     rows[0] = 1  # (row 0 is an input row: its picks are not used)
     ia, ib = pick[:, 0] % rows, pick[:, 1] % rows
@@ -412,10 +586,15 @@ def sample_circuit(mu: int, seed: int, break_gate: int | None = None, break_wire
     a, b, c = [0] * N, [0] * N, _mont_ints(pi) + [0] * (N - l)
     gate = lambda x: (q1i[x] * (a[x] + b[x]) + q2i[x] * a[x] % R_MOD * b[x] % R_MOD * rinv) % R_MOD * rinv % R_MOD
     ial, ibl = ia.tolist(), ib.tolist()
-    for x in range(l, N):
-        a[x], b[x] = c[ial[x]], c[ibl[x]]
-        c[x] = gate(x)
     one = (1 << 256) % R_MOD
+    for x in range(l, N):
+        if lk and lk["mask"][x]:
+            a[x], b[x] = lk["u"][lk["y"][x]], lk["v"][lk["y"][x]]
+            if x == lk["break"]:
+                a[x] = (a[x] + one) % R_MOD
+        else:
+            a[x], b[x] = c[ial[x]], c[ibl[x]]
+        c[x] = gate(x)
     if break_wire is not None:
         if not l <= break_wire < N:
             raise ValueError("break_wire must name a row past the input rows: the a slot of an input row is a fixed point")
@@ -423,18 +602,22 @@ def sample_circuit(mu: int, seed: int, break_gate: int | None = None, break_wire
         c[break_wire] = gate(break_wire)
     if break_gate is not None:
         c[break_gate] = (c[break_gate] + one) % R_MOD
-    return {"mu": mu, "l": l, "q1": q1, "q2": q2, "a": _limbs(a), "b": _limbs(b), "c": _limbs(c), "sigma": _copy_sigma(ia, ib, l, N), "public_inputs": pi,
-            "s": splitmix_fr(mu + 1, base + 5)}
+    return {"mu": mu, "l": l, "q1": q1, "q2": q2, "a": _limbs(a), "b": _limbs(b), "c": _limbs(c), "sigma": _copy_sigma(ia, ib, l, N, lk["mask"] if lk else None),
+            "public_inputs": pi, "s": splitmix_fr(mu + 1, base + 5)}
 
 
 def _limbs(xs) -> np.ndarray:
     return np.frombuffer(b"".join(x.to_bytes(32, "little") for x in xs), dtype="<u8").astype(np.uint64).reshape(-1, 4)
 
 
-def _copy_sigma(ia: np.ndarray, ib: np.ndarray, l: int, N: int) -> np.ndarray:
-    """one cycle per value: the users of c[y] are the a slots x with ia[x] = y and the b slots N + x with ib[x] = y, x >= l"""
+def _copy_sigma(ia: np.ndarray, ib: np.ndarray, l: int, N: int, fixed: np.ndarray | None = None) -> np.ndarray:
+    """one cycle per value: the users of c[y] are the a slots x with ia[x] = y and the b slots N + x with ib[x] = y, x >= l.  fixed (bool[N]):
+    rows whose a and b slots copy nothing and stay fixed points (the lookup rows)"""
     src = np.concatenate([ia[l:], ib[l:]])
     slot = np.concatenate([np.arange(l, N, dtype=np.uint64), np.arange(N + l, 2 * N, dtype=np.uint64)])
+    if fixed is not None:
+        keep = ~np.concatenate([fixed[l:], fixed[l:]])
+        src, slot = src[keep], slot[keep]
     order = np.lexsort((slot, src))
     src, slot = src[order], slot[order]
     sigma = np.arange(3 * N, dtype=np.uint64)
@@ -449,7 +632,7 @@ def _copy_sigma(ia: np.ndarray, ib: np.ndarray, l: int, N: int) -> np.ndarray:
 WIDE_SELECTORS = GATES["wide"].selectors
 
 
-def sample_circuit_wide(mu: int, seed: int, break_gate: int | None = None, break_wire: int | None = None) -> dict:
+def sample_circuit_wide(mu: int, seed: int, break_gate: int | None = None, break_wire: int | None = None, _lookup: dict | None = None) -> dict:
     """
     A satisfied circuit of the WIDE gate qL a + qR b + qM a b + qH a^5 - qO c + qC + in = 0 (numpy and python ints only; the same in
     host/zkhost/plonk.hpp): N = 2^mu rows, mu >= 2, l = min(4, N / 2).  Streams of field.splitmix_fr as in sample_circuit -- 1 = the l public
@@ -463,6 +646,7 @@ def sample_circuit_wide(mu: int, seed: int, break_gate: int | None = None, break
                                                                                    c = (qL a + qR b + qM a b + qH a^5 + qC) / qO
                         a selector the kind does not name is 0, and in = 0 there.
     sigma, break_gate K, break_wire K (K >= l: a[K] + 1, c[K] recomputed by the row's rule) and "s" as in sample_circuit.
+    (_lookup: the lookup rows of sample_circuit_lookup -- see _lookup_rows.)
     -> {"gate": "wide", "mu", "l", "qL", "qR", "qM", "qO", "qC", "qH", "a", "b", "c": [N, 4] Montgomery Fr, "sigma": [3N] u64,
         "public_inputs": [l, 4], "s": [mu + 1, 4]}
     """
@@ -485,6 +669,11 @@ def sample_circuit_wide(mu: int, seed: int, break_gate: int | None = None, break
             sel["qH"][x] = 1
         if kinds[x] == 3 and sel["qO"][x] == 0:
             sel["qO"][x] = 1
+    lk = _lookup
+    if lk:  # a lookup row is a pure product row: qM = qO = 1, every other selector 0
+        for x in np.flatnonzero(lk["mask"]).tolist():
+            for k in WIDE_SELECTORS:
+                sel[k][x] = 1 if k in ("qM", "qO") else 0
     rows = np.arange(N, dtype=np.uint64)
     rows[0] = 1  # (row 0 is an input row: its picks are not used)
     ia, ib = pick[:, 0] % rows, pick[:, 1] % rows
@@ -496,7 +685,12 @@ def sample_circuit_wide(mu: int, seed: int, break_gate: int | None = None, break
 
     ial, ibl = ia.tolist(), ib.tolist()
     for x in range(l, N):
-        a[x], b[x] = c[ial[x]], c[ibl[x]]
+        if lk and lk["mask"][x]:
+            a[x], b[x] = lk["u"][lk["y"][x]], lk["v"][lk["y"][x]]
+            if x == lk["break"]:
+                a[x] = (a[x] + 1) % R_MOD
+        else:
+            a[x], b[x] = c[ial[x]], c[ibl[x]]
         c[x] = out(x)
     if break_wire is not None:
         if not l <= break_wire < N:
@@ -506,8 +700,54 @@ def sample_circuit_wide(mu: int, seed: int, break_gate: int | None = None, break
     if break_gate is not None:
         c[break_gate] = (c[break_gate] + 1) % R_MOD
     mont = lambda xs: _limbs([(x << 256) % R_MOD for x in xs])
-    circuit = {"gate": "wide", "mu": mu, "l": l, "a": mont(a), "b": mont(b), "c": mont(c), "sigma": _copy_sigma(ia, ib, l, N), "public_inputs": pi,
+    circuit = {"gate": "wide", "mu": mu, "l": l, "a": mont(a), "b": mont(b), "c": mont(c), "sigma": _copy_sigma(ia, ib, l, N, lk["mask"] if lk else None), "public_inputs": pi,
                "s": splitmix_fr(mu + 1, base + 5)}
     circuit.update({k: mont(v) for k, v in sel.items()})
     return circuit
 
+
+def _lookup_rows(mask, y, u, v, break_row) -> dict:
+    """What sample_circuit_lookup hands to the two generators (struct LookupRows in host/zkhost/plonk.hpp): row x with mask[x] takes
+    a = u[y[x]], b = v[y[x]] in the place of copies and a product gate (c = a b); its a and b slots stay fixed points of sigma; row
+    break_row (None: none) gets a + 1 before its c is computed.  u, v: python ints in the domain the generator builds its rows in
+    (sample_circuit: Montgomery forms as they stand; sample_circuit_wide: canonical)"""
+    return {"mask": mask, "y": y, "u": u, "v": v, "break": break_row}
+
+
+def sample_circuit_lookup(mu: int, seed: int, gate: str | None = None, break_lookup: int | None = None) -> dict:
+    """
+    sample_circuit(mu, seed) -- with gate="wide": sample_circuit_wide -- plus lookup rows against a fixed multiplication table (numpy and python
+    ints only): N = 2^mu rows, mu >= 3.  Streams of field.splitmix_fr beside those of the two generators: 12 = u, 13 = v (D = N / 4 elements
+    each).  The table does not depend on the witness: entry y < D is (u_y, v_y, u_y v_y), padded to N by repeating entry D - 1.
+      row x >= l whose pick (stream 4) has an odd limb 3 is a lookup row: y = (limb 3 >> 1) mod D, a = u_y, b = v_y; its selectors make
+      c = a b (basic: q1 = 0, q2 = 1; wide: qM = qO = 1, the rest 0); qk = 1 and idx = y.  Its a and b slots are fixed points of sigma; its c
+      may be copied by later rows as usual.  Every other row is the generator's, with qk = 0 and idx = 0.
+    break_lookup K (a lookup row): a[K] + 1 and c[K] recomputed before any later row copies it -- every gate and the wiring still hold, and
+    the triple of row K is outside the table.
+    -> the generator's dict plus "lookup": {"qk", "t0", "t1", "t2": [N, 4] Montgomery Fr} and "idx": u32[N]
+    """
+    from .field import splitmix_fr
+
+    if mu < 3:
+        raise ValueError("mu >= 3 is needed")
+    if gate not in GATES:
+        raise ValueError(f"unknown gate kind {gate!r}")
+    N, base = 1 << mu, CIRCUIT_SEED + 1000 * seed
+    l, D = min(4, N // 2), N // 4
+    pick = splitmix_fr(N, base + 4)
+    mask = ((pick[:, 3] & np.uint64(1)) == 1) & (np.arange(N) >= l)
+    y = ((pick[:, 3] >> np.uint64(1)) % np.uint64(D)).astype(np.int64)
+    if break_lookup is not None and not (0 <= break_lookup < N and mask[break_lookup]):
+        raise ValueError("break_lookup must name a lookup row")
+    u, v = splitmix_fr(D, base + 12), splitmix_fr(D, base + 13)
+    as_ints = _ints if gate == "wide" else _mont_ints  # the domain the generator builds its rows in
+    plan = _lookup_rows(mask, y.tolist(), as_ints(u), as_ints(v), break_lookup)
+    circuit = (sample_circuit_wide if gate == "wide" else sample_circuit)(mu, seed, _lookup=plan)
+    rinv = pow(1 << 256, -1, R_MOD)
+    uv = _limbs([p * q % R_MOD * rinv % R_MOD for p, q in zip(_mont_ints(u), _mont_ints(v))])  # the Montgomery form of u_y v_y
+    pad = lambda t: np.concatenate([t, np.repeat(t[-1:], N - D, axis=0)])
+    qk = np.zeros((N, 4), dtype=np.uint64)
+    qk[mask] = fr_mont(1)
+    circuit["lookup"] = {"qk": qk, "t0": pad(u), "t1": pad(v), "t2": pad(uv)}
+    circuit["idx"] = np.where(mask, y, 0).astype(np.uint32)
+    return circuit

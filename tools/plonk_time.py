@@ -19,6 +19,16 @@ to stdout and to --out (default profiles/plonk_time.txt; '-' for stdout only).
   proof     plonk.prove / plonk.verify of the wide kind with the four phase times, and the basic kind's prove of the same run beside them.
 
 With --gate wide, --trace-mu M runs five zk_sumcheck_gate_wide calls at 2^M.
+
+--lookup measures Plonk with lookups instead (default --out profiles/plonk_lookup_time.txt):
+
+  sumcheck  zk_sumcheck_lookup_sel and zk_sumcheck_lookup_sel_fs (seven tables) against zk_sumcheck_lookup and zk_sumcheck_lookup_fs on the first
+            six of the same tables, with the band the multiplication count (23 / 22) and the traffic (7 / 6) predict;
+  proof     plonk.prove / plonk.verify on sample_circuit_lookup (both gate kinds, with --gate wide only the wide one) against plonk.prove
+            on the same circuit without its lookup part plus the stand-alone lookup.prove of the same size (and the matching verifiers):
+            neither baseline is touched by the lookup path, so the same run measures both sides.
+
+With --lookup, --trace-mu M runs five zk_sumcheck_lookup_sel calls at 2^M.
 """
 import argparse
 import json
@@ -56,10 +66,11 @@ def main():
     ap.add_argument("--seed", type=int, default=7)
     ap.add_argument("--trace-mu", type=int, default=0)
     ap.add_argument("--gate", choices=["wide"], default=None, help="measure the wide gate against the basic one instead")
+    ap.add_argument("--lookup", action="store_true", help="measure Plonk with lookups against the six-table sumcheck and the two separate proofs instead")
     ap.add_argument("--out", default=None, help="file the JSON lines are written to ('-': stdout only; default profiles/plonk_time.txt, with --gate wide profiles/widegate_time.txt)")
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "widegate_time.txt" if a.gate else "plonk_time.txt")
+        a.out = os.path.join(ROOT, "profiles", "plonk_lookup_time.txt" if a.lookup else "widegate_time.txt" if a.gate else "plonk_time.txt")
     import zkhip
     from zkhip import dist_primitive as dp
     from zkhip import nizk, plonk
@@ -136,6 +147,76 @@ def main():
                 del pk, vk, pcs, wires, proof
             g["wide_prove_over_basic"] = g["wide_prove_ms"] / g["basic_prove_ms"]
             emit(g)
+
+    def with_lookup():
+        from zkhip import lookup
+
+        band = lambda ratio: "below" if ratio < 1.05 else "above" if ratio > 1.17 else "within"  # against the predicted 1.05 .. 1.17
+
+        if a.trace_mu:
+            mu = a.trace_mu
+            tabs, gamma, chal = [filler(1 << mu, k) for k in range(7)], splitmix_fr(1, 3)[0], splitmix_fr(mu, 4)
+            for _ in range(5):
+                be.sumcheck_lookup_sel(tabs, 1 << mu, gamma, chal)
+            return
+        free = be.mem_info()[0]
+        for mu in [int(x) for x in a.mu.split(",") if x]:
+            N = 1 << mu
+            need = 32 * (7 * N + 7 * 3 * N // 4)  # seven tables and the ping-pong scratch of 7 x (N/2 + N/4)
+            if need > 0.8 * free:
+                emit({"sumcheck_mu": mu, "skipped": "needs %.1f GiB of %.1f GiB free" % (need / 2**30, free / 2**30)})
+                continue
+            tabs, gamma, chal = [filler(N, k) for k in range(7)], splitmix_fr(1, 3)[0], splitmix_fr(mu, 4)
+            tr = Transcript(be, b"time")
+            sel = timed(lambda: be.sumcheck_lookup_sel(tabs, N, gamma, chal), 3, a.reps)
+            sel_fs = timed(lambda: be.sumcheck_lookup_sel_fs(tabs, N, gamma, tr), 3, a.reps)
+            six = timed(lambda: be.sumcheck_lookup(tabs[:6], N, gamma, chal), 3, a.reps)
+            six_fs = timed(lambda: be.sumcheck_lookup_fs(tabs[:6], N, gamma, tr), 3, a.reps)
+            tr.free()
+            del tabs
+            emit({"sumcheck_mu": mu, "lookup_sel_ms": sel, "lookup_sel_fs_ms": sel_fs, "lookup_ms": six, "lookup_fs_ms": six_fs, "sel_over_lookup": sel / six,
+                  "sel_fs_over_lookup_fs": sel_fs / six_fs, "predicted": [1.05, 1.17], "prediction": band(sel / six), "prediction_fs": band(sel_fs / six_fs)})
+        for mu in [int(x) for x in a.proof_mu.split(",") if x]:
+            for kind in (["wide"] if a.gate else [None, "wide"]):
+                g = {"proof_mu": mu, "gate": kind or "basic"}
+                c = plonk.sample_circuit_lookup(mu, a.seed, gate=kind)
+                pcs = dp.PolynomialCommitmentCub.new(be, c["s"]).mature()
+                g2 = pr.powers_of_g2(ints(c["s"]))
+                wires, idx = [be.to_device(c[k]) for k in ("a", "b", "c")], be.to_device(c["idx"])
+                plain = {k: v for k, v in c.items() if k not in ("lookup", "idx")}
+                for name, circuit, kw in (("lookup", c, {"idx": idx}), ("plain", plain, {})):
+                    pk, vk = plonk.preprocess(be, pcs, circuit, g2)
+                    for rep in range(3):  # the last of three runs is reported (the first ones grow the arenas)
+                        tb = {}
+                        proof, g[name + "_prove_ms"] = once(lambda: plonk.prove(be, pk, *wires, c["public_inputs"], timing=tb, **kw))
+                        g.update({name + "_prove_" + k.replace("_s", "_ms"): v * 1e3 for k, v in tb.items()})
+                    for rep in range(2):
+                        ok, g[name + "_verify_ms"] = once(lambda: plonk.verify(be, vk, c["public_inputs"], proof))
+                    g[name + "_verdict"] = bool(ok)
+                    del pk, vk, proof
+                del wires, idx, pcs
+                # the stand-alone lookup of the same size: one column against one table
+                t, f, li = lookup.sample_lookup(mu, a.seed)
+                s = lookup.sample_srs(mu, a.seed)
+                pcs = dp.PolynomialCommitmentCub.new(be, s).mature()
+                lpk, lvk = lookup.preprocess(be, pcs, t, pr.powers_of_g2(ints(s)))
+                fd, lid = be.to_device(f), be.to_device(li)
+                for rep in range(3):
+                    lp, g["standalone_lookup_prove_ms"] = once(lambda: lookup.prove(be, lpk, fd, lid))
+                for rep in range(2):
+                    ok, g["standalone_lookup_verify_ms"] = once(lambda: lookup.verify(be, lvk, lp))
+                g["standalone_lookup_verdict"] = bool(ok)
+                del lpk, lvk, lp, fd, lid, pcs
+                g["prove_over_separate"] = g["lookup_prove_ms"] / (g["plain_prove_ms"] + g["standalone_lookup_prove_ms"])
+                g["verify_over_separate"] = g["lookup_verify_ms"] / (g["plain_verify_ms"] + g["standalone_lookup_verify_ms"])
+                emit(g)
+
+    if a.lookup:
+        with_lookup()
+        if out:
+            out.close()
+        be.close()
+        return 0
 
     if a.gate == "wide":
         wide_gate()
