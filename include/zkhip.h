@@ -48,7 +48,8 @@ typedef enum {
     ZK_ERR_NO_DEVICE = -4, /* no gfx950 device / library built without device code */
     ZK_ERR_DIV_ZERO = -5,  /* zero denominator in zk_fr_batch_div (reference: inverse().unwrap() panic) */
     ZK_ERR_OOM = -6,
-    ZK_ERR_COMM = -7       /* RCCL error / no communicator (reference: MPCNetError) */
+    ZK_ERR_COMM = -7,      /* RCCL error / no communicator (reference: MPCNetError) */
+    ZK_ERR_INTERNAL = -8   /* an invariant of the library itself does not hold (a bug, never the caller's input) */
 } zk_status;
 
 /* ---- context ------------------------------------------------------------------------ */
@@ -223,6 +224,26 @@ int zk_sumcheck_lookup(zk_ctx *ctx, const void *const d_tabs[6], size_t len, con
  * nothing is launched.  The inputs are not modified. */
 int zk_lookup3_multiplicities(zk_ctx *ctx, const void *const d_w[3], const void *const d_t[3], const void *d_qk,
                               const uint32_t *d_idx, size_t N, void *d_m);
+/* ---- lookups without caller indices: the device finds the table rows itself ----
+ * zk_lookup_find: for every row x of N = 2^n the SMALLEST y with t[y] == f[x] (all four limbs) as d_idx[x] (N u32), and the multiplicities
+ * m[y] = #{x : idx[x] = y} as N Fr in Montgomery form in d_m: bit for bit what zk_lookup_multiplicities writes for that idx.  Either output
+ * may be null, not both; an output that is given is written in all N entries on success.  Two phases on the ctx stream: every entry y < N is
+ * inserted into an open-addressing hash table of u32 slots (a power of two >= 2N of them, scratch of the ctx; linear probing; equal entries
+ * share ONE slot, which ends holding the smallest of their indices whatever the order of the threads -- a table padded by repeating an entry
+ * is the normal case), then every row walks the same sequence to its entry and counts on a u32 counter.  The result does not depend on the
+ * hash function.  Blocking (a status word is read back).  A row whose value is no entry of the table: ZK_ERR_INVALID, zk_last_error gives the
+ * number of such rows ("K of N rows ...", the wording of zk_lookup_multiplicities) and the smallest such row; the outputs are unspecified,
+ * nothing is read out of bounds.  N < 2, not a power of two or > 2^31 (the empty-slot mark stays outside the index range), f or t null, or
+ * both outputs null: ZK_ERR_INVALID, nothing is launched.  Scratch that does not fit the device: ZK_ERR_OOM.  A probe walk longer than the slot
+ * array (impossible at a load <= 0.5): ZK_ERR_INTERNAL.  The inputs are not modified. */
+int zk_lookup_find(zk_ctx *ctx, const void *d_f, const void *d_t, size_t N, uint32_t *d_idx, void *d_m);
+/* The selector-gated three-column form: a row with qk(x) = 1 gets the smallest y with (t0, t1, t2)(y) == (a, b, c)(x) in all twelve limbs; a
+ * row with qk(x) = 0 gets idx[x] = 0, is not counted and nothing else of it is read; m[y] = #{x : qk(x) = 1, idx[x] = y}, bit for bit what
+ * zk_lookup3_multiplicities writes for that idx.  A selected row whose triple is no entry of the table, or a qk that is neither 0 nor the
+ * Montgomery form of 1, is a bad row: ZK_ERR_INVALID with "K of N rows ..." and the smallest bad row in zk_last_error.  Everything else as
+ * zk_lookup_find (d_w: a, b, c; d_t: t0, t1, t2; a null column pointer: ZK_ERR_INVALID). */
+int zk_lookup3_find(zk_ctx *ctx, const void *const d_w[3], const void *const d_t[3], const void *d_qk, size_t N,
+                    uint32_t *d_idx, void *d_m);
 /* df = beta + a + zeta b + zeta^2 c and dt = beta + t0 + zeta t1 + zeta^2 t2 in ONE pass (N Fr each).  The inputs are not modified; an
  * output may not alias an input.  ASYNCHRONOUS on the ctx stream like zk_perm3_terms.  N < 2, not a power of two or > 2^35, or a null
  * pointer: ZK_ERR_INVALID, nothing is launched. */

@@ -25,6 +25,7 @@ static const TuneKey kTuneKeys[] = {
     {"multi_local_e", &Tuning::multi_local_e}, {"multi_pass_wg", &Tuning::multi_pass_wg},
     {"perm3_local_e", &Tuning::perm3_local_e}, {"gatew_local_e", &Tuning::gatew_local_e},
     {"lookup_local_e", &Tuning::lookup_local_e}, {"lookupsel_local_e", &Tuning::lookupsel_local_e},
+    {"find_force_slot", &Tuning::find_force_slot},
     {"msm_table_dc", &Tuning::msm_table_dc}, {"msm_qstep", &Tuning::msm_qstep}, {"msm_tile", &Tuning::msm_tile}, {"msm_pair", &Tuning::msm_pair},
     {"msm_fixq", &Tuning::msm_fixq}, {"msm_quad", &Tuning::msm_quad}, {"msm_stage", &Tuning::msm_stage}, {"msm_split", &Tuning::msm_split},
     {"msm_np", &Tuning::msm_np}, {"msm_fused_min", &Tuning::msm_fused_min}, {"msm_l2_tiled", &Tuning::msm_l2_tiled}, {"msm_tab_spt", &Tuning::msm_tab_spt}, {"msm_idx_ahead", &Tuning::msm_idx_ahead}, {"msm_share_l1", &Tuning::msm_share_l1}, {"srs_table_batched", &Tuning::srs_table_batched}, {"msm_debug", &Tuning::msm_debug}, {"msm_serial", &Tuning::msm_serial}, {"msm_size_classes", &Tuning::msm_size_classes},
@@ -462,6 +463,15 @@ int zk_sumcheck_lookup_sel(zk_ctx* ctx, const void* const d_tabs[7], size_t len,
     NEED(ctx, d_tabs && h_gamma && h_chal && h_out_evals && h_last);
     for (int k = 0; k < 7; k++) NEED(ctx, d_tabs[k]);
     return sumcheck_lookup_sel(ctx, d_tabs, len, h_gamma, h_chal, h_out_evals, h_last);
+}
+int zk_lookup_find(zk_ctx* ctx, const void* d_f, const void* d_t, size_t N, uint32_t* d_idx, void* d_m) {
+    NEED(ctx, d_f && d_t && (d_idx || d_m));
+    return lookup_find(ctx, d_f, d_t, N, d_idx, d_m);
+}
+int zk_lookup3_find(zk_ctx* ctx, const void* const d_w[3], const void* const d_t[3], const void* d_qk, size_t N, uint32_t* d_idx, void* d_m) {
+    NEED(ctx, d_w && d_t && d_qk && (d_idx || d_m));
+    for (int j = 0; j < 3; j++) NEED(ctx, d_w[j] && d_t[j]);
+    return lookup3_find(ctx, d_w, d_t, d_qk, N, d_idx, d_m);
 }
 int zk_eq_table_acc(zk_ctx* ctx, const uint64_t* h_point, size_t n, const uint64_t h_weight[4], void* d_acc) {
     NEED(ctx, d_acc && h_weight && (n == 0 || h_point));

@@ -136,6 +136,8 @@ struct Tuning {
     long lookup_local_e = 512;  // longest table (elements, a power of two <= 512) the single-workgroup LDS stage takes over; 1: HBM passes down to the last element
     // selector-gated lookup sumcheck (zk_lookup3.hip)
     long lookupsel_local_e = 512;  // longest table (elements, a power of two <= 512: seven tables are 112 KiB of LDS) the single-workgroup LDS stage takes over; 1: HBM passes down to the last element
+    // lookup find (zk_lookup_find.hip)
+    long find_force_slot = -1;  // TEST SWITCH: v >= 0 starts the walk of EVERY key at slot v mod slots (one collision chain; near the end of the array it wraps); -1: the hash
     // MSM (zk_msm.hip)
     long msm_table_dc = 0;    // window-table width delta (sweeps)
     long msm_qstep = 2;       // window-class quantisation step of batches
@@ -224,6 +226,7 @@ int sumcheck_gate_wide(zk_ctx* ctx, const void* const* d_tabs, size_t len, const
 
 // ---- zk_lookup.hip ----
 int lookup_multiplicities(zk_ctx* ctx, const void* d_f, const void* d_t, const uint32_t* d_idx, size_t N, void* d_m);
+int lookup_write_counts(zk_ctx* ctx, const uint32_t* d_cnt, size_t N, void* d_m);  // k_lookup_write on the ctx stream: N u32 counters -> N Montgomery Fr
 // d_tabs, h_last: E, df, dt, m, hf, ht; h_out_evals: rounds x 4 Fr
 int sumcheck_lookup(zk_ctx* ctx, const void* const* d_tabs, size_t len, const uint64_t* h_gamma, const uint64_t* h_chal, uint64_t* h_out_evals, uint64_t* h_last);
 
@@ -233,6 +236,11 @@ int lookup3_multiplicities(zk_ctx* ctx, const void* const* d_w, const void* cons
 int lookup3_terms(zk_ctx* ctx, const void* const* d_w, const void* const* d_t, size_t N, const uint64_t* h_zeta, const uint64_t* h_beta, void* d_df, void* d_dt);
 // d_tabs, h_last: E, df, dt, m, hf, ht, qk; h_out_evals: rounds x 4 Fr
 int sumcheck_lookup_sel(zk_ctx* ctx, const void* const* d_tabs, size_t len, const uint64_t* h_gamma, const uint64_t* h_chal, uint64_t* h_out_evals, uint64_t* h_last);
+
+// ---- zk_lookup_find.hip ----
+// the row-to-table indices found on the device (smallest index of an equal entry) and their multiplicities; d_idx or d_m may be null, not both
+int lookup_find(zk_ctx* ctx, const void* d_f, const void* d_t, size_t N, uint32_t* d_idx, void* d_m);
+int lookup3_find(zk_ctx* ctx, const void* const* d_w, const void* const* d_t, const void* d_qk, size_t N, uint32_t* d_idx, void* d_m);
 
 // ---- zk_batchopen.hip ----
 int eq_table_acc(zk_ctx* ctx, const uint64_t* h_point, size_t n, const uint64_t* h_weight, void* d_acc);

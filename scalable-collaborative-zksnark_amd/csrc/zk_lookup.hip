@@ -72,6 +72,14 @@ int lookup_multiplicities(zk_ctx* ctx, const void* d_f, const void* d_t, const u
     return ZK_OK;
 }
 
+// the second launch alone, for zk_lookup_find.hip, which counts on its own
+int lookup_write_counts(zk_ctx* ctx, const uint32_t* d_cnt, size_t N, void* d_m) {
+    const unsigned blocks = (unsigned)std::min<size_t>((N + kGateBlock - 1) / kGateBlock, (size_t)ctx->cu_count * 8);
+    hipLaunchKernelGGL(k_lookup_write, dim3(blocks), dim3(kGateBlock), 0, ctx->stream, (const u32*)d_cnt, N, d_m);
+    ZK_HIP(ctx, hipGetLastError());
+    return ZK_OK;
+}
+
 // ---------------------------------------------------------------------------------------
 // K16.  One round over tables of length 2 * half living in HBM.  partials: [t * nbw + 4 block + wave], 80-byte slots.
 // The values at t = 1 .. 3 come from v(t) = v(t-1) + (hi - lo): per t four multiplications (three reduced ones inside the

@@ -3,8 +3,10 @@
 // device transcript and verified by replaying the schedule on the host transcript.  One digest for one seed across the two hosts
 // (zkhip.lookup.proof_digest).
 //
-//     bin/lookup_check --n N [--seed S] [--distinct D] [--break K | --outside] [--sample-only]
+//     bin/lookup_check --n N [--seed S] [--distinct D] [--find] [--break K | --outside] [--sample-only]
 //
+// --find proves without the sample's indices: the device finds them (lookup_prove(.., kFind)); the sampler only ever names first occurrences,
+// so the digest is the one without --find.
 // --break K flips the lowest bit of one limb of record field K after proving (0: commitments, 1: rounds, 2: values, 3: the batch
 // instance's rounds, 4: its opening proof): the verifier rejects.  --outside changes one value of f so that it is not the table entry
 // its index names: the prover refuses.  Prints the proof digest and accept / reject / refused; exit 0 on accept, 1 on reject or
@@ -27,7 +29,7 @@ static bool number(const char *s, long long &out) {
     return end != s && *end == 0 && out >= 0;
 }
 
-static int run(size_t n, uint64_t seed, size_t distinct, long long brk, bool outside) {
+static int run(size_t n, uint64_t seed, size_t distinct, long long brk, bool outside, bool find) {
     Ctx be(0);
     const size_t N = size_t(1) << n;
     LookupSample s = sample_lookup(n, seed, distinct);
@@ -36,11 +38,14 @@ static int run(size_t n, uint64_t seed, size_t distinct, long long brk, bool out
     PolynomialCommitmentCub cub = PolynomialCommitmentCub::make(be, trap);
     std::shared_ptr<PcsVk> pcs_vk = make_pcs_vk(be, trap);
     const auto keys = lookup_preprocess(be, cub.mature(), be.to_device(s.t), N);
-    DevPtr idx = be.alloc(4 * N);
-    be.upload(idx, s.idx.data(), 4 * N);
+    DevPtr idx;
+    if (!find) {
+        idx = be.alloc(4 * N);
+        be.upload(idx, s.idx.data(), 4 * N);
+    }
     LookupProof proof;
     try {
-        proof = lookup_prove(be, cub.mature(), keys.first, be.to_device(s.f), idx);
+        proof = find ? lookup_prove(be, cub.mature(), keys.first, be.to_device(s.f), kFind) : lookup_prove(be, cub.mature(), keys.first, be.to_device(s.f), idx);
     } catch (const ZkError &e) {
         if (e.status != ZK_ERR_INVALID) throw;
         std::printf("lookup_check n=%zu seed=%llu: refused (%s)\n", n, (unsigned long long)seed, e.what());
@@ -62,11 +67,12 @@ static int run(size_t n, uint64_t seed, size_t distinct, long long brk, bool out
 
 int main(int argc, char **argv) {
     long long n = -1, seed = 7, distinct = 0, brk = -1;
-    bool outside = false, only_sample = false, usage = false;
+    bool outside = false, only_sample = false, usage = false, find = false;
     for (int i = 1; i < argc && !usage; ++i) {
         const std::string k = argv[i];
         if (k == "--outside") outside = true;
         else if (k == "--sample-only") only_sample = true;
+        else if (k == "--find") find = true;
         else if (i + 1 < argc && k == "--n") usage = !number(argv[++i], n);
         else if (i + 1 < argc && k == "--seed") usage = !number(argv[++i], seed);
         else if (i + 1 < argc && k == "--distinct") usage = !number(argv[++i], distinct);
@@ -74,7 +80,7 @@ int main(int argc, char **argv) {
         else usage = true;
     }
     if (usage || n < 0 || (brk >= 0 && outside)) {
-        std::fprintf(stderr, "usage: lookup_check --n N [--seed S] [--distinct D] [--break K | --outside] [--sample-only]\n");
+        std::fprintf(stderr, "usage: lookup_check --n N [--seed S] [--distinct D] [--find] [--break K | --outside] [--sample-only]\n");
         return 2;
     }
     if (n < 1 || n > 24 || brk > 4 || distinct > (1ll << n)) {
@@ -91,7 +97,7 @@ int main(int argc, char **argv) {
             std::fprintf(stderr, "lookup_check: no GPU visible -- this host has no CPU fallback (zk_device_count = %d)\n", ngpu);
             return 2;
         }
-        return run((size_t)n, (uint64_t)seed, (size_t)distinct, brk, outside);
+        return run((size_t)n, (uint64_t)seed, (size_t)distinct, brk, outside, find);
     } catch (const std::exception &e) {
         std::fprintf(stderr, "lookup_check: %s\n", e.what());
         return 2;

@@ -3,11 +3,12 @@
 // drawn from the device transcript and verified by replaying the schedule on the host transcript.  One digest for one seed across the
 // two hosts (zkhip.plonk.proof_digest).
 //
-//     bin/plonk_check --mu M [--seed S] [--gate wide] [--lookup [--break-lookup K]] [--break-gate K | --break-wire K | --bad-input | --break K|all]
+//     bin/plonk_check --mu M [--seed S] [--gate wide] [--lookup [--find] [--break-lookup K]] [--break-gate K | --break-wire K | --bad-input | --break K|all]
 //                     [--circuit-only | --sample-only]
 //
 // --lookup proves the test circuit with lookup rows (zkhip.plonk.sample_circuit_lookup, mu >= 3) under the label + "-lookup": three opening
-// proofs.  --break-lookup K moves the triple of lookup row K out of the table with gate and wiring intact: the prover refuses (exit 3, the
+// proofs.  --find (with --lookup) proves without the sample's indices: the device finds them (plonk_prove(.., kFind)); the sampler only ever
+// names first occurrences, so the digest is the one without --find.  --break-lookup K moves the triple of lookup row K out of the table with gate and wiring intact: the prover refuses (exit 3, the
 // device's "K of N rows" message on stderr).  --break K flips one bit of part K of the honest record before it is verified; the parts, in the
 // order of the digest: 0 commitments, 1 v_commitment, 2 p_rounds, 3 g_rounds, 4 g_values, 5 p_values, 6 v_values, 7 batch.rounds,
 // 8 batch.opening, 9 v_batch.rounds, 10 v_batch.opening and, with --lookup, 11 lookup.commitments, 12 lookup.rounds, 13 lookup.values,
@@ -40,7 +41,7 @@ static bool number(const char *s, long long &out) {
 
 struct Options {
     long long mu = -1, seed = 7, break_gate = -1, break_wire = -1, break_lookup = -1, break_part = -1;
-    bool bad_input = false, wide = false, lookup = false, break_all = false;
+    bool bad_input = false, wide = false, lookup = false, break_all = false, find = false;
 };
 
 static PlonkCircuit sample(const Options &o, bool broken) {
@@ -79,13 +80,14 @@ static int run(const Options &o) {
     PlonkVk vk;
     const PlonkPk pk = preprocess(be, cub.mature(), good, vk);
     DevPtr idx;
-    if (o.lookup) {
+    if (o.lookup && !o.find) {
         idx = be.alloc(4 * N);
         be.upload(idx, c.idx.data(), 4 * N);
     }
     PlonkProof proof;
     try {
-        proof = plonk_prove(be, cub.mature(), pk, be.to_device(c.a), be.to_device(c.b), be.to_device(c.c), good.public_inputs, idx);
+        proof = o.find ? plonk_prove(be, cub.mature(), pk, be.to_device(c.a), be.to_device(c.b), be.to_device(c.c), good.public_inputs, kFind)
+                       : plonk_prove(be, cub.mature(), pk, be.to_device(c.a), be.to_device(c.b), be.to_device(c.c), good.public_inputs, idx);
     } catch (const ZkError &e) {
         if (o.break_lookup < 0 || e.status != ZK_ERR_INVALID) throw;
         std::fprintf(stderr, "plonk_check: the prover refused: %s\n", e.what());
@@ -124,6 +126,7 @@ int main(int argc, char **argv) {
         if (k == "--bad-input") bad_input = true;
         else if (k == "--circuit-only" || k == "--sample-only") only_circuit = true;
         else if (k == "--lookup") o.lookup = true;
+        else if (k == "--find") o.find = true;
         else if (i + 1 < argc && k == "--break-lookup") usage = !number(argv[++i], o.break_lookup);
         else if (i + 1 < argc && k == "--break" && !std::strcmp(argv[i + 1], "all")) o.break_all = true, ++i;
         else if (i + 1 < argc && k == "--break") usage = !number(argv[++i], o.break_part);
@@ -136,8 +139,8 @@ int main(int argc, char **argv) {
     }
     const bool tamper = o.break_all || o.break_part >= 0;
     if (usage || mu < 0 || (break_gate >= 0) + (break_wire >= 0) + (bad_input ? 1 : 0) + (o.break_lookup >= 0) + (tamper ? 1 : 0) > 1 ||
-        (o.break_all && o.break_part >= 0) || (o.break_lookup >= 0 && !o.lookup) || (o.lookup && (break_gate >= 0 || break_wire >= 0))) {
-        std::fprintf(stderr, "usage: plonk_check --mu M [--seed S] [--gate wide] [--lookup [--break-lookup K]] [--break-gate K | --break-wire K | --bad-input | --break K|all] [--circuit-only | --sample-only]\n");
+        (o.break_all && o.break_part >= 0) || (o.break_lookup >= 0 && !o.lookup) || (o.find && !o.lookup) || (o.lookup && (break_gate >= 0 || break_wire >= 0))) {
+        std::fprintf(stderr, "usage: plonk_check --mu M [--seed S] [--gate wide] [--lookup [--find] [--break-lookup K]] [--break-gate K | --break-wire K | --bad-input | --break K|all] [--circuit-only | --sample-only]\n");
         return 2;
     }
     if (mu < 2 || mu > 24) {

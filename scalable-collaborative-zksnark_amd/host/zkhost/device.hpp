@@ -29,6 +29,11 @@ struct MsmLengthError : ZkError {
 
 class Ctx;
 
+// in the place of a prover's row-to-table indices: the device finds the first occurrence of every value itself (zkhip.lookup.FIND;
+// zk_lookup_find / zk_lookup3_find).  lookup_prove(.., kFind), plonk_prove(.., kFind)
+struct FindIndices {};
+static const FindIndices kFind{};
+
 // the zk_ctx itself: shared by the Ctx object and by every buffer / SRS level / job created from it, so that the library
 // context is destroyed only after the last of them (a buffer that outlives its `Ctx` variable stays valid and is freed properly)
 struct CtxHandle {
@@ -326,6 +331,21 @@ class Ctx {
         const void *pw[3] = {w[0].get(), w[1].get(), w[2].get()}, *pt[3] = {t[0].get(), t[1].get(), t[2].get()};
         check(zk_lookup3_multiplicities(h_, pw, pt, qk.get(), (const uint32_t *)idx.get(), N, m.get()));
         return m;
+    }
+    // zk_lookup_find: idx[x] = the smallest y with t[y] = f[x] (N u32) and the multiplicities of that idx (N Fr), found on the device.  A row
+    // whose value is no entry of the table: ZkError(ZK_ERR_INVALID)
+    std::pair<DevPtr, DevPtr> lookup_find(const DevPtr &f, const DevPtr &t, size_t N) {
+        DevPtr idx = alloc(4 * N), m = alloc_fr(N);
+        check(zk_lookup_find(h_, f.get(), t.get(), N, (uint32_t *)idx.get(), m.get()));
+        return {idx, m};
+    }
+    // zk_lookup3_find: the same for the rows with qk(x) = 1 of a Plonk circuit (idx = 0 where qk = 0); w = a, b, c; t = t0, t1, t2.  A selected
+    // row whose triple is no entry of the table, or a qk that is neither 0 nor 1: ZkError(ZK_ERR_INVALID)
+    std::pair<DevPtr, DevPtr> lookup3_find(const std::array<DevPtr, 3> &w, const std::array<DevPtr, 3> &t, const DevPtr &qk, size_t N) {
+        DevPtr idx = alloc(4 * N), m = alloc_fr(N);
+        const void *pw[3] = {w[0].get(), w[1].get(), w[2].get()}, *pt[3] = {t[0].get(), t[1].get(), t[2].get()};
+        check(zk_lookup3_find(h_, pw, pt, qk.get(), N, (uint32_t *)idx.get(), m.get()));
+        return {idx, m};
     }
     // zk_lookup3_terms: df = beta + a + zeta b + zeta^2 c, dt = beta + t0 + zeta t1 + zeta^2 t2 in one pass (asynchronous)
     std::pair<DevPtr, DevPtr> lookup3_terms(const std::array<DevPtr, 3> &w, const std::array<DevPtr, 3> &t, size_t N, const Fr &zeta, const Fr &beta) {

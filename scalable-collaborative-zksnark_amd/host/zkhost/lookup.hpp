@@ -52,13 +52,11 @@ inline std::pair<LookupPk, LookupVk> lookup_preprocess(Ctx &be, const PowersOfG 
     return {LookupPk{n, t, c}, LookupVk{n, c}};
 }
 
-// f: N Fr, idx: N u32, both on the device.  A row whose value is not the table entry it names: ZkError(ZK_ERR_INVALID); a zero
-// denominator: ZkError(ZK_ERR_DIV_ZERO)
-inline LookupProof lookup_prove(Ctx &be, const PowersOfG &pg, const LookupPk &pk, const DevPtr &f, const DevPtr &idx) {
+namespace detail {
+inline LookupProof lookup_prove_with(Ctx &be, const PowersOfG &pg, const LookupPk &pk, const DevPtr &f, const DevPtr &m) {
     const size_t n = pk.n, N = size_t(1) << n;
     LookupProof p;
     p.n = n;
-    DevPtr m = be.lookup_multiplicities(f, pk.t, idx, N);
     std::shared_ptr<DeviceTranscript> tr = be.transcript("lookup");
     const uint64_t n64 = n;
     be.absorb(*tr, &n64, 8);
@@ -86,6 +84,18 @@ inline LookupProof lookup_prove(Ctx &be, const PowersOfG &pg, const LookupPk &pk
     for (size_t j = 0; j < 5; ++j) claims.push_back(Claim{j, chal, p.values[j]});
     p.batch = detail::batch_prove_ni(be, pg, {f, pk.t, m, hf, ht}, N, claims, b_alpha, *tr);
     return p;
+}
+}  // namespace detail
+
+// f: N Fr, idx: N u32, both on the device.  A row whose value is not the table entry it names: ZkError(ZK_ERR_INVALID); a zero
+// denominator: ZkError(ZK_ERR_DIV_ZERO)
+inline LookupProof lookup_prove(Ctx &be, const PowersOfG &pg, const LookupPk &pk, const DevPtr &f, const DevPtr &idx) {
+    return detail::lookup_prove_with(be, pg, pk, f, be.lookup_multiplicities(f, pk.t, idx, size_t(1) << pk.n));
+}
+// the find mode: no idx; a row whose value is no entry of the table: ZkError(ZK_ERR_INVALID).  The record is the one of lookup_prove with the
+// indices of the first occurrences
+inline LookupProof lookup_prove(Ctx &be, const PowersOfG &pg, const LookupPk &pk, const DevPtr &f, FindIndices) {
+    return detail::lookup_prove_with(be, pg, pk, f, be.lookup_find(f, pk.t, size_t(1) << pk.n).second);
 }
 
 // the verifier's replay of the schedule; false on a malformed record

@@ -374,13 +374,13 @@ inline FrVec replay_rounds(HostTranscript &tr, const std::vector<FrVec> &rounds)
 }  // namespace detail
 
 // ---- prover ----  (pg: the levels of a PolynomialCommitment over mu + 1 variables; a zero alpha, of probability 2^-254, is refused)
-// idx: the N row-to-table indices (u32 on the device), needed exactly when the key has a lookup; a selected row whose triple is not the table
-// entry it names: ZkError(ZK_ERR_INVALID)
-inline PlonkProof plonk_prove(Ctx &be, const PowersOfG &pg, const PlonkPk &pk, const DevPtr &a, const DevPtr &b, const DevPtr &c, const FrVec &public_inputs,
-                              const DevPtr &idx = DevPtr()) {
+namespace detail {
+// find: the device finds the indices (zk_lookup3_find) and idx is not looked at
+inline PlonkProof plonk_prove_with(Ctx &be, const PowersOfG &pg, const PlonkPk &pk, const DevPtr &a, const DevPtr &b, const DevPtr &c, const FrVec &public_inputs,
+                                   const DevPtr &idx, bool find) {
     const size_t mu = pk.mu, l = pk.l, N = size_t(1) << mu;
     if (public_inputs.size() != l) throw ZkError(ZK_ERR_INVALID, "plonk_prove: l public inputs are needed");
-    if (pk.lookup != (idx.get() != nullptr)) throw ZkError(ZK_ERR_INVALID, "plonk_prove: idx is needed exactly when the key has a lookup");
+    if (pk.lookup != (find || idx.get() != nullptr)) throw ZkError(ZK_ERR_INVALID, "plonk_prove: idx is needed exactly when the key has a lookup");
     const GateDesc &gd = gate_desc(pk.gate);
     const size_t ns = gd.selectors;
     PlonkProof p;
@@ -400,7 +400,7 @@ inline PlonkProof plonk_prove(Ctx &be, const PowersOfG &pg, const PlonkPk &pk, c
     DevPtr m, df, dt, hf, ht;
     Fr zeta, beta_l, gamma_l, lambda;
     if (pk.lookup) {  // 2L
-        m = be.lookup3_multiplicities(w, pk.table, pk.qk, idx, N);
+        m = find ? be.lookup3_find(w, pk.table, pk.qk, N).second : be.lookup3_multiplicities(w, pk.table, pk.qk, idx, N);
         p.l_commitments.push_back(commit(be, pg, m, N));
         be.absorb(*tr, p.l_commitments.data(), 144);
         const FrVec zb = be.challenges(*tr, 2);
@@ -479,6 +479,20 @@ inline PlonkProof plonk_prove(Ctx &be, const PowersOfG &pg, const PlonkPk &pk, c
     p.v_batch = detail::batch_prove_ni(be, pg, {tree}, 2 * N, v_claims, b_alpha, *tr);
     if (pk.lookup) p.l_batch = detail::batch_prove_ni(be, pg, {pk.qk, pk.table[0], pk.table[1], pk.table[2], m, hf, ht}, N, l_claims, b_alpha, *tr);
     return p;
+}
+}  // namespace detail
+
+// idx: the N row-to-table indices (u32 on the device), needed exactly when the key has a lookup; a selected row whose triple is not the table
+// entry it names: ZkError(ZK_ERR_INVALID)
+inline PlonkProof plonk_prove(Ctx &be, const PowersOfG &pg, const PlonkPk &pk, const DevPtr &a, const DevPtr &b, const DevPtr &c, const FrVec &public_inputs,
+                              const DevPtr &idx = DevPtr()) {
+    return detail::plonk_prove_with(be, pg, pk, a, b, c, public_inputs, idx, false);
+}
+// the find mode (zkhip.plonk.FIND): no idx, the key must have a lookup; a selected row whose triple is no entry of the table:
+// ZkError(ZK_ERR_INVALID).  The record is the one of plonk_prove with the indices of the first occurrences
+inline PlonkProof plonk_prove(Ctx &be, const PowersOfG &pg, const PlonkPk &pk, const DevPtr &a, const DevPtr &b, const DevPtr &c, const FrVec &public_inputs,
+                              FindIndices) {
+    return detail::plonk_prove_with(be, pg, pk, a, b, c, public_inputs, DevPtr(), true);
 }
 
 // ---- verifier ----

@@ -51,6 +51,8 @@ SYMBOLS = [
     ("zk_lookup_multiplicities", _i, [_vp, _vp, _vp, _vp, _sz, _vp]),
     ("zk_sumcheck_lookup", _i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp]),
     ("zk_lookup3_multiplicities", _i, [_vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    ("zk_lookup_find", _i, [_vp, _vp, _vp, _sz, _vp, _vp]),
+    ("zk_lookup3_find", _i, [_vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     ("zk_lookup3_terms", _i, [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
     ("zk_sumcheck_lookup_sel", _i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp]),
     ("zk_eq_table_acc", _i, [_vp, _vp, _sz, _vp, _vp]),
@@ -140,7 +142,7 @@ class ScItem(ctypes.Structure):
                 ("h_last_g", _vp), ("d_out", _vp)]
 
 
-ZK_OK, ZK_ERR_INVALID, ZK_ERR_LENGTH, ZK_ERR_HIP, ZK_ERR_NO_DEVICE, ZK_ERR_DIV_ZERO, ZK_ERR_OOM, ZK_ERR_COMM = 0, -1, -2, -3, -4, -5, -6, -7
+ZK_OK, ZK_ERR_INVALID, ZK_ERR_LENGTH, ZK_ERR_HIP, ZK_ERR_NO_DEVICE, ZK_ERR_DIV_ZERO, ZK_ERR_OOM, ZK_ERR_COMM, ZK_ERR_INTERNAL = 0, -1, -2, -3, -4, -5, -6, -7, -8
 
 
 def build(force: bool = False) -> str:

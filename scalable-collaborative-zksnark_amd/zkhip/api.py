@@ -585,6 +585,30 @@ class Ctx:
         self._check(rc)
         return out
 
+    def lookup_find(self, f, t, N: int, idx=None, m=None):
+        """the row-to-table indices found on the device (zk_lookup_find; blocking): f, t device buffers of N Fr -> (idx, m), device buffers
+        of N u32 (idx[x] = the smallest y with t[y] = f[x]) and of N Fr (the multiplicities of that idx).  A row whose value is no entry of the
+        table: ValueError -- as is every other ZK_ERR_INVALID of the call (N < 2, not a power of two or > 2^31), with the library's message."""
+        idx, m = idx or self.alloc(max(4 * N, 1)), m or self.alloc(max(32 * N, 1))
+        rc = self.lib.zk_lookup_find(self.h, _ptr(f), _ptr(t), N, _ptr(idx), _ptr(m))
+        if rc == ZK_ERR_INVALID:
+            raise ValueError((self.lib.zk_last_error(self.h) or b"").decode())
+        self._check(rc)
+        return idx, m
+
+    def lookup3_find(self, ws, ts, qk, N: int, idx=None, m=None):
+        """the same for the lookup of a Plonk circuit (zk_lookup3_find; blocking): ws = (a, b, c), ts = (t0, t1, t2), qk device buffers of N Fr
+        -> (idx, m): idx[x] = the smallest y with (t0, t1, t2)[y] = (a, b, c)[x] where qk(x) = 1, 0 where qk(x) = 0.  A selected row whose triple
+        is no entry of the table, or a qk that is neither 0 nor 1: ValueError, with the library's message."""
+        if len(ws) != 3 or len(ts) != 3:
+            raise ValueError("three wire columns and three table columns are needed")
+        idx, m = idx or self.alloc(max(4 * N, 1)), m or self.alloc(max(32 * N, 1))
+        rc = self.lib.zk_lookup3_find(self.h, self._ptr_array(ws), self._ptr_array(ts), _ptr(qk), N, _ptr(idx), _ptr(m))
+        if rc == ZK_ERR_INVALID:
+            raise ValueError((self.lib.zk_last_error(self.h) or b"").decode())
+        self._check(rc)
+        return idx, m
+
     def lookup3_terms(self, ws, ts, N: int, zeta: np.ndarray, beta: np.ndarray):
         """df = beta + a + zeta b + zeta^2 c, dt = beta + t0 + zeta t1 + zeta^2 t2 in one pass (zk_lookup3_terms; asynchronous) -> (df, dt),
         device buffers of N Fr"""

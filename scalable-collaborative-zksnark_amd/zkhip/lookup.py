@@ -3,7 +3,8 @@ The lookup argument (LogUp) as a stand-alone non-interactive proof: every value 
 
 N = 2^n rows; f and t hold N Fr each (pad the table by repeating an entry, pad f with any table entry).  The caller supplies the
 row-to-table indices idx (u32[N], f[x] = t[idx[x]]); the multiplicities are m[y] = #{x : idx[x] = y} (zk_lookup_multiplicities, which
-checks every row on the way).  With a challenge beta
+checks every row on the way).  A caller that only knows THAT its values lie in the table passes idx = FIND: the device finds the first
+occurrence of every value itself (zk_lookup_find: idx and m in one call; `find_indices_host` is the same rule in numpy).  With a challenge beta
 
     df = beta + f,   dt = beta + t,   hf = 1 / df,   ht = m / dt
     sum_x 1 / (beta + f(x)) = sum_y m(y) / (beta + t(y))      <=>   f is contained in t          (N < char Fr)
@@ -40,6 +41,7 @@ from .zerocheck import _ints, eq_eval
 LABEL = b"lookup"
 COMMITTED = ("f", "m", "hf", "ht")    # the prover's commitments of a record
 OPENED = ("f", "t", "m", "hf", "ht")  # the five claimed values at r, and the tables of the batch instance
+FIND = "find"                         # in the place of idx: the device finds the indices (zk_lookup_find)
 
 
 def _u64(a, *shape) -> np.ndarray:
@@ -69,9 +71,10 @@ def preprocess(be, pcs, t, powers_of_g2=None):
 
 
 def prove(be, pk: dict, f, idx, timing: dict | None = None) -> dict:
-    """f: device buffer of N Fr (or an [N, 4] array); idx: N row-to-table indices (array or device buffer of u32) -> the record of the
-    module text.  A row whose value is not the table entry it names raises ValueError, a zero denominator ZeroDivisionError
-    (ZK_ERR_DIV_ZERO).  timing (optional dict) receives the wall seconds of the phases."""
+    """f: device buffer of N Fr (or an [N, 4] array); idx: N row-to-table indices (array or device buffer of u32), or FIND: the device finds
+    the first occurrence of every value (the record is the one of prove with those indices) -> the record of the module text.  A row whose
+    value is not the table entry it names -- with FIND: no entry at all -- raises ValueError, as does any other string; a zero denominator
+    ZeroDivisionError (ZK_ERR_DIV_ZERO).  timing (optional dict) receives the wall seconds of the phases."""
     import time
 
     from . import dist_primitive as dp
@@ -79,12 +82,14 @@ def prove(be, pk: dict, f, idx, timing: dict | None = None) -> dict:
 
     n, t, pcs = pk["n"], pk["t"], pk["pcs"]
     N = 1 << n
+    if isinstance(idx, str) and idx != FIND:
+        raise ValueError(f"idx must be the indices or FIND, not {idx!r}")
     if isinstance(f, np.ndarray):
         f = be.to_device(_u64(f, N, 4))
     if isinstance(idx, np.ndarray):
         idx = be.to_device(np.ascontiguousarray(idx, dtype=np.uint32).reshape(N))
     t0 = time.perf_counter()
-    m = be.lookup_multiplicities(f, t, idx, N)
+    m = be.lookup_find(f, t, N)[1] if isinstance(idx, str) else be.lookup_multiplicities(f, t, idx, N)
     tr = Transcript(be, LABEL)
     try:
         tr.absorb_u64(n).absorb(pk["commitment"])
@@ -209,6 +214,39 @@ def proof_digest(proof: dict) -> str:
     put(proof["commitments"]), put(proof["rounds"]), put(proof["values"])
     put(proof["batch"]["rounds"]), put(proof["batch"]["opening"])
     return h.hexdigest()
+
+
+def find_indices_host(t, f, qk=None) -> np.ndarray:
+    """numpy only -- the rule of zk_lookup_find / zk_lookup3_find on the host, for callers without a device: idx[x] = the smallest y with
+    t[y] = f[x].  t, f: [N, 4] arrays of one column, or sequences of columns ([N, 4] each: (t0, t1, t2) and (a, b, c)).  qk ([N, 4], optional):
+    rows with qk = 0 get 0 and are not looked up; a qk that is neither 0 nor the Montgomery form of 1 is a bad row.  A dictionary of first
+    occurrences.  ValueError, in the wording of the device ("K of N rows ...", the first such row named), when rows are missing from the table
+    or bad.  -> u32[N]"""
+    cols = lambda a: [_u64(a, -1, 4)] if isinstance(a, np.ndarray) and a.ndim == 2 else [_u64(c, -1, 4) for c in a]
+    keys = lambda cs: np.ascontiguousarray(np.concatenate(cs, axis=1), dtype="<u8")
+    tk, fk = keys(cols(t)), keys(cols(f))
+    N = len(tk)
+    if len(fk) != N or tk.shape[1] != fk.shape[1]:
+        raise ValueError("the rows and the table must have the same shape")
+    first = {}
+    for y in range(N):
+        first.setdefault(tk[y].tobytes(), y)
+    if qk is None:
+        sel, bad = np.ones(N, dtype=bool), []
+    else:
+        q = _u64(qk, N, 4)
+        zero, one = (q == 0).all(axis=1), (q == fr_mont(1)).all(axis=1)
+        sel, bad = one, np.flatnonzero(~(zero | one)).tolist()
+    idx = np.zeros(N, dtype=np.uint32)
+    for x in np.flatnonzero(sel).tolist():
+        y = first.get(fk[x].tobytes())
+        if y is None:
+            bad.append(x)
+        else:
+            idx[x] = y
+    if bad:
+        raise ValueError(f"find_indices_host: {len(bad)} of {N} rows are not in the table; the first is row {min(bad)}")
+    return idx
 
 
 # ---- the sample both hosts prove (one seed = one digest) ----

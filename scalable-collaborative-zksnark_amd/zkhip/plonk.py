@@ -44,7 +44,8 @@ repeating an entry).  Row x with qk(x) = 1 claims (a, b, c)(x) = (t0, t1, t2)(id
 row with qk(x) = 0 claims nothing.  With challenges zeta, beta_l, gamma_l, lambda and a point tau_l (LogUp with a selector):
 
     f = a + zeta b + zeta^2 c,  t = t0 + zeta t1 + zeta^2 t2,  df = beta_l + f,  dt = beta_l + t,  hf = qk / df,  ht = m / dt,
-    m[y] = #{x : qk(x) = 1, idx[x] = y},
+    m[y] = #{x : qk(x) = 1, idx[x] = y}            (idx = FIND: the device finds the first occurrence of every selected triple itself,
+                                                     zk_lookup3_find, and the record is the one of prove with those indices),
     sum_x hf(x) - ht(x) + E(x) [ hf(x) df(x) - qk(x) + gamma_l ( ht(x) dt(x) - m(x) ) ] = 0,      E = lambda eq(tau_l, .)
 
 one degree-3 sumcheck over the seven tables E, df, dt, m, hf, ht, qk (zk_sumcheck_lookup_sel_fs).  f is not committed: df(r) is linear in
@@ -84,6 +85,7 @@ P_VALUES = ("a", "b", "c", "ssigma0", "ssigma1", "ssigma2")          # at r_p
 BATCH_TABLES = ("q1", "q2", "a", "b", "c", "ssigma0", "ssigma1", "ssigma2")  # the tables of the mu-variate batch instance
 _SSIGMA = ("ssigma0", "ssigma1", "ssigma2")
 LOOKUP_SUFFIX = b"-lookup"
+FIND = "find"                                                        # in the place of idx: the device finds the indices (zk_lookup3_find)
 LOOKUP_VK_TABLES = ("qk", "t0", "t1", "t2")                          # preprocessed; their commitments follow the gate's in the vk
 LOOKUP_COMMITTED = ("m", "hf", "ht")                                  # the prover's commitments of the record's "lookup" part
 L_VALUES = ("a", "b", "c", "qk", "t0", "t1", "t2", "m", "hf", "ht")  # at r_l
@@ -230,8 +232,9 @@ def preprocess(be, pcs, circuit: dict, powers_of_g2=None):
 # ---- prover ----
 def prove(be, pk: dict, a, b, c, public_inputs, idx=None, timing: dict | None = None) -> dict:
     """a, b, c: device buffers of N Fr (or [N, 4] arrays); public_inputs: [l, 4] Montgomery Fr -> the record of the module text.
-    idx: the N row-to-table indices (array or device buffer of u32), required exactly when the key has a lookup (else ValueError); a selected
-    row whose triple is not the table entry it names raises ValueError.
+    idx: the N row-to-table indices (array or device buffer of u32) or FIND (the device finds them), required exactly when the key has a
+    lookup (else ValueError; any other string: ValueError); a selected row whose triple is not the table entry it names -- with FIND: no entry
+    at all -- raises ValueError.
     A zero denominator raises ZeroDivisionError (ZK_ERR_DIV_ZERO); a zero challenge alpha (probability 2^-254), from which ssigma_j(r_p)
     cannot be recovered, ValueError.  timing (optional dict) receives the wall seconds of the phases."""
     import time
@@ -248,7 +251,10 @@ def prove(be, pk: dict, a, b, c, public_inputs, idx=None, timing: dict | None = 
         raise ValueError(f"{l} public inputs needed, {len(pi)} given")
     if lookup != (idx is not None):
         raise ValueError("idx is needed exactly when the key has a lookup")
-    if lookup and not (isinstance(idx, int) or hasattr(idx, "ptr") or hasattr(idx, "data_ptr")):  # not on the device: an array or a sequence
+    find = isinstance(idx, str)
+    if find and idx != FIND:
+        raise ValueError(f"idx must be the indices or FIND, not {idx!r}")
+    if lookup and not (find or isinstance(idx, int) or hasattr(idx, "ptr") or hasattr(idx, "data_ptr")):  # not on the device: an array or a sequence
         idx = np.asarray(idx)
         if idx.size != N or idx.dtype.kind not in "ui":
             raise ValueError(f"idx must hold {N} unsigned integers")
@@ -266,7 +272,7 @@ def prove(be, pk: dict, a, b, c, public_inputs, idx=None, timing: dict | None = 
             raise ValueError("the challenge alpha is zero")
         if lookup:  # 2L
             w_cols, t_cols = [wires[k] for k in ("a", "b", "c")], [tabs[k] for k in ("t0", "t1", "t2")]
-            m = be.lookup3_multiplicities(w_cols, t_cols, tabs["qk"], idx, N)
+            m = be.lookup3_find(w_cols, t_cols, tabs["qk"], N)[1] if find else be.lookup3_multiplicities(w_cols, t_cols, tabs["qk"], idx, N)
             c_m = _u64(dp.commit(be, pcs, m, N), 18)
             zeta, beta_l = tr.absorb(c_m).challenges(2)
         nums, dens, P, Q = be.perm3_terms([wires[k] for k in ("a", "b", "c")], [tabs[f"ssigma{j}"] for j in range(3)], N, alpha, beta)
