@@ -244,6 +244,54 @@ int zk_lookup_find(zk_ctx *ctx, const void *d_f, const void *d_t, size_t N, uint
  * zk_lookup_find (d_w: a, b, c; d_t: t0, t1, t2; a null column pointer: ZK_ERR_INVALID). */
 int zk_lookup3_find(zk_ctx *ctx, const void *const d_w[3], const void *const d_t[3], const void *d_qk, size_t N,
                     uint32_t *d_idx, void *d_m);
+/* ---- Plonk witness generation and the witness check on the device ----
+ * The rules.  A circuit has N = 2^mu rows and 3N slots; slot j N + x is wire j of row x (a, b, c = 0, 1, 2).  The CLASSES are the cycles
+ * of sigma; every class carries one value.
+ *   Computing rows.  Row x is COMPUTING when its output coefficient is non-zero.  Basic gate (gate_kind 0; d_sel = q1, q2): every row, with
+ *     c = q1 (a + b) + q2 a b + in(x).  Wide gate (gate_kind 1; d_sel = qL, qR, qM, qO, qC, qH): the rows with qO(x) != 0, with
+ *     c = (qL a + qR b + qM a b + qH a^5 + qC + in(x)) / qO(x).  in holds the public inputs on rows 0 .. l - 1 and zero elsewhere: an
+ *     input row is the same rule, no special case.
+ *   Source of a class: the smallest c slot of a computing row in the class.  A class without one is FREE: its value is free[s] for its
+ *     smallest slot s (free: 3N Fr of the caller, read only at those slots; null: zeros).  Every slot of the class that is not itself the
+ *     c slot of a computing row takes the class's value.  Every computing row computes its own c: a second computing c slot in one class
+ *     is an equality assertion -- checked, not assigned.
+ *   Level of a computing row: 0 when the classes of both its a and b slots are free, otherwise 1 + the largest level of the source rows
+ *     of those classes.  A row that depends on itself, directly or through other rows, has no level: the plan is refused.
+ *   Check.  Row x is a BAD GATE ROW when the gate identity does not hold on it (after generation: only a non-computing row); slot s is a
+ *     BAD COPY when its value differs from the value of its class -- the c of the source row, or what the class's smallest slot holds
+ *     (after generation: only a further computing c slot).  On caller-given a, b, c every row and slot can fail.
+ *
+ * zk_witness_plan_create: the plan of one circuit, built once, on the host, in O(N): the cycles, the source of every slot, the levels
+ * (Kahn's algorithm), the rows ordered by (level, row), the launch schedule; uploads 3N + N u32, the level offsets and, with d_out_sel,
+ * N Fr of 1 / qO (zk_fr_batch_div; the only kernel of the call).  h_sigma: 3N slot numbers; d_out_sel: the output selector qO as N Fr on
+ * the device (fully reduced Montgomery forms), or NULL: every row computes (the basic gate).  N < 2, not a power of two or > 2^29, a
+ * sigma that is not a permutation, a qO that is not reduced below r ("the output selector of row X ..."; the test for zero is on the
+ * limbs): ZK_ERR_INVALID.  Rows without a level: ZK_ERR_INVALID, zk_last_error gives "K of N rows depend on their own output" and the smallest
+ * such row.  The plan belongs to ctx and must be freed before it. */
+typedef struct zk_witness_plan zk_witness_plan;
+int zk_witness_plan_create(zk_ctx *ctx, const uint64_t *h_sigma, const void *d_out_sel, size_t N, zk_witness_plan **out);
+void zk_witness_plan_free(zk_witness_plan *plan);
+/* levels: how many levels the computing rows have (the largest level + 1); max_level_rows: the rows of the largest level; launches: the
+ * level launches of one zk_plonk_witness -- a level of more than 256 rows is one launch of many workgroups, a run of consecutive
+ * levels of at most 256 rows each is ONE launch of ONE 256-thread workgroup that walks them with a barrier in between (the fill pass
+ * and the check are not counted).  Any output may be NULL. */
+int zk_witness_plan_info(const zk_witness_plan *plan, size_t *levels, size_t *max_level_rows, size_t *launches);
+/* zk_plonk_witness: a, b, c (N Fr each, fully reduced Montgomery forms; three distinct buffers) from the selectors, the l public inputs
+ * (host, l x 4 u64 Montgomery) and free.  The level launches follow one another on the ctx stream with no host read in between, no
+ * kernel waits on another workgroup; a last pass fills the rows that compute nothing; then the check below runs on the result
+ * (blocking: ONE status read).  A bad gate row or a bad copy: ZK_ERR_INVALID, zk_last_error gives "K of N rows do not satisfy the gate"
+ * / "K of 3N slots differ from the value of their class" and the smallest index; a, b, c then hold what was generated.  gate_kind other
+ * than 0 / 1, a wide gate on a plan built without d_out_sel (or the basic gate on one built with it), l > N, a null selector:
+ * ZK_ERR_INVALID, nothing is launched.  The division uses the plan's 1 / qO: d_sel[3] must be the selector the plan was built from.
+ * Nothing is read out of bounds whatever free and the selectors hold; the inputs are not modified. */
+int zk_plonk_witness(zk_ctx *ctx, const zk_witness_plan *plan, int gate_kind, const void *const *d_sel, const uint64_t *h_public_inputs,
+                     size_t l, const void *d_free, void *d_a, void *d_b, void *d_c);
+/* The check alone, on any a, b, c: h_bad = { bad gate rows, the smallest (2^64 - 1: none), bad copies, the smallest slot (2^64 - 1:
+ * none) }.  a, b, c must be fully reduced Montgomery forms, as zk_plonk_witness writes them: copies are compared limb for limb, so a
+ * wire at or above r is reported as a bad copy of its reduced twin (nothing is read out of bounds; the public inputs are reduced when
+ * read).  Returns ZK_OK whatever it counts (the report is the result); blocking, the inputs are not modified. */
+int zk_plonk_witness_check(zk_ctx *ctx, const zk_witness_plan *plan, int gate_kind, const void *const *d_sel,
+                           const uint64_t *h_public_inputs, size_t l, const void *d_a, const void *d_b, const void *d_c, uint64_t h_bad[4]);
 /* df = beta + a + zeta b + zeta^2 c and dt = beta + t0 + zeta t1 + zeta^2 t2 in ONE pass (N Fr each).  The inputs are not modified; an
  * output may not alias an input.  ASYNCHRONOUS on the ctx stream like zk_perm3_terms.  N < 2, not a power of two or > 2^35, or a null
  * pointer: ZK_ERR_INVALID, nothing is launched. */

@@ -473,6 +473,28 @@ int zk_lookup3_find(zk_ctx* ctx, const void* const d_w[3], const void* const d_t
     for (int j = 0; j < 3; j++) NEED(ctx, d_w[j] && d_t[j]);
     return lookup3_find(ctx, d_w, d_t, d_qk, N, d_idx, d_m);
 }
+int zk_witness_plan_create(zk_ctx* ctx, const uint64_t* h_sigma, const void* d_out_sel, size_t N, zk_witness_plan** out) {
+    NEED(ctx, h_sigma && out);
+    return witness_plan_create(ctx, h_sigma, d_out_sel, N, out);
+}
+void zk_witness_plan_free(zk_witness_plan* plan) { witness_plan_free(plan); }
+int zk_witness_plan_info(const zk_witness_plan* plan, size_t* levels, size_t* max_level_rows, size_t* launches) {
+    if (!plan) return ZK_ERR_INVALID;
+    if (levels) *levels = plan->levels;
+    if (max_level_rows) *max_level_rows = plan->max_level_rows;
+    if (launches) *launches = plan->launches.size();
+    return ZK_OK;
+}
+int zk_plonk_witness(zk_ctx* ctx, const zk_witness_plan* plan, int gate_kind, const void* const* d_sel, const uint64_t* h_public_inputs, size_t l, const void* d_free,
+                     void* d_a, void* d_b, void* d_c) {
+    NEED(ctx, plan && d_sel && (l == 0 || h_public_inputs) && d_a && d_b && d_c);
+    return plonk_witness(ctx, plan, gate_kind, d_sel, h_public_inputs, l, d_free, d_a, d_b, d_c);
+}
+int zk_plonk_witness_check(zk_ctx* ctx, const zk_witness_plan* plan, int gate_kind, const void* const* d_sel, const uint64_t* h_public_inputs, size_t l, const void* d_a,
+                           const void* d_b, const void* d_c, uint64_t h_bad[4]) {
+    NEED(ctx, plan && d_sel && (l == 0 || h_public_inputs) && d_a && d_b && d_c && h_bad);
+    return plonk_witness_check(ctx, plan, gate_kind, d_sel, h_public_inputs, l, d_a, d_b, d_c, h_bad);
+}
 int zk_eq_table_acc(zk_ctx* ctx, const uint64_t* h_point, size_t n, const uint64_t h_weight[4], void* d_acc) {
     NEED(ctx, d_acc && h_weight && (n == 0 || h_point));
     return eq_table_acc(ctx, h_point, n, h_weight, d_acc);

@@ -97,7 +97,27 @@ struct zk_transcript {
     bool stage_busy = false;
 };
 
+// Witness plan of one Plonk circuit (zk_witness.cpp builds it on the host, zk_witness.hip runs it): see include/zkhip.h
+struct zk_witness_plan {
+    zk_ctx* ctx = nullptr;
+    size_t N = 0;
+    uint32_t* d_src = nullptr;    // 3N: the source of every slot -- a row (its c slot holds the class's value), or kWitFree | the class's smallest slot
+    uint32_t* d_order = nullptr;  // N: the computing rows by (level, row), then the other rows in ascending order
+    uint32_t* d_lvoff = nullptr;  // levels + 1: level v is order[lvoff[v] .. lvoff[v + 1])
+    void* d_inv = nullptr;        // N Fr: 1 / qO on the computing rows, 0 elsewhere (null: built without an output selector, every row computes)
+    size_t computing = 0, levels = 0, max_level_rows = 0;
+    struct Launch {
+        uint32_t lv0, lv1;  // the levels [lv0, lv1): ONE level of more than kWitBlock rows (a grid of workgroups), or a run of levels of at most kWitBlock rows each (one workgroup)
+        bool grid;
+    };
+    std::vector<Launch> launches;
+    std::vector<uint32_t> lvoff;  // host copy of d_lvoff
+};
+
 namespace zk {
+
+static constexpr uint32_t kWitFree = 0x80000000u;  // flag of zk_witness_plan::d_src (3N <= 3 * 2^29 stays below it)
+static constexpr int kWitBlock = 256;
 
 // Experiment / diagnostics knobs of the whole library in ONE place.  Defaults are the shipped configuration; the only
 // ways to change them are zk_dbg_tune(key, value) (tests, tools) and the ZKHIP_TUNE="key=value,key=value" environment
@@ -241,6 +261,15 @@ int sumcheck_lookup_sel(zk_ctx* ctx, const void* const* d_tabs, size_t len, cons
 // the row-to-table indices found on the device (smallest index of an equal entry) and their multiplicities; d_idx or d_m may be null, not both
 int lookup_find(zk_ctx* ctx, const void* d_f, const void* d_t, size_t N, uint32_t* d_idx, void* d_m);
 int lookup3_find(zk_ctx* ctx, const void* const* d_w, const void* const* d_t, const void* d_qk, size_t N, uint32_t* d_idx, void* d_m);
+
+// ---- zk_witness.cpp (the plan, on the host) / zk_witness.hip (the kernels) ----
+int witness_plan_create(zk_ctx* ctx, const uint64_t* h_sigma, const void* d_out_sel, size_t N, zk_witness_plan** out);
+void witness_plan_free(zk_witness_plan* plan);
+int plonk_witness(zk_ctx* ctx, const zk_witness_plan* plan, int gate_kind, const void* const* d_sel, const uint64_t* h_pi, size_t l, const void* d_free, void* d_a, void* d_b,
+                  void* d_c);
+// h_bad: bad gate rows, the smallest (~0: none), bad copies, the smallest (~0: none)
+int plonk_witness_check(zk_ctx* ctx, const zk_witness_plan* plan, int gate_kind, const void* const* d_sel, const uint64_t* h_pi, size_t l, const void* d_a, const void* d_b,
+                        const void* d_c, uint64_t* h_bad);
 
 // ---- zk_batchopen.hip ----
 int eq_table_acc(zk_ctx* ctx, const uint64_t* h_point, size_t n, const uint64_t* h_weight, void* d_acc);

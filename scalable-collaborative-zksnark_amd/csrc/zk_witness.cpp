@@ -1,0 +1,190 @@
+// zk_witness.cpp -- the witness plan of one Plonk circuit, built ONCE per circuit on the host in O(N) (include/zkhip.h states the rules):
+//   1. sigma is checked to be a permutation of the 3N slots; the cycles are walked, every slot gets its SOURCE as a u32 -- the row whose
+//      c slot is the smallest c slot of a computing row in the cycle, or kWitFree | the cycle's smallest slot when it has none;
+//   2. the levels of the computing rows by Kahn's algorithm on the edges (source row of the a / b slot) -> row; what it cannot reach
+//      depends on its own output and the plan is refused;
+//   3. a counting sort by (level, row), the level offsets, and the launch schedule of zk_witness.hip: a level of more than kWitBlock rows
+//      is a launch of its own, a run of consecutive smaller levels is ONE launch of ONE workgroup;
+//   4. the uploads: src, the row order, the level offsets and, with an output selector, 1 / qO on the computing rows (zk_fr_batch_div).
+// Why on the host: it runs once per circuit and is serial on a deep circuit anyway; the per-proof work is zk_witness.hip.
+#include "fp.cuh"
+#include "zk_ctx.hpp"
+
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+namespace zk {
+
+void witness_plan_free(zk_witness_plan* plan) {
+    if (!plan) return;
+    if (plan->ctx) (void)hipSetDevice(plan->ctx->device);
+    if (plan->d_src) (void)hipFree(plan->d_src);
+    if (plan->d_order) (void)hipFree(plan->d_order);
+    if (plan->d_lvoff) (void)hipFree(plan->d_lvoff);
+    if (plan->d_inv) (void)hipFree(plan->d_inv);
+    delete plan;
+}
+
+namespace {
+struct PlanGuard {  // frees a half-built plan on every early return
+    zk_witness_plan* p;
+    ~PlanGuard() { witness_plan_free(p); }
+};
+struct DevGuard {
+    void* p = nullptr;
+    ~DevGuard() {
+        if (p) (void)hipFree(p);
+    }
+};
+int upload_u32(zk_ctx* ctx, const std::vector<uint32_t>& v, uint32_t** d_out) {
+    ZK_HIP(ctx, device_alloc(ctx, (void**)d_out, std::max<size_t>(v.size(), 1) * sizeof(uint32_t)));
+    if (!v.empty()) ZK_HIP(ctx, hipMemcpy(*d_out, v.data(), v.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    return ZK_OK;
+}
+}  // namespace
+
+int witness_plan_create(zk_ctx* ctx, const uint64_t* h_sigma, const void* d_out_sel, size_t N, zk_witness_plan** out) {
+    *out = nullptr;
+    if (N < 2 || (N & (N - 1)) || N > ((size_t)1 << 29)) return fail(ctx, ZK_ERR_INVALID, "zk_witness_plan_create: N = %zu is not a power of two in [2, 2^29]", N);
+    const size_t S = 3 * N;
+    ZK_HIP(ctx, hipSetDevice(ctx->device));
+    // sigma: every slot number below 3N, each exactly once
+    std::vector<uint8_t> mark(S, 0);
+    for (size_t s = 0; s < S; s++) {
+        const uint64_t t = h_sigma[s];
+        if (t >= S || mark[t]) return fail(ctx, ZK_ERR_INVALID, "zk_witness_plan_create: sigma is not a permutation of the %zu wire slots (entry %zu)", S, s);
+        mark[t] = 1;
+    }
+    // the computing rows: all of them, or those with a non-zero output selector
+    std::vector<uint8_t> comp(N, 1);
+    std::vector<uint64_t> qo;
+    if (d_out_sel) {
+        qo.resize(4 * N);
+        ZK_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the selector may have been produced on the ctx stream
+        ZK_HIP(ctx, hipMemcpy(qo.data(), d_out_sel, 32 * N, hipMemcpyDeviceToHost));
+        // fully reduced limbs only: r stored as it stands is zero mod r with non-zero limbs, a computing row with a zero denominator
+        uint64_t r[4];
+        for (int i = 0; i < 4; i++) r[i] = ((uint64_t)FrCfg::P(2 * i + 1) << 32) | FrCfg::P(2 * i);
+        for (size_t x = 0; x < N; x++) {
+            const uint64_t* q = &qo[4 * x];
+            int i = 3;
+            while (i > 0 && q[i] == r[i]) i--;
+            if (q[i] >= r[i]) return fail(ctx, ZK_ERR_INVALID, "zk_witness_plan_create: the output selector of row %zu is not reduced below r", x);
+            comp[x] = (q[0] | q[1] | q[2] | q[3]) != 0;
+        }
+    }
+    // 1. the cycles.  Slots are visited in ascending order, so a cycle is entered at its smallest slot
+    std::vector<uint32_t> src(S);
+    std::fill(mark.begin(), mark.end(), 0);
+    for (size_t s = 0; s < S; s++) {
+        if (mark[s]) continue;
+        size_t best = S, t = s;
+        do {
+            if (t >= 2 * N && comp[t - 2 * N] && t < best) best = t;
+            t = (size_t)h_sigma[t];
+        } while (t != s);
+        const uint32_t v = best < S ? (uint32_t)(best - 2 * N) : (kWitFree | (uint32_t)s);
+        do {
+            src[t] = v, mark[t] = 1;
+            t = (size_t)h_sigma[t];
+        } while (t != s);
+    }
+    // 2. levels.  A computing row x waits for the source rows of its a and b slots (an edge each, also when both are one row)
+    std::vector<uint32_t> start(N + 1, 0), level(N, 0);
+    std::vector<uint8_t> indeg(N, 0);
+    size_t nc = 0;
+    for (size_t x = 0; x < N; x++) {
+        if (!comp[x]) continue;
+        nc++;
+        for (int j = 0; j < 2; j++) {
+            const uint32_t v = src[j * N + x];
+            if (!(v & kWitFree)) start[v + 1]++, indeg[x]++;
+        }
+    }
+    for (size_t r = 0; r < N; r++) start[r + 1] += start[r];
+    std::vector<uint32_t> adj(start[N]), fill(start.begin(), start.end() - 1);
+    for (size_t x = 0; x < N; x++) {
+        if (!comp[x]) continue;
+        for (int j = 0; j < 2; j++) {
+            const uint32_t v = src[j * N + x];
+            if (!(v & kWitFree)) adj[fill[v]++] = (uint32_t)x;
+        }
+    }
+    std::vector<uint32_t> queue;
+    queue.reserve(nc);
+    for (size_t x = 0; x < N; x++)
+        if (comp[x] && !indeg[x]) queue.push_back((uint32_t)x);
+    uint32_t top = 0;
+    for (size_t head = 0; head < queue.size(); head++) {
+        const uint32_t r = queue[head];
+        top = std::max(top, level[r]);
+        for (uint32_t e = start[r]; e < start[r + 1]; e++) {
+            const uint32_t x = adj[e];
+            level[x] = std::max(level[x], level[r] + 1);
+            if (--indeg[x] == 0) queue.push_back(x);
+        }
+    }
+    if (queue.size() < nc) {
+        size_t first = N;
+        for (size_t x = 0; x < N && first == N; x++)
+            if (comp[x] && indeg[x]) first = x;
+        return fail(ctx, ZK_ERR_INVALID, "zk_witness_plan_create: %zu of %zu rows depend on their own output; the first is row %zu", nc - queue.size(), N, first);
+    }
+    // 3. (level, row) order by a counting sort; the rows that compute nothing follow in ascending order
+    zk_witness_plan* plan = new zk_witness_plan;
+    PlanGuard guard{plan};
+    plan->ctx = ctx, plan->N = N, plan->computing = nc;
+    const size_t levels = nc ? (size_t)top + 1 : 0;
+    plan->levels = levels;
+    std::vector<uint32_t>& lvoff = plan->lvoff;
+    lvoff.assign(levels + 1, 0);
+    for (size_t x = 0; x < N; x++)
+        if (comp[x]) lvoff[level[x] + 1]++;
+    for (size_t v = 0; v < levels; v++) {
+        plan->max_level_rows = std::max<size_t>(plan->max_level_rows, lvoff[v + 1]);
+        lvoff[v + 1] += lvoff[v];
+    }
+    std::vector<uint32_t> order(N), at(lvoff.begin(), lvoff.end() - (levels ? 1 : 0));
+    size_t rest = nc;
+    for (size_t x = 0; x < N; x++) {
+        if (comp[x]) order[at[level[x]]++] = (uint32_t)x;
+        else order[rest++] = (uint32_t)x;
+    }
+    for (size_t v = 0; v < levels;) {
+        size_t e = v + 1;
+        const bool grid = lvoff[v + 1] - lvoff[v] > (uint32_t)kWitBlock;
+        if (!grid)
+            while (e < levels && lvoff[e + 1] - lvoff[e] <= (uint32_t)kWitBlock) e++;
+        plan->launches.push_back({(uint32_t)v, (uint32_t)e, grid});
+        v = e;
+    }
+    // 4. uploads
+    int rc = upload_u32(ctx, src, &plan->d_src);
+    if (rc == ZK_OK) rc = upload_u32(ctx, order, &plan->d_order);
+    if (rc == ZK_OK) rc = upload_u32(ctx, lvoff, &plan->d_lvoff);
+    if (rc != ZK_OK) return rc;
+    if (d_out_sel) {
+        // 1 / qO by the batch inversion: numerator 1 and denominator qO on the computing rows, 0 / 1 elsewhere (no zero denominator)
+        uint64_t one[4];
+        for (int i = 0; i < 4; i++) one[i] = ((uint64_t)FrCfg::ONE(2 * i + 1) << 32) | FrCfg::ONE(2 * i);
+        std::vector<uint64_t> num(4 * N, 0);
+        for (size_t x = 0; x < N; x++) {
+            if (comp[x]) memcpy(&num[4 * x], one, 32);
+            else memcpy(&qo[4 * x], one, 32);
+        }
+        DevGuard d_num, d_den;
+        ZK_HIP(ctx, device_alloc(ctx, &d_num.p, 32 * N));
+        ZK_HIP(ctx, device_alloc(ctx, &d_den.p, 32 * N));
+        ZK_HIP(ctx, device_alloc(ctx, &plan->d_inv, 32 * N));
+        ZK_HIP(ctx, hipMemcpy(d_num.p, num.data(), 32 * N, hipMemcpyHostToDevice));
+        ZK_HIP(ctx, hipMemcpy(d_den.p, qo.data(), 32 * N, hipMemcpyHostToDevice));
+        rc = fr_batch_div(ctx, d_num.p, d_den.p, plan->d_inv, N);  // blocking
+        if (rc != ZK_OK) return rc;
+    }
+    guard.p = nullptr;
+    *out = plan;
+    return ZK_OK;
+}
+
+}  // namespace zk

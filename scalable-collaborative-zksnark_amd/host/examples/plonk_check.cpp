@@ -3,8 +3,8 @@
 // drawn from the device transcript and verified by replaying the schedule on the host transcript.  One digest for one seed across the
 // two hosts (zkhip.plonk.proof_digest).
 //
-//     bin/plonk_check --mu M [--seed S] [--gate wide] [--lookup [--find] [--break-lookup K]] [--break-gate K | --break-wire K | --bad-input | --break K|all]
-//                     [--circuit-only | --sample-only]
+//     bin/plonk_check --mu M [--seed S] [--gate wide] [--witness] [--lookup [--find] [--break-lookup K]] [--break-gate K | --break-wire K | --bad-input | --break K|all]
+//                     [--circuit-only | --sample-only [--time-sample R]]
 //
 // --lookup proves the test circuit with lookup rows (zkhip.plonk.sample_circuit_lookup, mu >= 3) under the label + "-lookup": three opening
 // proofs.  --find (with --lookup) proves without the sample's indices: the device finds them (plonk_prove(.., kFind)); the sampler only ever
@@ -15,17 +15,24 @@
 // 14 lookup.batch.rounds, 15 lookup.batch.opening.  --break all proves once and verifies one tampered copy per part: one line each, exit 1 when
 // every copy is rejected and 0 when one is accepted.
 //
+// --witness drops the sampler's a, b, c and generates them on the device (plonk_witness: zk_witness_plan_create + zk_plonk_witness) from the
+// circuit, the public inputs and -- with --lookup -- the free values of the lookup rows; the digest is the one without the flag.  Not with
+// --break-gate / --break-wire, which break the sampler's wires.
 // --gate wide proves the test circuit of the wide gate (zkhip.plonk.sample_circuit_wide: six selectors and a fifth-power term) instead.
 // --break-gate K adds 1 to c[K]; --break-wire K (K past the input rows) changes a[K] and recomputes c[K], so that only the copy
 // constraint fails; --bad-input hands the verifier a public input the prover did not use.  The verifier rejects each.  Prints the proof
 // digest and accept / reject; exit 0 on accept, 1 on reject, 2 on error (arguments are checked before any device is touched).
 // Without a GPU it refuses (no CPU fallback) -- but for --circuit-only (--sample-only is the same mode), which builds the test circuit, prints
 // the SHA-256 of its tables (the selectors, a, b, c, the public inputs, the trapdoor, sigma and, with --lookup, qk, t0, t1, t2, idx:
-// little-endian words in that order, zkhip.plonk.circuit_digest) and exits 0 without touching a device.
+// little-endian words in that order, zkhip.plonk.circuit_digest) and exits 0 without touching a device.  --time-sample R (with that mode)
+// samples 3 + R more times and prints a second line, the median of the last R calls' time in the sampler's ROW LOOP alone (the loop that
+// copies a, b and computes c; no draws, no sigma): the CPU baseline of tools/witness_time.py.
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <vector>
 
 #include "zkhost/hyperplonk.hpp"
 #include "zkhost/pcs_vk.hpp"
@@ -41,7 +48,8 @@ static bool number(const char *s, long long &out) {
 
 struct Options {
     long long mu = -1, seed = 7, break_gate = -1, break_wire = -1, break_lookup = -1, break_part = -1;
-    bool bad_input = false, wide = false, lookup = false, break_all = false, find = false;
+    long long time_sample = 0;
+    bool bad_input = false, wide = false, lookup = false, break_all = false, find = false, witness = false;
 };
 
 static PlonkCircuit sample(const Options &o, bool broken) {
@@ -50,7 +58,19 @@ static PlonkCircuit sample(const Options &o, bool broken) {
 }
 
 static int circuit_only(const Options &o) {
-    std::printf("circuit sha256 %s\n", circuit_digest(sample(o, true)).c_str());
+    const PlonkCircuit c = sample(o, true);
+    std::printf("circuit sha256 %s\n", circuit_digest(c).c_str());
+    if (o.time_sample > 0) {
+        // the sampler's row loop alone (detail::sample_loop_seconds): the median of R calls after three, one process
+        std::vector<double> t;
+        for (long long i = 0; i < 3 + o.time_sample; ++i) {
+            sample(o, true);
+            if (i >= 3) t.push_back(detail::sample_loop_seconds());
+        }
+        std::sort(t.begin(), t.end());
+        const size_t n = t.size();
+        std::printf("sample row loop seconds %.6f\n", n % 2 ? t[n / 2] : 0.5 * (t[n / 2 - 1] + t[n / 2]));
+    }
     return 0;
 }
 
@@ -86,8 +106,24 @@ static int run(const Options &o) {
     }
     PlonkProof proof;
     try {
-        proof = o.find ? plonk_prove(be, cub.mature(), pk, be.to_device(c.a), be.to_device(c.b), be.to_device(c.c), good.public_inputs, kFind)
-                       : plonk_prove(be, cub.mature(), pk, be.to_device(c.a), be.to_device(c.b), be.to_device(c.c), good.public_inputs, idx);
+        std::array<DevPtr, 3> w;
+        if (o.witness) {
+            // the sampler's a, b, c are dropped: the device generates them from the circuit, the public inputs and -- with a lookup -- the free
+            // values of the lookup rows, whose a and b slots are fixed points of sigma and hold the table's u, v
+            const std::shared_ptr<WitnessPlan> plan = witness_plan(be, good);
+            FrVec free;
+            if (o.lookup) {
+                free.assign(3 * N, Fr::zero());
+                for (size_t x = 0; x < N; ++x)
+                    if (!(c.qk[x] == Fr::zero())) free[x] = c.a[x], free[N + x] = c.b[x];
+            }
+            w = plonk_witness(be, pk, *plan, good.public_inputs, o.lookup ? &free : nullptr);
+            const std::array<size_t, 3> info = plan->info();
+            std::printf("witness on the device: %zu levels, %zu rows in the largest, %zu level launches\n", info[0], info[1], info[2]);
+        } else {
+            w = {be.to_device(c.a), be.to_device(c.b), be.to_device(c.c)};
+        }
+        proof = o.find ? plonk_prove(be, cub.mature(), pk, w[0], w[1], w[2], good.public_inputs, kFind) : plonk_prove(be, cub.mature(), pk, w[0], w[1], w[2], good.public_inputs, idx);
     } catch (const ZkError &e) {
         if (o.break_lookup < 0 || e.status != ZK_ERR_INVALID) throw;
         std::fprintf(stderr, "plonk_check: the prover refused: %s\n", e.what());
@@ -127,6 +163,8 @@ int main(int argc, char **argv) {
         else if (k == "--circuit-only" || k == "--sample-only") only_circuit = true;
         else if (k == "--lookup") o.lookup = true;
         else if (k == "--find") o.find = true;
+        else if (k == "--witness") o.witness = true;
+        else if (i + 1 < argc && k == "--time-sample") usage = !number(argv[++i], o.time_sample) || o.time_sample < 1;
         else if (i + 1 < argc && k == "--break-lookup") usage = !number(argv[++i], o.break_lookup);
         else if (i + 1 < argc && k == "--break" && !std::strcmp(argv[i + 1], "all")) o.break_all = true, ++i;
         else if (i + 1 < argc && k == "--break") usage = !number(argv[++i], o.break_part);
@@ -139,8 +177,9 @@ int main(int argc, char **argv) {
     }
     const bool tamper = o.break_all || o.break_part >= 0;
     if (usage || mu < 0 || (break_gate >= 0) + (break_wire >= 0) + (bad_input ? 1 : 0) + (o.break_lookup >= 0) + (tamper ? 1 : 0) > 1 ||
-        (o.break_all && o.break_part >= 0) || (o.break_lookup >= 0 && !o.lookup) || (o.find && !o.lookup) || (o.lookup && (break_gate >= 0 || break_wire >= 0))) {
-        std::fprintf(stderr, "usage: plonk_check --mu M [--seed S] [--gate wide] [--lookup [--find] [--break-lookup K]] [--break-gate K | --break-wire K | --bad-input | --break K|all] [--circuit-only | --sample-only]\n");
+        (o.break_all && o.break_part >= 0) || (o.break_lookup >= 0 && !o.lookup) || (o.find && !o.lookup) || (o.lookup && (break_gate >= 0 || break_wire >= 0)) ||
+        (o.witness && (break_gate >= 0 || break_wire >= 0)) || (o.time_sample > 0 && !only_circuit)) {
+        std::fprintf(stderr, "usage: plonk_check --mu M [--seed S] [--gate wide] [--witness] [--lookup [--find] [--break-lookup K]] [--break-gate K | --break-wire K | --bad-input | --break K|all] [--circuit-only | --sample-only [--time-sample R]]\n");
         return 2;
     }
     if (mu < 2 || mu > 24) {

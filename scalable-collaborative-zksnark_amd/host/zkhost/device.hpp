@@ -59,6 +59,27 @@ struct PcsVk {
     }
 };
 
+// the witness plan of one Plonk circuit held by the library (zk_witness_plan: sources, levels, launch schedule); it holds its ctx
+struct WitnessPlan {
+    CtxRef ctx;
+    zk_witness_plan *h = nullptr;
+    size_t N = 0;
+    bool wide = false;  // built with the wide gate's output selector
+    WitnessPlan(CtxRef c, zk_witness_plan *h_, size_t n, bool w) : ctx(std::move(c)), h(h_), N(n), wide(w) {}
+    WitnessPlan(const WitnessPlan &) = delete;
+    ~WitnessPlan() { zk_witness_plan_free(h); }
+    // levels, rows of the largest level, level launches of one zk_plonk_witness
+    std::array<size_t, 3> info() const {
+        std::array<size_t, 3> v{};
+        zk_witness_plan_info(h, &v[0], &v[1], &v[2]);
+        return v;
+    }
+};
+struct WitnessReport {  // zk_plonk_witness_check: the counts and the smallest row / slot (~0: none)
+    uint64_t bad_rows = 0, first_bad_row = ~0ull, bad_copies = 0, first_bad_copy = ~0ull;
+    bool ok() const { return !bad_rows && !bad_copies; }
+};
+
 // a Fiat-Shamir transcript whose state lives on the device (zk_transcript); freed before its ctx because it holds the ctx
 struct DeviceTranscript {
     CtxRef ctx;
@@ -680,6 +701,34 @@ class Ctx {
         G2 out;
         check(zk_msm_g2(h_, srs.handle(), offset, scalars.get(), n, out.data()));
         return out;
+    }
+    // ---- Plonk witness (zk_witness_plan_create, zk_plonk_witness, zk_plonk_witness_check) ----
+    // sigma: 3N slot numbers; out_sel: the wide gate's qO on the device (null: every row computes).  Rows that depend on their own output or a
+    // sigma that is not a permutation: ZkError(ZK_ERR_INVALID)
+    std::shared_ptr<WitnessPlan> witness_plan(const std::vector<uint64_t> &sigma, size_t N, const DevPtr *out_sel = nullptr) {
+        need(sigma.size() == 3 * N, "witness_plan: sigma must hold 3N slot numbers");
+        zk_witness_plan *p = nullptr;
+        check(zk_witness_plan_create(h_, sigma.data(), out_sel ? out_sel->get() : nullptr, N, &p));
+        return std::make_shared<WitnessPlan>(ref_, p, N, out_sel != nullptr);
+    }
+    // a, b, c generated on the device; free: 3N Fr or null (zeros).  A bad gate row or copy: ZkError(ZK_ERR_INVALID) with the library's message
+    std::array<DevPtr, 3> plonk_witness(const WitnessPlan &plan, const std::vector<DevPtr> &sel, const FrVec &public_inputs, const DevPtr *free = nullptr) {
+        std::array<DevPtr, 3> w = {alloc_fr(plan.N), alloc_fr(plan.N), alloc_fr(plan.N)};
+        std::vector<const void *> ps;
+        for (const DevPtr &d : sel) ps.push_back(d.get());
+        check(zk_plonk_witness(h_, plan.h, sel.size() == 6 ? 1 : 0, ps.data(), public_inputs.empty() ? nullptr : public_inputs[0].v, public_inputs.size(),
+                               free ? free->get() : nullptr, w[0].get(), w[1].get(), w[2].get()));
+        return w;
+    }
+    WitnessReport plonk_witness_check(const WitnessPlan &plan, const std::vector<DevPtr> &sel, const FrVec &public_inputs, const DevPtr &a, const DevPtr &b, const DevPtr &c) {
+        std::vector<const void *> ps;
+        for (const DevPtr &d : sel) ps.push_back(d.get());
+        uint64_t bad[4];
+        check(zk_plonk_witness_check(h_, plan.h, sel.size() == 6 ? 1 : 0, ps.data(), public_inputs.empty() ? nullptr : public_inputs[0].v, public_inputs.size(), a.get(),
+                                     b.get(), c.get(), bad));
+        WitnessReport r;
+        r.bad_rows = bad[0], r.first_bad_row = bad[1], r.bad_copies = bad[2], r.first_bad_copy = bad[3];
+        return r;
     }
     // g1_96: powers_of_g[0][0] as a 96-byte affine record (nullptr: the generator); powers_g2: n_g2 affine records at `stride`
     std::shared_ptr<PcsVk> pcs_vk(const void *g1_96, const void *powers_g2, size_t stride, size_t n_g2) {

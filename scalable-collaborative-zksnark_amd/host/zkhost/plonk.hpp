@@ -36,6 +36,8 @@
 //       hf, ht with seven claims at r_l.  Three opening proofs.
 // A circuit, key or record without a lookup behaves exactly as before.
 #pragma once
+#include <chrono>
+
 #include "nizk.hpp"
 
 namespace zkhost {
@@ -117,6 +119,35 @@ inline Fr gate_closed_form(GateKind k, const Fr &eq, const FrVec &g, const Fr &i
     return eq * (g[0] * (g[2] + g[3]) + g[1] * g[2] * g[3] - g[4] + in);
 }
 
+// ---- witness (zkhip.plonk.witness_plan / witness / check_witness; the rules: include/zkhip.h) ----
+// the plan of a circuit: built once, on the host inside the library; the wide gate's output selector qO is sel[3]
+inline std::shared_ptr<WitnessPlan> witness_plan(Ctx &be, const PlonkCircuit &c) {
+    const size_t N = size_t(1) << c.mu;
+    if (c.gate != GateKind::wide) return be.witness_plan(c.sigma, N);
+    const DevPtr qo = be.to_device(c.sel[3]);
+    return be.witness_plan(c.sigma, N, &qo);
+}
+inline void witness_need(bool ok, const char *what) {
+    if (!ok) throw ZkError(ZK_ERR_INVALID, what);
+}
+inline void witness_args(const PlonkPk &pk, const WitnessPlan &plan, const FrVec &public_inputs) {
+    witness_need(public_inputs.size() == pk.l, "plonk witness: the public-input count differs from the key's");
+    witness_need(plan.N == size_t(1) << pk.mu && plan.wide == (pk.gate == GateKind::wide), "plonk witness: the plan is not one of this key's circuit");
+}
+// the wires of pk's circuit from its public inputs and the values of its free classes (free: 3N elements read at the smallest slot of every
+// free class, or null: zeros) -> a, b, c on the device, which go straight into plonk_prove.  A broken gate or copy: ZkError(ZK_ERR_INVALID)
+inline std::array<DevPtr, 3> plonk_witness(Ctx &be, const PlonkPk &pk, const WitnessPlan &plan, const FrVec &public_inputs, const FrVec *free = nullptr) {
+    witness_args(pk, plan, public_inputs);
+    if (!free) return be.plonk_witness(plan, pk.sel, public_inputs);
+    witness_need(free->size() == 3 * plan.N, "plonk witness: free must hold 3N elements");
+    const DevPtr f = be.to_device(*free);
+    return be.plonk_witness(plan, pk.sel, public_inputs, &f);
+}
+inline WitnessReport plonk_check_witness(Ctx &be, const PlonkPk &pk, const WitnessPlan &plan, const DevPtr &a, const DevPtr &b, const DevPtr &c, const FrVec &public_inputs) {
+    witness_args(pk, plan, public_inputs);
+    return be.plonk_witness_check(plan, pk.sel, public_inputs, a, b, c);
+}
+
 namespace detail {
 // sigma: one cycle per value -- the c slot of row y, then the a / b slots that copy it in ascending slot order
 // fixed (optional, N flags): rows whose a and b slots copy nothing and stay fixed points (the lookup rows)
@@ -134,6 +165,13 @@ inline std::vector<uint64_t> copy_sigma(const std::vector<size_t> &ia, const std
         sigma[prev] = 2 * N + y;
     }
     return sigma;
+}
+// seconds the last sample_circuit / sample_circuit_wide call spent in its ROW LOOP -- the loop over the rows l .. N - 1 that copies a and
+// b and computes c (the wide one also places the row's selectors), without the SplitMix64 draws, the allocations, sigma and the
+// trapdoor: the CPU baseline of tools/witness_time.py
+inline double &sample_loop_seconds() {
+    static double s = 0;
+    return s;
 }
 }  // namespace detail
 // the lookup rows that sample_circuit_lookup hands to the two generators: row x with mask[x] takes a = u[y[x]], b = v[y[x]] in the place
@@ -170,6 +208,7 @@ inline PlonkCircuit sample_circuit(size_t mu, uint64_t seed, long long break_gat
         if (lk->mask[x]) q1[x] = Fr::zero(), q2[x] = Fr::one();
     std::vector<size_t> ia(N, 0), ib(N, 0);
     auto gate = [&](size_t x) { return q1[x] * (c.a[x] + c.b[x]) + q2[x] * c.a[x] * c.b[x]; };
+    const auto loop_start = std::chrono::steady_clock::now();
     for (size_t x = l; x < N; ++x) {
         ia[x] = pick[x].v[0] % x, ib[x] = pick[x].v[1] % x;
         if (lk && lk->mask[x]) {
@@ -180,6 +219,7 @@ inline PlonkCircuit sample_circuit(size_t mu, uint64_t seed, long long break_gat
         }
         c.c[x] = gate(x);
     }
+    detail::sample_loop_seconds() = std::chrono::duration<double>(std::chrono::steady_clock::now() - loop_start).count();
     if (break_wire >= 0) {
         if ((size_t)break_wire < l || (size_t)break_wire >= N) throw ZkError(ZK_ERR_INVALID, "sample_circuit: break_wire must name a row past the input rows");
         c.a[break_wire] += Fr::one();
@@ -218,6 +258,7 @@ inline PlonkCircuit sample_circuit_wide(size_t mu, uint64_t seed, long long brea
         const Fr s = c.sel[qL][x] * a + c.sel[qR][x] * c.b[x] + c.sel[qM][x] * a * c.b[x] + c.sel[qH][x] * a2 * a2 * a + c.sel[qC][x];
         return c.sel[qO][x] == Fr::one() ? s : s * c.sel[qO][x].inverse();
     };
+    const auto loop_start = std::chrono::steady_clock::now();
     for (size_t x = l; x < N; ++x) {
         const unsigned kind = pick[x].v[2] % 4;
         for (int k : named[kind]) c.sel[k][x] = drawn[k][x];
@@ -233,6 +274,7 @@ inline PlonkCircuit sample_circuit_wide(size_t mu, uint64_t seed, long long brea
         }
         c.c[x] = out(x);
     }
+    detail::sample_loop_seconds() = std::chrono::duration<double>(std::chrono::steady_clock::now() - loop_start).count();
     if (break_wire >= 0) {
         if ((size_t)break_wire < l || (size_t)break_wire >= N) throw ZkError(ZK_ERR_INVALID, "sample_circuit_wide: break_wire must name a row past the input rows");
         c.a[break_wire] += Fr::one();

@@ -53,6 +53,11 @@ SYMBOLS = [
     ("zk_lookup3_multiplicities", _i, [_vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     ("zk_lookup_find", _i, [_vp, _vp, _vp, _sz, _vp, _vp]),
     ("zk_lookup3_find", _i, [_vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    ("zk_witness_plan_create", _i, [_vp, _vp, _vp, _sz, _pp]),
+    ("zk_witness_plan_free", None, [_vp]),
+    ("zk_witness_plan_info", _i, [_vp, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t)]),
+    ("zk_plonk_witness", _i, [_vp, _vp, _i, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
+    ("zk_plonk_witness_check", _i, [_vp, _vp, _i, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
     ("zk_lookup3_terms", _i, [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
     ("zk_sumcheck_lookup_sel", _i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp]),
     ("zk_eq_table_acc", _i, [_vp, _vp, _sz, _vp, _vp]),

@@ -188,6 +188,39 @@ class PcsVk:
             pass
 
 
+class WitnessPlan:
+    """zk_witness_plan: the witness plan of one Plonk circuit (sources, levels, launch schedule), held by the library"""
+
+    def __init__(self, ctx: "Ctx", sigma, N: int, out_sel=None):
+        self.ctx, self.h, self.N = ctx, 0, int(N)
+        sg = np.ascontiguousarray(sigma, dtype=np.uint64).reshape(-1)
+        if len(sg) != 3 * self.N:
+            raise ValueError(f"sigma must hold {3 * self.N} slot numbers")
+        h = ctypes.c_void_p()
+        rc = ctx.lib.zk_witness_plan_create(ctx.h, _h(sg), _ptr(out_sel), self.N, ctypes.byref(h))
+        if rc == ZK_ERR_INVALID:
+            raise ValueError((ctx.lib.zk_last_error(ctx.h) or b"").decode())
+        ctx._check(rc)
+        self.h, self.wide = h.value, out_sel is not None
+
+    def info(self) -> dict:
+        """{"levels", "max_level_rows", "launches"} (zk_witness_plan_info)"""
+        v = [ctypes.c_size_t(0) for _ in range(3)]
+        self.ctx._check(self.ctx.lib.zk_witness_plan_info(self.h, *[ctypes.byref(x) for x in v]))
+        return dict(zip(("levels", "max_level_rows", "launches"), (int(x.value) for x in v)))
+
+    def free(self):
+        if self.h and getattr(self.ctx, "h", None):
+            self.ctx.lib.zk_witness_plan_free(self.h)
+        self.h = 0
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 def comm_init_all(ctxs) -> None:
     """zk_comm_init_all: one process holding a ctx per GPU (the reference's one-task-per-party model,
     mpc-net/src/multi.rs:330-352); ctxs[p] becomes party p.  Drive every party from its own thread afterwards."""
@@ -608,6 +641,36 @@ class Ctx:
             raise ValueError((self.lib.zk_last_error(self.h) or b"").decode())
         self._check(rc)
         return idx, m
+
+    def witness_plan(self, sigma, N: int, out_sel=None) -> WitnessPlan:
+        """the witness plan of a circuit (zk_witness_plan_create; host work, once per circuit): sigma 3N slot numbers, out_sel the wide gate's
+        qO as a device buffer of N fully reduced Fr (None: every row computes).  A sigma that is not a permutation, a qO at or above r, or
+        rows that depend on their own output: ValueError with the library's message."""
+        return WitnessPlan(self, sigma, N, out_sel)
+
+    def plonk_witness(self, plan: WitnessPlan, sels, public_inputs: np.ndarray, free=None, out=None):
+        """a, b, c generated on the device (zk_plonk_witness; blocking): sels the gate's selectors (2: basic, 6: wide) as device buffers,
+        public_inputs [l, 4], free a device buffer of 3N Fr or None -> (a, b, c), device buffers of N Fr.  A bad gate row or copy:
+        ValueError with the library's message."""
+        N = plan.N
+        pi = np.ascontiguousarray(public_inputs, dtype=np.uint64).reshape(-1, 4)
+        a, b, c = out or tuple(self.alloc(32 * N) for _ in range(3))
+        rc = self.lib.zk_plonk_witness(self.h, plan.h, int(len(sels) == 6), self._ptr_array(sels), _h(pi), len(pi), _ptr(free), _ptr(a), _ptr(b), _ptr(c))
+        if rc == ZK_ERR_INVALID:
+            raise ValueError((self.lib.zk_last_error(self.h) or b"").decode())
+        self._check(rc)
+        return a, b, c
+
+    def plonk_witness_check(self, plan: WitnessPlan, sels, public_inputs: np.ndarray, a, b, c) -> dict:
+        """zk_plonk_witness_check (blocking) -> {"bad_rows", "first_bad_row", "bad_copies", "first_bad_copy"} (the firsts None when there is none)"""
+        pi = np.ascontiguousarray(public_inputs, dtype=np.uint64).reshape(-1, 4)
+        bad = np.zeros(4, dtype=np.uint64)
+        rc = self.lib.zk_plonk_witness_check(self.h, plan.h, int(len(sels) == 6), self._ptr_array(sels), _h(pi), len(pi), _ptr(a), _ptr(b), _ptr(c), _h(bad))
+        if rc == ZK_ERR_INVALID:
+            raise ValueError((self.lib.zk_last_error(self.h) or b"").decode())
+        self._check(rc)
+        r, fr, k, fk = (int(x) for x in bad)
+        return {"bad_rows": r, "first_bad_row": fr if r else None, "bad_copies": k, "first_bad_copy": fk if k else None}
 
     def lookup3_terms(self, ws, ts, N: int, zeta: np.ndarray, beta: np.ndarray):
         """df = beta + a + zeta b + zeta^2 c, dt = beta + t0 + zeta t1 + zeta^2 t2 in one pass (zk_lookup3_terms; asynchronous) -> (df, dt),

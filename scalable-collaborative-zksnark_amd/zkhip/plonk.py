@@ -61,6 +61,23 @@ vk and the record carry "lookup"; the vk commitments are the gate's followed by 
 The record gains "lookup": {"commitments": [3, 18] (m, hf, ht), "rounds": [mu, 4, 4], "values": [10, 4], "batch": {"rounds": [mu, 3, 4],
 "opening": [mu, 18]}}.  A circuit, key or record without "lookup" behaves exactly as before.
 
+WITNESS.  witness_plan / witness / check_witness make and check the wires a, b, c of a circuit on the device (zk_witness_plan_create,
+zk_plonk_witness, zk_plonk_witness_check); preprocess and prove are not involved.  The rules (the same in include/zkhip.h):
+  * the classes are the cycles of sigma; every class carries one value;
+  * row x is COMPUTING when its output coefficient is non-zero.  Basic gate: every row, c = q1 (a + b) + q2 a b + in(x).  Wide gate: the
+    rows with qO(x) != 0, c = (qL a + qR b + qM a b + qH a^5 + qC + in(x)) / qO(x).  in holds the public inputs on rows 0 .. l - 1 and
+    zero elsewhere: an input row is the same rule, no special case;
+  * the SOURCE of a class is the smallest c slot of a computing row in it.  A class without one is FREE: its value is free[s] for its
+    smallest slot s (free: 3N Fr, read only at those slots; absent: 0).  Every slot of the class that is not itself the c slot of a
+    computing row takes the class's value; every computing row computes its own c, so a second computing c slot in one class is an
+    equality assertion -- checked, not assigned;
+  * the LEVEL of a computing row is 0 when the classes of both its a and b slots are free, otherwise 1 + the largest level of the source
+    rows of those classes.  A row that depends on itself, directly or through other rows, has no level: the plan is refused ("K of N
+    rows depend on their own output" and the smallest such row);
+  * the check: row x is a bad gate row when the gate identity does not hold on it (after generation only a non-computing row can be);
+    slot s is a bad copy when its value differs from its class's value (after generation only a further computing c slot can be).  On
+    caller-given a, b, c every row and slot can fail.
+
 Record: {"mu", "l", "commitments": [3, 18] (a, b, c), "v_commitment": [18], "p_rounds": [mu, 6, 4], "g_rounds": [mu, 5, 4],
          "g_values": [5, 4], "p_values": [6, 4], "v_values": [5, 4], "batch": {"rounds": [mu, 3, 4], "opening": [mu, 18]},
          "v_batch": {"rounds": [mu + 1, 3, 4], "opening": [mu + 1, 18]}}.
@@ -333,6 +350,45 @@ def prove(be, pk: dict, a, b, c, public_inputs, idx=None, timing: dict | None = 
             timing["lookup_s"] = t3l - t3
     return {"mu": mu, "l": l, "commitments": comms, "v_commitment": v_comm, "p_rounds": p_rounds, "g_rounds": g_rounds, "g_values": np.array(g_values),
             "p_values": p_values, "v_values": v_values, "batch": batch, "v_batch": v_batch, **gate.tag(), **lk_part}
+
+
+# ---- witness ----
+def witness_plan(be, circuit: dict):
+    """the witness plan of a circuit {"mu", "sigma", and with "gate": "wide" the output selector "qO"} (module text, WITNESS): built once per
+    circuit on the host inside the library (Ctx.witness_plan).  A sigma that is not a permutation, or rows that depend on their own
+    output: ValueError."""
+    gate = gate_of(circuit)
+    N = 1 << int(circuit["mu"])
+    qo = be.to_device(_u64(circuit["qO"], N, 4)) if gate.kind == "wide" else None
+    return be.witness_plan(np.ascontiguousarray(circuit["sigma"], dtype=np.uint64).reshape(-1), N, qo)
+
+
+def _witness_args(pk: dict, plan, public_inputs):
+    gate = gate_of(pk)
+    pi = _u64(public_inputs, -1, 4)
+    if len(pi) != pk["l"]:
+        raise ValueError(f"{pk['l']} public inputs needed, {len(pi)} given")
+    if plan.N != 1 << pk["mu"] or plan.wide != (gate.kind == "wide"):
+        raise ValueError("the plan is not one of this key's circuit")
+    return [pk["tables"][k] for k in gate.selectors], pi
+
+
+def witness(be, pk: dict, plan, public_inputs, free=None):
+    """the wires of pk's circuit from its public inputs ([l, 4] Montgomery Fr) and the values of its free classes (free: [3N, 4] array or
+    device buffer, read at the smallest slot of every free class; None: zeros) -> (a, b, c), device buffers of N Fr that go straight into
+    `prove`.  A witness that breaks a gate or a copy constraint: ValueError ("K of N rows ..." / "K of 3N slots ...")."""
+    sels, pi = _witness_args(pk, plan, public_inputs)
+    if isinstance(free, np.ndarray):
+        free = be.to_device(_u64(free, 3 * plan.N, 4))
+    return be.plonk_witness(plan, sels, pi, free)
+
+
+def check_witness(be, pk: dict, plan, a, b, c, public_inputs) -> dict:
+    """any a, b, c (device buffers or [N, 4] arrays) against the gate identity and the copy constraints of pk's circuit ->
+    {"bad_rows", "first_bad_row", "bad_copies", "first_bad_copy"}: the counts and the smallest row / slot (None: none)"""
+    sels, pi = _witness_args(pk, plan, public_inputs)
+    a, b, c = ((be.to_device(_u64(v, plan.N, 4)) if isinstance(v, np.ndarray) else v) for v in (a, b, c))
+    return be.plonk_witness_check(plan, sels, pi, a, b, c)
 
 
 # ---- verifier ----
