@@ -70,14 +70,11 @@ struct zk_ctx {
     size_t pool_bytes = 0;
     std::mutex pool_mu;  // a garbage collector may release buffers from another thread
     int cu_count = 256;
-    bool gate_lds_raised = false;  // zk_gate.hip: k_gate_local's dynamic LDS limit has been raised on this ctx's device
-    bool wiring_lds_raised = false;  // zk_wiring.hip: the same for k_wiring_local
-    bool multi_lds_raised = false;   // zk_batchopen.hip: the same for k_multi_local
-    bool fs_lds_raised[7] = {false, false, false, false, false, false, false};  // zk_fs.hip: the same for its seven local kernels (gate, wiring, multi, perm3, wide gate, lookup, selector-gated lookup)
-    bool perm3_lds_raised = false;   // zk_perm3.hip: the same for k_perm3_local
-    bool gatew_lds_raised = false;   // zk_gatew.hip: the same for k_gatew_local
-    bool lookup_lds_raised = false;  // zk_lookup.hip: the same for k_lookup_local
-    bool lookupsel_lds_raised = false;  // zk_lookup3.hip: the same for k_lookupsel_local
+    bool multi_lds_raised = false;   // zk_batchopen.hip: k_multi_local's dynamic LDS limit has been raised on this ctx's device
+    // the same for the local kernels of the fused identities, indexed by the Kind's kSlot (zk_gate.cuh; slot 2 of fs_lds_raised is the
+    // batch opening's k_multi_fs_local): k_sc_local<K> of the preset-challenge engine (zk_fused.cuh), k_fs_local<K> of zk_fs.hip
+    bool preset_lds_raised[7] = {false, false, false, false, false, false, false};
+    bool fs_lds_raised[7] = {false, false, false, false, false, false, false};
     // party exchanges (zk_comm.cpp): an RCCL communicator bound to this ctx's GPU
     void* comm = nullptr;
     int comm_rank = 0, comm_world = 1;

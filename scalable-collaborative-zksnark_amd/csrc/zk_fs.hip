@@ -1,6 +1,7 @@
 // zk_fs.hip -- the seven fused sumchecks (zk_gate.hip, zk_wiring.hip, zk_perm3.hip, zk_gatew.hip, zk_lookup.hip, zk_lookup3.hip, zk_batchopen.hip) with their challenges drawn from a
 // Fiat-Shamir transcript ON THE DEVICE (zk_transcript.hip, sha256.cuh): challenge r_p is a hash of round p's evaluations, so the
-// fold by r_p cannot share a sweep with round p's sums as it does in the preset-challenge kernels.  The shape here:
+// fold by r_p cannot share a sweep with round p's sums as it does in the preset-challenge kernels (zk_fused.cuh).  The identities are
+// the Kind structs of zk_gate.cuh, the ones the preset-challenge engine runs.  The shape here:
 //   pass 0            evaluate only: the sums of round 0 over the caller's tables (nothing is written but the partials),
 //   pass p >= 1       fold, then evaluate: a lane reads elements j, j + q, j + 2q, j + 3q of each table (q = a quarter of the
 //                     table), folds the pairs (j, j + 2q) and (j + q, j + 3q) with r_{p-1} LOADED FROM DEVICE MEMORY, writes the two
@@ -21,72 +22,10 @@
 
 namespace zk {
 
-// An identity eq(x) [ inner(tables 1 .. kTabs - 1) ]: its table count, the evaluations of a round (degree + 1), the longest table of
-// the local stage (kTabs tables of kLocalMax elements fit the CU's LDS), its slot of zk_ctx::fs_lds_raised, the waves per SIMD its pass is
-// compiled for, and the bracket.  kFree: the identity has a term free(tables), LINEAR in the
-// tables, that eq does not multiply; a lane sums it apart from the products (k_lookup_pass, zk_lookup.hip, says why).
-struct GateKind {  // eq, q1, q2, a, b, c, in
-    static constexpr int kTabs = 7;
-    static constexpr int kEvals = 5;
-    static constexpr int kSlot = 0;
-    static constexpr unsigned kLocalMax = kGateLocalMax;
-    static constexpr int kWaves = 2;
-    static constexpr bool kFree = false;
-    __device__ static __forceinline__ Fr inner(const Fr&, const Fr (&v)[kTabs]) { return gate_inner(v[1], v[2], v[3], v[4], v[5], v[6]); }
-};
-struct WireKind {  // eq, v1x, vx0, vx1, h, num, den
-    static constexpr int kTabs = 7;
-    static constexpr int kEvals = 4;
-    static constexpr int kSlot = 1;
-    static constexpr unsigned kLocalMax = kGateLocalMax;
-    static constexpr int kWaves = 2;
-    static constexpr bool kFree = false;
-    __device__ static __forceinline__ Fr inner(const Fr& gamma, const Fr (&v)[kTabs]) { return wiring_inner(gamma, v[1], v[2], v[3], v[4], v[5], v[6]); }
-};
-struct Perm3Kind {  // eq, v1x, vx0, vx1, h, n_0, n_1, n_2, d_0, d_1, d_2
-    static constexpr int kTabs = kPerm3Tabs;
-    static constexpr int kEvals = kPerm3Evals;
-    static constexpr int kSlot = 3;
-    static constexpr unsigned kLocalMax = kPerm3LocalMax;
-    static constexpr int kWaves = 1;  // 22 table registers of 8 limbs and six 17-limb sums: the 264 .. 512 register bracket
-    static constexpr bool kFree = false;
-    __device__ static __forceinline__ Fr inner(const Fr& gamma, const Fr (&v)[kTabs]) { return perm3_inner(gamma, v); }
-};
-struct GatewKind {  // eq, qL, qR, qM, qO, qC, qH, a, b, c, in
-    static constexpr int kTabs = kGatewTabs;
-    static constexpr int kEvals = kGatewEvals;
-    static constexpr int kSlot = 4;
-    static constexpr unsigned kLocalMax = kGatewLocalMax;
-    static constexpr int kWaves = 1;  // 22 table registers of 8 limbs and eight 17-limb sums: the 264 .. 512 register bracket
-    static constexpr bool kFree = false;
-    __device__ static __forceinline__ Fr inner(const Fr&, const Fr (&v)[kTabs]) { return gatew_inner(v); }
-};
-struct LookupKind {  // E, df, dt, m, hf, ht
-    static constexpr int kTabs = kLookupTabs;
-    static constexpr int kEvals = kLookupEvals;
-    static constexpr int kSlot = 5;
-    static constexpr unsigned kLocalMax = kGateLocalMax;
-    static constexpr int kWaves = 2;
-    static constexpr bool kFree = true;  // hf - ht
-    __device__ static __forceinline__ Fr inner(const Fr& gamma, const Fr (&v)[kTabs]) { return lookup_inner(gamma, v[1], v[2], v[3], v[4], v[5]); }
-    __device__ static __forceinline__ Fr free(const Fr (&v)[kTabs]) { return fr_sub(v[4], v[5]); }
-};
-
-struct LookupSelKind {  // E, df, dt, m, hf, ht, qk
-    static constexpr int kTabs = kLookupSelTabs;
-    static constexpr int kEvals = kLookupEvals;
-    static constexpr int kSlot = 6;
-    static constexpr unsigned kLocalMax = kGateLocalMax;
-    static constexpr int kWaves = 1;  // 28 table registers of 8 limbs (the fold reads four elements per table) and four 17-limb sums: the 264 .. 512 register bracket
-    static constexpr bool kFree = true;  // hf - ht
-    __device__ static __forceinline__ Fr inner(const Fr& gamma, const Fr (&v)[kTabs]) { return lookupsel_inner(gamma, v[1], v[2], v[3], v[4], v[5], v[6]); }
-    __device__ static __forceinline__ Fr free(const Fr (&v)[kTabs]) { return fr_sub(v[4], v[5]); }
-};
-
 // ---------------------------------------------------------------------------------------
 // One round of an identity of K::kTabs tables over HBM.  FOLD: the tables at `in` have 4 * half elements and are folded with *d_chal
 // into `out` (2 * half elements each) first; otherwise they have 2 * half elements and nothing is stored.
-// partials: [t * nbw + 4 block + wave], 80-byte slots, as k_gate_pass.
+// partials: [t * nbw + 4 block + wave], 80-byte slots, as k_sc_pass.
 // ---------------------------------------------------------------------------------------
 template <class K, bool FOLD>
 __global__ void __launch_bounds__(kGateBlock) __attribute__((amdgpu_waves_per_eu(1, K::kWaves)))
@@ -118,35 +57,10 @@ k_fs_pass(FsIn<K::kTabs> in, FsOut<K::kTabs> out, size_t half, const void* __res
             }
         }
         if constexpr (K::kFree) g0 = fr_add(g0, K::free(v)), gd = fr_add(gd, K::free(d));
-#pragma unroll
-        for (int t = 0; t < K::kEvals; t++) {
-            fp_mac_wide(w[t], v[0], K::inner(gamma.r, v));
-            if (t + 1 < K::kEvals) {
-#pragma unroll
-                for (int k = 0; k < K::kTabs; k++) v[k] = fr_add(v[k], d[k]);
-            }
-        }
+        kind_sums_wide<K>(w, gamma.r, v, d);
     }
-    if constexpr (K::kFree) {
-#pragma unroll
-        for (int t = 0; t < K::kEvals; t++) {  // free at t = g0 + t gd
-            gate_wide_add_hi(w[t], g0);
-            g0 = fr_add(g0, gd);
-        }
-    }
-    const unsigned wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const size_t nbw = (size_t)gridDim.x * (kGateBlock / 64);
-#pragma unroll
-    for (int t = 0; t < K::kEvals; t++) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            u32 o[17];
-#pragma unroll
-            for (int i = 0; i < 17; i++) o[i] = __shfl_down(w[t][i], off, 64);
-            gate_wide_add(w[t], o);
-        }
-        if (lane == 0) gate_wide_store(partials, (size_t)t * nbw + (size_t)blockIdx.x * (kGateBlock / 64) + wave, w[t]);
-    }
+    if constexpr (K::kFree) kind_free_wide<K>(w, g0, gd);
+    gate_wave_store_wide(w, partials);
 }
 
 // The NE sums of ONE pass, then the transcript: lane 0 writes the evaluations to the results, absorbs them, draws the round's
@@ -184,7 +98,7 @@ __global__ void __launch_bounds__(kGateBlock) k_fs_local(FsIn<K::kTabs> in, unsi
     extern __shared__ uint4 flds[];
     uint4* red = flds + 2 * (size_t)K::kTabs * E;              // [wave][t] Fr
     uint4* cs = red + 2 * (size_t)(kGateBlock / 64) * K::kEvals;  // the round's challenge
-    const unsigned tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const unsigned tid = threadIdx.x;
     if (d_pending) {
         const Fr r = fr_load(d_pending, 0);
         for (unsigned i = tid; i < E; i += kGateBlock)
@@ -214,27 +128,9 @@ __global__ void __launch_bounds__(kGateBlock) k_fs_local(FsIn<K::kTabs> in, unsi
                 v[k] = fr_load(flds, (size_t)k * E + j);
                 d[k] = fr_sub(fr_load(flds, (size_t)k * E + j + h), v[k]);
             }
-#pragma unroll
-            for (int t = 0; t < K::kEvals; t++) {
-                acc[t] = fr_add(acc[t], fr_mul(v[0], K::inner(gamma.r, v)));
-                if constexpr (K::kFree) acc[t] = fr_add(acc[t], K::free(v));
-                if (t + 1 < K::kEvals) {
-#pragma unroll
-                    for (int k = 0; k < K::kTabs; k++) v[k] = fr_add(v[k], d[k]);
-                }
-            }
+            kind_sums_fr<K>(acc, gamma.r, v, d);
         }
-#pragma unroll
-        for (int t = 0; t < K::kEvals; t++) {
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {
-                Fr o;
-#pragma unroll
-                for (int i = 0; i < 8; i++) o.l[i] = __shfl_down(acc[t].l[i], off, 64);
-                acc[t] = fr_add(acc[t], o);
-            }
-            if (lane == 0) fr_store(red, (size_t)wave * K::kEvals + t, acc[t]);
-        }
+        gate_wave_store_fr(acc, red);
         __syncthreads();
         if (tid == 0) {
             Fr ev[K::kEvals];
@@ -270,9 +166,11 @@ __global__ void __launch_bounds__(kGateBlock) k_fs_local(FsIn<K::kTabs> in, unsi
 template <bool FOLD>
 __global__ void __launch_bounds__(kGateBlock) k_multi_fs_pass(MultiIn in, MultiOut out, int count, size_t half, const void* __restrict__ d_chal,
                                                              void* __restrict__ partials) {
-    u32 w0[17], w1[17], w2[17];
+    u32 w[3][17];
 #pragma unroll
-    for (int i = 0; i < 17; i++) w0[i] = 0, w1[i] = 0, w2[i] = 0;
+    for (int t = 0; t < 3; t++)
+#pragma unroll
+        for (int i = 0; i < 17; i++) w[t][i] = 0;
     Fr r = fp_zero<FrCfg>();
     if (FOLD) r = fr_load(d_chal, 0);
 #pragma unroll 1
@@ -294,8 +192,8 @@ __global__ void __launch_bounds__(kGateBlock) k_multi_fs_pass(MultiIn in, MultiO
                 elo = fr_load(e, i), ehi = fr_load(e, i + half), flo = fr_load(f, i), fhi = fr_load(f, i + half);
             }
             const Fr de = fr_sub(ehi, elo), df = fr_sub(fhi, flo);
-            fp_mac_wide(w0, elo, flo);
-            fp_mac_wide(w1, ehi, fhi);
+            fp_mac_wide(w[0], elo, flo);
+            fp_mac_wide(w[1], ehi, fhi);
             Fr a, b;  // e_hi + de, f_hi + df as integers < 2r   dsumcheck.rs:55-72
             u32 c = 0;
 #pragma unroll
@@ -303,29 +201,10 @@ __global__ void __launch_bounds__(kGateBlock) k_multi_fs_pass(MultiIn in, MultiO
             c = 0;
 #pragma unroll
             for (int l = 0; l < 8; l++) b.l[l] = addc(fhi.l[l], df.l[l], c);
-            fp_mac_wide(w2, a, b);
+            fp_mac_wide(w[2], a, b);
         }
     }
-    const unsigned wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const size_t nbw = (size_t)gridDim.x * (kGateBlock / 64), slot = (size_t)blockIdx.x * (kGateBlock / 64) + wave;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        u32 o[17];
-#pragma unroll
-        for (int i = 0; i < 17; i++) o[i] = __shfl_down(w0[i], off, 64);
-        gate_wide_add(w0, o);
-#pragma unroll
-        for (int i = 0; i < 17; i++) o[i] = __shfl_down(w1[i], off, 64);
-        gate_wide_add(w1, o);
-#pragma unroll
-        for (int i = 0; i < 17; i++) o[i] = __shfl_down(w2[i], off, 64);
-        gate_wide_add(w2, o);
-    }
-    if (lane == 0) {
-        gate_wide_store(partials, slot, w0);
-        gate_wide_store(partials, nbw + slot, w1);
-        gate_wide_store(partials, 2 * nbw + slot, w2);
-    }
+    gate_wave_store_wide(w, partials);
 }
 
 // Local stage: the 2 count tables of E elements in LDS (table (j, which) at (2 j + which) E), items (j, i) spread over the lanes as
@@ -335,7 +214,7 @@ __global__ void __launch_bounds__(kGateBlock) k_multi_fs_local(MultiIn in, int c
     extern __shared__ uint4 mflds[];
     uint4* red = mflds + 2 * (size_t)(2 * count) * E;       // [wave][t] Fr
     uint4* cs = red + 2 * (size_t)(kGateBlock / 64) * 3;     // the round's challenge
-    const unsigned tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const unsigned tid = threadIdx.x;
     const unsigned lg = 31 - __clz(E);
     Fr rp = fp_zero<FrCfg>();
     if (d_pending) rp = fr_load(d_pending, 0);
@@ -368,17 +247,7 @@ __global__ void __launch_bounds__(kGateBlock) k_multi_fs_local(MultiIn in, int c
             acc[1] = fr_add(acc[1], fr_mul(ehi, fhi));
             acc[2] = fr_add(acc[2], fr_mul(fr_add(ehi, de), fr_add(fhi, df)));
         }
-#pragma unroll
-        for (int t = 0; t < 3; t++) {
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {
-                Fr o;
-#pragma unroll
-                for (int i = 0; i < 8; i++) o.l[i] = __shfl_down(acc[t].l[i], off, 64);
-                acc[t] = fr_add(acc[t], o);
-            }
-            if (lane == 0) fr_store(red, (size_t)wave * 3 + t, acc[t]);
-        }
+        gate_wave_store_fr(acc, red);
         __syncthreads();
         if (tid == 0) {
             Fr ev[3];
@@ -445,12 +314,6 @@ static int fs_plan(zk_ctx* ctx, const char* who, const zk_transcript* t, size_t 
     return ZK_OK;
 }
 
-static int local_e(zk_ctx* ctx, long knob, const char* name, size_t& emax, unsigned local_max = kGateLocalMax) {
-    emax = (size_t)knob;
-    if (emax < 1 || emax > local_max || (emax & (emax - 1))) return fail(ctx, ZK_ERR_INVALID, "%s must be a power of two in [1, %u]", name, local_max);
-    return ZK_OK;
-}
-
 template <class K>
 static int run_fs(zk_ctx* ctx, const char* who, const FsIn<K::kTabs>& first, size_t len, size_t emax, size_t per_cu, const GateChal& gamma, zk_transcript* t,
                    uint64_t* h_out_evals, uint64_t* h_last, uint64_t* h_chal_out) {
@@ -508,7 +371,7 @@ int sumcheck_gate_fs(zk_ctx* ctx, const void* const* d_tabs, size_t len, zk_tran
     for (int k = 0; k < GateKind::kTabs; k++) first.t[k] = d_tabs[k], first.sh[k] = 0;
     GateChal none;
     std::memset(&none, 0, sizeof(none));
-    return run_fs<GateKind>(ctx, "zk_sumcheck_gate_fs", first, len, emax, tuning().gate_pass_wg > 0 ? (size_t)tuning().gate_pass_wg : 2, none, t, h_out_evals, h_last,
+    return run_fs<GateKind>(ctx, "zk_sumcheck_gate_fs", first, len, emax, tuning().gate_pass_wg > 0 ? (size_t)tuning().gate_pass_wg : GateKind::kPerCu, none, t, h_out_evals, h_last,
                              h_chal_out);
 }
 
@@ -522,7 +385,7 @@ int sumcheck_wiring_fs(zk_ctx* ctx, const void* d_eq, const void* d_tree, const 
     const FsIn<WireKind::kTabs> first = {{d_eq, tree + N * 32, tree, tree + 32, tree, d_num, d_den}, {0, 0, 1, 1, 0, 0, 0}};
     GateChal gamma;
     std::memcpy(&gamma.r, h_gamma, 32);
-    return run_fs<WireKind>(ctx, "zk_sumcheck_wiring_fs", first, N, emax, tuning().wiring_pass_wg > 0 ? (size_t)tuning().wiring_pass_wg : 2, gamma, t, h_out_evals,
+    return run_fs<WireKind>(ctx, "zk_sumcheck_wiring_fs", first, N, emax, tuning().wiring_pass_wg > 0 ? (size_t)tuning().wiring_pass_wg : WireKind::kPerCu, gamma, t, h_out_evals,
                              h_last, h_chal_out);
 }
 
@@ -536,8 +399,7 @@ int sumcheck_perm3_fs(zk_ctx* ctx, const void* d_eq, const void* d_tree, const v
                                     {0, 0, 1, 1, 0, 0, 0, 0, 0, 0, 0}};
     GateChal gamma;
     std::memcpy(&gamma.r, h_gamma, 32);
-    return run_fs<Perm3Kind>(ctx, "zk_sumcheck_perm3_fs", first, N, emax, 1, gamma, t, h_out_evals,
-                             h_last, h_chal_out);
+    return run_fs<Perm3Kind>(ctx, "zk_sumcheck_perm3_fs", first, N, emax, Perm3Kind::kPerCu, gamma, t, h_out_evals, h_last, h_chal_out);
 }
 
 int sumcheck_gate_wide_fs(zk_ctx* ctx, const void* const* d_tabs, size_t len, zk_transcript* t, uint64_t* h_out_evals, uint64_t* h_last, uint64_t* h_chal_out) {
@@ -548,7 +410,7 @@ int sumcheck_gate_wide_fs(zk_ctx* ctx, const void* const* d_tabs, size_t len, zk
     for (int k = 0; k < kGatewTabs; k++) first.t[k] = d_tabs[k], first.sh[k] = 0;
     GateChal none;
     std::memset(&none, 0, sizeof(none));
-    return run_fs<GatewKind>(ctx, "zk_sumcheck_gate_wide_fs", first, len, emax, 1, none, t, h_out_evals, h_last, h_chal_out);
+    return run_fs<GatewKind>(ctx, "zk_sumcheck_gate_wide_fs", first, len, emax, GatewKind::kPerCu, none, t, h_out_evals, h_last, h_chal_out);
 }
 
 int sumcheck_lookup_fs(zk_ctx* ctx, const void* const* d_tabs, size_t len, const uint64_t* h_gamma, zk_transcript* t, uint64_t* h_out_evals, uint64_t* h_last,
@@ -560,7 +422,7 @@ int sumcheck_lookup_fs(zk_ctx* ctx, const void* const* d_tabs, size_t len, const
     for (int k = 0; k < kLookupTabs; k++) first.t[k] = d_tabs[k], first.sh[k] = 0;
     GateChal gamma;
     std::memcpy(&gamma.r, h_gamma, 32);
-    return run_fs<LookupKind>(ctx, "zk_sumcheck_lookup_fs", first, len, emax, 2, gamma, t, h_out_evals, h_last, h_chal_out);
+    return run_fs<LookupKind>(ctx, "zk_sumcheck_lookup_fs", first, len, emax, LookupKind::kPerCu, gamma, t, h_out_evals, h_last, h_chal_out);
 }
 
 int sumcheck_lookup_sel_fs(zk_ctx* ctx, const void* const* d_tabs, size_t len, const uint64_t* h_gamma, zk_transcript* t, uint64_t* h_out_evals, uint64_t* h_last,
@@ -572,7 +434,7 @@ int sumcheck_lookup_sel_fs(zk_ctx* ctx, const void* const* d_tabs, size_t len, c
     for (int k = 0; k < kLookupSelTabs; k++) first.t[k] = d_tabs[k], first.sh[k] = 0;
     GateChal gamma;
     std::memcpy(&gamma.r, h_gamma, 32);
-    return run_fs<LookupSelKind>(ctx, "zk_sumcheck_lookup_sel_fs", first, len, emax, 1, gamma, t, h_out_evals, h_last, h_chal_out);
+    return run_fs<LookupSelKind>(ctx, "zk_sumcheck_lookup_sel_fs", first, len, emax, LookupSelKind::kPerCu, gamma, t, h_out_evals, h_last, h_chal_out);
 }
 
 int sumcheck_multi_fs(zk_ctx* ctx, size_t count, const void* const* d_e, const void* const* d_f, size_t len, zk_transcript* t, uint64_t* h_out_triples,

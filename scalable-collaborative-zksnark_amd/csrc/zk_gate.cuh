@@ -1,5 +1,7 @@
-// zk_gate.cuh -- what the fused sumchecks (zk_gate.hip: gate identity, zk_wiring.hip: wiring identity, zk_batchopen.hip, zk_perm3.hip, zk_lookup.hip, zk_fs.hip) share: launch geometry, the
-// argument blocks of their kernels and the 544-bit lazily reduced sums (one 80-byte slot per wave, evaluation and pass).
+// zk_gate.cuh -- what the fused sumchecks share (the preset-challenge engine zk_fused.cuh and its six identities zk_gate.hip, zk_wiring.hip,
+// zk_perm3.hip, zk_gatew.hip, zk_lookup.hip, zk_lookup3.hip; zk_batchopen.hip; their transcript-driven forms in zk_fs.hip): launch
+// geometry, the argument blocks of the kernels, the 544-bit lazily reduced sums (one 80-byte slot per wave, evaluation and pass), the
+// brackets of the identities with the Kind structs that describe them, and the blocks every pass and every local stage repeat.
 #pragma once
 #include "fp.cuh"
 #include "zk_ctx.hpp"
@@ -10,7 +12,7 @@ static constexpr int kGateBlock = 256;
 static constexpr unsigned kGateLocalMax = 512;  // 7 x 512 x 32 B = 112 KiB of the CU's 160 KiB
 static constexpr int kGateWideBytes = 80;       // 17 limbs + 3 words of padding (the slot of zk_fr.hip's Wide)
 static constexpr int kGateMaxPasses = 40;
-static constexpr int kGateMaxLog = 35;         // longest table: 2^35 elements (capacity of the 544-bit sums, see k_gate_pass)
+static constexpr int kGateMaxLog = 35;         // longest table: 2^35 elements (capacity of the 544-bit sums, see k_sc_pass in zk_fused.cuh)
 
 struct GateChal {
     Fr r;
@@ -23,7 +25,7 @@ struct GateReducePlan {
     unsigned off[kGateMaxPasses];   // first slot of pass p in the partials block
 };
 
-// The table set of a fused identity of NT tables (zk_perm3.hip, zk_fs.hip): table k, element i, is the Fr at t[k] + 32 (i << sh[k]) --
+// The table set of a fused identity of NT tables: table k, element i, is the Fr at t[k] + 32 (i << sh[k]) --
 // sh = 1 reads every other element of the product tree (its views v(x,0) and v(x,1)), sh = 0 an ordinary table.
 template <int NT>
 struct FsIn {
@@ -74,7 +76,7 @@ __device__ __forceinline__ void gate_wide_load(u32 (&v)[17], const void* base, s
     v[16] = p[4].x;
 }
 
-// the brackets of the two identities (zk_gate.hip / zk_wiring.hip and their transcript-driven forms in zk_fs.hip)
+// the brackets of the identities
 // [ q1 (a + b) + (q2 a) b - c + in ] of one point: three multiplications
 __device__ __forceinline__ Fr gate_inner(const Fr& q1, const Fr& q2, const Fr& a, const Fr& b, const Fr& c, const Fr& in) {
     const Fr s = fr_mul(q1, fr_add(a, b));
@@ -145,6 +147,173 @@ __device__ __forceinline__ void gate_wide_add_hi(u32 (&a)[17], const Fr& g) {
     a[16] += c;
 }
 
+// ---------------------------------------------------------------------------------------
+// An identity eq(x) [ inner(tables 1 .. kTabs - 1) ] as the engines see it (zk_fused.cuh: preset challenges, zk_fs.hip: challenges from
+// a transcript): its table count, the evaluations of a round (degree + 1), the longest table of the local stage (kTabs tables of
+// kLocalMax elements fit the CU's LDS), its slot of zk_ctx::preset_lds_raised / fs_lds_raised, the waves per SIMD its pass is compiled
+// for, the workgroups per CU its pass is launched with, and the bracket.  kViews: the first tables are shifted views of the product
+// tree (FsIn::sh); a Kind without views compiles no shift.  kLoadsFirst: the order of loads and folds in the preset-challenge pass
+// (k_sc_pass, zk_fused.cuh).  kFree: the identity has a term free(tables), LINEAR in the tables, that
+// eq does not multiply; a lane sums it apart from the products (kind_free_wide says why).
+// ---------------------------------------------------------------------------------------
+struct GateKind {  // eq, q1, q2, a, b, c, in
+    static constexpr int kTabs = 7;
+    static constexpr int kEvals = 5;
+    static constexpr int kSlot = 0;
+    static constexpr unsigned kLocalMax = kGateLocalMax;
+    static constexpr int kWaves = 2;
+    static constexpr int kPerCu = 2;
+    static constexpr bool kViews = false;
+    static constexpr bool kLoadsFirst = false;
+    static constexpr bool kFree = false;
+    __device__ static __forceinline__ Fr inner(const Fr&, const Fr (&v)[kTabs]) { return gate_inner(v[1], v[2], v[3], v[4], v[5], v[6]); }
+};
+struct WireKind {  // eq, v1x, vx0, vx1, h, num, den
+    static constexpr int kTabs = 7;
+    static constexpr int kEvals = 4;
+    static constexpr int kSlot = 1;
+    static constexpr unsigned kLocalMax = kGateLocalMax;
+    static constexpr int kWaves = 2;
+    static constexpr int kPerCu = 2;
+    static constexpr bool kViews = true;
+    static constexpr bool kLoadsFirst = true;
+    static constexpr bool kFree = false;
+    __device__ static __forceinline__ Fr inner(const Fr& gamma, const Fr (&v)[kTabs]) { return wiring_inner(gamma, v[1], v[2], v[3], v[4], v[5], v[6]); }
+};
+struct Perm3Kind {  // eq, v1x, vx0, vx1, h, n_0, n_1, n_2, d_0, d_1, d_2
+    static constexpr int kTabs = kPerm3Tabs;
+    static constexpr int kEvals = kPerm3Evals;
+    static constexpr int kSlot = 3;
+    static constexpr unsigned kLocalMax = kPerm3LocalMax;
+    static constexpr int kWaves = 1;  // 22 table registers of 8 limbs and six 17-limb sums: the 264 .. 512 register bracket
+    static constexpr int kPerCu = 1;  // one wave per SIMD: one workgroup of four waves fills a CU
+    static constexpr bool kViews = true;
+    static constexpr bool kLoadsFirst = false;
+    static constexpr bool kFree = false;
+    __device__ static __forceinline__ Fr inner(const Fr& gamma, const Fr (&v)[kTabs]) { return perm3_inner(gamma, v); }
+};
+struct GatewKind {  // eq, qL, qR, qM, qO, qC, qH, a, b, c, in
+    static constexpr int kTabs = kGatewTabs;
+    static constexpr int kEvals = kGatewEvals;
+    static constexpr int kSlot = 4;
+    static constexpr unsigned kLocalMax = kGatewLocalMax;
+    static constexpr int kWaves = 1;  // 22 table registers of 8 limbs and eight 17-limb sums: the 264 .. 512 register bracket
+    static constexpr int kPerCu = 1;
+    static constexpr bool kViews = false;
+    static constexpr bool kLoadsFirst = false;
+    static constexpr bool kFree = false;
+    __device__ static __forceinline__ Fr inner(const Fr&, const Fr (&v)[kTabs]) { return gatew_inner(v); }
+};
+struct LookupKind {  // E, df, dt, m, hf, ht
+    static constexpr int kTabs = kLookupTabs;
+    static constexpr int kEvals = kLookupEvals;
+    static constexpr int kSlot = 5;
+    static constexpr unsigned kLocalMax = kGateLocalMax;
+    static constexpr int kWaves = 2;
+    static constexpr int kPerCu = 2;
+    static constexpr bool kViews = false;
+    static constexpr bool kLoadsFirst = true;
+    static constexpr bool kFree = true;  // hf - ht
+    __device__ static __forceinline__ Fr inner(const Fr& gamma, const Fr (&v)[kTabs]) { return lookup_inner(gamma, v[1], v[2], v[3], v[4], v[5]); }
+    __device__ static __forceinline__ Fr free(const Fr (&v)[kTabs]) { return fr_sub(v[4], v[5]); }
+};
+struct LookupSelKind {  // E, df, dt, m, hf, ht, qk
+    static constexpr int kTabs = kLookupSelTabs;
+    static constexpr int kEvals = kLookupEvals;
+    static constexpr int kSlot = 6;
+    static constexpr unsigned kLocalMax = kGateLocalMax;
+    // seven (value, difference) pairs are 112 VGPRs (the transcript-driven fold reads four elements per table: 28 table registers of 8
+    // limbs), four 17-limb sums 68, the two sums of hf - ht 16: with the temporaries of a multiplication that is past the 256 registers
+    // of two waves per SIMD (the six-table pass sits at 249) -- the 264 .. 512 register bracket
+    static constexpr int kWaves = 1;
+    static constexpr int kPerCu = 1;
+    static constexpr bool kViews = false;
+    static constexpr bool kLoadsFirst = true;
+    static constexpr bool kFree = true;  // hf - ht
+    __device__ static __forceinline__ Fr inner(const Fr& gamma, const Fr (&v)[kTabs]) { return lookupsel_inner(gamma, v[1], v[2], v[3], v[4], v[5], v[6]); }
+    __device__ static __forceinline__ Fr free(const Fr (&v)[kTabs]) { return fr_sub(v[4], v[5]); }
+};
+
+// ---------------------------------------------------------------------------------------
+// The blocks every pass and every local stage repeat.
+// ---------------------------------------------------------------------------------------
+// One index pair of an HBM pass: v = the tables at lo, d = hi - lo.  The values at t = 1 .. kEvals - 1 come from v(t) = v(t-1) + d; per
+// t the reduced multiplications of the bracket and the product with eq, left as a 512-bit integer and added to the 17-limb sum w[t].
+// v is stepped in place.
+template <class K>
+__device__ __forceinline__ void kind_sums_wide(u32 (&w)[K::kEvals][17], const Fr& gamma, Fr (&v)[K::kTabs], const Fr (&d)[K::kTabs]) {
+#pragma unroll
+    for (int t = 0; t < K::kEvals; t++) {
+        fp_mac_wide(w[t], v[0], K::inner(gamma, v));
+        if (t + 1 < K::kEvals) {
+#pragma unroll
+            for (int k = 0; k < K::kTabs; k++) v[k] = fr_add(v[k], d[k]);
+        }
+    }
+}
+// The same of a local stage: every sum is a reduced one there, so the free term is added to each point's product as it is.
+template <class K>
+__device__ __forceinline__ void kind_sums_fr(Fr (&acc)[K::kEvals], const Fr& gamma, Fr (&v)[K::kTabs], const Fr (&d)[K::kTabs]) {
+#pragma unroll
+    for (int t = 0; t < K::kEvals; t++) {
+        Fr p = fr_mul(v[0], K::inner(gamma, v));
+        if constexpr (K::kFree) p = fr_add(K::free(v), p);  // off the chain of additions into acc
+        acc[t] = fr_add(acc[t], p);
+        if (t + 1 < K::kEvals) {
+#pragma unroll
+            for (int k = 0; k < K::kTabs; k++) v[k] = fr_add(v[k], d[k]);
+        }
+    }
+}
+// The free term of a pass (the lookups' hf - ht) is linear in the tables: its value at t is g0 + t gd with g0 = free(lo) and
+// gd = free(hi - lo).  A lane keeps the modular sums of g0 and gd over its index pairs (two Fr, canonical) and adds g0 + t gd to sum t
+// ONCE, after its loop, as an integer times 2^256 (gate_wide_add_hi): the sums hold raw products of Montgomery forms a R b R and are
+// divided by R = 2^256 once, so a Montgomery form g R has to enter as g R 2^256.
+// Capacity of the sums: a product is < r^2 < 0.83 * 2^510 and the reduce adds ALL N/2 <= 2^34 products of a pass into one 544-bit
+// integer, < 0.83 * 2^544; on top come one term < r 2^256 < 2^511 per LANE, at most 2^17 lanes of a grid: < 2^528.  Hence N <= 2^35
+// (kGateMaxLog) as for the identities without such a term.  (One such term per index PAIR would not fit: 2^34 (r^2 + r 2^256) > 2^544.)
+template <class K>
+__device__ __forceinline__ void kind_free_wide(u32 (&w)[K::kEvals][17], Fr g0, const Fr& gd) {
+#pragma unroll
+    for (int t = 0; t < K::kEvals; t++) {
+        gate_wide_add_hi(w[t], g0);
+        g0 = fr_add(g0, gd);
+    }
+}
+// The end of a pass: the NE 17-limb sums of a wave by shuffle, lane 0 stores them.  partials: [t * nbw + 4 block + wave], 80-byte slots.
+template <int NE>
+__device__ __forceinline__ void gate_wave_store_wide(u32 (&w)[NE][17], void* __restrict__ partials) {
+    const unsigned wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const size_t nbw = (size_t)gridDim.x * (kGateBlock / 64);
+#pragma unroll
+    for (int t = 0; t < NE; t++) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            u32 o[17];
+#pragma unroll
+            for (int i = 0; i < 17; i++) o[i] = __shfl_down(w[t][i], off, 64);
+            gate_wide_add(w[t], o);
+        }
+        if (lane == 0) gate_wide_store(partials, (size_t)t * nbw + (size_t)blockIdx.x * (kGateBlock / 64) + wave, w[t]);
+    }
+}
+// The end of a round of a local stage: the NE reduced sums of a wave by shuffle, lane 0 stores them to LDS.  slots: [wave * NE + t] Fr.
+template <int NE>
+__device__ __forceinline__ void gate_wave_store_fr(Fr (&acc)[NE], uint4* slots) {
+    const unsigned wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+#pragma unroll
+    for (int t = 0; t < NE; t++) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            Fr o;
+#pragma unroll
+            for (int i = 0; i < 8; i++) o.l[i] = __shfl_down(acc[t].l[i], off, 64);
+            acc[t] = fr_add(acc[t], o);
+        }
+        if (lane == 0) fr_store(slots, (size_t)wave * NE + t, acc[t]);
+    }
+}
+
 // One workgroup of kGateBlock lanes adds the nbw per-wave partials from slot `base` on and reduces W0 + W1 R + W2 R^2 (a sum of
 // integer products of Montgomery forms) to W0 R^-1 + W1 + W2 R mod r, canonical: the value is lane 0's (the other lanes get zero).
 // lds: (kGateBlock / 64) slots, free again after the call's barrier.
@@ -185,6 +354,13 @@ __device__ __forceinline__ Fr gate_reduce_value(const void* __restrict__ partial
 __device__ __forceinline__ void gate_reduce_block(const void* __restrict__ partials, size_t base, unsigned nbw, uint4* lds, void* __restrict__ evals, size_t out) {
     const Fr s = gate_reduce_value(partials, base, nbw, lds);
     if (threadIdx.x == 0) fr_store(evals, out, s);
+}
+
+// hand-over point to the local stage, from a *_local_e knob (1 = HBM passes down to the last element)
+static inline int local_e(zk_ctx* ctx, long knob, const char* name, size_t& emax, unsigned local_max = kGateLocalMax) {
+    emax = (size_t)knob;
+    if (emax < 1 || emax > local_max || (emax & (emax - 1))) return fail(ctx, ZK_ERR_INVALID, "%s must be a power of two in [1, %u]", name, local_max);
+    return ZK_OK;
 }
 
 }  // namespace zk

@@ -8,23 +8,17 @@
 // With hf = qk / df, ht = m / dt and E = lambda eq(tau, .), sum_x L(x) = 0 states sum_x qk(x) / df(x) = sum_y m(y) / dt(y) and the
 // definitions of the two helper columns.  With qk = 1 everywhere K19 computes what K16 (zk_lookup.hip) computes, bit for bit.
 //
-// Conventions and shape of zk_lookup.hip: Fr in Montgomery form, 32-byte AoS elements, round i binds the TOP index bit, inputs are
-// never written, all sums are exact modular sums; one HBM pass per round while the tables are long (k_lookupsel_pass), the four sums
-// of a pass as 544-bit integers reduced once per sum and call (k_lookupsel_reduce), then every remaining round in one workgroup on
-// tables held in LDS (k_lookupsel_local).
-//
-// Registers of k_lookupsel_pass: seven (value, difference) pairs are 112 VGPRs, four 17-limb sums 68, the two sums of hf - ht 16: with
-// the temporaries of a multiplication that is past the 256 registers of two waves per SIMD (the six-table kernel sits at 249), so the
-// kernel is compiled for one wave per SIMD (the 264 .. 512 register bracket, as k_perm3_pass) and launched with one workgroup per CU.
-#include "zk_gate.cuh"
-
-#include <algorithm>
-#include <cstring>
+// Conventions of zk_lookup.hip: Fr in Montgomery form, 32-byte AoS elements, round i binds the TOP index bit, inputs are never
+// written, all sums are exact modular sums.  K19 is the preset-challenge engine of zk_fused.cuh over LookupSelKind (zk_gate.cuh).  Per
+// index pair and t four multiplications (three reduced ones inside the bracket, the product with E left as an integer), with the seven
+// folds 7 + 4 x 4 = 23 per index pair.  qk is subtracted as a reduced value INSIDE the bracket, before the wide multiplication with E:
+// the only term that E does not multiply stays hf - ht, the Kind's free term as in zk_lookup.hip (kind_free_wide, zk_gate.cuh; with one
+// workgroup per CU a grid has fewer lanes than the six-table pass, so its capacity argument holds).  Seven tables of 512 elements are
+// 112 KiB of the CU's 160 KiB of LDS.  LookupSelKind says why the pass is compiled for one wave per SIMD.
+#include "zk_fused.cuh"
 
 namespace zk {
 
-using LookupSelIn = FsIn<kLookupSelTabs>;  // sh is 0 throughout: seven ordinary tables
-using LookupSelOut = FsOut<kLookupSelTabs>;
 struct Lookup3Cols {
     const void* w[3];
     const void* t[3];
@@ -123,213 +117,14 @@ int lookup3_terms(zk_ctx* ctx, const void* const* d_w, const void* const* d_t, s
 }
 
 // ---------------------------------------------------------------------------------------
-// K19.  One round over tables of length 2 * half living in HBM.  partials: [t * nbw + 4 block + wave], 80-byte slots.
-// The values at t = 1 .. 3 come from v(t) = v(t-1) + (hi - lo): per t four multiplications (three reduced ones inside the bracket,
-// the product with E left as an integer for the lazily reduced sum), with the seven folds 7 + 4 x 4 = 23 per index pair.  qk is
-// subtracted as a reduced value INSIDE the bracket, before the wide multiplication with E: the only term that E does not multiply
-// stays hf - ht, as in k_lookup_pass.  It is linear in the tables: its value at t is g0 + t gd with g0 = hf_lo - ht_lo and
-// gd = (hf_hi - hf_lo) - (ht_hi - ht_lo).  A lane keeps the modular sums of g0 and gd over its index pairs (two Fr, canonical) and
-// adds g0 + t gd to sum t ONCE, after its loop, as an integer times 2^256 (gate_wide_add_hi).
-// Capacity of the sums, unchanged from k_lookup_pass: a product is < r^2 < 0.83 * 2^510 and k_lookupsel_reduce adds ALL N/2 <= 2^34
-// products of a pass into one 544-bit integer, < 0.83 * 2^544; on top come one term < r 2^256 < 2^511 per LANE, at most 2^17 lanes of
-// a grid (one workgroup per CU here: fewer than k_lookup_pass has): < 2^528.  Hence N <= 2^35 (kGateMaxLog).
-// ---------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(kGateBlock) __attribute__((amdgpu_waves_per_eu(1, 1)))
-k_lookupsel_pass(LookupSelIn in, LookupSelOut out, size_t half, GateChal ch, GateChal gamma, void* __restrict__ partials) {
-    u32 w[kLookupEvals][17];
-#pragma unroll
-    for (int t = 0; t < kLookupEvals; t++)
-#pragma unroll
-        for (int i = 0; i < 17; i++) w[t][i] = 0;
-    Fr g0 = fp_zero<FrCfg>(), gd = fp_zero<FrCfg>();
-    for (size_t j = (size_t)blockIdx.x * kGateBlock + threadIdx.x; j < half; j += (size_t)gridDim.x * kGateBlock) {
-        Fr v[kLookupSelTabs], d[kLookupSelTabs];
-#pragma unroll
-        for (int k = 0; k < kLookupSelTabs; k++) v[k] = fr_load(in.t[k], j), d[k] = fr_load(in.t[k], j + half);
-#pragma unroll
-        for (int k = 0; k < kLookupSelTabs; k++) {
-            d[k] = fr_sub(d[k], v[k]);
-            fr_store(out.t[k], j, fr_add(v[k], fr_mul(ch.r, d[k])));  // lo + r (hi - lo)   dsumcheck.rs:14-19
-        }
-        g0 = fr_add(g0, fr_sub(v[4], v[5]));
-        gd = fr_add(gd, fr_sub(d[4], d[5]));
-#pragma unroll
-        for (int t = 0; t < kLookupEvals; t++) {
-            fp_mac_wide(w[t], v[0], lookupsel_inner(gamma.r, v[1], v[2], v[3], v[4], v[5], v[6]));
-            if (t + 1 < kLookupEvals) {
-#pragma unroll
-                for (int k = 0; k < kLookupSelTabs; k++) v[k] = fr_add(v[k], d[k]);
-            }
-        }
-    }
-#pragma unroll
-    for (int t = 0; t < kLookupEvals; t++) {  // hf - ht at t = g0 + t gd
-        gate_wide_add_hi(w[t], g0);
-        g0 = fr_add(g0, gd);
-    }
-    const unsigned wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const size_t nbw = (size_t)gridDim.x * (kGateBlock / 64);
-#pragma unroll
-    for (int t = 0; t < kLookupEvals; t++) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            u32 o[17];
-#pragma unroll
-            for (int i = 0; i < 17; i++) o[i] = __shfl_down(w[t][i], off, 64);
-            gate_wide_add(w[t], o);
-        }
-        if (lane == 0) gate_wide_store(partials, (size_t)t * nbw + (size_t)blockIdx.x * (kGateBlock / 64) + wave, w[t]);
-    }
-}
-
-// The sums of all passes of a call in one launch: block (t, p) = evaluation t of pass p (gate_reduce_block, zk_gate.cuh).
-__global__ void __launch_bounds__(kGateBlock) k_lookupsel_reduce(const void* __restrict__ partials, GateReducePlan plan, void* __restrict__ evals) {
-    __shared__ uint4 lds[(kGateBlock / 64) * (kGateWideBytes / 16)];
-    const unsigned t = blockIdx.x, p = blockIdx.y, nbw = plan.nbw[p];
-    gate_reduce_block(partials, (size_t)plan.off[p] + (size_t)t * nbw, nbw, lds, evals, (size_t)p * kLookupEvals + t);
-}
-
-// ---------------------------------------------------------------------------------------
-// Local stage: all remaining rounds of tables of E <= 512 elements in one workgroup, as k_lookup_local: the seven tables sit in
-// LDS (7 x 512 x 32 B = 112 KiB of the CU's 160 KiB) and are folded in place (a lane reads elements j and j + h of each and writes j:
-// no other lane touches either before the round's barrier).  Sums of a round: wave shuffle, one LDS slot per wave (two sets, by
-// round parity), four lanes finish them.  Every sum is a reduced one here, so hf - ht is added to each point's product as it is.
-// ---------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(kGateBlock) k_lookupsel_local(LookupSelIn in, unsigned E, int rounds, GateTail chal, GateChal gamma, void* __restrict__ evals,
-                                                               void* __restrict__ last) {
-    extern __shared__ uint4 slds[];
-    uint4* red = slds + 2 * (size_t)kLookupSelTabs * E;  // [parity][wave][t] Fr
-    const unsigned tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    for (unsigned i = tid; i < E; i += kGateBlock)
-#pragma unroll
-        for (int k = 0; k < kLookupSelTabs; k++) fr_store(slds, (size_t)k * E + i, fr_load(in.t[k], i));
-    __syncthreads();
-    unsigned L = E;
-    for (int rd = 0; rd < rounds; rd++) {
-        const unsigned h = L >> 1;
-        const Fr r = fr_load(chal.c, rd);
-        Fr acc[kLookupEvals];
-#pragma unroll
-        for (int t = 0; t < kLookupEvals; t++) acc[t] = fp_zero<FrCfg>();
-        for (unsigned j = tid; j < h; j += kGateBlock) {
-            Fr v[kLookupSelTabs], d[kLookupSelTabs];
-#pragma unroll
-            for (int k = 0; k < kLookupSelTabs; k++) {
-                v[k] = fr_load(slds, (size_t)k * E + j);
-                d[k] = fr_sub(fr_load(slds, (size_t)k * E + j + h), v[k]);
-                fr_store(slds, (size_t)k * E + j, fr_add(v[k], fr_mul(r, d[k])));
-            }
-#pragma unroll
-            for (int t = 0; t < kLookupEvals; t++) {
-                const Fr p = fr_mul(v[0], lookupsel_inner(gamma.r, v[1], v[2], v[3], v[4], v[5], v[6]));
-                acc[t] = fr_add(acc[t], fr_add(fr_sub(v[4], v[5]), p));
-                if (t + 1 < kLookupEvals) {
-#pragma unroll
-                    for (int k = 0; k < kLookupSelTabs; k++) v[k] = fr_add(v[k], d[k]);
-                }
-            }
-        }
-        uint4* rs = red + 2 * (size_t)(rd & 1) * (kGateBlock / 64) * kLookupEvals;
-#pragma unroll
-        for (int t = 0; t < kLookupEvals; t++) {
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {
-                Fr o;
-#pragma unroll
-                for (int i = 0; i < 8; i++) o.l[i] = __shfl_down(acc[t].l[i], off, 64);
-                acc[t] = fr_add(acc[t], o);
-            }
-            if (lane == 0) fr_store(rs, (size_t)wave * kLookupEvals + t, acc[t]);
-        }
-        __syncthreads();
-        if (tid < kLookupEvals) {
-            Fr s = fr_load(rs, tid);
-            for (int g = 1; g < kGateBlock / 64; g++) s = fr_add(s, fr_load(rs, (size_t)g * kLookupEvals + tid));
-            fr_store(evals, (size_t)rd * kLookupEvals + tid, s);
-        }
-        L = h;
-    }
-    if (tid < kLookupSelTabs) fr_store(last, tid, fr_load(slds, (size_t)tid * E));
-}
-
-// ---------------------------------------------------------------------------------------
 // host driver
 // ---------------------------------------------------------------------------------------
 int sumcheck_lookup_sel(zk_ctx* ctx, const void* const* d_tabs, size_t len, const uint64_t* h_gamma, const uint64_t* h_chal, uint64_t* h_out_evals, uint64_t* h_last) {
-    if (len < 2 || (len & (len - 1))) return fail(ctx, ZK_ERR_INVALID, "zk_sumcheck_lookup_sel: len = %zu is not a power of two >= 2", len);
-    size_t rounds = 0;
-    while (((size_t)1 << rounds) < len) rounds++;
-    if (rounds > (size_t)kGateMaxLog) return fail(ctx, ZK_ERR_INVALID, "zk_sumcheck_lookup_sel: tables longer than 2^%d elements", kGateMaxLog);
-    // hand-over point to the local stage (knob lookupsel_local_e: 1 = HBM passes down to the last element)
-    size_t emax = (size_t)tuning().lookupsel_local_e;
-    if (emax < 1 || emax > kGateLocalMax || (emax & (emax - 1))) return fail(ctx, ZK_ERR_INVALID, "lookupsel_local_e must be a power of two in [1, %u]", kGateLocalMax);
-    ZK_HIP(ctx, hipSetDevice(ctx->device));
-    // plan: passes while the tables are longer than emax, one workgroup per CU (one wave per SIMD)
-    size_t npass = 0, part_slots = 0;
-    GateReducePlan rp;
-    std::memset(&rp, 0, sizeof(rp));
-    size_t blocks_of[kGateMaxPasses];
-    for (size_t m = len; m > emax; m >>= 1) {
-        if (npass == (size_t)kGateMaxPasses) return fail(ctx, ZK_ERR_INVALID, "zk_sumcheck_lookup_sel: table too long");
-        const size_t half = m >> 1;
-        const size_t blocks = std::min<size_t>((half + kGateBlock - 1) / kGateBlock, (size_t)ctx->cu_count);
-        blocks_of[npass] = blocks;
-        rp.nbw[npass] = (unsigned)(blocks * (kGateBlock / 64));
-        rp.off[npass] = (unsigned)part_slots;
-        part_slots += (size_t)kLookupEvals * rp.nbw[npass];
-        npass++;
-    }
-    const size_t fr = 32;
-    const size_t res_bytes = (rounds * kLookupEvals + kLookupSelTabs) * fr;
-    char* res = (char*)pinned(ctx, res_bytes);  // the kernels write the results straight into pinned host memory
-    if (!res) return ZK_ERR_OOM;
-    char* buf[2] = {nullptr, nullptr};
-    char* part = nullptr;
-    if (npass) {
-        // the arenas of the gate sumcheck: ping-pong tables (seven of len/2 and seven of len/4 elements) and the 544-bit partials
-        if (!(buf[0] = (char*)scratch(ctx, 0, kLookupSelTabs * (len / 2) * fr))) return ZK_ERR_OOM;
-        if (npass > 1 && !(buf[1] = (char*)scratch(ctx, 1, kLookupSelTabs * (len / 4) * fr))) return ZK_ERR_OOM;
-        if (!(part = (char*)scratch(ctx, 4, part_slots * kGateWideBytes))) return ZK_ERR_OOM;
-    }
+    FsIn<kLookupSelTabs> first;
+    for (int k = 0; k < kLookupSelTabs; k++) first.t[k] = d_tabs[k], first.sh[k] = 0;
     GateChal gamma;
     std::memcpy(&gamma.r, h_gamma, 32);
-    LookupSelIn cur;
-    for (int k = 0; k < kLookupSelTabs; k++) cur.t[k] = d_tabs[k], cur.sh[k] = 0;
-    size_t m = len;
-    for (size_t p = 0; p < npass; p++) {
-        const size_t half = m >> 1;
-        LookupSelOut o;
-        for (int k = 0; k < kLookupSelTabs; k++) o.t[k] = buf[p & 1] + (size_t)k * ((p & 1) ? len / 4 : len / 2) * fr;
-        GateChal ch;
-        std::memcpy(&ch.r, h_chal + 4 * p, 32);
-        hipLaunchKernelGGL(k_lookupsel_pass, dim3((unsigned)blocks_of[p]), dim3(kGateBlock), 0, ctx->stream, cur, o, half, ch, gamma,
-                           (void*)(part + (size_t)rp.off[p] * kGateWideBytes));
-        ZK_HIP(ctx, hipGetLastError());
-        for (int k = 0; k < kLookupSelTabs; k++) cur.t[k] = o.t[k];
-        m = half;
-    }
-    if (npass) {
-        hipLaunchKernelGGL(k_lookupsel_reduce, dim3(kLookupEvals, (unsigned)npass), dim3(kGateBlock), 0, ctx->stream, (const void*)part, rp, (void*)res);
-        ZK_HIP(ctx, hipGetLastError());
-    }
-    {
-        const int rl = (int)(rounds - npass);
-        GateTail tl;
-        std::memset(&tl, 0, sizeof(tl));
-        std::memcpy(tl.c, h_chal + 4 * npass, (size_t)rl * 32);
-        const size_t lds = (2 * (size_t)kLookupSelTabs * m + 2 * 2 * (kGateBlock / 64) * kLookupEvals) * sizeof(uint4);
-        if (lds > 64 * 1024 && !ctx->lookupsel_lds_raised) {  // once per ctx (= per device)
-            ZK_HIP(ctx, hipFuncSetAttribute((const void*)k_lookupsel_local, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            ctx->lookupsel_lds_raised = true;
-        }
-        hipLaunchKernelGGL(k_lookupsel_local, dim3(1), dim3(kGateBlock), lds, ctx->stream, cur, (unsigned)m, rl, tl, gamma,
-                           (void*)(res + npass * kLookupEvals * fr), (void*)(res + rounds * kLookupEvals * fr));
-        ZK_HIP(ctx, hipGetLastError());
-    }
-    ZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    std::memcpy(h_out_evals, res, rounds * kLookupEvals * fr);
-    std::memcpy(h_last, res + rounds * kLookupEvals * fr, kLookupSelTabs * fr);
-    return ZK_OK;
+    return run_preset<LookupSelKind>(ctx, "zk_sumcheck_lookup_sel", "len = ", first, len, tuning().lookupsel_local_e, "lookupsel_local_e", LookupSelKind::kPerCu, gamma, h_chal, h_out_evals, h_last);
 }
 
 }  // namespace zk
