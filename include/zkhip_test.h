@@ -31,6 +31,27 @@ int zk_dbg_g1_op(zk_ctx *ctx, int mode, const void *d_p96, const void *d_q96, vo
  * mode 0: p+q  1: (p+q)+p  2: (p+q)+(p+q) (full-addition doubling path)  3: p-q  4: 2(p+q) (doubling)  5: (p+q)-(p+q) */
 int zk_dbg_g2_op(zk_ctx *ctx, int mode, const void *d_p192, const void *d_q192, void *h_out, size_t n);
 
+/* The Fq layer of the pairing (csrc/fq30.cuh: 13 limbs of 30 bits, lazily reduced) at chosen representatives.  d_x, d_y: n integers
+ * below q, 48 bytes little-endian, re-limbed as they are (no Montgomery conversion); d_kx, d_ky: n u32 <= 15.  Lane i works on
+ * a = x + kx q and b = y + ky q (built by additions of q, so every representative below 16q).  d_out: 13 u32 limbs of the raw result
+ * per element at a 64-byte stride; d_flags: n u32, bit 0 = limbs 0..11 of the result are below 2^30.  All pointers are device memory.
+ * mode 0..7: csub_q, csub_2q, csub_4q, csub_8q, red4, red8, red16, canon8 (a only: d_y, d_ky may be null)
+ *      8..12: sub2, sub4, sub6, sub8, sub12 (a + K q - b)   13: add   14: add2x (a + 2b)
+ *      15: mul   16: sqr (a only)   17: mul2add (a b + b a)   18: inv (a only; 0 -> 0) */
+int zk_dbg_fq30_op(zk_ctx *ctx, int mode, const void *d_x, const void *d_kx, const void *d_y, const void *d_ky, void *d_out, void *d_flags,
+                   size_t n);
+
+/* The Fq2 / Fq6 / Fq12 tower of the pairing (csrc/fq12.cuh, csrc/zk_pairing.hip) one operation at a time.  d_a, d_b: n x 576 bytes in
+ * ark's layout (what zk_pairing returns); d_lift: n u32, bits 0..11 add q to those components of a after the conversion to the
+ * internal form, bits 12..23 to those of b (the residue stays, the representative becomes < 2q: the largest the tower's bound rule
+ * allows).  d_out: n x 576 bytes, ark's layout.  d_flags: n u32 taken on the value the function returned, before it is converted
+ * back: bit 0 = limbs 0..11 of every component below 2^30, bit 1 = every component below 2q.  All pointers are device memory.
+ * mode 0: mul  1: sqr  2: cyc_sqr  3: inv  4: conj  5..7: frob1..3  8: mul_by_014 (the line's c0, c1, c4 = b's c0.c0, c0.c1, c1.c1)
+ *      9: exp_by_x  10: final_exp  11: f6_mul  12: f6_inv (on the c0 halves; the result's c1 is zero)
+ *      13: f2_mul  14: f2_sqr  15: f2_inv (on c0.c0; the other components of the result are zero)
+ * Unary modes do not read d_b (may be null). */
+int zk_dbg_fq12_op(zk_ctx *ctx, int mode, const void *d_a, const void *d_b, const void *d_lift, void *d_out, void *d_flags, size_t n);
+
 #ifdef __cplusplus
 }
 #endif

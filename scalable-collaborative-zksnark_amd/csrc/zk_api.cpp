@@ -776,5 +776,14 @@ int zk_dbg_g2_op(zk_ctx* ctx, int mode, const void* p, const void* q, void* h_ou
     NEED(ctx, n == 0 || (p && q && h_out));
     return dbg_g2_op(ctx, mode, p, q, h_out, n);
 }
+int zk_dbg_fq30_op(zk_ctx* ctx, int mode, const void* d_x, const void* d_kx, const void* d_y, const void* d_ky, void* d_out, void* d_flags,
+                   size_t n) {
+    if (!ctx) return ZK_ERR_INVALID;  // (which pointers a mode needs is decided by dbg_fq30_op)
+    return dbg_fq30_op(ctx, mode, d_x, d_kx, d_y, d_ky, d_out, d_flags, n);
+}
+int zk_dbg_fq12_op(zk_ctx* ctx, int mode, const void* d_a, const void* d_b, const void* d_lift, void* d_out, void* d_flags, size_t n) {
+    if (!ctx) return ZK_ERR_INVALID;
+    return dbg_fq12_op(ctx, mode, d_a, d_b, d_lift, d_out, d_flags, n);
+}
 
 }  // extern "C"

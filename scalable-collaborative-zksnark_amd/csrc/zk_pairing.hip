@@ -436,3 +436,155 @@ int pcs_verify_batch(zk_ctx* ctx, const zk_pcs_vk* vk, size_t nvars, size_t coun
 }
 
 }  // namespace zk
+
+// ---- test hooks (include/zkhip_test.h): the field tower one operation at a time -----------------------------------------------------
+// They add kernels only: no function above changes.  One lane per element, kPairBlk lanes per workgroup.
+namespace zk {
+
+// x + k q by k carry-normalised additions of the limbs of q (k <= 15): every representative below 16q, also those >= 2^384
+__device__ __forceinline__ Fq30 dbg_plus_kq(Fq30 x, u32 k) {
+    Fq30 q;
+#pragma unroll
+    for (int i = 0; i < 13; i++) q.l[i] = Q30::Q(i);
+    k = k > 15u ? 15u : k;
+    for (u32 j = 0; j < k; j++) x = f30_add(x, q);
+    return x;
+}
+__device__ __forceinline__ bool dbg_normalised(const Fq30& v) {  // limbs 0..11 below 2^30
+    u32 o = 0;
+#pragma unroll
+    for (int i = 0; i < 12; i++) o |= v.l[i];
+    return (o >> 30) == 0;
+}
+__device__ __forceinline__ bool dbg_below_2q(const Fq30& v) {  // the borrow chain of f30_csub_2q (wide: no limb can alias)
+    long long bw = 0;
+#pragma unroll
+    for (int i = 0; i < 13; i++) bw = ((long long)v.l[i] - (long long)Q30::Q2(i) - bw) < 0 ? 1 : 0;
+    return bw != 0;
+}
+
+// x, y: n x 48-byte integers < q (re-limbed, not converted); kx, ky: n u32 <= 15; a = x + kx q, b = y + ky q.
+// out: 13 raw limbs per element at a 64-byte stride; flags: bit 0 = the result's limbs 0..11 are below 2^30.  Unary modes do not read y / ky.
+enum {
+    kF30CsubQ = 0, kF30Csub2Q, kF30Csub4Q, kF30Csub8Q, kF30Red4, kF30Red8, kF30Red16, kF30Canon8,
+    kF30Sub2, kF30Sub4, kF30Sub6, kF30Sub8, kF30Sub12, kF30Add, kF30Add2x, kF30Mul, kF30Sqr, kF30Mul2add, kF30Inv, kF30Modes
+};
+static __host__ __device__ bool dbg_fq30_binary(int mode) { return mode >= kF30Sub2 && mode <= kF30Mul2add && mode != kF30Sqr; }
+
+__global__ void __launch_bounds__(kPairBlk) k_dbg_fq30(size_t n, int mode, const void* __restrict__ x, const u32* __restrict__ kx,
+                                                       const void* __restrict__ y, const u32* __restrict__ ky, u32* __restrict__ out,
+                                                       u32* __restrict__ flags) {
+    const size_t i = (size_t)blockIdx.x * kPairBlk + threadIdx.x;
+    if (i >= n) return;
+    const Fq30 a = dbg_plus_kq(f30_load(x, i * 48), kx[i]);
+    Fq30 b = f30_zero();
+    if (dbg_fq30_binary(mode)) b = dbg_plus_kq(f30_load(y, i * 48), ky[i]);
+    Fq30 r = f30_zero();
+    switch (mode) {
+        case kF30CsubQ: r = f30_csub_q(a); break;
+        case kF30Csub2Q: r = f30_csub_2q(a); break;
+        case kF30Csub4Q: r = f30_csub_4q(a); break;
+        case kF30Csub8Q: r = f30_csub_8q(a); break;
+        case kF30Red4: r = f30_red4(a); break;
+        case kF30Red8: r = f30_red8(a); break;
+        case kF30Red16: r = f30_red16(a); break;
+        case kF30Canon8: r = f30_canon8(a); break;
+        case kF30Sub2: r = f30_sub2(a, b); break;
+        case kF30Sub4: r = f30_sub4(a, b); break;
+        case kF30Sub6: r = f30_sub6(a, b); break;
+        case kF30Sub8: r = f30_sub8(a, b); break;
+        case kF30Sub12: r = f30_sub12(a, b); break;
+        case kF30Add: r = f30_add(a, b); break;
+        case kF30Add2x: r = f30_add2x(a, b); break;
+        case kF30Mul: r = f30_mul(a, b); break;
+        case kF30Sqr: r = f30_sqr(a); break;
+        case kF30Mul2add: r = f30_mul2add(a, b, b, a); break;
+        case kF30Inv: r = f30_inv(a); break;
+        default: break;
+    }
+#pragma unroll
+    for (int k = 0; k < 16; k++) out[i * 16 + k] = k < 13 ? r.l[k] : 0u;
+    flags[i] = dbg_normalised(r) ? 1u : 0u;
+}
+
+// a, b: n x 576 bytes, ark's layout (reference Montgomery form, canonical); lift[i]: bits 0..11 add q to those components of a after
+// the conversion, bits 12..23 to those of b (same residue, representative < 2q: still inside the bound rule of fq12.cuh).
+// out: ark's layout.  flags, taken on the value the function returned, before the conversion back: bit 0 = limbs 0..11 of every
+// component below 2^30, bit 1 = every component below 2q.
+enum {
+    kF12Mul = 0, kF12Sqr, kF12CycSqr, kF12Inv, kF12Conj, kF12Frob1, kF12Frob2, kF12Frob3, kF12MulBy014, kF12ExpByX, kF12FinalExp,
+    kF6Mul, kF6Inv, kF2Mul, kF2Sqr, kF2Inv, kF12Modes
+};
+static __host__ __device__ bool dbg_fq12_binary(int mode) { return mode == kF12Mul || mode == kF12MulBy014 || mode == kF6Mul || mode == kF2Mul; }
+
+__device__ __forceinline__ Fq12x dbg_f12_in(const void* base, size_t idx, u32 lift) {
+    Fq12x a;
+#pragma unroll
+    for (int k = 0; k < 12; k++) f12_at(a, k) = dbg_plus_kq(f30_from_ref(f30_load(base, idx * 576 + 48 * k)), (lift >> k) & 1u);
+    return a;
+}
+__global__ void __launch_bounds__(kPairBlk) k_dbg_fq12(size_t n, int mode, const void* __restrict__ pa, const void* __restrict__ pb,
+                                                       const u32* __restrict__ lift, void* __restrict__ out, u32* __restrict__ flags) {
+    const size_t i = (size_t)blockIdx.x * kPairBlk + threadIdx.x;
+    if (i >= n) return;
+    const u32 lf = lift[i];
+    const Fq12x a = dbg_f12_in(pa, i, lf & 0xfffu);
+    Fq12x b = Fq12x{f6_zero(), f6_zero()};
+    if (dbg_fq12_binary(mode)) b = dbg_f12_in(pb, i, (lf >> 12) & 0xfffu);
+    Fq12x r = Fq12x{f6_zero(), f6_zero()};  // Fq6 results in c0, Fq2 results in c0.c0
+    switch (mode) {
+        case kF12Mul: r = f12_mul(a, b); break;
+        case kF12Sqr: r = f12_sqr(a); break;
+        case kF12CycSqr: r = f12_cyc_sqr(a); break;
+        case kF12Inv: r = f12_inv(a); break;
+        case kF12Conj: r = f12_conj(a); break;
+        case kF12Frob1: r = f12_frob<1>(a); break;
+        case kF12Frob2: r = f12_frob<2>(a); break;
+        case kF12Frob3: r = f12_frob<3>(a); break;
+        case kF12MulBy014: r = f12_mul_by_014(a, b.c0.c0, b.c0.c1, b.c1.c1); break;
+        case kF12ExpByX: r = f12_exp_by_x(a); break;
+        case kF12FinalExp: r = final_exp(a); break;
+        case kF6Mul: r.c0 = f6_mul(a.c0, b.c0); break;
+        case kF6Inv: r.c0 = f6_inv(a.c0); break;
+        case kF2Mul: r.c0.c0 = f2_mulr(a.c0.c0, b.c0.c0); break;
+        case kF2Sqr: r.c0.c0 = f2_sqrr(a.c0.c0); break;
+        case kF2Inv: r.c0.c0 = f2_inv(a.c0.c0); break;
+        default: break;
+    }
+    bool norm = true, lt2q = true;
+#pragma unroll
+    for (int k = 0; k < 12; k++) {
+        const Fq30& c = f12_at(r, k);
+        norm = norm && dbg_normalised(c);
+        lt2q = lt2q && dbg_below_2q(c);
+    }
+    flags[i] = (norm ? 1u : 0u) | (lt2q ? 2u : 0u);
+#pragma unroll
+    for (int k = 0; k < 12; k++) f30_store(out, i * 576 + 48 * k, f30_to_ref(f12_at(r, k)));
+}
+
+int dbg_fq30_op(zk_ctx* ctx, int mode, const void* d_x, const void* d_kx, const void* d_y, const void* d_ky, void* d_out, void* d_flags,
+                size_t n) {
+    if (mode < 0 || mode >= kF30Modes) return fail(ctx, ZK_ERR_INVALID, "zk_dbg_fq30_op: unknown mode %d", mode);
+    if (n == 0) return ZK_OK;
+    if (!d_x || !d_kx || !d_out || !d_flags || (dbg_fq30_binary(mode) && (!d_y || !d_ky))) return fail(ctx, ZK_ERR_INVALID, "null argument");
+    ZK_HIP(ctx, hipSetDevice(ctx->device));
+    hipLaunchKernelGGL(k_dbg_fq30, dim3((unsigned)((n + kPairBlk - 1) / kPairBlk)), dim3(kPairBlk), 0, ctx->stream, n, mode, d_x,
+                       (const u32*)d_kx, d_y, (const u32*)d_ky, (u32*)d_out, (u32*)d_flags);
+    ZK_HIP(ctx, hipGetLastError());
+    ZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return ZK_OK;
+}
+int dbg_fq12_op(zk_ctx* ctx, int mode, const void* d_a, const void* d_b, const void* d_lift, void* d_out, void* d_flags, size_t n) {
+    if (mode < 0 || mode >= kF12Modes) return fail(ctx, ZK_ERR_INVALID, "zk_dbg_fq12_op: unknown mode %d", mode);
+    if (n == 0) return ZK_OK;
+    if (!d_a || !d_lift || !d_out || !d_flags || (dbg_fq12_binary(mode) && !d_b)) return fail(ctx, ZK_ERR_INVALID, "null argument");
+    ZK_HIP(ctx, hipSetDevice(ctx->device));
+    hipLaunchKernelGGL(k_dbg_fq12, dim3((unsigned)((n + kPairBlk - 1) / kPairBlk)), dim3(kPairBlk), 0, ctx->stream, n, mode, d_a, d_b,
+                       (const u32*)d_lift, d_out, (u32*)d_flags);
+    ZK_HIP(ctx, hipGetLastError());
+    ZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return ZK_OK;
+}
+
+}  // namespace zk

@@ -1107,3 +1107,21 @@ class Ctx:
         out = np.zeros((n, 18), dtype=np.uint64)
         self._check(test_hooks().zk_dbg_g1_op(self.h, mode, _ptr(p), _ptr(q), _h(out), n))
         return out
+
+    FQ30_MODES = ("csub_q", "csub_2q", "csub_4q", "csub_8q", "red4", "red8", "red16", "canon8", "sub2", "sub4", "sub6", "sub8", "sub12",
+                  "add", "add2x", "mul", "sqr", "mul2add", "inv")
+    FQ12_MODES = ("mul", "sqr", "cyc_sqr", "inv", "conj", "frob1", "frob2", "frob3", "mul_by_014", "exp_by_x", "final_exp", "f6_mul",
+                  "f6_inv", "f2_mul", "f2_sqr", "f2_inv")
+
+    def dbg_fq30(self, mode: str, x, kx, y, ky, n):
+        """zk_dbg_fq30_op on device buffers (x, y: n x 48 bytes; kx, ky: n u32) -> (limbs [n, 13] u32, flags [n] u32)"""
+        out, flags = self.alloc(max(64 * n, 1)), self.alloc(max(4 * n, 1))
+        self._check(test_hooks().zk_dbg_fq30_op(self.h, self.FQ30_MODES.index(mode), _ptr(x), _ptr(kx), _ptr(y), _ptr(ky), _ptr(out),
+                                                _ptr(flags), n))
+        return out.download((n, 16), np.uint32)[:, :13], flags.download((n,), np.uint32)
+
+    def dbg_fq12(self, mode: str, a, b, lift, n):
+        """zk_dbg_fq12_op on device buffers (a, b: n x 576 bytes, ark layout; lift: n u32) -> (values [n, 72] u64, flags [n] u32)"""
+        out, flags = self.alloc(max(576 * n, 1)), self.alloc(max(4 * n, 1))
+        self._check(test_hooks().zk_dbg_fq12_op(self.h, self.FQ12_MODES.index(mode), _ptr(a), _ptr(b), _ptr(lift), _ptr(out), _ptr(flags), n))
+        return out.download((n, 72)), flags.download((n,), np.uint32)
