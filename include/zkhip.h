@@ -260,6 +260,21 @@ int zk_lookup3_find(zk_ctx *ctx, const void *const d_w[3], const void *const d_t
  *   Check.  Row x is a BAD GATE ROW when the gate identity does not hold on it (after generation: only a non-computing row); slot s is a
  *     BAD COPY when its value differs from the value of its class -- the c of the source row, or what the class's smallest slot holds
  *     (after generation: only a further computing c slot).  On caller-given a, b, c every row and slot can fail.
+ *   Lookups (additive: a plan built without one follows the rules above and nothing else).  A plan may be built with the lookup of the
+ *     circuit: the selector qk (N Fr, every entry 0 or the Montgomery form of 1) and the table columns t0, t1, t2 (N Fr each, fully
+ *     reduced, padded by repeating an entry).  THE TABLE MUST BE A FUNCTION OF ITS FIRST TWO COLUMNS: two entries with equal (t0, t1)
+ *     in all eight limbs have equal t2 (repeating a whole entry is therefore allowed).
+ *     Row x is LOOKUP-COMPUTING when qk(x) = 1 and it is not gate-computing (wide gate: qO(x) = 0; basic gate: never, every row is
+ *     gate-computing).  Its c is t2[y] for the smallest y with (t0, t1)[y] == (a, b)(x); with no such y its c is 0 and the check
+ *     reports the row.  A row with qk = 1 that is gate-computing stays gate-computing: the table only checks it.  Wherever the rules
+ *     above say "computing row" they mean gate-computing or lookup-computing: the source of a class, the levels (edges from the source
+ *     rows of the a and b slots), the refusal of rows that depend on their own output; a second computing c slot in a class is still an
+ *     equality assertion.
+ *     Check: row x is a BAD LOOKUP when qk(x) = 1 and (a, b, c)(x) is no table entry, whether the row is lookup- or gate-computing.
+ *     Because the table is a function this is exact with the pairs alone: the row is good iff (a, b) is the pair of some entry y and
+ *     c == t2[y].
+ *     On generated wires the index zk_lookup3_find gives for a lookup-computing row is the y the generator used (a smaller index with an
+ *     equal triple would have an equal pair), so the proof's multiplicities need nothing from the generator.
  *
  * zk_witness_plan_create: the plan of one circuit, built once, on the host, in O(N): the cycles, the source of every slot, the levels
  * (Kahn's algorithm), the rows ordered by (level, row), the launch schedule; uploads 3N + N u32, the level offsets and, with d_out_sel,
@@ -270,6 +285,16 @@ int zk_lookup3_find(zk_ctx *ctx, const void *const d_w[3], const void *const d_t
  * such row.  The plan belongs to ctx and must be freed before it. */
 typedef struct zk_witness_plan zk_witness_plan;
 int zk_witness_plan_create(zk_ctx *ctx, const uint64_t *h_sigma, const void *d_out_sel, size_t N, zk_witness_plan **out);
+/* The plan of a circuit WITH its lookup: zk_witness_plan_create, and the plan owns a KEY TABLE -- 2N u32 slots of the open-addressing
+ * protocol of zk_lookup_find over the pair (t0, t1), built once, here, on the device; the probes of every later call are plain loads.
+ * d_qk: N Fr; d_t: t0, t1, t2, N Fr each.  A qk entry that is neither 0 nor 1: ZK_ERR_INVALID, "K of N entries of qk are neither 0 nor 1"
+ * and the smallest such row.  A table that is no function of (t0, t1): ZK_ERR_INVALID, "K of N table entries repeat the pair (t0, t1) of
+ * an earlier entry with another t2; the first is entry Y" -- K counts the entries whose t2 differs from the t2 of the FIRST entry of their
+ * pair, Y is the smallest of them; neither depends on the order of the threads.  The knob find_force_slot applies to this table as to
+ * those of zk_lookup_find: it is read here, kept in the plan and used by every walk of the plan; no result depends on it.  Everything
+ * else as zk_witness_plan_create (the messages name this call).  Blocking.  zk_witness_plan_info and zk_witness_plan_free serve both. */
+int zk_witness_plan_create_lookup(zk_ctx *ctx, const uint64_t *h_sigma, const void *d_out_sel, const void *d_qk, const void *const d_t[3],
+                                  size_t N, zk_witness_plan **out);
 void zk_witness_plan_free(zk_witness_plan *plan);
 /* levels: how many levels the computing rows have (the largest level + 1); max_level_rows: the rows of the largest level; launches: the
  * level launches of one zk_plonk_witness -- a level of more than 256 rows is one launch of many workgroups, a run of consecutive
@@ -292,6 +317,21 @@ int zk_plonk_witness(zk_ctx *ctx, const zk_witness_plan *plan, int gate_kind, co
  * read).  Returns ZK_OK whatever it counts (the report is the result); blocking, the inputs are not modified. */
 int zk_plonk_witness_check(zk_ctx *ctx, const zk_witness_plan *plan, int gate_kind, const void *const *d_sel,
                            const uint64_t *h_public_inputs, size_t l, const void *d_a, const void *d_b, const void *d_c, uint64_t h_bad[4]);
+/* The two calls on a plan built by zk_witness_plan_create_lookup.  d_qk and d_t are passed per call, as the selectors are, and MUST be the
+ * ones the plan was built from (the plan keeps indices into the tables, not the tables; other tables of N entries give other wires and
+ * reports, never a read out of bounds).  zk_plonk_witness_lookup: zk_plonk_witness, and the lookup-computing rows of the wide gate take
+ * their c from the table in the level they belong to (the basic gate has none); the check then also counts the bad lookups, and a
+ * witness with any is refused: "K of N rows with qk = 1 hold a triple that is no table entry; the first is row R", joined to the two
+ * other reports with "; " when several fail (gate, copies, lookups in that order).  zk_plonk_witness_check_lookup: h_bad gains
+ * { bad lookups, the smallest such row (2^64 - 1: none) }.  A walk that passes every slot of the key table (impossible at a load <= 0.5):
+ * ZK_ERR_INTERNAL.  A _lookup call on a plan built without a lookup, or zk_plonk_witness / zk_plonk_witness_check on a plan built with
+ * one: ZK_ERR_INVALID with a message, nothing is launched. */
+int zk_plonk_witness_lookup(zk_ctx *ctx, const zk_witness_plan *plan, int gate_kind, const void *const *d_sel, const void *d_qk,
+                            const void *const d_t[3], const uint64_t *h_public_inputs, size_t l, const void *d_free, void *d_a, void *d_b,
+                            void *d_c);
+int zk_plonk_witness_check_lookup(zk_ctx *ctx, const zk_witness_plan *plan, int gate_kind, const void *const *d_sel, const void *d_qk,
+                                  const void *const d_t[3], const uint64_t *h_public_inputs, size_t l, const void *d_a, const void *d_b,
+                                  const void *d_c, uint64_t h_bad[6]);
 /* df = beta + a + zeta b + zeta^2 c and dt = beta + t0 + zeta t1 + zeta^2 t2 in ONE pass (N Fr each).  The inputs are not modified; an
  * output may not alias an input.  ASYNCHRONOUS on the ctx stream like zk_perm3_terms.  N < 2, not a power of two or > 2^35, or a null
  * pointer: ZK_ERR_INVALID, nothing is launched. */

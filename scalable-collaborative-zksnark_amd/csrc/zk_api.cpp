@@ -475,7 +475,12 @@ int zk_lookup3_find(zk_ctx* ctx, const void* const d_w[3], const void* const d_t
 }
 int zk_witness_plan_create(zk_ctx* ctx, const uint64_t* h_sigma, const void* d_out_sel, size_t N, zk_witness_plan** out) {
     NEED(ctx, h_sigma && out);
-    return witness_plan_create(ctx, h_sigma, d_out_sel, N, out);
+    return witness_plan_create(ctx, h_sigma, d_out_sel, nullptr, nullptr, N, out);
+}
+int zk_witness_plan_create_lookup(zk_ctx* ctx, const uint64_t* h_sigma, const void* d_out_sel, const void* d_qk, const void* const d_t[3], size_t N, zk_witness_plan** out) {
+    NEED(ctx, h_sigma && d_qk && d_t && out);
+    for (int j = 0; j < 3; j++) NEED(ctx, d_t[j]);
+    return witness_plan_create(ctx, h_sigma, d_out_sel, d_qk, d_t, N, out);
 }
 void zk_witness_plan_free(zk_witness_plan* plan) { witness_plan_free(plan); }
 int zk_witness_plan_info(const zk_witness_plan* plan, size_t* levels, size_t* max_level_rows, size_t* launches) {
@@ -488,12 +493,24 @@ int zk_witness_plan_info(const zk_witness_plan* plan, size_t* levels, size_t* ma
 int zk_plonk_witness(zk_ctx* ctx, const zk_witness_plan* plan, int gate_kind, const void* const* d_sel, const uint64_t* h_public_inputs, size_t l, const void* d_free,
                      void* d_a, void* d_b, void* d_c) {
     NEED(ctx, plan && d_sel && (l == 0 || h_public_inputs) && d_a && d_b && d_c);
-    return plonk_witness(ctx, plan, gate_kind, d_sel, h_public_inputs, l, d_free, d_a, d_b, d_c);
+    return plonk_witness(ctx, plan, gate_kind, d_sel, nullptr, nullptr, h_public_inputs, l, d_free, d_a, d_b, d_c);
+}
+int zk_plonk_witness_lookup(zk_ctx* ctx, const zk_witness_plan* plan, int gate_kind, const void* const* d_sel, const void* d_qk, const void* const d_t[3],
+                            const uint64_t* h_public_inputs, size_t l, const void* d_free, void* d_a, void* d_b, void* d_c) {
+    NEED(ctx, plan && d_sel && d_qk && d_t && (l == 0 || h_public_inputs) && d_a && d_b && d_c);
+    for (int j = 0; j < 3; j++) NEED(ctx, d_t[j]);
+    return plonk_witness(ctx, plan, gate_kind, d_sel, d_qk, d_t, h_public_inputs, l, d_free, d_a, d_b, d_c);
 }
 int zk_plonk_witness_check(zk_ctx* ctx, const zk_witness_plan* plan, int gate_kind, const void* const* d_sel, const uint64_t* h_public_inputs, size_t l, const void* d_a,
                            const void* d_b, const void* d_c, uint64_t h_bad[4]) {
     NEED(ctx, plan && d_sel && (l == 0 || h_public_inputs) && d_a && d_b && d_c && h_bad);
-    return plonk_witness_check(ctx, plan, gate_kind, d_sel, h_public_inputs, l, d_a, d_b, d_c, h_bad);
+    return plonk_witness_check(ctx, plan, gate_kind, d_sel, nullptr, nullptr, h_public_inputs, l, d_a, d_b, d_c, h_bad);
+}
+int zk_plonk_witness_check_lookup(zk_ctx* ctx, const zk_witness_plan* plan, int gate_kind, const void* const* d_sel, const void* d_qk, const void* const d_t[3],
+                                  const uint64_t* h_public_inputs, size_t l, const void* d_a, const void* d_b, const void* d_c, uint64_t h_bad[6]) {
+    NEED(ctx, plan && d_sel && d_qk && d_t && (l == 0 || h_public_inputs) && d_a && d_b && d_c && h_bad);
+    for (int j = 0; j < 3; j++) NEED(ctx, d_t[j]);
+    return plonk_witness_check(ctx, plan, gate_kind, d_sel, d_qk, d_t, h_public_inputs, l, d_a, d_b, d_c, h_bad);
 }
 int zk_eq_table_acc(zk_ctx* ctx, const uint64_t* h_point, size_t n, const uint64_t h_weight[4], void* d_acc) {
     NEED(ctx, d_acc && h_weight && (n == 0 || h_point));

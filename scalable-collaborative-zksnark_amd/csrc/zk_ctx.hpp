@@ -101,7 +101,13 @@ struct zk_witness_plan {
     uint32_t* d_src = nullptr;    // 3N: the source of every slot -- a row (its c slot holds the class's value), or kWitFree | the class's smallest slot
     uint32_t* d_order = nullptr;  // N: the computing rows by (level, row), then the other rows in ascending order
     uint32_t* d_lvoff = nullptr;  // levels + 1: level v is order[lvoff[v] .. lvoff[v + 1])
-    void* d_inv = nullptr;        // N Fr: 1 / qO on the computing rows, 0 elsewhere (null: built without an output selector, every row computes)
+    void* d_inv = nullptr;        // N Fr: 1 / qO on the gate-computing rows, 0 elsewhere (null: built without an output selector, every row computes)
+    // a lookup plan (zk_witness_plan_create_lookup): the key table of (t0, t1) -- 2N u32 slots of the protocol of zk_find.cuh, built once on
+    // the device -- and the start slot its walks were built with (the knob find_force_slot at creation; every later walk must use the same).
+    // The lookup-computing rows carry kWitLookup in their d_order entry.
+    uint32_t* d_slots = nullptr;
+    long force = -1;
+    bool lookup = false;
     size_t computing = 0, levels = 0, max_level_rows = 0;
     struct Launch {
         uint32_t lv0, lv1;  // the levels [lv0, lv1): ONE level of more than kWitBlock rows (a grid of workgroups), or a run of levels of at most kWitBlock rows each (one workgroup)
@@ -114,6 +120,7 @@ struct zk_witness_plan {
 namespace zk {
 
 static constexpr uint32_t kWitFree = 0x80000000u;  // flag of zk_witness_plan::d_src (3N <= 3 * 2^29 stays below it)
+static constexpr uint32_t kWitLookup = 0x80000000u;  // flag of zk_witness_plan::d_order: a lookup-computing row (N <= 2^29 stays below it)
 static constexpr int kWitBlock = 256;
 
 // Experiment / diagnostics knobs of the whole library in ONE place.  Defaults are the shipped configuration; the only
@@ -260,13 +267,18 @@ int lookup_find(zk_ctx* ctx, const void* d_f, const void* d_t, size_t N, uint32_
 int lookup3_find(zk_ctx* ctx, const void* const* d_w, const void* const* d_t, const void* d_qk, size_t N, uint32_t* d_idx, void* d_m);
 
 // ---- zk_witness.cpp (the plan, on the host) / zk_witness.hip (the kernels) ----
-int witness_plan_create(zk_ctx* ctx, const uint64_t* h_sigma, const void* d_out_sel, size_t N, zk_witness_plan** out);
+// d_qk, d_t: null (a plain plan), or the lookup selector and t0, t1, t2 (a lookup plan)
+int witness_plan_create(zk_ctx* ctx, const uint64_t* h_sigma, const void* d_out_sel, const void* d_qk, const void* const* d_t, size_t N, zk_witness_plan** out);
+// zk_witness.hip: the slots of a lookup plan's key table built from (t0, t1) with the start slot `force`, then every entry's t2 compared
+// with the t2 of the first entry of its pair (blocking; the function rule of include/zkhip.h)
+int witness_key_table(zk_ctx* ctx, const char* name, const void* const* d_t, size_t N, long force, uint32_t* d_slots);
 void witness_plan_free(zk_witness_plan* plan);
-int plonk_witness(zk_ctx* ctx, const zk_witness_plan* plan, int gate_kind, const void* const* d_sel, const uint64_t* h_pi, size_t l, const void* d_free, void* d_a, void* d_b,
-                  void* d_c);
-// h_bad: bad gate rows, the smallest (~0: none), bad copies, the smallest (~0: none)
-int plonk_witness_check(zk_ctx* ctx, const zk_witness_plan* plan, int gate_kind, const void* const* d_sel, const uint64_t* h_pi, size_t l, const void* d_a, const void* d_b,
-                        const void* d_c, uint64_t* h_bad);
+// d_qk, d_t: null on a plain plan; the selector and the tables the plan was built from on a lookup plan
+int plonk_witness(zk_ctx* ctx, const zk_witness_plan* plan, int gate_kind, const void* const* d_sel, const void* d_qk, const void* const* d_t, const uint64_t* h_pi, size_t l,
+                  const void* d_free, void* d_a, void* d_b, void* d_c);
+// h_bad: bad gate rows, the smallest (~0: none), bad copies, the smallest (~0: none) and, on a lookup plan, bad lookups, the smallest (~0: none)
+int plonk_witness_check(zk_ctx* ctx, const zk_witness_plan* plan, int gate_kind, const void* const* d_sel, const void* d_qk, const void* const* d_t, const uint64_t* h_pi,
+                        size_t l, const void* d_a, const void* d_b, const void* d_c, uint64_t* h_bad);
 
 // ---- zk_batchopen.hip ----
 int eq_table_acc(zk_ctx* ctx, const uint64_t* h_point, size_t n, const uint64_t* h_weight, void* d_acc);

@@ -7,7 +7,8 @@
 // Conventions of zk_lookup.hip / zk_lookup3.hip: Fr in Montgomery form, 32-byte AoS elements, inputs never written, work on the ctx stream,
 // scratch from the ctx arenas.
 //
-// The slot protocol.  slots = a power of two >= 2N (load <= 0.5), filled with kFindEmpty = 2^32 - 1 (N <= 2^31 keeps every index below it).
+// The slot protocol (its device functions are zk_find.cuh, shared with the key table of zk_witness.hip).  slots = a power of two >= 2N
+// (load <= 0.5), filled with kFindEmpty = 2^32 - 1 (N <= 2^31 keeps every index below it).
 // Entry y starts at slot mix(limbs of entry y) mod slots and walks upwards, wrapping round the end:
 //     prev = atomicCAS(slot, EMPTY, y):   EMPTY           the slot is claimed for the key of entry y; done
 //                                         an index v      entry v == entry y in all limbs ?  atomicMin(slot, y), done  :  next slot
@@ -26,22 +27,15 @@
 // so this cannot fire either: internal flag).
 //
 // Registers and occupancy (hipcc --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage): the key of a thread is 8 (NC = 1) or 24
-// (NC = 3) VGPRs, the candidate entry is loaded and compared one column at a time; K20 takes 30 / 48 VGPRs, K21 26 / 42, no scratch, no
+// (NC = 3) VGPRs, the candidate entry is loaded and compared one column at a time; K20 takes 30 / 48 VGPRs, K21 26 / 44, no scratch, no
 // LDS: eight waves per SIMD for all four, which is what a walk of dependent random reads wants.  Grid: 8 workgroups of 256 per CU.
-#include "zk_gate.cuh"
+#include "zk_find.cuh"
 
 #include <algorithm>
 #include <cstring>
 
 namespace zk {
 
-static constexpr u32 kFindEmpty = 0xffffffffu;
-
-template <int NC>
-struct FindCols {
-    const void* w[NC];  // the rows: f, or a, b, c
-    const void* t[NC];  // the table: t, or t0, t1, t2
-};
 // status of a call, 32 bytes in arena 4 before the counters: zeroed, `first` set to 2^32 - 1
 struct FindStatus {
     unsigned long long bad;  // rows that are not in the table, or whose qk is neither 0 nor 1
@@ -50,33 +44,6 @@ struct FindStatus {
     u32 first;               // the smallest bad row
     u32 pad1[3];
 };
-
-// 64-bit mix of all limbs of a key (a multiply-xorshift chain closed by the finaliser of MurmurHash3)
-template <int NC>
-__device__ __forceinline__ u64 find_hash(const Fr (&k)[NC]) {
-    u64 h = 0x243f6a8885a308d3ull;
-#pragma unroll
-    for (int j = 0; j < NC; j++)
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            h ^= ((u64)k[j].l[2 * i + 1] << 32) | k[j].l[2 * i];
-            h *= 0x9e3779b97f4a7c15ull;
-            h ^= h >> 29;
-        }
-    h ^= h >> 33;
-    h *= 0xff51afd7ed558ccdull;
-    h ^= h >> 33;
-    h *= 0xc4ceb9fe1a85ec53ull;
-    h ^= h >> 33;
-    return h;
-}
-template <int NC>
-__device__ __forceinline__ bool find_equal(const Fr (&k)[NC], const FindCols<NC>& c, size_t v) {  // the key against table entry v
-    bool eq = true;
-#pragma unroll
-    for (int j = 0; j < NC; j++) eq = eq && fp_eq(k[j], fr_load(c.t[j], v));
-    return eq;
-}
 
 // ---------------------------------------------------------------------------------------
 // K20.  mask = slots - 1; force >= 0: every key starts at slot force & mask (knob find_force_slot).
@@ -87,22 +54,7 @@ __global__ void __launch_bounds__(kGateBlock) k_find_build(FindCols<NC> c, size_
         Fr k[NC];
 #pragma unroll
         for (int j = 0; j < NC; j++) k[j] = fr_load(c.t[j], y);
-        u64 s = (force >= 0 ? (u64)force : find_hash<NC>(k)) & mask;
-        bool done = false;
-        for (u64 step = 0; step <= mask; step++, s = (s + 1) & mask) {
-            const u32 prev = atomicCAS(&slots[s], kFindEmpty, (u32)y);
-            if (prev == kFindEmpty) {  // claimed
-                done = true;
-                break;
-            }
-            if (prev >= N) break;  // not an index: cannot happen
-            if (find_equal<NC>(k, c, prev)) {
-                if ((u32)y < prev) atomicMin(&slots[s], (u32)y);  // the slot's index only falls: one that is already smaller stays smaller
-                done = true;
-                break;
-            }
-        }
-        if (!done) atomicOr(&st->internal, 1u);
+        if (!find_insert<NC>(k, c, N, y, slots, mask, force)) atomicOr(&st->internal, 1u);
     }
 }
 
@@ -129,21 +81,8 @@ __global__ void __launch_bounds__(kGateBlock) k_find_probe(FindCols<NC> c, const
         Fr k[NC];
 #pragma unroll
         for (int j = 0; j < NC; j++) k[j] = fr_load(c.w[j], x);
-        u64 s = (force >= 0 ? (u64)force : find_hash<NC>(k)) & mask;
-        int end = 0;  // 1 hit, 2 miss
-        u32 v = kFindEmpty;
-        for (u64 step = 0; step <= mask; step++, s = (s + 1) & mask) {
-            v = slots[s];
-            if (v == kFindEmpty) {
-                end = 2;
-                break;
-            }
-            if (v >= N) break;  // not an index: cannot happen
-            if (find_equal<NC>(k, c, v)) {
-                end = 1;
-                break;
-            }
-        }
+        u32 v;
+        const int end = find_walk<NC>(k, c, N, slots, mask, force, v);  // 1 hit, 2 miss
         if (end == 1) {
             if (idx) idx[x] = v;
             if (cnt) atomicAdd(&cnt[v], 1u);

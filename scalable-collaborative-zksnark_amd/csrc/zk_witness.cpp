@@ -5,7 +5,10 @@
 //      depends on its own output and the plan is refused;
 //   3. a counting sort by (level, row), the level offsets, and the launch schedule of zk_witness.hip: a level of more than kWitBlock rows
 //      is a launch of its own, a run of consecutive smaller levels is ONE launch of ONE workgroup;
-//   4. the uploads: src, the row order, the level offsets and, with an output selector, 1 / qO on the computing rows (zk_fr_batch_div).
+//   4. the uploads: src, the row order, the level offsets and, with an output selector, 1 / qO on the gate-computing rows (zk_fr_batch_div).
+// A LOOKUP plan (d_qk, d_t given) differs in two places: before step 1 the selector qk is read and checked (0 or 1), the key table of
+// (t0, t1) is built on the device (zk_witness.hip, witness_key_table) and the rows with qk = 1 that are not gate-computing become
+// LOOKUP-COMPUTING; steps 1 - 3 treat both kinds alike, and the order entry of a lookup-computing row carries kWitLookup.
 // Why on the host: it runs once per circuit and is serial on a deep circuit anyway; the per-proof work is zk_witness.hip.
 #include "fp.cuh"
 #include "zk_ctx.hpp"
@@ -23,6 +26,7 @@ void witness_plan_free(zk_witness_plan* plan) {
     if (plan->d_order) (void)hipFree(plan->d_order);
     if (plan->d_lvoff) (void)hipFree(plan->d_lvoff);
     if (plan->d_inv) (void)hipFree(plan->d_inv);
+    if (plan->d_slots) (void)hipFree(plan->d_slots);
     delete plan;
 }
 
@@ -44,19 +48,20 @@ int upload_u32(zk_ctx* ctx, const std::vector<uint32_t>& v, uint32_t** d_out) {
 }
 }  // namespace
 
-int witness_plan_create(zk_ctx* ctx, const uint64_t* h_sigma, const void* d_out_sel, size_t N, zk_witness_plan** out) {
+int witness_plan_create(zk_ctx* ctx, const uint64_t* h_sigma, const void* d_out_sel, const void* d_qk, const void* const* d_t, size_t N, zk_witness_plan** out) {
     *out = nullptr;
-    if (N < 2 || (N & (N - 1)) || N > ((size_t)1 << 29)) return fail(ctx, ZK_ERR_INVALID, "zk_witness_plan_create: N = %zu is not a power of two in [2, 2^29]", N);
+    const char* name = d_qk ? "zk_witness_plan_create_lookup" : "zk_witness_plan_create";
+    if (N < 2 || (N & (N - 1)) || N > ((size_t)1 << 29)) return fail(ctx, ZK_ERR_INVALID, "%s: N = %zu is not a power of two in [2, 2^29]", name, N);
     const size_t S = 3 * N;
     ZK_HIP(ctx, hipSetDevice(ctx->device));
     // sigma: every slot number below 3N, each exactly once
     std::vector<uint8_t> mark(S, 0);
     for (size_t s = 0; s < S; s++) {
         const uint64_t t = h_sigma[s];
-        if (t >= S || mark[t]) return fail(ctx, ZK_ERR_INVALID, "zk_witness_plan_create: sigma is not a permutation of the %zu wire slots (entry %zu)", S, s);
+        if (t >= S || mark[t]) return fail(ctx, ZK_ERR_INVALID, "%s: sigma is not a permutation of the %zu wire slots (entry %zu)", name, S, s);
         mark[t] = 1;
     }
-    // the computing rows: all of them, or those with a non-zero output selector
+    // the gate-computing rows: all of them, or those with a non-zero output selector
     std::vector<uint8_t> comp(N, 1);
     std::vector<uint64_t> qo;
     if (d_out_sel) {
@@ -70,9 +75,38 @@ int witness_plan_create(zk_ctx* ctx, const uint64_t* h_sigma, const void* d_out_
             const uint64_t* q = &qo[4 * x];
             int i = 3;
             while (i > 0 && q[i] == r[i]) i--;
-            if (q[i] >= r[i]) return fail(ctx, ZK_ERR_INVALID, "zk_witness_plan_create: the output selector of row %zu is not reduced below r", x);
+            if (q[i] >= r[i]) return fail(ctx, ZK_ERR_INVALID, "%s: the output selector of row %zu is not reduced below r", name, x);
             comp[x] = (q[0] | q[1] | q[2] | q[3]) != 0;
         }
+    }
+    const std::vector<uint8_t> gate_comp = comp;
+    zk_witness_plan* plan = new zk_witness_plan;
+    PlanGuard guard{plan};
+    plan->ctx = ctx, plan->N = N;
+    // a lookup plan: qk holds only 0 and the Montgomery 1; the key table; the lookup-computing rows (kind 2 in comp)
+    if (d_qk) {
+        std::vector<uint64_t> qk(4 * N);
+        ZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        ZK_HIP(ctx, hipMemcpy(qk.data(), d_qk, 32 * N, hipMemcpyDeviceToHost));
+        uint64_t one[4];
+        for (int i = 0; i < 4; i++) one[i] = ((uint64_t)FrCfg::ONE(2 * i + 1) << 32) | FrCfg::ONE(2 * i);
+        size_t bad = 0, first = N;
+        for (size_t x = 0; x < N; x++) {
+            const uint64_t* q = &qk[4 * x];
+            const bool is1 = !memcmp(q, one, 32);
+            if (!is1 && (q[0] | q[1] | q[2] | q[3])) {
+                if (!bad++) first = x;
+            } else if (is1 && !comp[x]) {
+                comp[x] = 2;
+            }
+        }
+        if (bad) return fail(ctx, ZK_ERR_INVALID, "%s: %zu of %zu entries of qk are neither 0 nor 1; the first is row %zu", name, bad, N, first);
+        const long force = tuning().find_force_slot;
+        if (force < -1) return fail(ctx, ZK_ERR_INVALID, "find_force_slot must be -1 or a slot number");
+        plan->lookup = true, plan->force = force;
+        ZK_HIP(ctx, device_alloc(ctx, (void**)&plan->d_slots, 2 * N * sizeof(uint32_t)));
+        const int rc = witness_key_table(ctx, name, d_t, N, force, plan->d_slots);
+        if (rc != ZK_OK) return rc;
     }
     // 1. the cycles.  Slots are visited in ascending order, so a cycle is entered at its smallest slot
     std::vector<uint32_t> src(S);
@@ -129,12 +163,10 @@ int witness_plan_create(zk_ctx* ctx, const uint64_t* h_sigma, const void* d_out_
         size_t first = N;
         for (size_t x = 0; x < N && first == N; x++)
             if (comp[x] && indeg[x]) first = x;
-        return fail(ctx, ZK_ERR_INVALID, "zk_witness_plan_create: %zu of %zu rows depend on their own output; the first is row %zu", nc - queue.size(), N, first);
+        return fail(ctx, ZK_ERR_INVALID, "%s: %zu of %zu rows depend on their own output; the first is row %zu", name, nc - queue.size(), N, first);
     }
     // 3. (level, row) order by a counting sort; the rows that compute nothing follow in ascending order
-    zk_witness_plan* plan = new zk_witness_plan;
-    PlanGuard guard{plan};
-    plan->ctx = ctx, plan->N = N, plan->computing = nc;
+    plan->computing = nc;
     const size_t levels = nc ? (size_t)top + 1 : 0;
     plan->levels = levels;
     std::vector<uint32_t>& lvoff = plan->lvoff;
@@ -148,7 +180,7 @@ int witness_plan_create(zk_ctx* ctx, const uint64_t* h_sigma, const void* d_out_
     std::vector<uint32_t> order(N), at(lvoff.begin(), lvoff.end() - (levels ? 1 : 0));
     size_t rest = nc;
     for (size_t x = 0; x < N; x++) {
-        if (comp[x]) order[at[level[x]]++] = (uint32_t)x;
+        if (comp[x]) order[at[level[x]]++] = (uint32_t)x | (comp[x] == 2 ? kWitLookup : 0);
         else order[rest++] = (uint32_t)x;
     }
     for (size_t v = 0; v < levels;) {
@@ -165,12 +197,12 @@ int witness_plan_create(zk_ctx* ctx, const uint64_t* h_sigma, const void* d_out_
     if (rc == ZK_OK) rc = upload_u32(ctx, lvoff, &plan->d_lvoff);
     if (rc != ZK_OK) return rc;
     if (d_out_sel) {
-        // 1 / qO by the batch inversion: numerator 1 and denominator qO on the computing rows, 0 / 1 elsewhere (no zero denominator)
+        // 1 / qO by the batch inversion: numerator 1 and denominator qO on the gate-computing rows, 0 / 1 elsewhere (no zero denominator)
         uint64_t one[4];
         for (int i = 0; i < 4; i++) one[i] = ((uint64_t)FrCfg::ONE(2 * i + 1) << 32) | FrCfg::ONE(2 * i);
         std::vector<uint64_t> num(4 * N, 0);
         for (size_t x = 0; x < N; x++) {
-            if (comp[x]) memcpy(&num[4 * x], one, 32);
+            if (gate_comp[x]) memcpy(&num[4 * x], one, 32);
             else memcpy(&qo[4 * x], one, 32);
         }
         DevGuard d_num, d_den;

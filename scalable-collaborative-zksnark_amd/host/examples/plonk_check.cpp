@@ -3,7 +3,7 @@
 // drawn from the device transcript and verified by replaying the schedule on the host transcript.  One digest for one seed across the
 // two hosts (zkhip.plonk.proof_digest).
 //
-//     bin/plonk_check --mu M [--seed S] [--gate wide] [--witness] [--lookup [--find] [--break-lookup K]] [--break-gate K | --break-wire K | --bad-input | --break K|all]
+//     bin/plonk_check --mu M [--seed S] [--gate wide] [--witness] [--lookup | --lookup-fn [--find] [--break-lookup K]] [--break-gate K | --break-wire K | --bad-input | --break K|all]
 //                     [--circuit-only | --sample-only [--time-sample R]]
 //
 // --lookup proves the test circuit with lookup rows (zkhip.plonk.sample_circuit_lookup, mu >= 3) under the label + "-lookup": three opening
@@ -15,6 +15,10 @@
 // 14 lookup.batch.rounds, 15 lookup.batch.opening.  --break all proves once and verifies one tampered copy per part: one line each, exit 1 when
 // every copy is rejected and 0 when one is accepted.
 //
+// --lookup-fn (with --gate wide) is --lookup on the circuit of zkhip.plonk.sample_circuit_lookup_fn instead: lookup rows with the gate switched
+// off against an XOR table.  With --witness the plan is built WITH the lookup (zk_witness_plan_create_lookup) and the device takes the c of
+// those rows from the table (zk_plonk_witness_lookup), from the public inputs and the sampler's free values alone; --break-lookup K (a lookup
+// row with a free a) moves that value out of the table: with --witness the generator refuses, without it the prover does (exit 3).
 // --witness drops the sampler's a, b, c and generates them on the device (plonk_witness: zk_witness_plan_create + zk_plonk_witness) from the
 // circuit, the public inputs and -- with --lookup -- the free values of the lookup rows; the digest is the one without the flag.  Not with
 // --break-gate / --break-wire, which break the sampler's wires.
@@ -49,10 +53,11 @@ static bool number(const char *s, long long &out) {
 struct Options {
     long long mu = -1, seed = 7, break_gate = -1, break_wire = -1, break_lookup = -1, break_part = -1;
     long long time_sample = 0;
-    bool bad_input = false, wide = false, lookup = false, break_all = false, find = false, witness = false;
+    bool bad_input = false, wide = false, lookup = false, break_all = false, find = false, witness = false, lookup_fn = false;
 };
 
 static PlonkCircuit sample(const Options &o, bool broken) {
+    if (o.lookup_fn) return sample_circuit_lookup_fn((size_t)o.mu, (uint64_t)o.seed, broken ? o.break_lookup : -1);
     if (o.lookup) return sample_circuit_lookup((size_t)o.mu, (uint64_t)o.seed, o.wide, broken ? o.break_lookup : -1);
     return (o.wide ? sample_circuit_wide : sample_circuit)((size_t)o.mu, (uint64_t)o.seed, broken ? o.break_gate : -1, broken ? o.break_wire : -1, nullptr);
 }
@@ -110,9 +115,11 @@ static int run(const Options &o) {
         if (o.witness) {
             // the sampler's a, b, c are dropped: the device generates them from the circuit, the public inputs and -- with a lookup -- the free
             // values of the lookup rows, whose a and b slots are fixed points of sigma and hold the table's u, v
-            const std::shared_ptr<WitnessPlan> plan = witness_plan(be, good);
+            const std::shared_ptr<WitnessPlan> plan = witness_plan(be, good, o.lookup_fn);
             FrVec free;
-            if (o.lookup) {
+            if (o.lookup_fn) {
+                free = c.free;
+            } else if (o.lookup) {
                 free.assign(3 * N, Fr::zero());
                 for (size_t x = 0; x < N; ++x)
                     if (!(c.qk[x] == Fr::zero())) free[x] = c.a[x], free[N + x] = c.b[x];
@@ -162,6 +169,7 @@ int main(int argc, char **argv) {
         if (k == "--bad-input") bad_input = true;
         else if (k == "--circuit-only" || k == "--sample-only") only_circuit = true;
         else if (k == "--lookup") o.lookup = true;
+        else if (k == "--lookup-fn") o.lookup = o.lookup_fn = true;
         else if (k == "--find") o.find = true;
         else if (k == "--witness") o.witness = true;
         else if (i + 1 < argc && k == "--time-sample") usage = !number(argv[++i], o.time_sample) || o.time_sample < 1;
@@ -178,8 +186,8 @@ int main(int argc, char **argv) {
     const bool tamper = o.break_all || o.break_part >= 0;
     if (usage || mu < 0 || (break_gate >= 0) + (break_wire >= 0) + (bad_input ? 1 : 0) + (o.break_lookup >= 0) + (tamper ? 1 : 0) > 1 ||
         (o.break_all && o.break_part >= 0) || (o.break_lookup >= 0 && !o.lookup) || (o.find && !o.lookup) || (o.lookup && (break_gate >= 0 || break_wire >= 0)) ||
-        (o.witness && (break_gate >= 0 || break_wire >= 0)) || (o.time_sample > 0 && !only_circuit)) {
-        std::fprintf(stderr, "usage: plonk_check --mu M [--seed S] [--gate wide] [--witness] [--lookup [--find] [--break-lookup K]] [--break-gate K | --break-wire K | --bad-input | --break K|all] [--circuit-only | --sample-only [--time-sample R]]\n");
+        (o.witness && (break_gate >= 0 || break_wire >= 0)) || (o.time_sample > 0 && !only_circuit) || (o.lookup_fn && (!wide || o.time_sample > 0))) {
+        std::fprintf(stderr, "usage: plonk_check --mu M [--seed S] [--gate wide] [--witness] [--lookup | --gate wide --lookup-fn [--find] [--break-lookup K]] [--break-gate K | --break-wire K | --bad-input | --break K|all] [--circuit-only | --sample-only [--time-sample R]]\n");
         return 2;
     }
     if (mu < 2 || mu > 24) {

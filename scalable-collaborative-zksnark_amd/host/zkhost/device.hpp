@@ -59,13 +59,15 @@ struct PcsVk {
     }
 };
 
-// the witness plan of one Plonk circuit held by the library (zk_witness_plan: sources, levels, launch schedule); it holds its ctx
+// the witness plan of one Plonk circuit held by the library (zk_witness_plan: sources, levels, launch schedule and, built with a lookup,
+// the key table of (t0, t1)); it holds its ctx
 struct WitnessPlan {
     CtxRef ctx;
     zk_witness_plan *h = nullptr;
     size_t N = 0;
-    bool wide = false;  // built with the wide gate's output selector
-    WitnessPlan(CtxRef c, zk_witness_plan *h_, size_t n, bool w) : ctx(std::move(c)), h(h_), N(n), wide(w) {}
+    bool wide = false;    // built with the wide gate's output selector
+    bool lookup = false;  // built by zk_witness_plan_create_lookup: the _lookup calls serve it, the plain ones refuse it
+    WitnessPlan(CtxRef c, zk_witness_plan *h_, size_t n, bool w, bool lk = false) : ctx(std::move(c)), h(h_), N(n), wide(w), lookup(lk) {}
     WitnessPlan(const WitnessPlan &) = delete;
     ~WitnessPlan() { zk_witness_plan_free(h); }
     // levels, rows of the largest level, level launches of one zk_plonk_witness
@@ -75,9 +77,9 @@ struct WitnessPlan {
         return v;
     }
 };
-struct WitnessReport {  // zk_plonk_witness_check: the counts and the smallest row / slot (~0: none)
-    uint64_t bad_rows = 0, first_bad_row = ~0ull, bad_copies = 0, first_bad_copy = ~0ull;
-    bool ok() const { return !bad_rows && !bad_copies; }
+struct WitnessReport {  // zk_plonk_witness_check(_lookup): the counts and the smallest row / slot (~0: none); the lookups on a lookup plan only
+    uint64_t bad_rows = 0, first_bad_row = ~0ull, bad_copies = 0, first_bad_copy = ~0ull, bad_lookups = 0, first_bad_lookup = ~0ull;
+    bool ok() const { return !bad_rows && !bad_copies && !bad_lookups; }
 };
 
 // a Fiat-Shamir transcript whose state lives on the device (zk_transcript); freed before its ctx because it holds the ctx
@@ -728,6 +730,38 @@ class Ctx {
                                      b.get(), c.get(), bad));
         WitnessReport r;
         r.bad_rows = bad[0], r.first_bad_row = bad[1], r.bad_copies = bad[2], r.first_bad_copy = bad[3];
+        return r;
+    }
+    // ---- the same with the circuit's lookup (zk_witness_plan_create_lookup, zk_plonk_witness_lookup, zk_plonk_witness_check_lookup) ----
+    // qk, table = t0, t1, t2: N Fr each on the device.  Beyond witness_plan's refusals: a qk entry that is neither 0 nor 1, a table that is no
+    // function of (t0, t1): ZkError(ZK_ERR_INVALID) with the library's message.  The two calls take the qk and the table the plan was built from
+    std::shared_ptr<WitnessPlan> witness_plan_lookup(const std::vector<uint64_t> &sigma, size_t N, const DevPtr *out_sel, const DevPtr &qk, const std::array<DevPtr, 3> &table) {
+        need(sigma.size() == 3 * N, "witness_plan_lookup: sigma must hold 3N slot numbers");
+        const void *t[3] = {table[0].get(), table[1].get(), table[2].get()};
+        zk_witness_plan *p = nullptr;
+        check(zk_witness_plan_create_lookup(h_, sigma.data(), out_sel ? out_sel->get() : nullptr, qk.get(), t, N, &p));
+        return std::make_shared<WitnessPlan>(ref_, p, N, out_sel != nullptr, true);
+    }
+    std::array<DevPtr, 3> plonk_witness_lookup(const WitnessPlan &plan, const std::vector<DevPtr> &sel, const DevPtr &qk, const std::array<DevPtr, 3> &table,
+                                               const FrVec &public_inputs, const DevPtr *free = nullptr) {
+        std::array<DevPtr, 3> w = {alloc_fr(plan.N), alloc_fr(plan.N), alloc_fr(plan.N)};
+        std::vector<const void *> ps;
+        for (const DevPtr &d : sel) ps.push_back(d.get());
+        const void *t[3] = {table[0].get(), table[1].get(), table[2].get()};
+        check(zk_plonk_witness_lookup(h_, plan.h, sel.size() == 6 ? 1 : 0, ps.data(), qk.get(), t, public_inputs.empty() ? nullptr : public_inputs[0].v, public_inputs.size(),
+                                      free ? free->get() : nullptr, w[0].get(), w[1].get(), w[2].get()));
+        return w;
+    }
+    WitnessReport plonk_witness_check_lookup(const WitnessPlan &plan, const std::vector<DevPtr> &sel, const DevPtr &qk, const std::array<DevPtr, 3> &table,
+                                             const FrVec &public_inputs, const DevPtr &a, const DevPtr &b, const DevPtr &c) {
+        std::vector<const void *> ps;
+        for (const DevPtr &d : sel) ps.push_back(d.get());
+        const void *t[3] = {table[0].get(), table[1].get(), table[2].get()};
+        uint64_t bad[6];
+        check(zk_plonk_witness_check_lookup(h_, plan.h, sel.size() == 6 ? 1 : 0, ps.data(), qk.get(), t, public_inputs.empty() ? nullptr : public_inputs[0].v,
+                                            public_inputs.size(), a.get(), b.get(), c.get(), bad));
+        WitnessReport r;
+        r.bad_rows = bad[0], r.first_bad_row = bad[1], r.bad_copies = bad[2], r.first_bad_copy = bad[3], r.bad_lookups = bad[4], r.first_bad_lookup = bad[5];
         return r;
     }
     // g1_96: powers_of_g[0][0] as a 96-byte affine record (nullptr: the generator); powers_g2: n_g2 affine records at `stride`

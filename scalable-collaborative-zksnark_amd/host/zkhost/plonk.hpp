@@ -62,6 +62,7 @@ struct PlonkCircuit {
     bool lookup = false;
     FrVec qk, t0, t1, t2;               // with a lookup: the selector and the table, N elements each
     std::vector<uint32_t> idx;          // with a lookup: the prover's row-to-table indices
+    FrVec free;                         // sample_circuit_lookup_fn only: the free values at their slots (3N elements, 0 elsewhere); not in the digest
 };
 struct PlonkVk {
     GateKind gate = GateKind::basic;
@@ -120,12 +121,17 @@ inline Fr gate_closed_form(GateKind k, const Fr &eq, const FrVec &g, const Fr &i
 }
 
 // ---- witness (zkhip.plonk.witness_plan / witness / check_witness; the rules: include/zkhip.h) ----
-// the plan of a circuit: built once, on the host inside the library; the wide gate's output selector qO is sel[3]
-inline std::shared_ptr<WitnessPlan> witness_plan(Ctx &be, const PlonkCircuit &c) {
+// the plan of a circuit: built once, on the host inside the library; the wide gate's output selector qO is sel[3].  lookup: the plan of
+// the circuit WITH its lookup (required then; the key table of (t0, t1) is built on the device) -- plonk_witness / plonk_check_witness
+// dispatch on the plan.  The default ignores a lookup the circuit may carry
+inline std::shared_ptr<WitnessPlan> witness_plan(Ctx &be, const PlonkCircuit &c, bool lookup = false) {
     const size_t N = size_t(1) << c.mu;
-    if (c.gate != GateKind::wide) return be.witness_plan(c.sigma, N);
-    const DevPtr qo = be.to_device(c.sel[3]);
-    return be.witness_plan(c.sigma, N, &qo);
+    DevPtr qo;
+    if (c.gate == GateKind::wide) qo = be.to_device(c.sel[3]);
+    const DevPtr *out_sel = c.gate == GateKind::wide ? &qo : nullptr;
+    if (!lookup) return be.witness_plan(c.sigma, N, out_sel);
+    if (!c.lookup) throw ZkError(ZK_ERR_INVALID, "witness_plan: a lookup plan needs a circuit with a lookup");
+    return be.witness_plan_lookup(c.sigma, N, out_sel, be.to_device(c.qk), {be.to_device(c.t0), be.to_device(c.t1), be.to_device(c.t2)});
 }
 inline void witness_need(bool ok, const char *what) {
     if (!ok) throw ZkError(ZK_ERR_INVALID, what);
@@ -133,18 +139,23 @@ inline void witness_need(bool ok, const char *what) {
 inline void witness_args(const PlonkPk &pk, const WitnessPlan &plan, const FrVec &public_inputs) {
     witness_need(public_inputs.size() == pk.l, "plonk witness: the public-input count differs from the key's");
     witness_need(plan.N == size_t(1) << pk.mu && plan.wide == (pk.gate == GateKind::wide), "plonk witness: the plan is not one of this key's circuit");
+    witness_need(!plan.lookup || pk.lookup, "plonk witness: a lookup plan needs a key with the lookup's tables");
 }
 // the wires of pk's circuit from its public inputs and the values of its free classes (free: 3N elements read at the smallest slot of every
 // free class, or null: zeros) -> a, b, c on the device, which go straight into plonk_prove.  A broken gate or copy: ZkError(ZK_ERR_INVALID)
 inline std::array<DevPtr, 3> plonk_witness(Ctx &be, const PlonkPk &pk, const WitnessPlan &plan, const FrVec &public_inputs, const FrVec *free = nullptr) {
     witness_args(pk, plan, public_inputs);
-    if (!free) return be.plonk_witness(plan, pk.sel, public_inputs);
-    witness_need(free->size() == 3 * plan.N, "plonk witness: free must hold 3N elements");
-    const DevPtr f = be.to_device(*free);
-    return be.plonk_witness(plan, pk.sel, public_inputs, &f);
+    DevPtr f;
+    if (free) {
+        witness_need(free->size() == 3 * plan.N, "plonk witness: free must hold 3N elements");
+        f = be.to_device(*free);
+    }
+    if (plan.lookup) return be.plonk_witness_lookup(plan, pk.sel, pk.qk, pk.table, public_inputs, free ? &f : nullptr);
+    return be.plonk_witness(plan, pk.sel, public_inputs, free ? &f : nullptr);
 }
 inline WitnessReport plonk_check_witness(Ctx &be, const PlonkPk &pk, const WitnessPlan &plan, const DevPtr &a, const DevPtr &b, const DevPtr &c, const FrVec &public_inputs) {
     witness_args(pk, plan, public_inputs);
+    if (plan.lookup) return be.plonk_witness_check_lookup(plan, pk.sel, pk.qk, pk.table, public_inputs, a, b, c);
     return be.plonk_witness_check(plan, pk.sel, public_inputs, a, b, c);
 }
 
@@ -309,6 +320,80 @@ inline PlonkCircuit sample_circuit_lookup(size_t mu, uint64_t seed, bool wide = 
     c.qk.assign(N, Fr::zero()), c.idx.assign(N, 0);
     for (size_t x = 0; x < N; ++x)
         if (lk.mask[x]) c.qk[x] = Fr::one(), c.idx[x] = (uint32_t)lk.y[x];
+    return c;
+}
+// The test circuit of zkhip.plonk.sample_circuit_lookup_fn, bit for bit: the wide gate, lookup rows with the gate switched off against the
+// XOR table on k = min(4, mu / 2) bits (entry y < 4^k is (y >> k, y & (2^k - 1), their XOR), padded to N by repeating the last entry).
+// Streams 1 public inputs, 5 trapdoor, 14 picks.  Row x >= l by limb 2 of pick x mod 8: 0 .. 5 a LOOKUP row (every gate selector 0, qk = 1,
+// c = a XOR b; a copies the c of the (limb 0 mod E)-th of the E earlier lookup rows when bits 3 .. 5 of limb 2 are 0 and E > 0, and is
+// otherwise free -- a fixed point of sigma holding limb 3 & (2^k - 1); b likewise with bits 6 .. 8, limb 1, (limb 3 >> 8) & (2^k - 1)),
+// 6 linear (qL = qR = qO = 1, c = a + b), 7 product (qM = qO = 1, c = a b), both on a = c[limb 0 mod x], b = c[limb 1 mod x].
+// break_row K (a lookup row with a free a): that free value + 2^k, so the pair is in no entry; c[K] = 0 as the generator leaves it, idx[K] = 0.
+inline PlonkCircuit sample_circuit_lookup_fn(size_t mu, uint64_t seed, long long break_row = -1) {
+    if (mu < 3) throw ZkError(ZK_ERR_INVALID, "sample_circuit_lookup_fn: mu >= 3");
+    PlonkCircuit c;
+    const size_t N = size_t(1) << mu, l = 4, k = mu / 2 < 4 ? mu / 2 : 4, D = size_t(1) << (2 * k);
+    const uint64_t base = 0x91A70000ull + 1000 * seed, low = (uint64_t(1) << k) - 1;
+    enum { qL, qR, qM, qO, qC, qH };
+    c.gate = GateKind::wide, c.mu = mu, c.l = l, c.lookup = true;
+    c.public_inputs = SplitMix64(base + 1).fr_vec(l);
+    const FrVec pick = SplitMix64(base + 14).fr_vec(N);
+    c.sel.assign(6, FrVec(N, Fr::zero()));
+    for (FrVec *t : {&c.a, &c.b, &c.c, &c.qk}) t->assign(N, Fr::zero());
+    c.free.assign(3 * N, Fr::zero()), c.idx.assign(N, 0);
+    std::vector<std::vector<uint64_t>> users(N);  // row y -> the slots that copy c[y]
+    std::vector<size_t> lookups;                  // the lookup rows so far
+    std::vector<uint64_t> small(N, 0);            // the c of a lookup row as an integer
+    for (size_t x = 0; x < l; ++x) c.sel[qO][x] = Fr::one(), c.c[x] = c.public_inputs[x];
+    bool broke = false;
+    for (size_t x = l; x < N; ++x) {
+        const uint64_t *p = pick[x].v;
+        const unsigned kind = p[2] % 8;
+        if (kind < 6) {
+            c.qk[x] = Fr::one();
+            uint64_t w[2];
+            for (size_t j = 0; j < 2; ++j) {
+                const uint64_t bits = (p[2] >> (3 + 3 * j)) & 7;
+                if (bits == 0 && !lookups.empty()) {
+                    const size_t y = lookups[p[j] % lookups.size()];
+                    w[j] = small[y];
+                    users[y].push_back(j * N + x);
+                } else {
+                    w[j] = (j == 0 ? p[3] : p[3] >> 8) & low;
+                    if (j == 0 && (long long)x == break_row) w[j] += uint64_t(1) << k, broke = true;
+                    c.free[j * N + x] = Fr::from_u64(w[j]);
+                }
+            }
+            const bool hit = w[0] <= low && w[1] <= low;
+            small[x] = hit ? w[0] ^ w[1] : 0;
+            c.a[x] = Fr::from_u64(w[0]), c.b[x] = Fr::from_u64(w[1]), c.c[x] = Fr::from_u64(small[x]);
+            c.idx[x] = hit ? (uint32_t)((w[0] << k) | w[1]) : 0;
+            lookups.push_back(x);
+        } else {
+            const size_t ya = p[0] % x, yb = p[1] % x;
+            c.a[x] = c.c[ya], c.b[x] = c.c[yb];
+            users[ya].push_back(x), users[yb].push_back(N + x);
+            c.sel[qO][x] = Fr::one();
+            if (kind == 6) c.sel[qL][x] = c.sel[qR][x] = Fr::one(), c.c[x] = c.a[x] + c.b[x];
+            else c.sel[qM][x] = Fr::one(), c.c[x] = c.a[x] * c.b[x];
+        }
+    }
+    if (break_row >= 0 && !broke) throw ZkError(ZK_ERR_INVALID, "sample_circuit_lookup_fn: break_row must name a lookup row with a free a");
+    c.sigma.resize(3 * N);
+    for (size_t i = 0; i < 3 * N; ++i) c.sigma[i] = i;
+    for (size_t y = 0; y < N; ++y) {
+        if (users[y].empty()) continue;
+        std::sort(users[y].begin(), users[y].end());
+        uint64_t prev = 2 * N + y;
+        for (uint64_t u : users[y]) c.sigma[prev] = u, prev = u;
+        c.sigma[prev] = 2 * N + y;
+    }
+    c.t0.resize(N), c.t1.resize(N), c.t2.resize(N);
+    for (size_t i = 0; i < N; ++i) {
+        const uint64_t y = i < D ? i : D - 1;
+        c.t0[i] = Fr::from_u64(y >> k), c.t1[i] = Fr::from_u64(y & low), c.t2[i] = Fr::from_u64((y >> k) ^ (y & low));
+    }
+    c.s = SplitMix64(base + 5).fr_vec(mu + 1);
     return c;
 }
 // SHA-256 of a sampled circuit's tables: the selectors, a, b, c, the public inputs, the trapdoor, sigma (u64) and, with a lookup, qk, t0,

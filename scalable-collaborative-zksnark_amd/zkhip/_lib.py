@@ -58,6 +58,9 @@ SYMBOLS = [
     ("zk_witness_plan_info", _i, [_vp, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t)]),
     ("zk_plonk_witness", _i, [_vp, _vp, _i, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
     ("zk_plonk_witness_check", _i, [_vp, _vp, _i, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
+    ("zk_witness_plan_create_lookup", _i, [_vp, _vp, _vp, _vp, _vp, _sz, _pp]),
+    ("zk_plonk_witness_lookup", _i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
+    ("zk_plonk_witness_check_lookup", _i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
     ("zk_lookup3_terms", _i, [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
     ("zk_sumcheck_lookup_sel", _i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp]),
     ("zk_eq_table_acc", _i, [_vp, _vp, _sz, _vp, _vp]),

@@ -189,19 +189,25 @@ class PcsVk:
 
 
 class WitnessPlan:
-    """zk_witness_plan: the witness plan of one Plonk circuit (sources, levels, launch schedule), held by the library"""
+    """zk_witness_plan: the witness plan of one Plonk circuit (sources, levels, launch schedule and, built with qk and ts, the key table
+    of its lookup), held by the library"""
 
-    def __init__(self, ctx: "Ctx", sigma, N: int, out_sel=None):
+    def __init__(self, ctx: "Ctx", sigma, N: int, out_sel=None, qk=None, ts=None):
         self.ctx, self.h, self.N = ctx, 0, int(N)
         sg = np.ascontiguousarray(sigma, dtype=np.uint64).reshape(-1)
         if len(sg) != 3 * self.N:
             raise ValueError(f"sigma must hold {3 * self.N} slot numbers")
+        if (qk is None) != (ts is None) or (ts is not None and len(ts) != 3):
+            raise ValueError("a lookup plan needs qk and the three table columns")
         h = ctypes.c_void_p()
-        rc = ctx.lib.zk_witness_plan_create(ctx.h, _h(sg), _ptr(out_sel), self.N, ctypes.byref(h))
+        if qk is None:
+            rc = ctx.lib.zk_witness_plan_create(ctx.h, _h(sg), _ptr(out_sel), self.N, ctypes.byref(h))
+        else:
+            rc = ctx.lib.zk_witness_plan_create_lookup(ctx.h, _h(sg), _ptr(out_sel), _ptr(qk), ctx._ptr_array(ts), self.N, ctypes.byref(h))
         if rc == ZK_ERR_INVALID:
             raise ValueError((ctx.lib.zk_last_error(ctx.h) or b"").decode())
         ctx._check(rc)
-        self.h, self.wide = h.value, out_sel is not None
+        self.h, self.wide, self.lookup = h.value, out_sel is not None, qk is not None
 
     def info(self) -> dict:
         """{"levels", "max_level_rows", "launches"} (zk_witness_plan_info)"""
@@ -648,29 +654,49 @@ class Ctx:
         rows that depend on their own output: ValueError with the library's message."""
         return WitnessPlan(self, sigma, N, out_sel)
 
-    def plonk_witness(self, plan: WitnessPlan, sels, public_inputs: np.ndarray, free=None, out=None):
+    def witness_plan_lookup(self, sigma, N: int, out_sel, qk, ts) -> WitnessPlan:
+        """the witness plan of a circuit with its lookup (zk_witness_plan_create_lookup; blocking: the key table of (t0, t1) is built on
+        the device): qk and ts = (t0, t1, t2) device buffers of N Fr.  Beyond witness_plan's refusals: a qk entry that is neither 0 nor 1,
+        a table that is no function of (t0, t1) -- ValueError with the library's message."""
+        return WitnessPlan(self, sigma, N, out_sel, qk, ts)
+
+    def plonk_witness(self, plan: WitnessPlan, sels, public_inputs: np.ndarray, free=None, out=None, qk=None, ts=None):
         """a, b, c generated on the device (zk_plonk_witness; blocking): sels the gate's selectors (2: basic, 6: wide) as device buffers,
         public_inputs [l, 4], free a device buffer of 3N Fr or None -> (a, b, c), device buffers of N Fr.  A bad gate row or copy:
-        ValueError with the library's message."""
+        ValueError with the library's message.  With qk and ts = (t0, t1, t2), the ones a lookup plan was built from:
+        zk_plonk_witness_lookup (a bad lookup is refused in the same way)."""
         N = plan.N
         pi = np.ascontiguousarray(public_inputs, dtype=np.uint64).reshape(-1, 4)
         a, b, c = out or tuple(self.alloc(32 * N) for _ in range(3))
-        rc = self.lib.zk_plonk_witness(self.h, plan.h, int(len(sels) == 6), self._ptr_array(sels), _h(pi), len(pi), _ptr(free), _ptr(a), _ptr(b), _ptr(c))
+        if qk is None and ts is None:
+            rc = self.lib.zk_plonk_witness(self.h, plan.h, int(len(sels) == 6), self._ptr_array(sels), _h(pi), len(pi), _ptr(free), _ptr(a), _ptr(b), _ptr(c))
+        else:
+            rc = self.lib.zk_plonk_witness_lookup(self.h, plan.h, int(len(sels) == 6), self._ptr_array(sels), _ptr(qk), self._ptr_array(ts), _h(pi), len(pi), _ptr(free),
+                                                  _ptr(a), _ptr(b), _ptr(c))
         if rc == ZK_ERR_INVALID:
             raise ValueError((self.lib.zk_last_error(self.h) or b"").decode())
         self._check(rc)
         return a, b, c
 
-    def plonk_witness_check(self, plan: WitnessPlan, sels, public_inputs: np.ndarray, a, b, c) -> dict:
-        """zk_plonk_witness_check (blocking) -> {"bad_rows", "first_bad_row", "bad_copies", "first_bad_copy"} (the firsts None when there is none)"""
+    def plonk_witness_check(self, plan: WitnessPlan, sels, public_inputs: np.ndarray, a, b, c, qk=None, ts=None) -> dict:
+        """zk_plonk_witness_check (blocking) -> {"bad_rows", "first_bad_row", "bad_copies", "first_bad_copy"} (the firsts None when there is none).
+        With qk and ts = (t0, t1, t2) of a lookup plan: zk_plonk_witness_check_lookup, and the dict gains "bad_lookups", "first_bad_lookup"."""
         pi = np.ascontiguousarray(public_inputs, dtype=np.uint64).reshape(-1, 4)
-        bad = np.zeros(4, dtype=np.uint64)
-        rc = self.lib.zk_plonk_witness_check(self.h, plan.h, int(len(sels) == 6), self._ptr_array(sels), _h(pi), len(pi), _ptr(a), _ptr(b), _ptr(c), _h(bad))
+        lookup = not (qk is None and ts is None)
+        bad = np.zeros(6 if lookup else 4, dtype=np.uint64)
+        if lookup:
+            rc = self.lib.zk_plonk_witness_check_lookup(self.h, plan.h, int(len(sels) == 6), self._ptr_array(sels), _ptr(qk), self._ptr_array(ts), _h(pi), len(pi), _ptr(a),
+                                                        _ptr(b), _ptr(c), _h(bad))
+        else:
+            rc = self.lib.zk_plonk_witness_check(self.h, plan.h, int(len(sels) == 6), self._ptr_array(sels), _h(pi), len(pi), _ptr(a), _ptr(b), _ptr(c), _h(bad))
         if rc == ZK_ERR_INVALID:
             raise ValueError((self.lib.zk_last_error(self.h) or b"").decode())
         self._check(rc)
-        r, fr, k, fk = (int(x) for x in bad)
-        return {"bad_rows": r, "first_bad_row": fr if r else None, "bad_copies": k, "first_bad_copy": fk if k else None}
+        r, fr, k, fk = (int(x) for x in bad[:4])
+        out = {"bad_rows": r, "first_bad_row": fr if r else None, "bad_copies": k, "first_bad_copy": fk if k else None}
+        if lookup:
+            out.update(bad_lookups=int(bad[4]), first_bad_lookup=int(bad[5]) if bad[4] else None)
+        return out
 
     def lookup3_terms(self, ws, ts, N: int, zeta: np.ndarray, beta: np.ndarray):
         """df = beta + a + zeta b + zeta^2 c, dt = beta + t0 + zeta t1 + zeta^2 t2 in one pass (zk_lookup3_terms; asynchronous) -> (df, dt),

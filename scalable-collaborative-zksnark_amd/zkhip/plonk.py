@@ -77,6 +77,18 @@ zk_plonk_witness, zk_plonk_witness_check); preprocess and prove are not involved
   * the check: row x is a bad gate row when the gate identity does not hold on it (after generation only a non-computing row can be);
     slot s is a bad copy when its value differs from its class's value (after generation only a further computing c slot can be).  On
     caller-given a, b, c every row and slot can fail.
+A plan built with lookup=True also knows the circuit's lookup (zk_witness_plan_create_lookup; additive -- without it the rules above hold
+and nothing else):
+  * the table must be a FUNCTION of its first two columns: two entries with equal (t0, t1) have equal t2 (repeating a whole entry is
+    allowed); otherwise the plan is refused ("K of N table entries repeat the pair (t0, t1) of an earlier entry with another t2" and the
+    smallest such entry), as it is for a qk entry that is neither 0 nor 1;
+  * row x is LOOKUP-COMPUTING when qk(x) = 1 and it is not gate-computing (wide gate: qO(x) = 0; basic gate: never).  Its c is t2[y] for
+    the smallest y with (t0, t1)[y] = (a, b)(x); without such a y its c is 0 and the check reports the row.  A row with qk = 1 that is
+    gate-computing stays gate-computing: the table only checks it.  "Computing" in the rules above means either kind;
+  * the check gains the BAD LOOKUPS: the rows with qk = 1 whose (a, b, c) is no table entry, of either kind; `witness` refuses them ("K
+    of N rows with qk = 1 hold a triple that is no table entry" and the smallest such row);
+  * on generated wires the index zk_lookup3_find gives for a lookup-computing row is the y the generator used, so
+    prove(..., idx=FIND) on them needs nothing from the generator.
 
 Record: {"mu", "l", "commitments": [3, 18] (a, b, c), "v_commitment": [18], "p_rounds": [mu, 6, 4], "g_rounds": [mu, 5, 4],
          "g_values": [5, 4], "p_values": [6, 4], "v_values": [5, 4], "batch": {"rounds": [mu, 3, 4], "opening": [mu, 18]},
@@ -353,42 +365,72 @@ def prove(be, pk: dict, a, b, c, public_inputs, idx=None, timing: dict | None = 
 
 
 # ---- witness ----
-def witness_plan(be, circuit: dict):
+def witness_plan(be, circuit: dict, lookup: bool = False):
     """the witness plan of a circuit {"mu", "sigma", and with "gate": "wide" the output selector "qO"} (module text, WITNESS): built once per
     circuit on the host inside the library (Ctx.witness_plan).  A sigma that is not a permutation, or rows that depend on their own
-    output: ValueError."""
+    output: ValueError.  lookup=True: the plan of the circuit WITH its "lookup" (required then; Ctx.witness_plan_lookup builds the key
+    table of (t0, t1) on the device) -- a qk that is not 0 / 1 or a table that is no function of (t0, t1): ValueError.  The default
+    ignores a lookup the circuit may carry."""
     gate = gate_of(circuit)
     N = 1 << int(circuit["mu"])
     qo = be.to_device(_u64(circuit["qO"], N, 4)) if gate.kind == "wide" else None
-    return be.witness_plan(np.ascontiguousarray(circuit["sigma"], dtype=np.uint64).reshape(-1), N, qo)
+    sigma = np.ascontiguousarray(circuit["sigma"], dtype=np.uint64).reshape(-1)
+    if not lookup:
+        return be.witness_plan(sigma, N, qo)
+    if not has_lookup(circuit):
+        raise ValueError("lookup=True needs a circuit with a lookup")
+    lk = {k: be.to_device(_u64(circuit["lookup"][k], N, 4)) for k in LOOKUP_VK_TABLES}
+    return be.witness_plan_lookup(sigma, N, qo, lk["qk"], [lk[k] for k in LOOKUP_VK_TABLES[1:]])
+
+
+def witness_key(be, circuit: dict) -> dict:
+    """what witness / check_witness read of a proving key, without an SRS or commitments: mu, l, the gate kind and, on the device, the
+    selectors and -- for a circuit with a lookup -- qk, t0, t1, t2.  For callers that generate or check wires without proving."""
+    gate = gate_of(circuit)
+    N = 1 << int(circuit["mu"])
+    tabs = {k: be.to_device(_u64(circuit[k], N, 4)) for k in gate.selectors}
+    tag = gate.tag()
+    if has_lookup(circuit):
+        tabs.update({k: be.to_device(_u64(circuit["lookup"][k], N, 4)) for k in LOOKUP_VK_TABLES})
+        tag = dict(tag, lookup=True)
+    return {"mu": int(circuit["mu"]), "l": int(circuit["l"]), "tables": tabs, **tag}
 
 
 def _witness_args(pk: dict, plan, public_inputs):
+    """-> (selectors, public inputs, the keyword arguments of a lookup plan: qk and ts from the key's tables)"""
     gate = gate_of(pk)
     pi = _u64(public_inputs, -1, 4)
     if len(pi) != pk["l"]:
         raise ValueError(f"{pk['l']} public inputs needed, {len(pi)} given")
     if plan.N != 1 << pk["mu"] or plan.wide != (gate.kind == "wide"):
         raise ValueError("the plan is not one of this key's circuit")
-    return [pk["tables"][k] for k in gate.selectors], pi
+    lk = {}
+    if getattr(plan, "lookup", False):
+        if any(k not in pk["tables"] for k in LOOKUP_VK_TABLES):
+            raise ValueError("a lookup plan needs a key with the lookup's tables")
+        lk = {"qk": pk["tables"]["qk"], "ts": [pk["tables"][k] for k in LOOKUP_VK_TABLES[1:]]}
+    return [pk["tables"][k] for k in gate.selectors], pi, lk
 
 
 def witness(be, pk: dict, plan, public_inputs, free=None):
     """the wires of pk's circuit from its public inputs ([l, 4] Montgomery Fr) and the values of its free classes (free: [3N, 4] array or
     device buffer, read at the smallest slot of every free class; None: zeros) -> (a, b, c), device buffers of N Fr that go straight into
-    `prove`.  A witness that breaks a gate or a copy constraint: ValueError ("K of N rows ..." / "K of 3N slots ...")."""
-    sels, pi = _witness_args(pk, plan, public_inputs)
+    `prove`.  A witness that breaks a gate or a copy constraint: ValueError ("K of N rows ..." / "K of 3N slots ...").  On a lookup plan
+    (witness_plan(..., lookup=True)) the lookup-computing rows take their c from pk's table, and a row with qk = 1 whose triple is no
+    table entry is refused too."""
+    sels, pi, lk = _witness_args(pk, plan, public_inputs)
     if isinstance(free, np.ndarray):
         free = be.to_device(_u64(free, 3 * plan.N, 4))
-    return be.plonk_witness(plan, sels, pi, free)
+    return be.plonk_witness(plan, sels, pi, free, **lk)
 
 
 def check_witness(be, pk: dict, plan, a, b, c, public_inputs) -> dict:
     """any a, b, c (device buffers or [N, 4] arrays) against the gate identity and the copy constraints of pk's circuit ->
-    {"bad_rows", "first_bad_row", "bad_copies", "first_bad_copy"}: the counts and the smallest row / slot (None: none)"""
-    sels, pi = _witness_args(pk, plan, public_inputs)
+    {"bad_rows", "first_bad_row", "bad_copies", "first_bad_copy"}: the counts and the smallest row / slot (None: none); on a lookup plan
+    also {"bad_lookups", "first_bad_lookup"}"""
+    sels, pi, lk = _witness_args(pk, plan, public_inputs)
     a, b, c = ((be.to_device(_u64(v, plan.N, 4)) if isinstance(v, np.ndarray) else v) for v in (a, b, c))
-    return be.plonk_witness_check(plan, sels, pi, a, b, c)
+    return be.plonk_witness_check(plan, sels, pi, a, b, c, **lk)
 
 
 # ---- verifier ----
@@ -812,4 +854,88 @@ def sample_circuit_lookup(mu: int, seed: int, gate: str | None = None, break_loo
     qk[mask] = fr_mont(1)
     circuit["lookup"] = {"qk": qk, "t0": pad(u), "t1": pad(v), "t2": pad(uv)}
     circuit["idx"] = np.where(mask, y, 0).astype(np.uint32)
+    return circuit
+
+
+def sample_circuit_lookup_fn(mu: int, seed: int, break_row: int | None = None) -> dict:
+    """
+    A satisfied WIDE-gate circuit whose lookup rows have the gate switched off: the table, not the gate, gives their c (numpy and python
+    ints only): N = 2^mu rows, mu >= 3, l = min(4, N / 2).
+    Table: XOR on k = min(4, mu // 2) bits -- entry y < 4^k is (y >> k, y & (2^k - 1), their XOR), padded to N by repeating the last entry.
+    Streams of field.splitmix_fr: 1 = the l public inputs and 5 = the SRS trapdoor as in sample_circuit, 14 = the picks of this sampler.
+      rows 0 .. l - 1   input rows: qO = 1, every other selector 0, a = b = 0, c = the public input;
+      row x >= l        its kind is limb 2 of pick x mod 8:
+                          0 .. 5  LOOKUP  every gate selector 0, qk = 1, c = a XOR b.  a is a copy of the c of an earlier lookup row when
+                                  bits 3 .. 5 of limb 2 are all 0 and there is one -- the (limb 0 mod E)-th of the E earlier lookup rows --
+                                  and otherwise FREE: the slot is a fixed point of sigma and holds limb 3 & (2^k - 1).  b likewise with
+                                  bits 6 .. 8, limb 1 and (limb 3 >> 8) & (2^k - 1).  XOR outputs stay below 2^k, so chains arise;
+                          6       linear   qL = qR = qO = 1: c = a + b      with a = c[limb 0 mod x], b = c[limb 1 mod x] (any earlier row);
+                          7       product  qM = qO = 1:      c = a b        likewise.
+    sigma: one cycle per copied c -- its c slot, then the slots that copy it in ascending order; every other slot is a fixed point.
+    break_row K (a lookup row with a free a) adds 2^k to that free value: the pair is in no entry, the row's c is 0 as the witness
+    generator leaves it, and idx[K] = 0.
+    -> the dict of sample_circuit_wide plus "lookup": {"qk", "t0", "t1", "t2": [N, 4] Montgomery Fr}, "free": [3N, 4] (the free values at
+       their slots, 0 elsewhere) and "idx": u32[N], the first-occurrence indices as lookup.find_indices_host gives them
+    """
+    from .field import splitmix_fr
+
+    if mu < 3:
+        raise ValueError("mu >= 3 is needed")
+    N, base = 1 << mu, CIRCUIT_SEED + 1000 * seed
+    l, k = min(4, N // 2), min(4, mu // 2)
+    D, low = 1 << (2 * k), (1 << k) - 1
+    pi, pick = splitmix_fr(l, base + 1), splitmix_fr(N, base + 14).tolist()
+    sel = {q: [0] * N for q in WIDE_SELECTORS}
+    qk, idx, free = [0] * N, [0] * N, [0] * (3 * N)
+    a, b, c = [0] * N, [0] * N, _ints(pi) + [0] * (N - l)
+    users = {}       # row y -> the slots that copy c[y], in ascending order per column
+    lookups = []     # the lookup rows so far
+    for x in range(l):
+        sel["qO"][x] = 1
+    for x in range(l, N):
+        p0, p1, p2, p3 = pick[x]
+        kind = p2 % 8
+        if kind < 6:
+            qk[x] = 1
+            for j, (w, bits, p, small) in enumerate(((a, (p2 >> 3) & 7, p0, p3 & low), (b, (p2 >> 6) & 7, p1, (p3 >> 8) & low))):
+                if bits == 0 and lookups:
+                    y = lookups[p % len(lookups)]
+                    w[x] = c[y]
+                    users.setdefault(y, []).append(j * N + x)
+                else:
+                    if j == 0 and x == break_row:
+                        small += 1 << k
+                    w[x] = free[j * N + x] = small
+            if x == break_row and free[x] < (1 << k):
+                raise ValueError("break_row must name a lookup row with a free a")
+            hit = a[x] <= low and b[x] <= low
+            c[x] = a[x] ^ b[x] if hit else 0
+            idx[x] = (a[x] << k) | b[x] if hit else 0
+            lookups.append(x)
+        else:
+            ya, yb = p0 % x, p1 % x
+            a[x], b[x] = c[ya], c[yb]
+            users.setdefault(ya, []).append(x)
+            users.setdefault(yb, []).append(N + x)
+            sel["qO"][x] = 1
+            if kind == 6:
+                sel["qL"][x] = sel["qR"][x] = 1
+                c[x] = (a[x] + b[x]) % R_MOD
+            else:
+                sel["qM"][x] = 1
+                c[x] = a[x] * b[x] % R_MOD
+    if break_row is not None and not (l <= break_row < N and qk[break_row]):
+        raise ValueError("break_row must name a lookup row with a free a")
+    sigma = np.arange(3 * N, dtype=np.uint64)
+    for y, slots in users.items():
+        cyc = [2 * N + y] + sorted(slots)
+        for s, t in zip(cyc, cyc[1:] + cyc[:1]):
+            sigma[s] = t
+    mont = lambda xs: _limbs([(x << 256) % R_MOD for x in xs])
+    ys = [min(y, D - 1) for y in range(N)]
+    circuit = {"gate": "wide", "mu": mu, "l": l, "a": mont(a), "b": mont(b), "c": mont(c), "sigma": sigma, "public_inputs": pi, "s": splitmix_fr(mu + 1, base + 5)}
+    circuit.update({q: mont(v) for q, v in sel.items()})
+    circuit["lookup"] = {"qk": mont(qk), "t0": mont([y >> k for y in ys]), "t1": mont([y & low for y in ys]), "t2": mont([(y >> k) ^ (y & low) for y in ys])}
+    circuit["free"] = mont(free)
+    circuit["idx"] = np.array(idx, dtype=np.uint32)
     return circuit

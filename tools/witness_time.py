@@ -9,6 +9,13 @@ of the compiled host.  The witness time does NOT include the plan build (once pe
 counterpart of the plan, its sigma construction, is not in the loop time either.  Writes profiles/witness_time.txt.
 
     python tools/witness_time.py [--mu 16 20] [--gate wide] [--reps 20] [--out profiles/witness_time.txt]
+
+--lookup-fn: what a lookup-computing row costs.  zk_plonk_witness_lookup on plonk.sample_circuit_lookup_fn (lookup rows with the gate
+switched off: their c comes from the XOR table) beside zk_plonk_witness on plonk.sample_circuit_wide of the same size -- the plain wide
+path, which a lookup plan does not touch, as the yardstick --, the plan build of each (the lookup plan's includes the key table, built on
+the device), the share of lookup-computing rows and the level counts.  The same protocol.  Writes profiles/witness_lookup_time.txt.
+
+    python tools/witness_time.py --lookup-fn [--mu 16 20] [--reps 20] [--out profiles/witness_lookup_time.txt]
 """
 import argparse
 import os
@@ -42,19 +49,62 @@ def host_loop_ms(mu, seed, wide, reps):
     return float(re.search(r"sample row loop seconds ([0-9.]+)", r.stdout).group(1)) * 1e3
 
 
+def lookup_fn(ctx, o):
+    import numpy as np
+
+    from zkhip import plonk
+
+    lines = [f"# tools/witness_time.py --lookup-fn: seed={o.seed}; ms; every figure: warm-up 3, median of {o.reps} blocking calls, one process; the witness figures "
+             f"exclude the plan build; yardstick: zk_plonk_witness on sample_circuit_wide of the same size"]
+    for mu in o.mu:
+        N, row = 1 << mu, {}
+        for name, c, lk in (("lookup-fn", plonk.sample_circuit_lookup_fn(mu, o.seed), True), ("wide", plonk.sample_circuit_wide(mu, o.seed), False)):
+            pk, pi = plonk.witness_key(ctx, c), c["public_inputs"]
+            ts = []
+            for i in range(3 + o.reps):  # warm-up 3; every plan but the last is freed at once, outside the timed region
+                t = time.perf_counter()
+                plan = plonk.witness_plan(ctx, c, lookup=lk)
+                ts.append((time.perf_counter() - t) * 1e3)
+                if i < 2 + o.reps:
+                    plan.free()
+            plan_ms = statistics.median(ts[3:])
+            free = ctx.to_device(np.ascontiguousarray(c["free"], dtype=np.uint64)) if lk else None
+            out = []
+            wit_ms = median_ms(lambda: out.append(plonk.witness(ctx, pk, plan, pi, free)) or out.__delitem__(slice(0, -1)), o.reps, 3)
+            assert all((x.download((N, 4)) == c[k]).all() for x, k in zip(out[-1], "abc")), "the generated wires are not the sampler's"
+            row[name] = (wit_ms, plan_ms, plan.info())
+            if lk:
+                share = float(((c["lookup"]["qk"] != 0).any(axis=1) & (c["qO"] == 0).all(axis=1)).mean())
+        (lw, lp, li), (ww, wp, wi) = row["lookup-fn"], row["wide"]
+        lines.append(f"mu={mu}: zk_plonk_witness_lookup {lw:.3f} ({100 * share:.1f} % lookup-computing rows; levels={li['levels']} max_level_rows={li['max_level_rows']} "
+                     f"launches={li['launches']}; plan build {lp:.1f}) | zk_plonk_witness wide {ww:.3f} (levels={wi['levels']} max_level_rows={wi['max_level_rows']} "
+                     f"launches={wi['launches']}; plan build {wp:.1f}) | ratio {lw / ww:.2f}x")
+        print(lines[-1], flush=True)
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--lookup-fn", action="store_true")
     ap.add_argument("--mu", type=int, nargs="+", default=[16, 20])
     ap.add_argument("--gate", choices=["wide"], default=None)
     ap.add_argument("--seed", type=int, default=7)
     ap.add_argument("--reps", type=int, default=20)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "witness_time.txt"))
+    ap.add_argument("--out", default=None)
     o = ap.parse_args()
+    o.out = o.out or os.path.join(ROOT, "profiles", "witness_lookup_time.txt" if o.lookup_fn else "witness_time.txt")
     import zkhip
     from zkhip import dist_primitive as dp
     from zkhip import plonk
 
     ctx = zkhip.Ctx(0)
+    if o.lookup_fn:
+        lines = lookup_fn(ctx, o)
+        os.makedirs(os.path.dirname(os.path.abspath(o.out)), exist_ok=True)
+        with open(o.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+        ctx.close()
+        return
     lines = [f"# tools/witness_time.py: gate={o.gate or 'basic'} seed={o.seed}; ms; every figure: warm-up 3, median of {o.reps} blocking calls (device figures: one process; "
              f"host row loop: one process of the compiled host); zk_plonk_witness excludes the plan build, the host row loop excludes the draws and sigma"]
     for mu in o.mu:
