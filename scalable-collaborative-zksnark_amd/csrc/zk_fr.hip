@@ -1231,6 +1231,9 @@ static int sc_validate(zk_ctx* ctx, const ScCall& c) {
     if (c.mode < 0 || c.mode > 3) return fail(ctx, ZK_ERR_INVALID, "bad mode");
     if (c.len == 0 || (c.len & (c.len - 1))) return fail(ctx, ZK_ERR_INVALID, "table length %zu is not a power of two", c.len);
     if (c.rounds > (size_t)ilog2(c.len)) return fail(ctx, ZK_ERR_INVALID, "more rounds than variables");
+    // a knob value the launches cannot honour is an error, not a silent default (launch_local knows these two workgroup sizes only)
+    const long lt = tuning().sc_local_threads;
+    if (lt != 256 && lt != kLocalThreads) return fail(ctx, ZK_ERR_INVALID, "knob sc_local_threads = %ld: a local-stage workgroup has 256 or 1024 threads", lt);
     return ZK_OK;
 }
 
