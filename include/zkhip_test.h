@@ -31,6 +31,24 @@ int zk_dbg_g1_op(zk_ctx *ctx, int mode, const void *d_p96, const void *d_q96, vo
  * mode 0: p+q  1: (p+q)+p  2: (p+q)+(p+q) (full-addition doubling path)  3: p-q  4: 2(p+q) (doubling)  5: (p+q)-(p+q) */
 int zk_dbg_g2_op(zk_ctx *ctx, int mode, const void *d_p192, const void *d_q192, void *h_out, size_t n);
 
+/* The XYZZ group formulas of the MSM (csrc/curve30.cuh for G1, csrc/curve30_g2.cuh for G2: zk_dbg_xyzz2_op) one operation at a time, at
+ * chosen representatives.  d_a, d_b: n operands of four coordinates X, Y, ZZ, ZZZ, each an integer below q in 48 bytes little-endian,
+ * re-limbed as they are (no Montgomery conversion); for G2 eight integers per operand, c0 then c1 of every coordinate.  d_lift_a,
+ * d_lift_b: n u32, one nibble per coordinate from bit 0 up (per component for G2): the coordinate becomes value + k q by additions of q,
+ * k clamped to what the invariant X < 8q, Y < 4q, ZZ < 2q, ZZZ < 2q allows (7, 3, 1, 1).  ZZ = 0 with lift 0 is infinity.  d_out: the raw
+ * result, 13 u32 limbs per coordinate (per component) at a 64-byte stride, 256 B (G2: 512 B) per element; nothing is reduced or normalised.
+ * d_rep: n u32 (mode 6 only, may be null otherwise).  All pointers are device memory.
+ * mode 0: madd(acc = a, p = (b.X, b.Y))   1: the same with neg   (b with lift 0: the affine operand)
+ *      2: add(a, b)   3: dbl(a)   4: dbl_affine(a.X, a.Y)   (3, 4 do not read d_b, d_lift_b: may be null)
+ *      5: add_quad, four lanes per element: a_i is stored at index i and b_i at index N + i (N = n rounded up to 64) of a scratch array in
+ *         the blocked 64-point chunk layout, the sums are read back with xyzz30_load / xyzz2_load
+ *      6: acc_quad, four lanes per element: acc = a_i, then d_rep[i] (at most 3) times acc += b_i from the same scratch array
+ * ZK_ERR_INVALID for an unknown mode or a null pointer, before any launch. */
+int zk_dbg_xyzz_op(zk_ctx *ctx, int mode, const void *d_a, const void *d_lift_a, const void *d_b, const void *d_lift_b, const void *d_rep,
+                   void *d_out, size_t n);
+int zk_dbg_xyzz2_op(zk_ctx *ctx, int mode, const void *d_a, const void *d_lift_a, const void *d_b, const void *d_lift_b, const void *d_rep,
+                    void *d_out, size_t n);
+
 /* The Fq layer of the pairing (csrc/fq30.cuh: 13 limbs of 30 bits, lazily reduced) at chosen representatives.  d_x, d_y: n integers
  * below q, 48 bytes little-endian, re-limbed as they are (no Montgomery conversion); d_kx, d_ky: n u32 <= 15.  Lane i works on
  * a = x + kx q and b = y + ky q (built by additions of q, so every representative below 16q).  d_out: 13 u32 limbs of the raw result

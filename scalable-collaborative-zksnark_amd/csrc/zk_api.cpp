@@ -802,5 +802,15 @@ int zk_dbg_fq12_op(zk_ctx* ctx, int mode, const void* d_a, const void* d_b, cons
     if (!ctx) return ZK_ERR_INVALID;
     return dbg_fq12_op(ctx, mode, d_a, d_b, d_lift, d_out, d_flags, n);
 }
+int zk_dbg_xyzz_op(zk_ctx* ctx, int mode, const void* d_a, const void* d_lift_a, const void* d_b, const void* d_lift_b, const void* d_rep,
+                   void* d_out, size_t n) {
+    if (!ctx) return ZK_ERR_INVALID;  // (which pointers a mode needs is decided by dbg_xyzz_op)
+    return dbg_xyzz_op(ctx, mode, d_a, d_lift_a, d_b, d_lift_b, d_rep, d_out, n);
+}
+int zk_dbg_xyzz2_op(zk_ctx* ctx, int mode, const void* d_a, const void* d_lift_a, const void* d_b, const void* d_lift_b, const void* d_rep,
+                    void* d_out, size_t n) {
+    if (!ctx) return ZK_ERR_INVALID;
+    return dbg_xyzz2_op(ctx, mode, d_a, d_lift_a, d_b, d_lift_b, d_rep, d_out, n);
+}
 
 }  // extern "C"

@@ -1487,6 +1487,183 @@ static __global__ void __launch_bounds__(kBlk) k_dbg_g1(const void* __restrict__
 }
 
 #endif
+// ---- test hooks zk_dbg_xyzz_op / zk_dbg_xyzz2_op (include/zkhip_test.h): the group formulas at chosen representatives ----
+// x + k q by k carry-normalised additions of the limbs of q, k clamped to the invariant's maximum of the coordinate
+__device__ __forceinline__ Fq30 dbgx_plus_kq(Fq30 x, u32 k, u32 kmax) {
+    Fq30 q;
+#pragma unroll
+    for (int i = 0; i < 13; i++) q.l[i] = Q30::Q(i);
+    k = k > kmax ? kmax : k;
+    for (u32 j = 0; j < k; j++) x = f30_add(x, q);
+    return x;
+}
+__device__ __forceinline__ void dbgx_raw(u32* __restrict__ out, size_t slot, const Fq30& v) {  // 13 raw limbs at a 64-byte stride
+#pragma unroll
+    for (int k = 0; k < 16; k++) out[slot * 16 + k] = k < 13 ? v.l[k] : 0u;
+}
+enum { kXzMadd = 0, kXzMaddNeg, kXzAdd, kXzDbl, kXzDblAffine, kXzAddQuad, kXzAccQuad, kXzModes };
+static bool dbgx_binary(int mode) { return mode != kXzDbl && mode != kXzDblAffine; }
+#ifndef ZK_MSM_TU_G2  // (G1 translation unit only)
+// operand i: X | Y | ZZ | ZZZ, 48-byte integers below q, internal form; lift[i]: one nibble per coordinate
+__device__ __forceinline__ Xyzz30 dbgx_load(const void* __restrict__ p, const u32* __restrict__ lift, size_t i) {
+    const u32 lf = lift[i];
+    Xyzz30 r;
+    r.x = dbgx_plus_kq(f30_load(p, i * 192), lf & 15u, 7);
+    r.y = dbgx_plus_kq(f30_load(p, i * 192 + 48), (lf >> 4) & 15u, 3);
+    r.zz = dbgx_plus_kq(f30_load(p, i * 192 + 96), (lf >> 8) & 15u, 1);
+    r.zzz = dbgx_plus_kq(f30_load(p, i * 192 + 144), (lf >> 12) & 15u, 1);
+    return r;
+}
+__device__ __forceinline__ void dbgx_store_raw(u32* __restrict__ out, size_t i, const Xyzz30& r) {
+    dbgx_raw(out, 4 * i, r.x);
+    dbgx_raw(out, 4 * i + 1, r.y);
+    dbgx_raw(out, 4 * i + 2, r.zz);
+    dbgx_raw(out, 4 * i + 3, r.zzz);
+}
+// modes 0..4: one lane per element
+static __global__ void __launch_bounds__(64) k_dbg_xyzz(size_t n, int mode, const void* __restrict__ pa, const u32* __restrict__ la,
+                                                        const void* __restrict__ pb, const u32* __restrict__ lb, u32* __restrict__ out) {
+    const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    Xyzz30 a = dbgx_load(pa, la, i), r;
+    if (mode == kXzMadd || mode == kXzMaddNeg) {
+        const Xyzz30 b = dbgx_load(pb, lb, i);
+        r = a;
+        xyzz30_madd(r, Aff30{b.x, b.y}, mode == kXzMaddNeg);
+    } else if (mode == kXzAdd) {
+        r = xyzz30_add(a, dbgx_load(pb, lb, i));
+    } else if (mode == kXzDbl) {
+        r = xyzz30_dbl(a);
+    } else {
+        r = xyzz30_dbl_affine(a.x, a.y);
+    }
+    dbgx_store_raw(out, i, r);
+}
+// modes 5, 6: A_i at index i, B_i at index N + i of a scratch array in the chunk layout
+static __global__ void __launch_bounds__(64) k_dbg_xyzz_fill(size_t n, size_t N, const void* __restrict__ pa, const u32* __restrict__ la,
+                                                             const void* __restrict__ pb, const u32* __restrict__ lb, void* __restrict__ arr) {
+    const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    xyzz30_store(arr, i, dbgx_load(pa, la, i));
+    xyzz30_store(arr, N + i, dbgx_load(pb, lb, i));
+}
+// four lanes per element; mode 5: sums[i] = arr[i] + arr[N + i] (chunk layout); mode 6: rep[i] times acc += arr[N + i], raw to out
+static __global__ void __launch_bounds__(kBlk) k_dbg_xyzz_quad(size_t n, size_t N, int mode, const void* __restrict__ arr, void* __restrict__ sums,
+                                                               const void* __restrict__ pa, const u32* __restrict__ la,
+                                                               const u32* __restrict__ rep, u32* __restrict__ out) {
+    const size_t tq = (size_t)blockIdx.x * kBlk + threadIdx.x;
+    const size_t g = tq >> 2;
+    const int role = (int)(tq & 3);
+    if (g >= n) return;  // whole quads leave together
+    if (mode == kXzAddQuad) {
+        xyzz30_add_quad(arr, g, N + g, sums, g, role);
+        return;
+    }
+    Xyzz30 acc = dbgx_load(pa, la, g);
+    const u32 trips = rep[g] > 3u ? 3u : rep[g];
+    for (u32 t = 0; t < trips; t++) acc = xyzz30_acc_quad(acc, arr, N + g, role);
+    if (role == 0) dbgx_store_raw(out, g, acc);
+}
+static __global__ void __launch_bounds__(64) k_dbg_xyzz_read(size_t n, const void* __restrict__ sums, u32* __restrict__ out) {
+    const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
+    if (i < n) dbgx_store_raw(out, i, xyzz30_load(sums, i));
+}
+#else  // (G2 translation unit only): the same with every coordinate a pair, c0 then c1
+__device__ __forceinline__ Fq2x dbgx_load2(const void* __restrict__ p, size_t off, u32 lf, u32 kmax) {
+    return Fq2x{dbgx_plus_kq(f30_load(p, off), lf & 15u, kmax), dbgx_plus_kq(f30_load(p, off + 48), (lf >> 4) & 15u, kmax)};
+}
+__device__ __forceinline__ Xyzz2 dbgx_load(const void* __restrict__ p, const u32* __restrict__ lift, size_t i) {
+    const u32 lf = lift[i];
+    Xyzz2 r;
+    r.x = dbgx_load2(p, i * 384, lf, 7);
+    r.y = dbgx_load2(p, i * 384 + 96, lf >> 8, 3);
+    r.zz = dbgx_load2(p, i * 384 + 192, lf >> 16, 1);
+    r.zzz = dbgx_load2(p, i * 384 + 288, lf >> 24, 1);
+    return r;
+}
+__device__ __forceinline__ void dbgx_store_raw(u32* __restrict__ out, size_t i, const Xyzz2& r) {
+    dbgx_raw(out, 8 * i, r.x.c0);
+    dbgx_raw(out, 8 * i + 1, r.x.c1);
+    dbgx_raw(out, 8 * i + 2, r.y.c0);
+    dbgx_raw(out, 8 * i + 3, r.y.c1);
+    dbgx_raw(out, 8 * i + 4, r.zz.c0);
+    dbgx_raw(out, 8 * i + 5, r.zz.c1);
+    dbgx_raw(out, 8 * i + 6, r.zzz.c0);
+    dbgx_raw(out, 8 * i + 7, r.zzz.c1);
+}
+static __global__ void __launch_bounds__(64) k_dbg_xyzz(size_t n, int mode, const void* __restrict__ pa, const u32* __restrict__ la,
+                                                        const void* __restrict__ pb, const u32* __restrict__ lb, u32* __restrict__ out) {
+    const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    Xyzz2 a = dbgx_load(pa, la, i), r;
+    if (mode == kXzMadd || mode == kXzMaddNeg) {
+        const Xyzz2 b = dbgx_load(pb, lb, i);
+        r = a;
+        xyzz2_madd(r, Aff2{b.x, b.y}, mode == kXzMaddNeg);
+    } else if (mode == kXzAdd) {
+        r = xyzz2_add(a, dbgx_load(pb, lb, i));
+    } else if (mode == kXzDbl) {
+        r = xyzz2_dbl(a);
+    } else {
+        r = xyzz2_dbl_affine(a.x, a.y);
+    }
+    dbgx_store_raw(out, i, r);
+}
+static __global__ void __launch_bounds__(64) k_dbg_xyzz_fill(size_t n, size_t N, const void* __restrict__ pa, const u32* __restrict__ la,
+                                                             const void* __restrict__ pb, const u32* __restrict__ lb, void* __restrict__ arr) {
+    const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    xyzz2_store(arr, i, dbgx_load(pa, la, i));
+    xyzz2_store(arr, N + i, dbgx_load(pb, lb, i));
+}
+static __global__ void __launch_bounds__(kBlk) k_dbg_xyzz_quad(size_t n, size_t N, int mode, const void* __restrict__ arr, void* __restrict__ sums,
+                                                               const void* __restrict__ pa, const u32* __restrict__ la,
+                                                               const u32* __restrict__ rep, u32* __restrict__ out) {
+    const size_t tq = (size_t)blockIdx.x * kBlk + threadIdx.x;
+    const size_t g = tq >> 2;
+    const int role = (int)(tq & 3);
+    if (g >= n) return;  // whole quads leave together
+    if (mode == kXzAddQuad) {
+        xyzz2_add_quad(arr, g, N + g, sums, g, role);
+        return;
+    }
+    Xyzz2 acc = dbgx_load(pa, la, g);
+    const u32 trips = rep[g] > 3u ? 3u : rep[g];
+    for (u32 t = 0; t < trips; t++) acc = xyzz2_acc_quad(acc, arr, N + g, role);
+    if (role == 0) dbgx_store_raw(out, g, acc);
+}
+static __global__ void __launch_bounds__(64) k_dbg_xyzz_read(size_t n, const void* __restrict__ sums, u32* __restrict__ out) {
+    const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
+    if (i < n) dbgx_store_raw(out, i, xyzz2_load(sums, i));
+}
+#endif
+// host side of both hooks (kPt: bytes of one XYZZ point in the chunk layout; `name`: for the error text)
+static int dbgx_run(zk_ctx* ctx, const char* name, size_t kPt, int mode, const void* d_a, const void* d_lift_a, const void* d_b,
+                    const void* d_lift_b, const void* d_rep, void* d_out, size_t n) {
+    if (mode < 0 || mode >= kXzModes) return fail(ctx, ZK_ERR_INVALID, "%s: unknown mode %d", name, mode);
+    if (!d_a || !d_lift_a || !d_out || (dbgx_binary(mode) && (!d_b || !d_lift_b)) || (mode == kXzAccQuad && !d_rep))
+        return fail(ctx, ZK_ERR_INVALID, "%s: null argument", name);
+    if (n == 0) return ZK_OK;
+    ZK_HIP(ctx, hipSetDevice(ctx->device));
+    const unsigned blocks = (unsigned)((n + 63) / 64);
+    if (mode < kXzAddQuad) {
+        hipLaunchKernelGGL(k_dbg_xyzz, dim3(blocks), dim3(64), 0, ctx->stream, n, mode, d_a, (const u32*)d_lift_a, d_b, (const u32*)d_lift_b,
+                           (u32*)d_out);
+    } else {
+        const size_t N = (n + 63) / 64 * 64;  // operands A at [0, N), B at [N, 2N), the sums of mode 5 at [2N, 3N)
+        char* arr = (char*)scratch(ctx, 3, 3 * N * kPt);
+        if (!arr) return ZK_ERR_OOM;
+        hipLaunchKernelGGL(k_dbg_xyzz_fill, dim3(blocks), dim3(64), 0, ctx->stream, n, N, d_a, (const u32*)d_lift_a, d_b, (const u32*)d_lift_b,
+                           (void*)arr);
+        hipLaunchKernelGGL(k_dbg_xyzz_quad, dim3((unsigned)((4 * n + kBlk - 1) / kBlk)), dim3(kBlk), 0, ctx->stream, n, N, mode,
+                           (const void*)arr, (void*)(arr + 2 * N * kPt), d_a, (const u32*)d_lift_a, (const u32*)d_rep, (u32*)d_out);
+        if (mode == kXzAddQuad)
+            hipLaunchKernelGGL(k_dbg_xyzz_read, dim3(blocks), dim3(64), 0, ctx->stream, n, (const void*)(arr + 2 * N * kPt), (u32*)d_out);
+    }
+    ZK_HIP(ctx, hipGetLastError());
+    ZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return ZK_OK;
+}
 #ifdef ZK_MSM_TU_G2  // (G2 translation unit only)
 // test hook: the G2 formulas on pairs of affine points (reference form, 192 B); output through CvG2::finish (288 B Jacobian)
 // mode 0: p + q   1: (p + q) + p   2: (p + q) + (p + q)   3: p - q   4: 2 (p + q) by the doubling   5: (p + q) - (p + q)
@@ -2708,6 +2885,10 @@ int dbg_g1_op(zk_ctx* ctx, int mode, const void* p, const void* q, void* h_out, 
     for (size_t i = 0; i < n; i++) zkhost::write_normalised(load_xyzz_host(&h[i * 24]), (uint64_t*)h_out + 18 * i);
     return ZK_OK;
 }
+int dbg_xyzz_op(zk_ctx* ctx, int mode, const void* d_a, const void* d_lift_a, const void* d_b, const void* d_lift_b, const void* d_rep,
+                void* d_out, size_t n) {
+    return dbgx_run(ctx, "zk_dbg_xyzz_op", 192, mode, d_a, d_lift_a, d_b, d_lift_b, d_rep, d_out, n);
+}
 
 #else
 namespace zk {
@@ -2729,6 +2910,10 @@ int dbg_g2_op(zk_ctx* ctx, int mode, const void* p, const void* q, void* h_out, 
         zkhost::write_normalised(j, (uint64_t*)h_out + 36 * i);
     }
     return ZK_OK;
+}
+int dbg_xyzz2_op(zk_ctx* ctx, int mode, const void* d_a, const void* d_lift_a, const void* d_b, const void* d_lift_b, const void* d_rep,
+                 void* d_out, size_t n) {
+    return dbgx_run(ctx, "zk_dbg_xyzz2_op", 384, mode, d_a, d_lift_a, d_b, d_lift_b, d_rep, d_out, n);
 }
 #endif
 

@@ -143,6 +143,8 @@ TEST_SYMBOLS = [
     ("zk_dbg_g2_op", _i, [_vp, _i, _vp, _vp, _vp, _sz]),
     ("zk_dbg_fq30_op", _i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz]),
     ("zk_dbg_fq12_op", _i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _sz]),
+    ("zk_dbg_xyzz_op", _i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz]),
+    ("zk_dbg_xyzz2_op", _i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz]),
 ]
 
 class ScItem(ctypes.Structure):

@@ -1151,3 +1151,14 @@ class Ctx:
         out, flags = self.alloc(max(576 * n, 1)), self.alloc(max(4 * n, 1))
         self._check(test_hooks().zk_dbg_fq12_op(self.h, self.FQ12_MODES.index(mode), _ptr(a), _ptr(b), _ptr(lift), _ptr(out), _ptr(flags), n))
         return out.download((n, 72)), flags.download((n,), np.uint32)
+
+    XYZZ_MODES = ("madd", "madd_neg", "add", "dbl", "dbl_affine", "add_quad", "acc_quad")
+
+    def dbg_xyzz(self, g2: bool, mode: str, a, lift_a, b, lift_b, rep, n):
+        """zk_dbg_xyzz_op / zk_dbg_xyzz2_op (g2) on device buffers (a, b: n operands of 4 (8) integers below q, 48 bytes each, internal
+        form; lift_a, lift_b, rep: n u32) -> raw limbs [n, 4 (8), 13] u32 in the order X, Y, ZZ, ZZZ (c0 then c1 for G2)"""
+        nc = 8 if g2 else 4
+        out = self.alloc(max(64 * nc * n, 1))
+        fn = test_hooks().zk_dbg_xyzz2_op if g2 else test_hooks().zk_dbg_xyzz_op
+        self._check(fn(self.h, self.XYZZ_MODES.index(mode), _ptr(a), _ptr(lift_a), _ptr(b), _ptr(lift_b), _ptr(rep), _ptr(out), n))
+        return out.download((n, nc, 16), np.uint32)[:, :, :13]
