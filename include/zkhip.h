@@ -643,6 +643,30 @@ int zk_pcs_vk_free(zk_ctx *ctx, zk_pcs_vk *vk);
 int zk_pcs_verify_batch(zk_ctx *ctx, const zk_pcs_vk *vk, size_t nvars, size_t count, const uint64_t *h_commitments,
                         const uint64_t *h_values, const uint64_t *h_proofs, const uint64_t *h_points, uint8_t *h_ok);
 
+/* ---- G1 points from outside: decompression and subgroup membership (csrc/zk_g1check.hip) ----------------------------------------
+ * This is the check zk_pairing / zk_pcs_verify_batch leave to their caller.  One device lane per point; a bad point is a STATUS,
+ * not an error: both functions return ZK_OK whenever they ran (count = 0 included), ZK_ERR_INVALID only for null pointers with
+ * count > 0.  Each call makes one synchronisation of the ctx stream.
+ *   status 0  ok: on the curve and in the prime-order subgroup (the point at infinity is a member)
+ *          1  bad encoding (zk_g1_check: a coordinate that is not canonical, >= q)
+ *          2  x is not the abscissa of a curve point (zk_g1_check: the point is not on the curve)
+ *          3  on the curve, not in G1
+ * Membership is phi(P) == -[x^2]P with phi(x, y) = (beta x, y), |x| = 0xd201000000010000 (Scott, "A note on group membership
+ * tests for G1, G2 and GT on BLS pairing-friendly curves"): two 64-bit scalar multiplications, complete for every input (equal
+ * and opposite operands, infinity on the way), constant trip counts. */
+#define ZK_G1_OK 0
+#define ZK_G1_BAD_ENCODING 1
+#define ZK_G1_NOT_ON_CURVE 2
+#define ZK_G1_NOT_IN_SUBGROUP 3
+/* h_in48: count x 48 bytes, the zcash / arkworks compressed encoding: big-endian x, top three bits of byte 0 = (compressed,
+ * infinity, y is the larger root: y > (q - 1) / 2).  Refused with status 1: the compressed bit clear; x >= q; the infinity bit
+ * together with any other bit or byte, the sign bit included.  h_out18: count x 18 u64 normalised Jacobian, Montgomery form,
+ * (x, y, 1) or (1, 1, 0) for infinity -- what zk_msm_g1 returns; written for status 0 and 3, all zero for status 1 and 2. */
+int zk_g1_decompress_check(zk_ctx *ctx, size_t count, const void *h_in48, uint64_t *h_out18, uint8_t *h_status);
+/* h_points18: count x 18 u64 Jacobian (X, Y, Z), Montgomery form, any representative; Z = 0 is infinity whatever X and Y are (as
+ * in zk_pcs_verify_batch).  The curve equation is checked as Y^2 == X^3 + 4 Z^6: no inversion. */
+int zk_g1_check(zk_ctx *ctx, size_t count, const uint64_t *h_points18, uint8_t *h_status);
+
 /* (the zk_dbg_* test hooks of the library are declared in include/zkhip_test.h: they are not part of this surface) */
 
 #ifdef __cplusplus

@@ -752,6 +752,14 @@ int zk_pcs_verify_batch(zk_ctx* ctx, const zk_pcs_vk* vk, size_t nvars, size_t c
     NEED(ctx, vk && (count == 0 || (h_commitments && h_values && h_ok && (nvars == 0 || (h_proofs && h_points)))));
     return pcs_verify_batch(ctx, vk, nvars, count, h_commitments, h_values, h_proofs, h_points, h_ok);
 }
+int zk_g1_decompress_check(zk_ctx* ctx, size_t count, const void* h_in48, uint64_t* h_out18, uint8_t* h_status) {
+    NEED(ctx, count == 0 || (h_in48 && h_out18 && h_status));
+    return g1_decompress_check(ctx, count, h_in48, h_out18, h_status);
+}
+int zk_g1_check(zk_ctx* ctx, size_t count, const uint64_t* h_points18, uint8_t* h_status) {
+    NEED(ctx, count == 0 || (h_points18 && h_status));
+    return g1_check(ctx, count, h_points18, h_status);
+}
 int zk_msm_window(size_t n) { return msm_pick_window(n); }
 int zk_msm_set_window(zk_ctx* ctx, int c) {
     if (!ctx || c < 0 || c > 20) return ZK_ERR_INVALID;

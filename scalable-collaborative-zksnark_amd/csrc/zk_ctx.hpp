@@ -354,6 +354,10 @@ int pcs_vk_create(zk_ctx* ctx, const void* h_g1_96, const void* h_powers_g2, siz
 void pcs_vk_free(zk_pcs_vk* vk);
 int pcs_verify_batch(zk_ctx* ctx, const zk_pcs_vk* vk, size_t nvars, size_t count, const uint64_t* h_comm, const uint64_t* h_values,
                      const uint64_t* h_proofs, const uint64_t* h_points, uint8_t* h_ok);
+// ---- zk_g1check.hip ----
+int g1_decompress_check(zk_ctx* ctx, size_t count, const void* h_in48, uint64_t* h_out18, uint8_t* h_status);
+int g1_check(zk_ctx* ctx, size_t count, const uint64_t* h_points18, uint8_t* h_status);
+// ---- zk_pairing.hip: test hooks ----
 int dbg_fq30_op(zk_ctx* ctx, int mode, const void* d_x, const void* d_kx, const void* d_y, const void* d_ky, void* d_out, void* d_flags,
                 size_t n);
 int dbg_fq12_op(zk_ctx* ctx, int mode, const void* d_a, const void* d_b, const void* d_lift, void* d_out, void* d_flags, size_t n);

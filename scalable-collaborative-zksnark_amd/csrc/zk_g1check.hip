@@ -1,0 +1,304 @@
+// zk_g1check.hip -- validation of G1 points that come from outside: decompression of the 48-byte zcash / arkworks encoding and
+// membership in the prime-order subgroup, one lane per point (zk_g1_decompress_check, zk_g1_check).
+//
+//   k_g1_decompress  48 bytes -> (x, y): flags, x < q, y = (x^3 + 4)^((q+1)/4), y^2 == x^3 + 4, the root the sign bit names
+//   k_g1_load_jac    18 u64 Jacobian (any representative) -> XYZZ: canonical coordinates, Y^2 == X^3 + 4 Z^6
+//   k_g1_subgroup    phi(P) == -[x^2]P  (Scott, "A note on group membership tests for G1, G2 and GT on BLS pairing-friendly curves"):
+//                    phi(x, y) = (beta x, y) acts on G1 as the root -x^2 of l^2 + l + 1 (x^4 - x^2 + 1 = r), and on no other point of
+//                    E(Fq) like it.  [x^2]P is two passes of 63 doublings and 5 additions (|x| = 0xd201000000010000), the comparison
+//                    is by cross-multiplication: no inversion.
+// The first two write the point as a flat XYZZ record (internal Montgomery form) and a status byte; the third reads both and turns a
+// status 0 into 3 when the point is outside G1.  Two kernels, not one: the square root is a chain of field elements (3 live values),
+// the scalar multiplication holds three points (12); kept apart each is allocated for what it needs, and zk_g1_check runs the second
+// one only.  Every loop has a constant trip count: the exponent and the scalar are constants, no input can make a lane spin.
+// The additions are complete (equal operands, opposite operands, infinity on either side): a point of order 3 has 2T = -T and meets
+// those cases in the first steps of the ladder.
+#include <hip/hip_runtime.h>
+
+#include "curve30.cuh"
+#include "zk_ctx.hpp"
+
+namespace zk {
+
+namespace g1c {
+__host__ __device__ constexpr u32 R2(int i) {  // 2^780 mod q: canonical integer -> internal form (x 2^390)
+    constexpr u32 t[13] = {0x0510070fu, 0x3b19070du, 0x0132243au, 0x299bb0e8u, 0x3507af6eu, 0x3b81ec77u, 0x21b145efu, 0x0a487bb4u, 0x370a4144u, 0x05dcb4cbu, 0x18c97900u, 0x3812b364u, 0x000f696eu};
+    return t[i];
+}
+__host__ __device__ constexpr u32 FOUR(int i) {  // 4 (the curve's b), internal form
+    constexpr u32 t[13] = {0x0347fcb8u, 0x27600000u, 0x12002b11u, 0x3803379bu, 0x090c7212u, 0x1a7e0e88u, 0x373e0376u, 0x26d0b683u, 0x17bb09b0u, 0x17663c4au, 0x12ca7c51u, 0x167f3e80u, 0x000577a6u};
+    return t[i];
+}
+// beta = 0x5f19672fdf76ce51ba69c6076a0f77eaddb3a93be6f89688de17d813620a00022e01fffffffefffe, internal form: the cube root of unity whose
+// endomorphism is multiplication by -x^2 on G1 (the other one belongs to x^2 - 1)
+__host__ __device__ constexpr u32 BETA(int i) {
+    constexpr u32 t[13] = {0x229d39fcu, 0x11661b79u, 0x3a68a8f8u, 0x09dabbd8u, 0x12744b7eu, 0x22bc97d4u, 0x3c5ccd3eu, 0x1cf87540u, 0x0197e4f4u, 0x3433d1ecu, 0x0d20861fu, 0x33953662u, 0x000edc53u};
+    return t[i];
+}
+__host__ __device__ constexpr u32 HALF(int i) {  // (q - 1) / 2, a plain integer
+    constexpr u32 t[13] = {0x3fffd555u, 0x33fdffffu, 0x0a9ffffdu, 0x157fffd6u, 0x187b120fu, 0x21a541edu, 0x2895fb39u, 0x29709e70u, 0x166bb23bu, 0x0f6c8697u, 0x34d258ddu, 0x3d472ffcu, 0x000d0088u};
+    return t[i];
+}
+// (q + 1) / 4 in 32-bit words, 379 bits
+__device__ const u32 kSqrtExp[12] = {0xffffeaabu, 0xee7fbfffu, 0xac54ffffu, 0x07aaffffu, 0x3dac3d89u, 0xd9cc34a8u, 0x3ce144afu, 0xd91dd2e1u, 0x90d2eb35u, 0x92c6e9edu, 0x8e5ff9a6u, 0x0680447au};
+constexpr int kSqrtBits = 379;
+constexpr unsigned long long kXAbs = 0xd201000000010000ULL;
+constexpr int kBlk = 64;
+enum : unsigned char { kOk = 0, kBadEncoding = 1, kNotOnCurve = 2, kNotInG1 = 3 };
+}  // namespace g1c
+
+#define ZK_G1C_CONST(name, T)                                    \
+    __device__ __forceinline__ Fq30 name() {                     \
+        Fq30 r;                                                  \
+        _Pragma("unroll") for (int i = 0; i < 13; i++) r.l[i] = T(i); \
+        return r;                                                \
+    }
+ZK_G1C_CONST(g1c_r2, g1c::R2)
+ZK_G1C_CONST(g1c_four, g1c::FOUR)
+ZK_G1C_CONST(g1c_beta, g1c::BETA)
+ZK_G1C_CONST(g1c_one_ref, Q30::C384)  // 2^384 mod q: the reference form of 1
+#undef ZK_G1C_CONST
+
+// v < q for a normalised v < 2^384
+__device__ __forceinline__ bool g1c_lt_q(const Fq30& v) {
+    u32 bw = 0;
+#pragma unroll
+    for (int i = 0; i < 13; i++) bw = (v.l[i] - Q30::Q(i) - bw) >> 31;
+    return bw != 0;
+}
+// v > (q - 1) / 2 for a canonical plain integer v
+__device__ __forceinline__ bool g1c_is_larger(const Fq30& v) {
+    u32 bw = 0;
+#pragma unroll
+    for (int i = 0; i < 13; i++) bw = (g1c::HALF(i) - v.l[i] - bw) >> 31;
+    return bw != 0;
+}
+__device__ __forceinline__ bool g1c_same(const Fq30& a, const Fq30& b) {  // canonical operands
+    u32 o = 0;
+#pragma unroll
+    for (int i = 0; i < 13; i++) o |= a.l[i] ^ b.l[i];
+    return o == 0;
+}
+__device__ __forceinline__ void g1c_store_words(void* base, size_t byte_off, int nwords16, u32 v) {  // nwords16 x 16 bytes of v
+    uint4* p = reinterpret_cast<uint4*>(reinterpret_cast<char*>(base) + byte_off);
+    for (int i = 0; i < nwords16; i++) p[i] = make_uint4(v, v, v, v);
+}
+// the 18-word result record: (x, y, 1), or (1, 1, 0) for infinity, reference Montgomery form
+__device__ __forceinline__ void g1c_store_jac(void* out, size_t i, const Fq30& x_ref, const Fq30& y_ref, bool inf) {
+    const Fq30 one = g1c_one_ref();
+    f30_store(out, i * 144, inf ? one : x_ref);
+    f30_store(out, i * 144 + 48, inf ? one : y_ref);
+    f30_store(out, i * 144 + 96, inf ? f30_zero() : one);
+}
+
+// 2p (dbl-2008-s-1, a = 0) and a + b below: the formulas of xyzz30_dbl / xyzz30_add of curve30.cuh, inlined.  There the doubling is a rare
+// path behind a call (__noinline__); here it IS the hot path.  k_g1_subgroup built on the curve30.cuh pair takes 255 VGPRs + 105 AGPRs
+// and 640 bytes of scratch per lane (the call's stack frame); with these two it takes 256 + 21 and none.  A change of either
+// formula must be made in both files; tests/test_gpu_g1check.py (this copy) and tests/test_gpu_xyzz.py (that one) check each against a model.
+__device__ __forceinline__ Xyzz30 g1c_dbl(const Xyzz30& p) {
+    if (xyzz30_is_inf(p)) return p;
+    Xyzz30 r;
+    const Fq30 U = f30_add(p.y, p.y);               // < 8q
+    const Fq30 V = f30_sqr(U);
+    const Fq30 W = f30_mul(U, V);
+    const Fq30 S = f30_mul(p.x, V);                 // 8q * 2q
+    const Fq30 xx = f30_sqr(p.x);                   // 64 q^2
+    const Fq30 M = f30_add(f30_add(xx, xx), xx);    // < 6q
+    const Fq30 X3 = f30_sub4(f30_sqr(M), f30_add(S, S));  // < 6q
+    r.y = f30_sub2(f30_mul(M, f30_sub8(S, X3)), f30_mul(W, p.y));  // < 4q
+    r.x = X3;
+    r.zz = f30_mul(V, p.zz);
+    r.zzz = f30_mul(W, p.zzz);
+    return r;
+}
+// a + b (add-2008-s), complete: xyzz30_add of curve30.cuh with the doubling inlined
+__device__ __forceinline__ Xyzz30 g1c_add(const Xyzz30& a, const Xyzz30& b) {
+    if (xyzz30_is_inf(a)) return b;
+    if (xyzz30_is_inf(b)) return a;
+    const Fq30 U1 = f30_mul(a.x, b.zz);       // 8q * 2q
+    const Fq30 U2 = f30_mul(b.x, a.zz);
+    const Fq30 S1 = f30_mul(a.y, b.zzz);      // 4q * 2q
+    const Fq30 S2 = f30_mul(b.y, a.zzz);
+    const Fq30 P = f30_sub2(U2, U1);          // < 4q
+    const Fq30 R = f30_sub2(S2, S1);          // < 4q
+    const Fq30 PP = f30_sqr(P);
+    const Fq30 PPP = f30_mul(P, PP);
+    const Fq30 Q = f30_mul(U1, PP);
+    const Fq30 ZZ3 = f30_mul(f30_mul(a.zz, b.zz), PP);
+    Xyzz30 r;
+    if (f30_is_zero_2q(ZZ3)) {  // same x: the same point or its opposite
+        if (f30_all_zero(f30_canon8(R))) r = g1c_dbl(a);
+        else xyzz30_set_inf(r);
+        return r;
+    }
+    r.x = f30_sub6(f30_sqr(R), f30_add2x(PPP, Q));                          // < 8q
+    r.y = f30_mul2add(R, f30_sub8(Q, r.x), f30_sub2(f30_zero(), S1), PPP);  // 4q*10q + 2q*2q -> < 2q
+    r.zz = ZZ3;
+    r.zzz = f30_mul(f30_mul(a.zzz, b.zzz), PPP);
+    return r;
+}
+
+// in48: count x 48 bytes.  pts: count flat XYZZ records (written for status 0 and 3).  out18: count x 144 bytes (zero for status 1, 2).
+static __global__ void __launch_bounds__(g1c::kBlk) k_g1_decompress(size_t count, const void* __restrict__ in48, void* __restrict__ pts,
+                                                                   void* __restrict__ out18, unsigned char* __restrict__ status) {
+    const size_t i = (size_t)blockIdx.x * g1c::kBlk + threadIdx.x;
+    if (i >= count) return;
+    // big-endian bytes -> little-endian words: word k of the integer is the byte-swapped word 11 - k of the record
+    u32 w[12];
+    const uint4* p = reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(in48) + i * 48);
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        const uint4 v = p[k];
+        w[11 - 4 * k] = __builtin_bswap32(v.x);
+        w[10 - 4 * k] = __builtin_bswap32(v.y);
+        w[9 - 4 * k] = __builtin_bswap32(v.z);
+        w[8 - 4 * k] = __builtin_bswap32(v.w);
+    }
+    const bool compressed = (w[11] >> 31) & 1u, inf = (w[11] >> 30) & 1u, sign = (w[11] >> 29) & 1u;
+    w[11] &= 0x1fffffffu;
+    u32 any = 0;
+#pragma unroll
+    for (int k = 0; k < 12; k++) any |= w[k];
+    const Fq30 xc = f30_from_words(w);
+    const bool bad = !compressed || (inf ? (sign || any != 0) : !g1c_lt_q(xc));
+    if (bad || inf) {
+        status[i] = bad ? g1c::kBadEncoding : g1c::kOk;
+        if (bad) {
+            g1c_store_words(out18, i * 144, 9, 0u);
+        } else {
+            g1c_store_jac(out18, i, xc, xc, true);
+            g1c_store_words(pts, i * 192, 12, 0u);  // ZZ = 0: infinity
+        }
+        return;
+    }
+    const Fq30 x = f30_canon8(f30_mul(xc, g1c_r2()));                 // internal form, canonical
+    const Fq30 rhs = f30_add(f30_mul(f30_sqr(x), x), g1c_four());     // x^3 + 4 < 3q
+    Fq30 y = rhs;                                                     // rhs^((q+1)/4): the top bit, then 378 squarings
+#pragma unroll 1
+    for (int b = g1c::kSqrtBits - 2; b >= 0; b--) {
+        y = f30_sqr(y);
+        if ((g1c::kSqrtExp[b >> 5] >> (b & 31)) & 1u) y = f30_mul(y, rhs);  // (the same branch in every lane)
+    }
+    if (!g1c_same(f30_canon8(f30_sqr(y)), f30_canon8(rhs))) {
+        status[i] = g1c::kNotOnCurve;
+        g1c_store_words(out18, i * 144, 9, 0u);
+        return;
+    }
+    Fq30 unit = f30_zero();
+    unit.l[0] = 1;
+    const Fq30 y_plain = f30_canon8(f30_mul(y, unit));  // out of Montgomery form: "larger" is a property of the integer
+    y = f30_canon8(y);
+    if (g1c_is_larger(y_plain) != sign) y = f30_neg_canon(y);
+    status[i] = g1c::kOk;
+    g1c_store_jac(out18, i, f30_to_ref(x), f30_to_ref(y), false);
+    f30_store(pts, i * 192, x);
+    f30_store(pts, i * 192 + 48, y);
+    f30_store(pts, i * 192 + 96, f30_one());
+    f30_store(pts, i * 192 + 144, f30_one());
+}
+
+// in18: count x 18 u64 (X, Y, Z), reference Montgomery form.  Z = 0 is infinity whatever X and Y are (as in zk_pcs_verify_batch).
+static __global__ void __launch_bounds__(g1c::kBlk) k_g1_load_jac(size_t count, const void* __restrict__ in18, void* __restrict__ pts,
+                                                                 unsigned char* __restrict__ status) {
+    const size_t i = (size_t)blockIdx.x * g1c::kBlk + threadIdx.x;
+    if (i >= count) return;
+    const Fq30 xr = f30_load(in18, i * 144), yr = f30_load(in18, i * 144 + 48), zr = f30_load(in18, i * 144 + 96);
+    if (!g1c_lt_q(xr) || !g1c_lt_q(yr) || !g1c_lt_q(zr)) {
+        status[i] = g1c::kBadEncoding;
+        return;
+    }
+    if (f30_all_zero(zr)) {
+        status[i] = g1c::kOk;
+        g1c_store_words(pts, i * 192, 12, 0u);
+        return;
+    }
+    const Fq30 X = f30_from_ref(xr), Y = f30_from_ref(yr), Z = f30_from_ref(zr);  // canonical
+    const Fq30 ZZ = f30_sqr(Z), ZZZ = f30_mul(ZZ, Z);                            // < 2q
+    // Y^2 == X^3 + 4 Z^6
+    const Fq30 rhs = f30_mul2add(f30_sqr(X), X, f30_sqr(ZZZ), g1c_four());
+    if (!g1c_same(f30_canon8(f30_sqr(Y)), f30_canon8(rhs))) {
+        status[i] = g1c::kNotOnCurve;
+        return;
+    }
+    status[i] = g1c::kOk;
+    f30_store(pts, i * 192, X);  // (X, Y, Z^2, Z^3) is the XYZZ form of the same point
+    f30_store(pts, i * 192 + 48, Y);
+    f30_store(pts, i * 192 + 96, ZZ);
+    f30_store(pts, i * 192 + 144, ZZZ);
+}
+
+static __global__ void __launch_bounds__(g1c::kBlk) k_g1_subgroup(size_t count, const void* __restrict__ pts, unsigned char* __restrict__ status) {
+    const size_t i = (size_t)blockIdx.x * g1c::kBlk + threadIdx.x;
+    if (i >= count || status[i] != g1c::kOk) return;
+    Xyzz30 P;
+    P.x = f30_load(pts, i * 192);
+    P.y = f30_load(pts, i * 192 + 48);
+    P.zz = f30_load(pts, i * 192 + 96);
+    P.zzz = f30_load(pts, i * 192 + 144);
+    if (xyzz30_is_inf(P)) return;  // the neutral element is a member
+    Xyzz30 base = P, acc = P;
+#pragma unroll 1
+    for (int pass = 0; pass < 2; pass++) {  // acc = [|x|] base, twice: the top bit, then 63 doublings and 5 additions
+        acc = base;
+#pragma unroll 1
+        for (int b = 62; b >= 0; b--) {
+            acc = g1c_dbl(acc);
+            if ((g1c::kXAbs >> b) & 1ULL) acc = g1c_add(acc, base);
+        }
+        base = acc;
+    }
+    // (beta Px / Pzz, Py / Pzzz) == (Ax / Azz, -Ay / Azzz), cross-multiplied; infinity is no such point
+    bool ok = !xyzz30_is_inf(acc);
+    if (ok) {
+        const Fq30 l = f30_mul(f30_mul(g1c_beta(), P.x), acc.zz);  // q * 8q, then 2q * 2q
+        const Fq30 r = f30_mul(acc.x, P.zz);                       // 8q * 2q
+        const Fq30 s = f30_mul2add(P.y, acc.zzz, acc.y, P.zzz);    // 4q*2q + 4q*2q -> < 2q
+        ok = g1c_same(f30_canon8(l), f30_canon8(r)) && f30_is_zero_2q(s);
+    }
+    if (!ok) status[i] = g1c::kNotInG1;
+}
+
+// ---- host side ---------------------------------------------------------------------------------------------------------------------
+// Both calls stage in scratch arena 11, the one pairing_run (zk_pairing.hip) uses: a verifier calls them back to back with the pairing,
+// every user synchronises the ctx stream before it returns, and an arena only ever grows -- so the few KiB needed here are always
+// inside what the pairing of the same proof allocates, and no call sees another's data in flight.
+static inline size_t g1c_up256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+int g1_decompress_check(zk_ctx* ctx, size_t count, const void* h_in48, uint64_t* h_out18, uint8_t* h_status) {
+    if (count == 0) return ZK_OK;
+    ZK_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t o_in = 0, o_pts = o_in + g1c_up256(count * 48), o_out = o_pts + g1c_up256(count * 192), o_st = o_out + g1c_up256(count * 144),
+                 total = o_st + g1c_up256(count);
+    char* d = static_cast<char*>(scratch(ctx, 11, total));
+    if (!d) return ZK_ERR_OOM;
+    const dim3 grid((unsigned)((count + g1c::kBlk - 1) / g1c::kBlk)), blk(g1c::kBlk);
+    ZK_HIP(ctx, hipMemcpyAsync(d + o_in, h_in48, count * 48, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_g1_decompress, grid, blk, 0, ctx->stream, count, (const void*)(d + o_in), (void*)(d + o_pts), (void*)(d + o_out),
+                       (unsigned char*)(d + o_st));
+    ZK_HIP(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_g1_subgroup, grid, blk, 0, ctx->stream, count, (const void*)(d + o_pts), (unsigned char*)(d + o_st));
+    ZK_HIP(ctx, hipGetLastError());
+    ZK_HIP(ctx, hipMemcpyAsync(h_out18, d + o_out, count * 144, hipMemcpyDeviceToHost, ctx->stream));
+    ZK_HIP(ctx, hipMemcpyAsync(h_status, d + o_st, count, hipMemcpyDeviceToHost, ctx->stream));
+    ZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return ZK_OK;
+}
+
+int g1_check(zk_ctx* ctx, size_t count, const uint64_t* h_points18, uint8_t* h_status) {
+    if (count == 0) return ZK_OK;
+    ZK_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t o_in = 0, o_pts = o_in + g1c_up256(count * 144), o_st = o_pts + g1c_up256(count * 192), total = o_st + g1c_up256(count);
+    char* d = static_cast<char*>(scratch(ctx, 11, total));
+    if (!d) return ZK_ERR_OOM;
+    const dim3 grid((unsigned)((count + g1c::kBlk - 1) / g1c::kBlk)), blk(g1c::kBlk);
+    ZK_HIP(ctx, hipMemcpyAsync(d + o_in, h_points18, count * 144, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_g1_load_jac, grid, blk, 0, ctx->stream, count, (const void*)(d + o_in), (void*)(d + o_pts), (unsigned char*)(d + o_st));
+    ZK_HIP(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_g1_subgroup, grid, blk, 0, ctx->stream, count, (const void*)(d + o_pts), (unsigned char*)(d + o_st));
+    ZK_HIP(ctx, hipGetLastError());
+    ZK_HIP(ctx, hipMemcpyAsync(h_status, d + o_st, count, hipMemcpyDeviceToHost, ctx->stream));
+    ZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return ZK_OK;
+}
+
+}  // namespace zk

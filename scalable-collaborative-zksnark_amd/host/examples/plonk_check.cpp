@@ -4,8 +4,16 @@
 // two hosts (zkhip.plonk.proof_digest).
 //
 //     bin/plonk_check --mu M [--seed S] [--gate wide] [--witness] [--lookup | --lookup-fn [--find] [--break-lookup K]] [--break-gate K | --break-wire K | --bad-input | --break K|all]
-//                     [--circuit-only | --sample-only [--time-sample R]]
+//                     [--circuit-only | --sample-only [--time-sample R]] [--bytes [--dump-proof FILE] [--torsion K]]
+//     bin/plonk_check --g1check-time K [--reps R]
 //
+// --bytes proves, encodes the record (zkhost/proof_io.hpp: the byte format of zkhip/proof_io.py) and verifies THE BYTES with verify_bytes:
+// one device call validates every G1 point (canonical encoding, on the curve, in the prime-order subgroup) before plonk_verify runs.  Prints
+// the SHA-256 of the bytes -- one digest for one seed in both hosts -- and the verdict; --dump-proof FILE writes the bytes.  --torsion K adds
+// a point of order 3 to point K of the encoding (K counts the G1 points in the order of the bytes) before verifying: the point stays on the
+// curve and leaves G1, and the refusal names it ("refused: opening point 7 of v_batch: not in the subgroup", exit 1).
+// --g1check-time K needs no GPU: the host rule (g1_decompress_check_host, serial big integers) on the K points G, 2G, .., KG, warm-up 3,
+// the median of R (default 20) calls, one line in ms -- the compiled host's column of tools/g1check_time.py.
 // --lookup proves the test circuit with lookup rows (zkhip.plonk.sample_circuit_lookup, mu >= 3) under the label + "-lookup": three opening
 // proofs.  --find (with --lookup) proves without the sample's indices: the device finds them (plonk_prove(.., kFind)); the sampler only ever
 // names first occurrences, so the digest is the one without --find.  --break-lookup K moves the triple of lookup row K out of the table with gate and wiring intact: the prover refuses (exit 3, the
@@ -41,6 +49,9 @@
 #include "zkhost/hyperplonk.hpp"
 #include "zkhost/pcs_vk.hpp"
 #include "zkhost/plonk.hpp"
+#include "zkhost/proof_io.hpp"
+#include "zkhost/sha256.hpp"
+#include <chrono>
 
 using namespace zkhost;
 
@@ -52,7 +63,9 @@ static bool number(const char *s, long long &out) {
 
 struct Options {
     long long mu = -1, seed = 7, break_gate = -1, break_wire = -1, break_lookup = -1, break_part = -1;
-    long long time_sample = 0;
+    long long time_sample = 0, torsion = -1, g1check_time = 0, reps = 20;
+    bool bytes = false;
+    std::string dump_proof;
     bool bad_input = false, wide = false, lookup = false, break_all = false, find = false, witness = false, lookup_fn = false;
 };
 
@@ -77,6 +90,64 @@ static int circuit_only(const Options &o) {
         std::printf("sample row loop seconds %.6f\n", n % 2 ? t[n / 2] : 0.5 * (t[n / 2 - 1] + t[n / 2]));
     }
     return 0;
+}
+
+// the host rule on G, 2G, .., KG: median of `reps` calls after three, ms
+static int g1check_time(const Options &o) {
+    const size_t k = (size_t)o.g1check_time;
+    const G1Affine g = g1_deserialize_compressed((const uint8_t *)"\x97\xf1\xd3\xa7\x31\x97\xd7\x94\x26\x95\x63\x8c\x4f\xa9\xac\x0f\xc3\x68\x8c\x4f\x97\x74\xb9\x05"
+                                                                   "\xa1\x4e\x3a\x3f\x17\x1b\xac\x58\x6c\x55\xe8\x3f\xf9\x7a\x1a\xef\xfb\x3a\xf0\x0a\xdb\x22\xc6\xbb");
+    const detail::JacQ G{g.x, g.y, Fq::one()};
+    detail::JacQ acc{Fq::one(), Fq::one(), Fq::zero()};
+    Bytes enc;
+    for (size_t i = 0; i < k; ++i) {
+        acc = detail::jq_add(acc, G);
+        const Fq zi = acc.z.inverse(), zi2 = zi * zi;
+        g1_serialize_compressed(G1Affine{acc.x * zi2, acc.y * zi2 * zi, false}, enc);
+    }
+    G1Vec pts;
+    std::vector<uint8_t> st;
+    std::vector<double> t;
+    for (long long i = 0; i < 3 + o.reps; ++i) {
+        const auto t0 = std::chrono::steady_clock::now();
+        g1_decompress_check_host(enc.data(), k, pts, st);
+        if (i >= 3) t.push_back(std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+    }
+    bool all_ok = true;
+    for (uint8_t s : st) all_ok = all_ok && s == kG1Ok;
+    std::sort(t.begin(), t.end());
+    const size_t n = t.size();
+    Sha256 h;
+    h.update(pts.data(), 144 * pts.size());
+    std::printf("g1check host points %zu ms %.6f all_ok %d points_sha256 %s\n", k, n % 2 ? t[n / 2] : 0.5 * (t[n / 2 - 1] + t[n / 2]), all_ok ? 1 : 0, h.hex().c_str());
+    return all_ok ? 0 : 1;
+}
+
+// --bytes: encode, (--torsion K: point K += a point of order 3), verify the bytes
+static bool check_bytes(Ctx &be, const Options &o, const PcsVk &vk_mu, const PcsVk &vk_mu1, const PlonkVk &vk, const FrVec &pi, const PlonkProof &proof) {
+    Bytes data = proof_to_bytes(proof);
+    Sha256 h;
+    h.update(data.data(), data.size());
+    std::printf("bytes sha256 %s (%zu bytes)\n", h.hex().c_str(), data.size());
+    if (!o.dump_proof.empty()) detail::write_file(o.dump_proof, data);
+    if (o.torsion >= 0) {
+        const ParsedProof pp = parse_proof(data);
+        const size_t K = (size_t)o.torsion;
+        if (K >= pp.point_offsets.size()) throw std::invalid_argument("--torsion names one of the encoding's " + std::to_string(pp.point_offsets.size()) + " points");
+        const size_t off = pp.point_offsets[K];
+        const G1Affine p = g1_deserialize_compressed(&data[off]);
+        const detail::JacQ sum = detail::jq_add(p.infinity ? detail::JacQ{Fq::one(), Fq::one(), Fq::zero()} : detail::JacQ{p.x, p.y, Fq::one()},
+                                                detail::JacQ{Fq::zero(), Fq::from_u64(2), Fq::one()});  // (0, 2): 0^3 + 4 = 2^2, order 3
+        const Fq zi = sum.z.inverse(), zi2 = zi * zi;
+        Bytes enc;
+        g1_serialize_compressed(G1Affine{sum.x * zi2, sum.y * zi2 * zi, false}, enc);
+        std::memcpy(&data[off], enc.data(), 48);
+        std::printf("torsion: a point of order 3 added to %s\n", (pp.point_parts[K].first + "[" + std::to_string(pp.point_parts[K].second) + "]").c_str());
+    }
+    std::string why;
+    const bool ok = verify_bytes(be, vk_mu, vk_mu1, vk, pi, data, &why);
+    if (!ok) std::printf("refused: %s\n", why.c_str());
+    return ok;
 }
 
 static const char *const kParts[16] = {"commitments", "v_commitment", "p_rounds", "g_rounds", "g_values", "p_values", "v_values", "batch.rounds", "batch.opening",
@@ -151,6 +222,8 @@ static int run(const Options &o) {
             any = any || acc;
         }
         ok = any;
+    } else if (o.bytes) {
+        ok = check_bytes(be, o, *vk_mu, *vk_mu1, vk, pi, proof);
     } else {
         if (o.break_part >= 0) flip(proof, (int)o.break_part);
         ok = plonk_verify(be, *vk_mu, *vk_mu1, vk, pi, proof);
@@ -172,6 +245,11 @@ int main(int argc, char **argv) {
         else if (k == "--lookup-fn") o.lookup = o.lookup_fn = true;
         else if (k == "--find") o.find = true;
         else if (k == "--witness") o.witness = true;
+        else if (k == "--bytes") o.bytes = true;
+        else if (i + 1 < argc && k == "--dump-proof") o.dump_proof = argv[++i];
+        else if (i + 1 < argc && k == "--torsion") usage = !number(argv[++i], o.torsion);
+        else if (i + 1 < argc && k == "--g1check-time") usage = !number(argv[++i], o.g1check_time) || o.g1check_time < 1;
+        else if (i + 1 < argc && k == "--reps") usage = !number(argv[++i], o.reps) || o.reps < 1;
         else if (i + 1 < argc && k == "--time-sample") usage = !number(argv[++i], o.time_sample) || o.time_sample < 1;
         else if (i + 1 < argc && k == "--break-lookup") usage = !number(argv[++i], o.break_lookup);
         else if (i + 1 < argc && k == "--break" && !std::strcmp(argv[i + 1], "all")) o.break_all = true, ++i;
@@ -184,10 +262,19 @@ int main(int argc, char **argv) {
         else usage = true;
     }
     const bool tamper = o.break_all || o.break_part >= 0;
+    if (o.g1check_time > 0 && !usage && mu < 0 && argc <= 5) {
+        try {
+            return g1check_time(o);
+        } catch (const std::exception &e) {
+            std::fprintf(stderr, "plonk_check: %s\n", e.what());
+            return 2;
+        }
+    }
+    usage = usage || o.g1check_time > 0 || ((o.torsion >= 0 || !o.dump_proof.empty()) && !o.bytes) || (o.bytes && tamper);
     if (usage || mu < 0 || (break_gate >= 0) + (break_wire >= 0) + (bad_input ? 1 : 0) + (o.break_lookup >= 0) + (tamper ? 1 : 0) > 1 ||
         (o.break_all && o.break_part >= 0) || (o.break_lookup >= 0 && !o.lookup) || (o.find && !o.lookup) || (o.lookup && (break_gate >= 0 || break_wire >= 0)) ||
         (o.witness && (break_gate >= 0 || break_wire >= 0)) || (o.time_sample > 0 && !only_circuit) || (o.lookup_fn && (!wide || o.time_sample > 0))) {
-        std::fprintf(stderr, "usage: plonk_check --mu M [--seed S] [--gate wide] [--witness] [--lookup | --gate wide --lookup-fn [--find] [--break-lookup K]] [--break-gate K | --break-wire K | --bad-input | --break K|all] [--circuit-only | --sample-only [--time-sample R]]\n");
+        std::fprintf(stderr, "usage: plonk_check --mu M [--seed S] [--gate wide] [--witness] [--lookup | --gate wide --lookup-fn [--find] [--break-lookup K]] [--break-gate K | --break-wire K | --bad-input | --break K|all] [--circuit-only | --sample-only [--time-sample R]] [--bytes [--dump-proof FILE] [--torsion K]] | --g1check-time K [--reps R]\n");
         return 2;
     }
     if (mu < 2 || mu > 24) {

@@ -782,6 +782,20 @@ class Ctx {
         return std::vector<bool>(ok.begin(), ok.begin() + count);
     }
 
+    // zk_g1_decompress_check: k x 48 bytes of compressed G1 -> the normalised points and one status per point (0 ok, 1 bad encoding,
+    // 2 x not on the curve, 3 not in G1); a bad point is a status, not an error.  The check zk_pcs_verify_batch leaves to its caller
+    void g1_decompress_check(const uint8_t *in48, size_t k, G1Vec &points, std::vector<uint8_t> &status) {
+        points.assign(k, G1{});
+        status.assign(k, 0);
+        if (k) check(zk_g1_decompress_check(h_, k, in48, points[0].data(), status.data()));
+    }
+    // zk_g1_check: Jacobian points in any representative -> one status per point
+    std::vector<uint8_t> g1_check(const G1Vec &points) {
+        std::vector<uint8_t> status(points.size(), 0);
+        if (!points.empty()) check(zk_g1_check(h_, points.size(), points[0].data(), status.data()));
+        return status;
+    }
+
     G1Vec g1_lincomb_batch(const G1Vec &points, const FrVec &scalars_canonical, size_t count) {
         size_t n = scalars_canonical.size();
         need(points.size() == n * count, "g1_lincomb_batch: points != count x scalars");

@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+from typing import Tuple
 
 import numpy as np
 
@@ -1027,6 +1028,28 @@ class Ctx:
         ok = np.zeros(max(count, 1), dtype=np.uint8)
         self._check(self.lib.zk_pcs_verify_batch(self.h, vk.h, nvars, count, _h(cm), _h(vals), _h(pf), _h(pts), _h(ok)))
         return ok[:count].astype(bool)
+
+    # ---- G1 points from outside: decompression and subgroup membership (csrc/zk_g1check.hip) ----
+    def g1_decompress_check(self, data) -> Tuple[np.ndarray, np.ndarray]:
+        """k compressed G1 points (bytes, or a uint8 array of k x 48) -> (points [k, 18] normalised Jacobian, status [k] uint8):
+        0 ok, 1 bad encoding, 2 x not on the curve, 3 on the curve but not in G1 (include/zkhip.h; points of status 1 and 2 are zero)"""
+        raw = np.ascontiguousarray(np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else data, dtype=np.uint8).reshape(-1)
+        if raw.size % 48:
+            raise ValueError(f"{raw.size} bytes is not a whole number of 48-byte points")
+        k = raw.size // 48
+        out = np.zeros((k, 18), dtype=np.uint64)
+        st = np.zeros(k, dtype=np.uint8)
+        if k:
+            self._check(self.lib.zk_g1_decompress_check(self.h, k, _h(raw), _h(out), _h(st)))
+        return out, st
+
+    def g1_check(self, points) -> np.ndarray:
+        """points [k, 18] Jacobian in any representative -> status [k] uint8: 0 ok, 1 a coordinate >= q, 2 not on the curve, 3 not in G1"""
+        pts = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 18)
+        st = np.zeros(len(pts), dtype=np.uint8)
+        if len(pts):
+            self._check(self.lib.zk_g1_check(self.h, len(pts), _h(pts), _h(st)))
+        return st
 
     # ---- party exchanges through the C ABI (RCCL communicator inside the ctx) ----
     def comm_unique_id(self) -> bytes:

@@ -104,6 +104,7 @@ import numpy as np
 from . import batch_open as bo
 from . import wiring as wr
 from .field import R_MOD, fr_from_mont, fr_mont
+from .proof_io import check_points, parse_proof, proof_from_bytes, proof_to_bytes, verify_bytes  # noqa: F401  (proof bytes, re-exported)
 from .transcript import HostTranscript, Transcript
 from .zerocheck import _ints, eq_eval, gate_value, wide_gate_value
 
@@ -595,7 +596,8 @@ def field_checks(vk: dict, public_inputs, proof: dict, finals=None, v_finals=Non
 
 def verify(be, vk: dict, public_inputs, proof: dict) -> bool:
     """the replay, the checks of failed_checks, then one zk_pcs_verify_batch per batch instance: two, with a lookup three (vk["pcs"]:
-    wiring.verifying_keys)"""
+    wiring.verifying_keys).  The record's G1 points are taken as given (on the curve is checked, the subgroup is not): a record from
+    outside goes through proof_io.verify_bytes / check_points first."""
     if vk.get("pcs") is None:
         raise ValueError("the verifying key holds no pairing keys (preprocess without powers_of_g2)")
     try:

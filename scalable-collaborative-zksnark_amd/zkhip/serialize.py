@@ -174,3 +174,113 @@ def fr_device_to_file(ctx, buf, n: int, path: str) -> None:
     a = tmp.download((n, 4))
     with open(path, "wb") as f:
         f.write(struct.pack("<Q", n) + a.astype("<u8").tobytes())
+
+
+# ---------------------------------------------------------------------------------------
+# G1 points from outside: the rule of zk_g1_decompress_check (include/zkhip.h) in Python integers, for callers without a
+# device.  status 0 ok, 1 bad encoding, 2 x is not on the curve, 3 on the curve but not in G1.
+# ---------------------------------------------------------------------------------------
+G1_OK, G1_BAD_ENCODING, G1_NOT_ON_CURVE, G1_NOT_IN_SUBGROUP = 0, 1, 2, 3
+G1_STATUS_TEXT = {G1_OK: "ok", G1_BAD_ENCODING: "bad encoding", G1_NOT_ON_CURVE: "x is not on the curve", G1_NOT_IN_SUBGROUP: "not in the subgroup"}
+X_ABS = 0xD201000000010000
+# phi(x, y) = (BETA x, y) is multiplication by -X_ABS^2 on G1 (X_ABS^4 - X_ABS^2 + 1 = r); the other cube root of unity is X_ABS^2 - 1
+BETA = 0x5F19672FDF76CE51BA69C6076A0F77EADDB3A93BE6F89688DE17D813620A00022E01FFFFFFFEFFFE
+
+
+def _jac_dbl(P):
+    X, Y, Z = P
+    if Z == 0:
+        return P
+    A, B = X * X % Q_MOD, Y * Y % Q_MOD
+    C = B * B % Q_MOD
+    D = 2 * ((X + B) * (X + B) - A - C) % Q_MOD
+    E = 3 * A % Q_MOD
+    X3 = (E * E - 2 * D) % Q_MOD
+    return (X3, (E * (D - X3) - 8 * C) % Q_MOD, 2 * Y * Z % Q_MOD)
+
+
+def _jac_add(P, R):
+    """complete: equal operands, opposite operands and infinity on either side"""
+    if P[2] == 0:
+        return R
+    if R[2] == 0:
+        return P
+    (X1, Y1, Z1), (X2, Y2, Z2) = P, R
+    Z1Z1, Z2Z2 = Z1 * Z1 % Q_MOD, Z2 * Z2 % Q_MOD
+    U1, U2 = X1 * Z2Z2 % Q_MOD, X2 * Z1Z1 % Q_MOD
+    S1, S2 = Y1 * Z2 * Z2Z2 % Q_MOD, Y2 * Z1 * Z1Z1 % Q_MOD
+    if U1 == U2:
+        return _jac_dbl(P) if S1 == S2 else (1, 1, 0)
+    H, r = (U2 - U1) % Q_MOD, (S2 - S1) % Q_MOD
+    HH = H * H % Q_MOD
+    HHH, V = H * HH % Q_MOD, U1 * HH % Q_MOD
+    X3 = (r * r - HHH - 2 * V) % Q_MOD
+    return (X3, (r * (V - X3) - S1 * HHH) % Q_MOD, Z1 * Z2 * H % Q_MOD)
+
+
+def _jac_mul(P, k: int):
+    acc = (1, 1, 0)
+    for bit in bin(k)[2:]:
+        acc = _jac_dbl(acc)
+        if bit == "1":
+            acc = _jac_add(acc, P)
+    return acc
+
+
+def g1_in_subgroup(P: Point) -> bool:
+    """phi(P) == -[x^2]P for a point of the curve (Scott's test, the one of csrc/zk_g1check.hip); infinity is a member"""
+    if P is None:
+        return True
+    x, y = P
+    X, Y, Z = _jac_mul(_jac_mul((x, y, 1), X_ABS), X_ABS)
+    if Z == 0:
+        return False
+    ZZ = Z * Z % Q_MOD
+    return (BETA * x * ZZ - X) % Q_MOD == 0 and (y * ZZ * Z + Y) % Q_MOD == 0
+
+
+def g1_point_words(P: Point):
+    """the library's normalised Jacobian record of a point: 18 u64, (x, y, 1) or (1, 1, 0) for infinity, Montgomery form"""
+    import numpy as np
+
+    from .field import fq_mont
+
+    one = fq_mont(1)
+    if P is None:
+        return np.concatenate([one, one, np.zeros(6, dtype=np.uint64)])
+    return np.concatenate([fq_mont(P[0]), fq_mont(P[1]), one])
+
+
+def g1_decompress_check_host(data):
+    """k compressed points (bytes or a uint8 array of k x 48) -> (points [k, 18], status [k] uint8): the results of
+    Ctx.g1_decompress_check, bit for bit (the points of status 1 and 2 are zero)"""
+    import numpy as np
+
+    raw = bytes(data) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, dtype=np.uint8).tobytes()
+    if len(raw) % 48:
+        raise ValueError(f"{len(raw)} bytes is not a whole number of 48-byte points")
+    k = len(raw) // 48
+    pts, st = np.zeros((k, 18), dtype=np.uint64), np.zeros(k, dtype=np.uint8)
+    for i in range(k):
+        b = raw[48 * i : 48 * i + 48]
+        rest = int.from_bytes(bytes([b[0] & 0x1F]) + b[1:], "big")
+        if not b[0] & 0x80:
+            st[i] = G1_BAD_ENCODING
+        elif b[0] & 0x40:
+            if b[0] & 0x20 or rest:
+                st[i] = G1_BAD_ENCODING
+            else:
+                pts[i] = g1_point_words(None)
+        elif rest >= Q_MOD:
+            st[i] = G1_BAD_ENCODING
+        else:
+            y = _sqrt_fq((rest * rest * rest + 4) % Q_MOD)
+            if y is None:
+                st[i] = G1_NOT_ON_CURVE
+                continue
+            if (y > (Q_MOD - 1) // 2) != bool(b[0] & 0x20):
+                y = Q_MOD - y
+            pts[i] = g1_point_words((rest, y))
+            if not g1_in_subgroup((rest, y)):
+                st[i] = G1_NOT_IN_SUBGROUP
+    return pts, st
