@@ -314,18 +314,22 @@ static int fs_plan(zk_ctx* ctx, const char* who, const zk_transcript* t, size_t 
     return ZK_OK;
 }
 
+// b: the identity's binding of the caller's arguments (Bound, zk_gate.cuh); its *_local_e knob is checked before anything else
 template <class K>
-static int run_fs(zk_ctx* ctx, const char* who, const FsIn<K::kTabs>& first, size_t len, size_t emax, size_t per_cu, const GateChal& gamma, zk_transcript* t,
-                   uint64_t* h_out_evals, uint64_t* h_last, uint64_t* h_chal_out) {
+static int run_fs(zk_ctx* ctx, const char* who, const Bound<K>& b, size_t len, zk_transcript* t, uint64_t* h_out_evals, uint64_t* h_last, uint64_t* h_chal_out) {
+    const GateChal& gamma = b.gamma;
+    size_t emax;
+    int rc = local_e(ctx, b.knob, b.knob_name, emax, K::kLocalMax);
+    if (rc) return rc;
     FsPlan pl;
-    const int rc = fs_plan(ctx, who, t, len, kGateMaxLog, emax, per_cu, K::kEvals, K::kTabs, pl);
+    rc = fs_plan(ctx, who, t, len, kGateMaxLog, emax, b.per_cu, K::kEvals, K::kTabs, pl);
     if (rc) return rc;
     const size_t fr = 32, rounds = pl.rounds, npass = pl.npass;
     char* res = (char*)pinned(ctx, (rounds * K::kEvals + K::kTabs + rounds) * fr);  // evaluations | last | challenges, written by the kernels
     if (!res) return ZK_ERR_OOM;
     char* res_last = res + rounds * K::kEvals * fr;
     char* res_chal = res_last + K::kTabs * fr;
-    FsIn<K::kTabs> cur = first;
+    FsIn<K::kTabs> cur = b.first;
     for (size_t p = 0; p < npass; p++) {
         const size_t half = len >> (p + 1);
         if (p == 0) {
@@ -364,77 +368,31 @@ static int run_fs(zk_ctx* ctx, const char* who, const FsIn<K::kTabs>& first, siz
 }
 
 int sumcheck_gate_fs(zk_ctx* ctx, const void* const* d_tabs, size_t len, zk_transcript* t, uint64_t* h_out_evals, uint64_t* h_last, uint64_t* h_chal_out) {
-    size_t emax;
-    const int rc = local_e(ctx, tuning().gate_local_e, "gate_local_e", emax);
-    if (rc) return rc;
-    FsIn<GateKind::kTabs> first;
-    for (int k = 0; k < GateKind::kTabs; k++) first.t[k] = d_tabs[k], first.sh[k] = 0;
-    GateChal none;
-    std::memset(&none, 0, sizeof(none));
-    return run_fs<GateKind>(ctx, "zk_sumcheck_gate_fs", first, len, emax, tuning().gate_pass_wg > 0 ? (size_t)tuning().gate_pass_wg : GateKind::kPerCu, none, t, h_out_evals, h_last,
-                             h_chal_out);
+    return run_fs<GateKind>(ctx, "zk_sumcheck_gate_fs", bind_gate(d_tabs), len, t, h_out_evals, h_last, h_chal_out);
 }
 
 int sumcheck_wiring_fs(zk_ctx* ctx, const void* d_eq, const void* d_tree, const void* d_num, const void* d_den, size_t N, const uint64_t* h_gamma, zk_transcript* t,
                        uint64_t* h_out_evals, uint64_t* h_last, uint64_t* h_chal_out) {
-    size_t emax;
-    const int rc = local_e(ctx, tuning().wiring_local_e, "wiring_local_e", emax);
-    if (rc) return rc;
-    // the views of the tree: v1x its upper half, (vx0, vx1) every other element from its base / one element on, h its lower half
-    const char* tree = (const char*)d_tree;
-    const FsIn<WireKind::kTabs> first = {{d_eq, tree + N * 32, tree, tree + 32, tree, d_num, d_den}, {0, 0, 1, 1, 0, 0, 0}};
-    GateChal gamma;
-    std::memcpy(&gamma.r, h_gamma, 32);
-    return run_fs<WireKind>(ctx, "zk_sumcheck_wiring_fs", first, N, emax, tuning().wiring_pass_wg > 0 ? (size_t)tuning().wiring_pass_wg : WireKind::kPerCu, gamma, t, h_out_evals,
-                             h_last, h_chal_out);
+    return run_fs<WireKind>(ctx, "zk_sumcheck_wiring_fs", bind_wiring(d_eq, d_tree, d_num, d_den, N, h_gamma), N, t, h_out_evals, h_last, h_chal_out);
 }
 
 int sumcheck_perm3_fs(zk_ctx* ctx, const void* d_eq, const void* d_tree, const void* const* d_num, const void* const* d_den, size_t N, const uint64_t* h_gamma,
                       zk_transcript* t, uint64_t* h_out_evals, uint64_t* h_last, uint64_t* h_chal_out) {
-    size_t emax;
-    const int rc = local_e(ctx, tuning().perm3_local_e, "perm3_local_e", emax, kPerm3LocalMax);
-    if (rc) return rc;
-    const char* tree = (const char*)d_tree;
-    const FsIn<kPerm3Tabs> first = {{d_eq, tree + N * 32, tree, tree + 32, tree, d_num[0], d_num[1], d_num[2], d_den[0], d_den[1], d_den[2]},
-                                    {0, 0, 1, 1, 0, 0, 0, 0, 0, 0, 0}};
-    GateChal gamma;
-    std::memcpy(&gamma.r, h_gamma, 32);
-    return run_fs<Perm3Kind>(ctx, "zk_sumcheck_perm3_fs", first, N, emax, Perm3Kind::kPerCu, gamma, t, h_out_evals, h_last, h_chal_out);
+    return run_fs<Perm3Kind>(ctx, "zk_sumcheck_perm3_fs", bind_perm3(d_eq, d_tree, d_num, d_den, N, h_gamma), N, t, h_out_evals, h_last, h_chal_out);
 }
 
 int sumcheck_gate_wide_fs(zk_ctx* ctx, const void* const* d_tabs, size_t len, zk_transcript* t, uint64_t* h_out_evals, uint64_t* h_last, uint64_t* h_chal_out) {
-    size_t emax;
-    const int rc = local_e(ctx, tuning().gatew_local_e, "gatew_local_e", emax, kGatewLocalMax);
-    if (rc) return rc;
-    FsIn<kGatewTabs> first;
-    for (int k = 0; k < kGatewTabs; k++) first.t[k] = d_tabs[k], first.sh[k] = 0;
-    GateChal none;
-    std::memset(&none, 0, sizeof(none));
-    return run_fs<GatewKind>(ctx, "zk_sumcheck_gate_wide_fs", first, len, emax, GatewKind::kPerCu, none, t, h_out_evals, h_last, h_chal_out);
+    return run_fs<GatewKind>(ctx, "zk_sumcheck_gate_wide_fs", bind_gate_wide(d_tabs), len, t, h_out_evals, h_last, h_chal_out);
 }
 
 int sumcheck_lookup_fs(zk_ctx* ctx, const void* const* d_tabs, size_t len, const uint64_t* h_gamma, zk_transcript* t, uint64_t* h_out_evals, uint64_t* h_last,
                        uint64_t* h_chal_out) {
-    size_t emax;
-    const int rc = local_e(ctx, tuning().lookup_local_e, "lookup_local_e", emax);
-    if (rc) return rc;
-    FsIn<kLookupTabs> first;
-    for (int k = 0; k < kLookupTabs; k++) first.t[k] = d_tabs[k], first.sh[k] = 0;
-    GateChal gamma;
-    std::memcpy(&gamma.r, h_gamma, 32);
-    return run_fs<LookupKind>(ctx, "zk_sumcheck_lookup_fs", first, len, emax, LookupKind::kPerCu, gamma, t, h_out_evals, h_last, h_chal_out);
+    return run_fs<LookupKind>(ctx, "zk_sumcheck_lookup_fs", bind_lookup(d_tabs, h_gamma), len, t, h_out_evals, h_last, h_chal_out);
 }
 
 int sumcheck_lookup_sel_fs(zk_ctx* ctx, const void* const* d_tabs, size_t len, const uint64_t* h_gamma, zk_transcript* t, uint64_t* h_out_evals, uint64_t* h_last,
                            uint64_t* h_chal_out) {
-    size_t emax;
-    const int rc = local_e(ctx, tuning().lookupsel_local_e, "lookupsel_local_e", emax);
-    if (rc) return rc;
-    FsIn<kLookupSelTabs> first;
-    for (int k = 0; k < kLookupSelTabs; k++) first.t[k] = d_tabs[k], first.sh[k] = 0;
-    GateChal gamma;
-    std::memcpy(&gamma.r, h_gamma, 32);
-    return run_fs<LookupSelKind>(ctx, "zk_sumcheck_lookup_sel_fs", first, len, emax, LookupSelKind::kPerCu, gamma, t, h_out_evals, h_last, h_chal_out);
+    return run_fs<LookupSelKind>(ctx, "zk_sumcheck_lookup_sel_fs", bind_lookup_sel(d_tabs, h_gamma), len, t, h_out_evals, h_last, h_chal_out);
 }
 
 int sumcheck_multi_fs(zk_ctx* ctx, size_t count, const void* const* d_e, const void* const* d_f, size_t len, zk_transcript* t, uint64_t* h_out_triples,

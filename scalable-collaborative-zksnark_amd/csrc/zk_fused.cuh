@@ -124,19 +124,19 @@ __global__ void __launch_bounds__(kGateBlock) k_sc_local(FsIn<K::kTabs> in, unsi
 
 // ---------------------------------------------------------------------------------------
 // The host driver of a call.  who: the C ABI's name of the call, noun: how its refusal names the length ("table length ", "N = ").
-// first: the caller's tables (for the Kinds with views, the views of the tree and their shifts); knob, knob_name: the identity's
-// *_local_e knob, the hand-over length (checked after the length, as every refusal of the length names the call); per_cu: workgroups
-// per CU of the passes; h_chal: one challenge per round.
+// b: the identity's binding of the caller's arguments (Bound, zk_gate.cuh); its *_local_e knob, the hand-over length, is checked after
+// the length, as every refusal of the length names the call.  h_chal: one challenge per round.
 // ---------------------------------------------------------------------------------------
 template <class K>
-static int run_preset(zk_ctx* ctx, const char* who, const char* noun, const FsIn<K::kTabs>& first, size_t len, long knob, const char* knob_name, size_t per_cu, const GateChal& gamma,
-                      const uint64_t* h_chal, uint64_t* h_out_evals, uint64_t* h_last) {
+static int run_preset(zk_ctx* ctx, const char* who, const char* noun, const Bound<K>& b, size_t len, const uint64_t* h_chal, uint64_t* h_out_evals, uint64_t* h_last) {
+    const GateChal& gamma = b.gamma;
+    const size_t per_cu = b.per_cu;
     if (len < 2 || (len & (len - 1))) return fail(ctx, ZK_ERR_INVALID, "%s: %s%zu is not a power of two >= 2", who, noun, len);
     size_t rounds = 0;
     while (((size_t)1 << rounds) < len) rounds++;
     if (rounds > (size_t)kGateMaxLog) return fail(ctx, ZK_ERR_INVALID, "%s: tables longer than 2^%d elements", who, kGateMaxLog);
     size_t emax;
-    const int rc = local_e(ctx, knob, knob_name, emax, K::kLocalMax);
+    const int rc = local_e(ctx, b.knob, b.knob_name, emax, K::kLocalMax);
     if (rc) return rc;
     ZK_HIP(ctx, hipSetDevice(ctx->device));
     // plan: passes while the tables are longer than emax
@@ -165,7 +165,7 @@ static int run_preset(zk_ctx* ctx, const char* who, const char* noun, const FsIn
         if (npass > 1 && !(buf[1] = (char*)scratch(ctx, 1, K::kTabs * (len / 4) * fr))) return ZK_ERR_OOM;
         if (!(part = (char*)scratch(ctx, 4, part_slots * kGateWideBytes))) return ZK_ERR_OOM;
     }
-    FsIn<K::kTabs> cur = first;
+    FsIn<K::kTabs> cur = b.first;
     for (size_t p = 0; p < npass; p++) {
         FsOut<K::kTabs> o;
         for (int k = 0; k < K::kTabs; k++) o.t[k] = buf[p & 1] + (size_t)k * ((p & 1) ? len / 4 : len / 2) * fr;

@@ -1,8 +1,11 @@
 // zk_gate.cuh -- what the fused sumchecks share (the preset-challenge engine zk_fused.cuh and its six identities zk_gate.hip, zk_wiring.hip,
 // zk_perm3.hip, zk_gatew.hip, zk_lookup.hip, zk_lookup3.hip; zk_batchopen.hip; their transcript-driven forms in zk_fs.hip): launch
 // geometry, the argument blocks of the kernels, the 544-bit lazily reduced sums (one 80-byte slot per wave, evaluation and pass), the
-// brackets of the identities with the Kind structs that describe them, and the blocks every pass and every local stage repeat.
+// brackets of the identities with the Kind structs that describe them, the blocks every pass and every local stage repeat, and (host
+// only) the binding of each identity's caller arguments, written once for its preset-challenge and its transcript-driven entry point.
 #pragma once
+#include <cstring>
+
 #include "fp.cuh"
 #include "zk_ctx.hpp"
 
@@ -361,6 +364,65 @@ static inline int local_e(zk_ctx* ctx, long knob, const char* name, size_t& emax
     emax = (size_t)knob;
     if (emax < 1 || emax > local_max || (emax & (emax - 1))) return fail(ctx, ZK_ERR_INVALID, "%s must be a power of two in [1, %u]", name, local_max);
     return ZK_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// Host only.  What the two entry points of an identity -- preset challenges in its own file, challenges from a transcript in
+// zk_fs.hip -- hand their engine (run_preset, run_fs), bound ONCE from the caller's arguments: the tables, gamma (zero for an identity
+// without one), the identity's *_local_e knob with its name, and the workgroups per CU of its passes.
+// ---------------------------------------------------------------------------------------
+template <class K>
+struct Bound {
+    FsIn<K::kTabs> first;
+    GateChal gamma;
+    long knob;
+    const char* knob_name;
+    size_t per_cu;
+};
+static inline GateChal load_gamma(const uint64_t* h_gamma) {  // null: the identity has no gamma
+    GateChal g;
+    std::memset(&g, 0, sizeof(g));
+    if (h_gamma) std::memcpy(&g.r, h_gamma, 32);
+    return g;
+}
+// a *_pass_wg knob, or the Kind's own kPerCu where the knob is 0
+static inline size_t pass_wg(long knob, int per_cu) { return knob > 0 ? (size_t)knob : (size_t)per_cu; }
+// plain tables, no shift
+template <int NT>
+static inline FsIn<NT> plain_tables(const void* const* d_tabs) {
+    FsIn<NT> in;
+    for (int k = 0; k < NT; k++) in.t[k] = d_tabs[k], in.sh[k] = 0;
+    return in;
+}
+// eq, then the views of the tree -- v1x its upper half, (vx0, vx1) every other element from its base / one element on, h its lower
+// half -- then the NT - 5 plain tables of `rest`
+template <int NT>
+static inline FsIn<NT> tree_tables(const void* d_eq, const void* d_tree, size_t N, const void* const (&rest)[NT - 5]) {
+    const char* tree = (const char*)d_tree;
+    FsIn<NT> in = {{d_eq, tree + N * 32, tree, tree + 32, tree}, {0, 0, 1, 1, 0}};
+    for (int k = 5; k < NT; k++) in.t[k] = rest[k - 5], in.sh[k] = 0;
+    return in;
+}
+
+static inline Bound<GateKind> bind_gate(const void* const* d_tabs) {
+    return {plain_tables<GateKind::kTabs>(d_tabs), load_gamma(nullptr), tuning().gate_local_e, "gate_local_e", pass_wg(tuning().gate_pass_wg, GateKind::kPerCu)};
+}
+static inline Bound<WireKind> bind_wiring(const void* d_eq, const void* d_tree, const void* d_num, const void* d_den, size_t N, const uint64_t* h_gamma) {
+    return {tree_tables<WireKind::kTabs>(d_eq, d_tree, N, {d_num, d_den}), load_gamma(h_gamma), tuning().wiring_local_e, "wiring_local_e",
+            pass_wg(tuning().wiring_pass_wg, WireKind::kPerCu)};
+}
+static inline Bound<Perm3Kind> bind_perm3(const void* d_eq, const void* d_tree, const void* const* d_num, const void* const* d_den, size_t N, const uint64_t* h_gamma) {
+    return {tree_tables<kPerm3Tabs>(d_eq, d_tree, N, {d_num[0], d_num[1], d_num[2], d_den[0], d_den[1], d_den[2]}), load_gamma(h_gamma), tuning().perm3_local_e,
+            "perm3_local_e", (size_t)Perm3Kind::kPerCu};
+}
+static inline Bound<GatewKind> bind_gate_wide(const void* const* d_tabs) {
+    return {plain_tables<kGatewTabs>(d_tabs), load_gamma(nullptr), tuning().gatew_local_e, "gatew_local_e", (size_t)GatewKind::kPerCu};
+}
+static inline Bound<LookupKind> bind_lookup(const void* const* d_tabs, const uint64_t* h_gamma) {
+    return {plain_tables<kLookupTabs>(d_tabs), load_gamma(h_gamma), tuning().lookup_local_e, "lookup_local_e", (size_t)LookupKind::kPerCu};
+}
+static inline Bound<LookupSelKind> bind_lookup_sel(const void* const* d_tabs, const uint64_t* h_gamma) {
+    return {plain_tables<kLookupSelTabs>(d_tabs), load_gamma(h_gamma), tuning().lookupsel_local_e, "lookupsel_local_e", (size_t)LookupSelKind::kPerCu};
 }
 
 }  // namespace zk

@@ -72,12 +72,7 @@ int eq_table_seeded(zk_ctx* ctx, const uint64_t* h_point, size_t n, const uint64
 }
 
 int sumcheck_gate(zk_ctx* ctx, const void* const* d_tabs, size_t len, const uint64_t* h_chal, uint64_t* h_out_evals, uint64_t* h_last) {
-    FsIn<GateKind::kTabs> first;
-    for (int k = 0; k < GateKind::kTabs; k++) first.t[k] = d_tabs[k], first.sh[k] = 0;
-    GateChal none;
-    std::memset(&none, 0, sizeof(none));
-    return run_preset<GateKind>(ctx, "zk_sumcheck_gate", "table length ", first, len, tuning().gate_local_e, "gate_local_e", tuning().gate_pass_wg > 0 ? (size_t)tuning().gate_pass_wg : GateKind::kPerCu, none,
-                                h_chal, h_out_evals, h_last);
+    return run_preset<GateKind>(ctx, "zk_sumcheck_gate", "table length ", bind_gate(d_tabs), len, h_chal, h_out_evals, h_last);
 }
 
 }  // namespace zk

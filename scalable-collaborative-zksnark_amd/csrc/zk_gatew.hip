@@ -18,11 +18,7 @@
 namespace zk {
 
 int sumcheck_gate_wide(zk_ctx* ctx, const void* const* d_tabs, size_t len, const uint64_t* h_chal, uint64_t* h_out_evals, uint64_t* h_last) {
-    FsIn<kGatewTabs> first;
-    for (int k = 0; k < kGatewTabs; k++) first.t[k] = d_tabs[k], first.sh[k] = 0;
-    GateChal none;
-    std::memset(&none, 0, sizeof(none));
-    return run_preset<GatewKind>(ctx, "zk_sumcheck_gate_wide", "table length ", first, len, tuning().gatew_local_e, "gatew_local_e", GatewKind::kPerCu, none, h_chal, h_out_evals, h_last);
+    return run_preset<GatewKind>(ctx, "zk_sumcheck_gate_wide", "table length ", bind_gate_wide(d_tabs), len, h_chal, h_out_evals, h_last);
 }
 
 }  // namespace zk

@@ -79,11 +79,7 @@ int lookup_write_counts(zk_ctx* ctx, const uint32_t* d_cnt, size_t N, void* d_m)
 // host driver
 // ---------------------------------------------------------------------------------------
 int sumcheck_lookup(zk_ctx* ctx, const void* const* d_tabs, size_t len, const uint64_t* h_gamma, const uint64_t* h_chal, uint64_t* h_out_evals, uint64_t* h_last) {
-    FsIn<kLookupTabs> first;
-    for (int k = 0; k < kLookupTabs; k++) first.t[k] = d_tabs[k], first.sh[k] = 0;
-    GateChal gamma;
-    std::memcpy(&gamma.r, h_gamma, 32);
-    return run_preset<LookupKind>(ctx, "zk_sumcheck_lookup", "len = ", first, len, tuning().lookup_local_e, "lookup_local_e", LookupKind::kPerCu, gamma, h_chal, h_out_evals, h_last);
+    return run_preset<LookupKind>(ctx, "zk_sumcheck_lookup", "len = ", bind_lookup(d_tabs, h_gamma), len, h_chal, h_out_evals, h_last);
 }
 
 }  // namespace zk

@@ -120,11 +120,7 @@ int lookup3_terms(zk_ctx* ctx, const void* const* d_w, const void* const* d_t, s
 // host driver
 // ---------------------------------------------------------------------------------------
 int sumcheck_lookup_sel(zk_ctx* ctx, const void* const* d_tabs, size_t len, const uint64_t* h_gamma, const uint64_t* h_chal, uint64_t* h_out_evals, uint64_t* h_last) {
-    FsIn<kLookupSelTabs> first;
-    for (int k = 0; k < kLookupSelTabs; k++) first.t[k] = d_tabs[k], first.sh[k] = 0;
-    GateChal gamma;
-    std::memcpy(&gamma.r, h_gamma, 32);
-    return run_preset<LookupSelKind>(ctx, "zk_sumcheck_lookup_sel", "len = ", first, len, tuning().lookupsel_local_e, "lookupsel_local_e", LookupSelKind::kPerCu, gamma, h_chal, h_out_evals, h_last);
+    return run_preset<LookupSelKind>(ctx, "zk_sumcheck_lookup_sel", "len = ", bind_lookup_sel(d_tabs, h_gamma), len, h_chal, h_out_evals, h_last);
 }
 
 }  // namespace zk

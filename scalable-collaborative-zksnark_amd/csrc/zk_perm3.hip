@@ -78,13 +78,7 @@ int perm3_terms(zk_ctx* ctx, const void* const* d_w, const void* const* d_ssigma
 
 int sumcheck_perm3(zk_ctx* ctx, const void* d_eq, const void* d_tree, const void* const* d_num, const void* const* d_den, size_t N, const uint64_t* h_gamma,
                    const uint64_t* h_chal, uint64_t* h_out_evals, uint64_t* h_last) {
-    // the views of the tree: v1x its upper half, (vx0, vx1) every other element from its base / one element on, h its lower half
-    const char* tree = (const char*)d_tree;
-    const FsIn<kPerm3Tabs> first = {{d_eq, tree + N * 32, tree, tree + 32, tree, d_num[0], d_num[1], d_num[2], d_den[0], d_den[1], d_den[2]},
-                                    {0, 0, 1, 1, 0, 0, 0, 0, 0, 0, 0}};
-    GateChal gamma;
-    std::memcpy(&gamma.r, h_gamma, 32);
-    return run_preset<Perm3Kind>(ctx, "zk_sumcheck_perm3", "N = ", first, N, tuning().perm3_local_e, "perm3_local_e", Perm3Kind::kPerCu, gamma, h_chal, h_out_evals, h_last);
+    return run_preset<Perm3Kind>(ctx, "zk_sumcheck_perm3", "N = ", bind_perm3(d_eq, d_tree, d_num, d_den, N, h_gamma), N, h_chal, h_out_evals, h_last);
 }
 
 }  // namespace zk

@@ -22,13 +22,7 @@ namespace zk {
 // ---------------------------------------------------------------------------------------
 int sumcheck_wiring(zk_ctx* ctx, const void* d_eq, const void* d_tree, const void* d_num, const void* d_den, size_t N, const uint64_t* h_gamma,
                     const uint64_t* h_chal, uint64_t* h_out_evals, uint64_t* h_last) {
-    // the views of the tree: v1x its upper half, (vx0, vx1) every other element from its base / one element on, h its lower half
-    const char* tree = (const char*)d_tree;
-    const FsIn<WireKind::kTabs> first = {{d_eq, tree + N * 32, tree, tree + 32, tree, d_num, d_den}, {0, 0, 1, 1, 0, 0, 0}};
-    GateChal gamma;
-    std::memcpy(&gamma.r, h_gamma, 32);
-    return run_preset<WireKind>(ctx, "zk_sumcheck_wiring", "N = ", first, N, tuning().wiring_local_e, "wiring_local_e", tuning().wiring_pass_wg > 0 ? (size_t)tuning().wiring_pass_wg : WireKind::kPerCu, gamma,
-                                h_chal, h_out_evals, h_last);
+    return run_preset<WireKind>(ctx, "zk_sumcheck_wiring", "N = ", bind_wiring(d_eq, d_tree, d_num, d_den, N, h_gamma), N, h_chal, h_out_evals, h_last);
 }
 
 }  // namespace zk

@@ -53,12 +53,6 @@ inline FrVec eq_coefficients(size_t n_tables, const std::vector<Claim> &claims, 
     for (size_t k = 0; k < claims.size(); ++k) e[claims[k].table] += w[k] * eq_eval(claims[k].point, rho);
     return e;
 }
-// the degree-2 polynomial through (0, t0), (1, t1), (2, t2) at x   dsumcheck.rs:562-575
-inline Fr product_round_target(const std::array<Fr, 3> &t, const Fr &x) {
-    const Fr half = Fr::from_u64(2).inverse();
-    const Fr b = (Fr::from_u64(4) * t[1] - t[2] - Fr::from_u64(3) * t[0]) * half, a = (t[2] - t[1] - t[1] + t[0]) * half;
-    return t[0] + x * (b + x * a);
-}
 
 // E_j on the device (a null DevPtr for a table without claims): the first claim on a table is a_k eq(z_k, .), later ones are added in
 inline std::vector<DevPtr> combined_eq_tables(Ctx &be, size_t n_tables, size_t n, const std::vector<Claim> &claims, const Fr &alpha) {
@@ -96,7 +90,7 @@ inline BatchOpenProof batch_open_prove(Ctx &be, const PowersOfG &pg, const std::
 }
 
 // The verifier's field arithmetic (no GPU) -> a bit per failed check (0: all hold; bit 0: a malformed record or statement):
-//   1. p_0(0) + p_0(1) == S and p_i(0) + p_i(1) == p_{i-1}(rho_{i-1});  y (optional) receives p_{n-1}(rho_{n-1});
+//   1. p_0(0) + p_0(1) == S and p_i(0) + p_i(1) == p_{i-1}(rho_{i-1}), on the nodes 0 .. 2 (round_chain.hpp; dsumcheck.rs:558-588);  y (optional) receives p_{n-1}(rho_{n-1});
 //   2. only when finals = the J values f_j(rho) are given: y == sum_j e_j f_j(rho) (the real verifier gets this from the pairing).
 inline unsigned failed_checks(size_t n_tables, const std::vector<Claim> &claims, const BatchOpenProof &proof, const Fr &alpha, const FrVec &rho,
                               Fr *y = nullptr, const FrVec *finals = nullptr) {
@@ -104,11 +98,8 @@ inline unsigned failed_checks(size_t n_tables, const std::vector<Claim> &claims,
     if (n == 0 || proof.rounds.size() != n || proof.opening.size() != n || claims.empty()) return 1u;
     for (const Claim &c : claims)
         if (c.table >= n_tables || c.point.size() != n) return 1u;
-    Fr target = claimed_sum(claims, alpha);
-    for (size_t i = 0; i < n; ++i) {
-        if (proof.rounds[i][0] + proof.rounds[i][1] != target) return 1u << 1;
-        target = product_round_target(proof.rounds[i], rho[i]);
-    }
+    Fr target;
+    if (!round_chain(proof.rounds, 3, rho, claimed_sum(claims, alpha), &target)) return 1u << 1;
     if (y) *y = target;
     if (finals) {
         const FrVec e = eq_coefficients(n_tables, claims, alpha, rho);

@@ -268,25 +268,16 @@ class Ctx {
     }
     // zk_sumcheck_gate: tabs = eq, q1, q2, a, b, c, in -> r.sums = 5 Fr per round (t = 0 .. 4), `last` = the seven remaining elements
     ScResult sumcheck_gate(const std::array<DevPtr, 7> &tabs, size_t len, const FrVec &chal, FrVec &last) {
-        size_t n = log2_exact(len);
-        need(n >= 1 && chal.size() >= n, "sumcheck_gate: fewer challenges than rounds");
-        ScResult r;
-        r.sums.resize(5 * n);
-        last.assign(7, Fr::zero());
-        check(zk_sumcheck_gate(h_, tabs[0].get(), tabs[1].get(), tabs[2].get(), tabs[3].get(), tabs[4].get(), tabs[5].get(), tabs[6].get(), len, chal[0].v,
-                               r.sums[0].v, last[0].v));
-        return r;
+        return fused(kFusedGate, false, len, chal, last, [&](uint64_t *sums, uint64_t *lst) {
+            return zk_sumcheck_gate(h_, tabs[0].get(), tabs[1].get(), tabs[2].get(), tabs[3].get(), tabs[4].get(), tabs[5].get(), tabs[6].get(), len, chal[0].v, sums, lst);
+        });
     }
     // zk_sumcheck_wiring: tree = the 2N Fr of product_tree -> r.sums = 4 Fr per round (t = 0 .. 3), `last` = eq, v1x, vx0, vx1, h, num, den
     ScResult sumcheck_wiring(const DevPtr &eq, const DevPtr &tree, const DevPtr &num, const DevPtr &den, size_t N, const Fr &gamma, const FrVec &chal,
                              FrVec &last) {
-        size_t mu = log2_exact(N);
-        need(mu >= 1 && chal.size() >= mu, "sumcheck_wiring: fewer challenges than rounds");
-        ScResult r;
-        r.sums.resize(4 * mu);
-        last.assign(7, Fr::zero());
-        check(zk_sumcheck_wiring(h_, eq.get(), tree.get(), num.get(), den.get(), N, gamma.v, chal[0].v, r.sums[0].v, last[0].v));
-        return r;
+        return fused(kFusedWiring, false, N, chal, last, [&](uint64_t *sums, uint64_t *lst) {
+            return zk_sumcheck_wiring(h_, eq.get(), tree.get(), num.get(), den.get(), N, gamma.v, chal[0].v, sums, lst);
+        });
     }
     // zk_perm3_terms: the derived tables of the three-column wiring identity in one pass (asynchronous)
     struct Perm3Terms {
@@ -308,26 +299,15 @@ class Ctx {
     // zk_sumcheck_perm3: tree = the 2N Fr of product_tree -> r.sums = 6 Fr per round (t = 0 .. 5), `last` = eq, v1x, vx0, vx1, h, n_0..2, d_0..2
     ScResult sumcheck_perm3(const DevPtr &eq, const DevPtr &tree, const std::array<DevPtr, 3> &num, const std::array<DevPtr, 3> &den, size_t N, const Fr &gamma,
                             const FrVec &chal, FrVec &last) {
-        size_t mu = log2_exact(N);
-        need(mu >= 1 && chal.size() >= mu, "sumcheck_perm3: fewer challenges than rounds");
-        ScResult r;
-        r.sums.resize(6 * mu);
-        last.assign(11, Fr::zero());
-        const void *pn[3] = {num[0].get(), num[1].get(), num[2].get()}, *pd[3] = {den[0].get(), den[1].get(), den[2].get()};
-        check(zk_sumcheck_perm3(h_, eq.get(), tree.get(), pn, pd, N, gamma.v, chal[0].v, r.sums[0].v, last[0].v));
-        return r;
+        const auto pn = ptrs(num), pd = ptrs(den);
+        return fused(kFusedPerm3, false, N, chal, last, [&](uint64_t *sums, uint64_t *lst) {
+            return zk_sumcheck_perm3(h_, eq.get(), tree.get(), pn.data(), pd.data(), N, gamma.v, chal[0].v, sums, lst);
+        });
     }
     // zk_sumcheck_gate_wide: tabs = eq, qL, qR, qM, qO, qC, qH, a, b, c, in -> r.sums = 8 Fr per round (t = 0 .. 7), `last` = the eleven remaining elements
     ScResult sumcheck_gate_wide(const std::array<DevPtr, 11> &tabs, size_t len, const FrVec &chal, FrVec &last) {
-        size_t n = log2_exact(len);
-        need(n >= 1 && chal.size() >= n, "sumcheck_gate_wide: fewer challenges than rounds");
-        ScResult r;
-        r.sums.resize(8 * n);
-        last.assign(11, Fr::zero());
-        const void *p[11];
-        for (int k = 0; k < 11; k++) p[k] = tabs[k].get();
-        check(zk_sumcheck_gate_wide(h_, p, len, chal[0].v, r.sums[0].v, last[0].v));
-        return r;
+        const auto p = ptrs(tabs);
+        return fused(kFusedGateWide, false, len, chal, last, [&](uint64_t *sums, uint64_t *lst) { return zk_sumcheck_gate_wide(h_, p.data(), len, chal[0].v, sums, lst); });
     }
     // zk_lookup_multiplicities: m[y] = #{x : idx[x] = y} as N Fr; idx = N u32 on the device.  A row that is not in the table: ZkError(ZK_ERR_INVALID)
     DevPtr lookup_multiplicities(const DevPtr &f, const DevPtr &t, const DevPtr &idx, size_t N) {
@@ -337,15 +317,8 @@ class Ctx {
     }
     // zk_sumcheck_lookup: tabs = E, df, dt, m, hf, ht -> r.sums = 4 Fr per round (t = 0 .. 3), `last` = the six remaining elements
     ScResult sumcheck_lookup(const std::array<DevPtr, 6> &tabs, size_t len, const Fr &gamma, const FrVec &chal, FrVec &last) {
-        size_t n = log2_exact(len);
-        need(n >= 1 && chal.size() >= n, "sumcheck_lookup: fewer challenges than rounds");
-        ScResult r;
-        r.sums.resize(4 * n);
-        last.assign(6, Fr::zero());
-        const void *p[6];
-        for (int k = 0; k < 6; k++) p[k] = tabs[k].get();
-        check(zk_sumcheck_lookup(h_, p, len, gamma.v, chal[0].v, r.sums[0].v, last[0].v));
-        return r;
+        const auto p = ptrs(tabs);
+        return fused(kFusedLookup, false, len, chal, last, [&](uint64_t *sums, uint64_t *lst) { return zk_sumcheck_lookup(h_, p.data(), len, gamma.v, chal[0].v, sums, lst); });
     }
     // zk_lookup3_multiplicities: m[y] = #{x : qk(x) = 1, idx[x] = y} as N Fr; w = a, b, c; t = t0, t1, t2; idx = N u32 on the device.  A selected
     // row whose triple is not the table entry it names, or a qk that is neither 0 nor 1: ZkError(ZK_ERR_INVALID)
@@ -379,15 +352,8 @@ class Ctx {
     }
     // zk_sumcheck_lookup_sel: tabs = E, df, dt, m, hf, ht, qk -> r.sums = 4 Fr per round (t = 0 .. 3), `last` = the seven remaining elements
     ScResult sumcheck_lookup_sel(const std::array<DevPtr, 7> &tabs, size_t len, const Fr &gamma, const FrVec &chal, FrVec &last) {
-        size_t n = log2_exact(len);
-        need(n >= 1 && chal.size() >= n, "sumcheck_lookup_sel: fewer challenges than rounds");
-        ScResult r;
-        r.sums.resize(4 * n);
-        last.assign(7, Fr::zero());
-        const void *p[7];
-        for (int k = 0; k < 7; k++) p[k] = tabs[k].get();
-        check(zk_sumcheck_lookup_sel(h_, p, len, gamma.v, chal[0].v, r.sums[0].v, last[0].v));
-        return r;
+        const auto p = ptrs(tabs);
+        return fused(kFusedLookupSel, false, len, chal, last, [&](uint64_t *sums, uint64_t *lst) { return zk_sumcheck_lookup_sel(h_, p.data(), len, gamma.v, chal[0].v, sums, lst); });
     }
     // zk_eq_table_acc: acc[x] += weight * eq(point, x), acc = 2^n Fr (asynchronous)
     void eq_table_acc(const FrVec &point, const Fr &weight, const DevPtr &acc) {
@@ -431,74 +397,40 @@ class Ctx {
         return out;
     }
     ScResult sumcheck_gate_fs(const std::array<DevPtr, 7> &tabs, size_t len, DeviceTranscript &t, FrVec &last, FrVec &chal) {
-        size_t n = log2_exact(len);
-        need(n >= 1, "sumcheck_gate_fs: at least one round");
-        ScResult r;
-        r.sums.resize(5 * n);
-        last.assign(7, Fr::zero());
-        chal.assign(n, Fr::zero());
-        check(zk_sumcheck_gate_fs(h_, tabs[0].get(), tabs[1].get(), tabs[2].get(), tabs[3].get(), tabs[4].get(), tabs[5].get(), tabs[6].get(), len, t.h, r.sums[0].v,
-                                  last[0].v, chal[0].v));
-        return r;
+        chal.assign(log2_exact(len), Fr::zero());
+        return fused(kFusedGate, true, len, chal, last, [&](uint64_t *sums, uint64_t *lst) {
+            return zk_sumcheck_gate_fs(h_, tabs[0].get(), tabs[1].get(), tabs[2].get(), tabs[3].get(), tabs[4].get(), tabs[5].get(), tabs[6].get(), len, t.h, sums, lst, chal[0].v);
+        });
     }
     ScResult sumcheck_wiring_fs(const DevPtr &eq, const DevPtr &tree, const DevPtr &num, const DevPtr &den, size_t N, const Fr &gamma, DeviceTranscript &t, FrVec &last,
                                 FrVec &chal) {
-        size_t mu = log2_exact(N);
-        need(mu >= 1, "sumcheck_wiring_fs: at least one round");
-        ScResult r;
-        r.sums.resize(4 * mu);
-        last.assign(7, Fr::zero());
-        chal.assign(mu, Fr::zero());
-        check(zk_sumcheck_wiring_fs(h_, eq.get(), tree.get(), num.get(), den.get(), N, gamma.v, t.h, r.sums[0].v, last[0].v, chal[0].v));
-        return r;
+        chal.assign(log2_exact(N), Fr::zero());
+        return fused(kFusedWiring, true, N, chal, last, [&](uint64_t *sums, uint64_t *lst) {
+            return zk_sumcheck_wiring_fs(h_, eq.get(), tree.get(), num.get(), den.get(), N, gamma.v, t.h, sums, lst, chal[0].v);
+        });
     }
     ScResult sumcheck_perm3_fs(const DevPtr &eq, const DevPtr &tree, const std::array<DevPtr, 3> &num, const std::array<DevPtr, 3> &den, size_t N, const Fr &gamma,
                                DeviceTranscript &t, FrVec &last, FrVec &chal) {
-        size_t mu = log2_exact(N);
-        need(mu >= 1, "sumcheck_perm3_fs: at least one round");
-        ScResult r;
-        r.sums.resize(6 * mu);
-        last.assign(11, Fr::zero());
-        chal.assign(mu, Fr::zero());
-        const void *pn[3] = {num[0].get(), num[1].get(), num[2].get()}, *pd[3] = {den[0].get(), den[1].get(), den[2].get()};
-        check(zk_sumcheck_perm3_fs(h_, eq.get(), tree.get(), pn, pd, N, gamma.v, t.h, r.sums[0].v, last[0].v, chal[0].v));
-        return r;
+        const auto pn = ptrs(num), pd = ptrs(den);
+        chal.assign(log2_exact(N), Fr::zero());
+        return fused(kFusedPerm3, true, N, chal, last, [&](uint64_t *sums, uint64_t *lst) {
+            return zk_sumcheck_perm3_fs(h_, eq.get(), tree.get(), pn.data(), pd.data(), N, gamma.v, t.h, sums, lst, chal[0].v);
+        });
     }
     ScResult sumcheck_gate_wide_fs(const std::array<DevPtr, 11> &tabs, size_t len, DeviceTranscript &t, FrVec &last, FrVec &chal) {
-        size_t n = log2_exact(len);
-        need(n >= 1, "sumcheck_gate_wide_fs: at least one round");
-        ScResult r;
-        r.sums.resize(8 * n);
-        last.assign(11, Fr::zero());
-        chal.assign(n, Fr::zero());
-        const void *p[11];
-        for (int k = 0; k < 11; k++) p[k] = tabs[k].get();
-        check(zk_sumcheck_gate_wide_fs(h_, p, len, t.h, r.sums[0].v, last[0].v, chal[0].v));
-        return r;
+        const auto p = ptrs(tabs);
+        chal.assign(log2_exact(len), Fr::zero());
+        return fused(kFusedGateWide, true, len, chal, last, [&](uint64_t *sums, uint64_t *lst) { return zk_sumcheck_gate_wide_fs(h_, p.data(), len, t.h, sums, lst, chal[0].v); });
     }
     ScResult sumcheck_lookup_fs(const std::array<DevPtr, 6> &tabs, size_t len, const Fr &gamma, DeviceTranscript &t, FrVec &last, FrVec &chal) {
-        size_t n = log2_exact(len);
-        need(n >= 1, "sumcheck_lookup_fs: at least one round");
-        ScResult r;
-        r.sums.resize(4 * n);
-        last.assign(6, Fr::zero());
-        chal.assign(n, Fr::zero());
-        const void *p[6];
-        for (int k = 0; k < 6; k++) p[k] = tabs[k].get();
-        check(zk_sumcheck_lookup_fs(h_, p, len, gamma.v, t.h, r.sums[0].v, last[0].v, chal[0].v));
-        return r;
+        const auto p = ptrs(tabs);
+        chal.assign(log2_exact(len), Fr::zero());
+        return fused(kFusedLookup, true, len, chal, last, [&](uint64_t *sums, uint64_t *lst) { return zk_sumcheck_lookup_fs(h_, p.data(), len, gamma.v, t.h, sums, lst, chal[0].v); });
     }
     ScResult sumcheck_lookup_sel_fs(const std::array<DevPtr, 7> &tabs, size_t len, const Fr &gamma, DeviceTranscript &t, FrVec &last, FrVec &chal) {
-        size_t n = log2_exact(len);
-        need(n >= 1, "sumcheck_lookup_sel_fs: at least one round");
-        ScResult r;
-        r.sums.resize(4 * n);
-        last.assign(7, Fr::zero());
-        chal.assign(n, Fr::zero());
-        const void *p[7];
-        for (int k = 0; k < 7; k++) p[k] = tabs[k].get();
-        check(zk_sumcheck_lookup_sel_fs(h_, p, len, gamma.v, t.h, r.sums[0].v, last[0].v, chal[0].v));
-        return r;
+        const auto p = ptrs(tabs);
+        chal.assign(log2_exact(len), Fr::zero());
+        return fused(kFusedLookupSel, true, len, chal, last, [&](uint64_t *sums, uint64_t *lst) { return zk_sumcheck_lookup_sel_fs(h_, p.data(), len, gamma.v, t.h, sums, lst, chal[0].v); });
     }
     ScResult sumcheck_multi_fs(const std::vector<DevPtr> &es, const std::vector<DevPtr> &fs, size_t len, DeviceTranscript &t, FrVec &last_e, FrVec &last_f,
                                FrVec &chal) {
@@ -814,6 +746,33 @@ class Ctx {
   private:
     static void need(bool ok, const char *what) {
         if (!ok) throw ZkError(ZK_ERR_INVALID, what);
+    }
+    // The six fused identities (each in a preset-challenge and a transcript-driven form): the name of the preset member, the elements
+    // folded out into `last`, the evaluations per round.
+    struct Fused {
+        const char *name;
+        size_t tabs, evals;
+    };
+    static constexpr Fused kFusedGate{"sumcheck_gate", 7, 5}, kFusedWiring{"sumcheck_wiring", 7, 4}, kFusedPerm3{"sumcheck_perm3", 11, 6},
+        kFusedGateWide{"sumcheck_gate_wide", 11, 8}, kFusedLookup{"sumcheck_lookup", 6, 4}, kFusedLookupSel{"sumcheck_lookup_sel", 7, 4};
+    // What their twelve members share: the round count checked -- and, for the preset form, the challenge count -- r.sums and `last` sized,
+    // then call(sums, last), which lays out the identity's pointers for its C call.  fs: the transcript-driven form, whose member has
+    // sized its own `chal` to receive the challenges.
+    template <class Call>
+    ScResult fused(const Fused &id, bool fs, size_t len, const FrVec &chal, FrVec &last, Call call) {
+        const size_t n = log2_exact(len);
+        if (n < 1 || (!fs && chal.size() < n)) throw ZkError(ZK_ERR_INVALID, std::string(id.name) + (fs ? "_fs: at least one round" : ": fewer challenges than rounds"));
+        ScResult r;
+        r.sums.resize(id.evals * n);
+        last.assign(id.tabs, Fr::zero());
+        check(call(r.sums[0].v, last[0].v));
+        return r;
+    }
+    template <size_t N>
+    static std::array<const void *, N> ptrs(const std::array<DevPtr, N> &t) {
+        std::array<const void *, N> p;
+        for (size_t k = 0; k < N; ++k) p[k] = t[k].get();
+        return p;
     }
     template <class F>
     DevPtr binary(F fn, const DevPtr &a, const DevPtr &b, size_t n) {

@@ -130,11 +130,8 @@ inline std::vector<Claim> lookup_claims(const LookupChallenges &c, const LookupP
 inline unsigned lookup_failed_checks(const LookupVk &vk, const LookupProof &p, const FrVec *finals = nullptr, Fr *y = nullptr) {
     LookupChallenges c;
     if (!lookup_challenges(vk, p, c) || p.batch.opening.size() != p.n) return 1u;
-    Fr target = Fr::zero();
-    for (size_t i = 0; i < p.n; ++i) {
-        if (p.rounds[i][0] + p.rounds[i][1] != target) return 1u << 1;
-        target = round_poly_at(p.rounds[i], c.chal[i]);
-    }
+    Fr target;
+    if (!round_chain(p.rounds, 4, c.chal, Fr::zero(), &target)) return 1u << 1;
     const FrVec &v = p.values;
     if (target != lookup_value(c.lambda * eq_eval(c.tau, c.chal), v[0], v[1], v[2], v[3], v[4], c.beta, c.gamma)) return 1u << 2;
     if (failed_checks(5, detail::lookup_claims(c, p), p.batch, c.b_alpha, c.rho, y, finals)) return 1u << 3;

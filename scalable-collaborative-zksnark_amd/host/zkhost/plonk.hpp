@@ -411,20 +411,6 @@ inline std::string circuit_digest(const PlonkCircuit &c) {
 }
 
 // ---- the verifier's closed forms ----
-inline Fr round_poly_nodes(const Fr *e, size_t K, const Fr &x) {  // the polynomial of degree K - 1 through (k, e[k]) at x
-    Fr acc = Fr::zero();
-    for (size_t k = 0; k < K; ++k) {
-        Fr num = Fr::one(), den = Fr::one();
-        for (size_t m = 0; m < K; ++m)
-            if (m != k) num *= x - Fr::from_u64(m), den *= Fr::from_u64(k) - Fr::from_u64(m);
-        acc += e[k] * num * den.inverse();
-    }
-    return acc;
-}
-template <size_t K>
-inline Fr round_poly_nodes(const std::array<Fr, K> &e, const Fr &x) {
-    return round_poly_nodes(e.data(), K, x);
-}
 // in(r): prod_{i < mu - k} (1 - r_i) * sum_y pi[y] eq(y, r_{mu-k..}), index bit 0 the TOP bit
 inline Fr in_eval(const FrVec &pi, const FrVec &r) {
     size_t k = 0;
@@ -670,21 +656,9 @@ inline unsigned plonk_failed_checks(const PlonkVk &vk, const FrVec &pi, const Pl
     const size_t mu = vk.mu, N = size_t(1) << mu, ns = gate_desc(vk.gate).selectors;
     if (p.gate != vk.gate || p.lookup != vk.lookup) return 1u;
     unsigned bad = 0;
-    Fr p_target = Fr::zero(), g_target = Fr::zero();
-    for (size_t i = 0; i < mu; ++i) {
-        if (p.p_rounds[i][0] + p.p_rounds[i][1] != p_target) {
-            bad |= 1u << 1;
-            break;
-        }
-        p_target = round_poly_nodes(p.p_rounds[i], c.r_p[i]);
-    }
-    for (size_t i = 0; i < mu; ++i) {
-        if (p.g_rounds[i][0] + p.g_rounds[i][1] != g_target) {
-            bad |= 1u << 2;
-            break;
-        }
-        g_target = round_poly_nodes(p.g_rounds[i].data(), p.g_rounds[i].size(), c.r_g[i]);
-    }
+    Fr p_target, g_target;
+    if (!round_chain(p.p_rounds, 6, c.r_p, Fr::zero(), &p_target)) bad |= 1u << 1;
+    if (!round_chain(p.g_rounds, gate_desc(vk.gate).evals, c.r_g, Fr::zero(), &g_target)) bad |= 1u << 2;
     const FrVec &g = p.g_values, &v = p.p_values, &t = p.v_values;  // g: the selectors, a, b, c;  t: v(0,r), v(1,r), v(r,0), v(r,1), v(1,..,1,0)
     if (!(bad & (1u << 2)) && g_target != gate_closed_form(vk.gate, eq_eval(c.tau_g, c.r_g), g, in_eval(pi, c.r_g))) bad |= 1u << 3;
     const Fr ids = slot_eval(c.r_p);
@@ -700,14 +674,8 @@ inline unsigned plonk_failed_checks(const PlonkVk &vk, const FrVec &pi, const Pl
     if (vk.lookup) detail::lookup_claims(p, c.r_l, claims, l_claims);
     if (failed_checks(ns + 6, claims, p.batch, c.b_alpha, c.rho_mu) || failed_checks(1, v_claims, p.v_batch, c.b_alpha, c.rho_mu1)) bad |= 1u << 6;
     if (vk.lookup) {
-        Fr target = Fr::zero();
-        for (size_t i = 0; i < mu; ++i) {
-            if (p.l_rounds[i][0] + p.l_rounds[i][1] != target) {
-                bad |= 1u << 7;
-                break;
-            }
-            target = round_poly_nodes(p.l_rounds[i], c.r_l[i]);
-        }
+        Fr target;
+        if (!round_chain(p.l_rounds, 4, c.r_l, Fr::zero(), &target)) bad |= 1u << 7;
         if (!(bad & (1u << 7)) && target != lookup3_value(c.lambda * eq_eval(c.tau_l, c.r_l), p.l_values, c.zeta, c.beta_l, c.gamma_l)) bad |= 1u << 8;
         if (failed_checks(7, l_claims, p.l_batch, c.b_alpha, c.rho_l)) bad |= 1u << 9;
     }

@@ -32,21 +32,6 @@ struct WiringScalars {
     FrVec tau, chal;
 };
 
-// the degree-3 polynomial through (k, e[k]), k = 0 .. 3, at x (Lagrange)
-inline Fr round_poly_at(const std::array<Fr, 4> &e, const Fr &x) {
-    Fr acc = Fr::zero();
-    for (int k = 0; k < 4; ++k) {
-        Fr num = Fr::one(), den = Fr::one();
-        for (int m = 0; m < 4; ++m)
-            if (m != k) {
-                num *= x - Fr::from_u64((uint64_t)m);
-                den *= Fr::from_u64((uint64_t)k) - Fr::from_u64((uint64_t)m);
-            }
-        acc += e[k] * num * den.inverse();
-    }
-    return acc;
-}
-
 // the five (mu + 1)-variate points at which the tree is opened
 inline std::vector<FrVec> v_points(const FrVec &r) {
     std::vector<FrVec> p(5, r);
@@ -60,18 +45,15 @@ inline std::vector<FrVec> v_points(const FrVec &r) {
 }
 
 // The verifier's field arithmetic (no GPU) -> a bit per failed check (0: all hold; bit 0: a malformed record):
-//   1. p_0(0) + p_0(1) == 0 and p_i(0) + p_i(1) == p_{i-1}(r_{i-1});
+//   1. p_0(0) + p_0(1) == 0 and p_i(0) + p_i(1) == p_{i-1}(r_{i-1}), on the nodes 0 .. 3 (round_chain.hpp);
 //   2. p_{mu-1}(r_{mu-1}) == eq(tau, r) [ v(1,r) - v(r,0) v(r,1) + gamma ((w + alpha ssigma + beta) v(0,r) - (w + alpha sid + beta)) ];
 //   3. the opened v(1,..,1,0) == 1.
 inline unsigned failed_checks(const WiringProof &proof, const WiringScalars &sc) {
     const size_t mu = proof.rounds.size();
     if (mu == 0 || sc.tau.size() != mu || sc.chal.size() != mu || proof.openings.size() != 3 || proof.v_openings.size() != 5) return 1u;
     unsigned bad = 0;
-    Fr target = Fr::zero();
-    for (size_t i = 0; i < mu && !bad; ++i) {
-        if (proof.rounds[i][0] + proof.rounds[i][1] != target) bad |= 1u << 1;
-        target = round_poly_at(proof.rounds[i], sc.chal[i]);
-    }
+    Fr target;
+    if (!round_chain(proof.rounds, 4, sc.chal, Fr::zero(), &target)) bad |= 1u << 1;
     const Fr &w = proof.openings[0].value, &sid = proof.openings[1].value, &ssigma = proof.openings[2].value;
     const Fr &v0r = proof.v_openings[0].value, &v1r = proof.v_openings[1].value, &vr0 = proof.v_openings[2].value, &vr1 = proof.v_openings[3].value;
     const Fr num = w + sc.alpha * sid + sc.beta, den = w + sc.alpha * ssigma + sc.beta;

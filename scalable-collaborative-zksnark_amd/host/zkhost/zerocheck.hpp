@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "dist_primitive.hpp"
+#include "round_chain.hpp"
 
 namespace zkhost {
 
@@ -40,21 +41,6 @@ inline Fr eq_eval(const FrVec &tau, const FrVec &r) {
     return v;
 }
 
-// the degree-4 polynomial through (k, e[k]), k = 0 .. 4, at x (Lagrange; the degree-2 analogue: dsumcheck.rs:562-575)
-inline Fr round_poly_at(const std::array<Fr, 5> &e, const Fr &x) {
-    Fr acc = Fr::zero();
-    for (int k = 0; k < 5; ++k) {
-        Fr num = Fr::one(), den = Fr::one();
-        for (int m = 0; m < 5; ++m)
-            if (m != k) {
-                num *= x - Fr::from_u64((uint64_t)m);
-                den *= Fr::from_u64((uint64_t)k) - Fr::from_u64((uint64_t)m);
-            }
-        acc += e[k] * num * den.inverse();
-    }
-    return acc;
-}
-
 // the wide Plonk gate (zk_sumcheck_gate_wide) at one point: eq [ qL a + qR b + qM a b + qH a^5 - qO c + qC + in ]
 inline Fr wide_gate_value(const Fr &eq, const Fr &qL, const Fr &qR, const Fr &qM, const Fr &qO, const Fr &qC, const Fr &qH, const Fr &a, const Fr &b, const Fr &c,
                           const Fr &in) {
@@ -62,16 +48,13 @@ inline Fr wide_gate_value(const Fr &eq, const Fr &qL, const Fr &qR, const Fr &qM
     return eq * (qL * a + qR * b + qM * a * b + qH * a2 * a2 * a - qO * c + qC + in);
 }
 
-// The verifier's field arithmetic (no GPU): p_0(0) + p_0(1) == 0; p_i(0) + p_i(1) == p_{i-1}(r_{i-1}); and
+// The verifier's field arithmetic (no GPU): the round chain from 0 on the nodes 0 .. 4 (round_chain.hpp), and
 // p_{n-1}(r_{n-1}) == eq(tau, r) [q1 (a + b) + q2 a b - c + in] on the six opened values.
 inline bool verify_rounds(const GateProof &proof, const FrVec &tau, const FrVec &chal) {
     const size_t n = proof.rounds.size();
     if (n == 0 || tau.size() != n || chal.size() != n || proof.openings.size() != 6) return false;
-    Fr target = Fr::zero();
-    for (size_t i = 0; i < n; ++i) {
-        if (proof.rounds[i][0] + proof.rounds[i][1] != target) return false;
-        target = round_poly_at(proof.rounds[i], chal[i]);
-    }
+    Fr target;
+    if (!round_chain(proof.rounds, 5, chal, Fr::zero(), &target)) return false;
     const Fr &a = proof.openings[0].value, &b = proof.openings[1].value, &c = proof.openings[2].value, &in = proof.openings[3].value,
              &q1 = proof.openings[4].value, &q2 = proof.openings[5].value;
     return target == eq_eval(tau, chal) * (q1 * (a + b) + q2 * a * b - c + in);

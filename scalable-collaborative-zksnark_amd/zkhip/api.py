@@ -514,29 +514,42 @@ class Ctx:
         self._check(self.lib.zk_eq_table(self.h, _h(point), len(point), _ptr(out)))
         return out
 
-    def sumcheck_gate(self, eq, q1, q2, a, b, c, inp, length: int, chal: np.ndarray):
-        """the gate identity eq [q1 (a + b) + q2 a b - c + in] as one degree-4 sumcheck -> (evals [n,5,4], last [7,4])"""
+    # the six fused identities: ABI name -> (tables folded out into `last`, evaluations per round, a gamma is passed)
+    _FUSED = {"gate": (7, 5, False), "wiring": (7, 4, True), "perm3": (11, 6, True), "gate_wide": (11, 8, False), "lookup": (6, 4, True), "lookup_sel": (7, 4, True)}
+
+    def _fused(self, name: str, fs: bool, ptrs: tuple, length: int, gamma, drive):
+        """What the twelve fused sumchecks share.  name: a key of _FUSED; ptrs: the pointer arguments of the C call, laid out by the caller
+        (who has checked how many tables it was given); drive: the preset challenges (zk_sumcheck_<name>) or, with fs, the transcript they are drawn from
+        (zk_sumcheck_<name>_fs).  -> (evals [n, evals, 4], last [tabs, 4]) and, with fs, chal [n, 4]"""
+        tabs, evals, has_gamma = self._FUSED[name]
         n = max(length.bit_length() - 1, 0)
-        chal = np.ascontiguousarray(chal, dtype=np.uint64).reshape(-1, 4)
+        out, last = np.zeros((n, evals, 4), dtype=np.uint64), np.zeros((tabs, 4), dtype=np.uint64)
+        gamma = np.ascontiguousarray(gamma, dtype=np.uint64).reshape(4) if has_gamma else None  # a local: it must outlive the call
+        args = (self.h, *ptrs, length) + ((_h(gamma),) if has_gamma else ())
+        if fs:
+            drawn = np.zeros((n, 4), dtype=np.uint64)
+            self._check(getattr(self.lib, f"zk_sumcheck_{name}_fs")(*args, self._tr(drive), _h(out), _h(last), _h(drawn)))
+            return out, last, drawn
+        chal = np.ascontiguousarray(drive, dtype=np.uint64).reshape(-1, 4)
         if len(chal) < n:
             raise ValueError(f"{n} challenges needed, {len(chal)} given")
-        out = np.zeros((n, 5, 4), dtype=np.uint64)
-        last = np.zeros((7, 4), dtype=np.uint64)
-        self._check(self.lib.zk_sumcheck_gate(self.h, _ptr(eq), _ptr(q1), _ptr(q2), _ptr(a), _ptr(b), _ptr(c), _ptr(inp), length, _h(chal), _h(out), _h(last)))
+        self._check(getattr(self.lib, f"zk_sumcheck_{name}")(*args, _h(chal), _h(out), _h(last)))
         return out, last
+
+    def _check_rows(self, rc: int) -> None:
+        """_check for the calls that look at the caller's rows: their ZK_ERR_INVALID is a ValueError with the library's message"""
+        if rc == ZK_ERR_INVALID:
+            raise ValueError((self.lib.zk_last_error(self.h) or b"").decode())
+        self._check(rc)
+
+    def sumcheck_gate(self, eq, q1, q2, a, b, c, inp, length: int, chal: np.ndarray):
+        """the gate identity eq [q1 (a + b) + q2 a b - c + in] as one degree-4 sumcheck -> (evals [n,5,4], last [7,4])"""
+        return self._fused("gate", False, tuple(_ptr(t) for t in (eq, q1, q2, a, b, c, inp)), length, None, chal)
 
     def sumcheck_wiring(self, eq, tree, num, den, N: int, gamma: np.ndarray, chal: np.ndarray):
         """the wiring identity eq [v(1,x) - v(x,0) v(x,1) + gamma (den h - num)] on the product tree of h (2N Fr, read in place) as one
         degree-3 sumcheck -> (evals [mu,4,4], last [7,4]: eq, v1x, vx0, vx1, h, num, den)"""
-        mu = max(N.bit_length() - 1, 0)
-        chal = np.ascontiguousarray(chal, dtype=np.uint64).reshape(-1, 4)
-        gamma = np.ascontiguousarray(gamma, dtype=np.uint64).reshape(4)
-        if len(chal) < mu:
-            raise ValueError(f"{mu} challenges needed, {len(chal)} given")
-        out = np.zeros((mu, 4, 4), dtype=np.uint64)
-        last = np.zeros((7, 4), dtype=np.uint64)
-        self._check(self.lib.zk_sumcheck_wiring(self.h, _ptr(eq), _ptr(tree), _ptr(num), _ptr(den), N, _h(gamma), _h(chal), _h(out), _h(last)))
-        return out, last
+        return self._fused("wiring", False, (_ptr(eq), _ptr(tree), _ptr(num), _ptr(den)), N, gamma, chal)
 
     @staticmethod
     def _ptr_array(bufs):
@@ -562,29 +575,14 @@ class Ctx:
         read in place) as one degree-5 sumcheck -> (evals [mu,6,4], last [11,4]: eq, v1x, vx0, vx1, h, n_0..2, d_0..2)"""
         if len(nums) != 3 or len(dens) != 3:
             raise ValueError("three numerator and three denominator tables are needed")
-        mu = max(N.bit_length() - 1, 0)
-        chal = np.ascontiguousarray(chal, dtype=np.uint64).reshape(-1, 4)
-        gamma = np.ascontiguousarray(gamma, dtype=np.uint64).reshape(4)
-        if len(chal) < mu:
-            raise ValueError(f"{mu} challenges needed, {len(chal)} given")
-        out = np.zeros((mu, 6, 4), dtype=np.uint64)
-        last = np.zeros((11, 4), dtype=np.uint64)
-        self._check(self.lib.zk_sumcheck_perm3(self.h, _ptr(eq), _ptr(tree), self._ptr_array(nums), self._ptr_array(dens), N, _h(gamma), _h(chal), _h(out), _h(last)))
-        return out, last
+        return self._fused("perm3", False, (_ptr(eq), _ptr(tree), self._ptr_array(nums), self._ptr_array(dens)), N, gamma, chal)
 
     def sumcheck_gate_wide(self, tabs, length: int, chal: np.ndarray):
         """the wide gate identity eq [qL a + qR b + qM a b + qH a^5 - qO c + qC + in] as one degree-7 sumcheck; tabs: the eleven device
         buffers eq, qL, qR, qM, qO, qC, qH, a, b, c, in of `length` Fr -> (evals [n,8,4], last [11,4] in that order)"""
         if len(tabs) != 11:
             raise ValueError("eleven tables are needed: eq, qL, qR, qM, qO, qC, qH, a, b, c, in")
-        n = max(length.bit_length() - 1, 0)
-        chal = np.ascontiguousarray(chal, dtype=np.uint64).reshape(-1, 4)
-        if len(chal) < n:
-            raise ValueError(f"{n} challenges needed, {len(chal)} given")
-        out = np.zeros((n, 8, 4), dtype=np.uint64)
-        last = np.zeros((11, 4), dtype=np.uint64)
-        self._check(self.lib.zk_sumcheck_gate_wide(self.h, self._ptr_array(tabs), length, _h(chal), _h(out), _h(last)))
-        return out, last
+        return self._fused("gate_wide", False, (self._ptr_array(tabs),), length, None, chal)
 
     def lookup_multiplicities(self, f, t, idx, N: int, out=None):
         """m[y] = #{x : idx[x] = y} as N Fr for the lookup argument (zk_lookup_multiplicities; blocking): f, t device buffers of N Fr, idx one
@@ -592,9 +590,7 @@ class Ctx:
         (N < 2, not a power of two or > 2^32, a null pointer), with the library's message."""
         out = out or self.alloc(max(32 * N, 1))
         rc = self.lib.zk_lookup_multiplicities(self.h, _ptr(f), _ptr(t), _ptr(idx), N, _ptr(out))
-        if rc == ZK_ERR_INVALID:
-            raise ValueError((self.lib.zk_last_error(self.h) or b"").decode())
-        self._check(rc)
+        self._check_rows(rc)
         return out
 
     def sumcheck_lookup(self, tabs, length: int, gamma: np.ndarray, chal: np.ndarray):
@@ -602,15 +598,7 @@ class Ctx:
         E, df, dt, m, hf, ht of `length` Fr -> (evals [n,4,4], last [6,4] in that order)"""
         if len(tabs) != 6:
             raise ValueError("six tables are needed: E, df, dt, m, hf, ht")
-        n = max(length.bit_length() - 1, 0)
-        gamma = np.ascontiguousarray(gamma, dtype=np.uint64).reshape(4)
-        chal = np.ascontiguousarray(chal, dtype=np.uint64).reshape(-1, 4)
-        if len(chal) < n:
-            raise ValueError(f"{n} challenges needed, {len(chal)} given")
-        out = np.zeros((n, 4, 4), dtype=np.uint64)
-        last = np.zeros((6, 4), dtype=np.uint64)
-        self._check(self.lib.zk_sumcheck_lookup(self.h, self._ptr_array(tabs), length, _h(gamma), _h(chal), _h(out), _h(last)))
-        return out, last
+        return self._fused("lookup", False, (self._ptr_array(tabs),), length, gamma, chal)
 
     def lookup3_multiplicities(self, ws, ts, qk, idx, N: int, out=None):
         """m[y] = #{x : qk(x) = 1, idx[x] = y} as N Fr for the lookup of a Plonk circuit (zk_lookup3_multiplicities; blocking): ws = (a, b, c),
@@ -620,9 +608,7 @@ class Ctx:
             raise ValueError("three wire columns and three table columns are needed")
         out = out or self.alloc(max(32 * N, 1))
         rc = self.lib.zk_lookup3_multiplicities(self.h, self._ptr_array(ws), self._ptr_array(ts), _ptr(qk), _ptr(idx), N, _ptr(out))
-        if rc == ZK_ERR_INVALID:
-            raise ValueError((self.lib.zk_last_error(self.h) or b"").decode())
-        self._check(rc)
+        self._check_rows(rc)
         return out
 
     def lookup_find(self, f, t, N: int, idx=None, m=None):
@@ -631,9 +617,7 @@ class Ctx:
         table: ValueError -- as is every other ZK_ERR_INVALID of the call (N < 2, not a power of two or > 2^31), with the library's message."""
         idx, m = idx or self.alloc(max(4 * N, 1)), m or self.alloc(max(32 * N, 1))
         rc = self.lib.zk_lookup_find(self.h, _ptr(f), _ptr(t), N, _ptr(idx), _ptr(m))
-        if rc == ZK_ERR_INVALID:
-            raise ValueError((self.lib.zk_last_error(self.h) or b"").decode())
-        self._check(rc)
+        self._check_rows(rc)
         return idx, m
 
     def lookup3_find(self, ws, ts, qk, N: int, idx=None, m=None):
@@ -644,9 +628,7 @@ class Ctx:
             raise ValueError("three wire columns and three table columns are needed")
         idx, m = idx or self.alloc(max(4 * N, 1)), m or self.alloc(max(32 * N, 1))
         rc = self.lib.zk_lookup3_find(self.h, self._ptr_array(ws), self._ptr_array(ts), _ptr(qk), N, _ptr(idx), _ptr(m))
-        if rc == ZK_ERR_INVALID:
-            raise ValueError((self.lib.zk_last_error(self.h) or b"").decode())
-        self._check(rc)
+        self._check_rows(rc)
         return idx, m
 
     def witness_plan(self, sigma, N: int, out_sel=None) -> WitnessPlan:
@@ -674,9 +656,7 @@ class Ctx:
         else:
             rc = self.lib.zk_plonk_witness_lookup(self.h, plan.h, int(len(sels) == 6), self._ptr_array(sels), _ptr(qk), self._ptr_array(ts), _h(pi), len(pi), _ptr(free),
                                                   _ptr(a), _ptr(b), _ptr(c))
-        if rc == ZK_ERR_INVALID:
-            raise ValueError((self.lib.zk_last_error(self.h) or b"").decode())
-        self._check(rc)
+        self._check_rows(rc)
         return a, b, c
 
     def plonk_witness_check(self, plan: WitnessPlan, sels, public_inputs: np.ndarray, a, b, c, qk=None, ts=None) -> dict:
@@ -690,9 +670,7 @@ class Ctx:
                                                         _ptr(b), _ptr(c), _h(bad))
         else:
             rc = self.lib.zk_plonk_witness_check(self.h, plan.h, int(len(sels) == 6), self._ptr_array(sels), _h(pi), len(pi), _ptr(a), _ptr(b), _ptr(c), _h(bad))
-        if rc == ZK_ERR_INVALID:
-            raise ValueError((self.lib.zk_last_error(self.h) or b"").decode())
-        self._check(rc)
+        self._check_rows(rc)
         r, fr, k, fk = (int(x) for x in bad[:4])
         out = {"bad_rows": r, "first_bad_row": fr if r else None, "bad_copies": k, "first_bad_copy": fk if k else None}
         if lookup:
@@ -714,15 +692,7 @@ class Ctx:
         buffers E, df, dt, m, hf, ht, qk of `length` Fr -> (evals [n,4,4], last [7,4] in that order)"""
         if len(tabs) != 7:
             raise ValueError("seven tables are needed: E, df, dt, m, hf, ht, qk")
-        n = max(length.bit_length() - 1, 0)
-        gamma = np.ascontiguousarray(gamma, dtype=np.uint64).reshape(4)
-        chal = np.ascontiguousarray(chal, dtype=np.uint64).reshape(-1, 4)
-        if len(chal) != n:
-            raise ValueError(f"{n} challenges needed, {len(chal)} given")
-        out = np.zeros((n, 4, 4), dtype=np.uint64)
-        last = np.zeros((7, 4), dtype=np.uint64)
-        self._check(self.lib.zk_sumcheck_lookup_sel(self.h, self._ptr_array(tabs), length, _h(gamma), _h(chal), _h(out), _h(last)))
-        return out, last
+        return self._fused("lookup_sel", False, (self._ptr_array(tabs),), length, gamma, chal)
 
     def eq_table_acc(self, point: np.ndarray, weight: np.ndarray, acc):
         """acc[x] += weight * eq(point, x), acc a device buffer of 2^n Fr (zk_eq_table_acc; asynchronous) -> acc"""
@@ -761,59 +731,35 @@ class Ctx:
 
     def sumcheck_gate_fs(self, eq, q1, q2, a, b, c, inp, length: int, transcript):
         """sumcheck_gate with round i's challenge = hash of round i's evaluations -> (evals [n,5,4], last [7,4], chal [n,4])"""
-        n = max(length.bit_length() - 1, 0)
-        out, last, chal = np.zeros((n, 5, 4), dtype=np.uint64), np.zeros((7, 4), dtype=np.uint64), np.zeros((n, 4), dtype=np.uint64)
-        self._check(self.lib.zk_sumcheck_gate_fs(self.h, _ptr(eq), _ptr(q1), _ptr(q2), _ptr(a), _ptr(b), _ptr(c), _ptr(inp), length, self._tr(transcript), _h(out),
-                                                 _h(last), _h(chal)))
-        return out, last, chal
+        return self._fused("gate", True, tuple(_ptr(t) for t in (eq, q1, q2, a, b, c, inp)), length, None, transcript)
 
     def sumcheck_wiring_fs(self, eq, tree, num, den, N: int, gamma: np.ndarray, transcript):
         """sumcheck_wiring with derived challenges -> (evals [mu,4,4], last [7,4], chal [mu,4])"""
-        mu = max(N.bit_length() - 1, 0)
-        gamma = np.ascontiguousarray(gamma, dtype=np.uint64).reshape(4)
-        out, last, chal = np.zeros((mu, 4, 4), dtype=np.uint64), np.zeros((7, 4), dtype=np.uint64), np.zeros((mu, 4), dtype=np.uint64)
-        self._check(self.lib.zk_sumcheck_wiring_fs(self.h, _ptr(eq), _ptr(tree), _ptr(num), _ptr(den), N, _h(gamma), self._tr(transcript), _h(out), _h(last), _h(chal)))
-        return out, last, chal
+        return self._fused("wiring", True, (_ptr(eq), _ptr(tree), _ptr(num), _ptr(den)), N, gamma, transcript)
 
     def sumcheck_perm3_fs(self, eq, tree, nums, dens, N: int, gamma: np.ndarray, transcript):
         """sumcheck_perm3 with derived challenges -> (evals [mu,6,4], last [11,4], chal [mu,4])"""
         if len(nums) != 3 or len(dens) != 3:
             raise ValueError("three numerator and three denominator tables are needed")
-        mu = max(N.bit_length() - 1, 0)
-        gamma = np.ascontiguousarray(gamma, dtype=np.uint64).reshape(4)
-        out, last, chal = np.zeros((mu, 6, 4), dtype=np.uint64), np.zeros((11, 4), dtype=np.uint64), np.zeros((mu, 4), dtype=np.uint64)
-        self._check(self.lib.zk_sumcheck_perm3_fs(self.h, _ptr(eq), _ptr(tree), self._ptr_array(nums), self._ptr_array(dens), N, _h(gamma), self._tr(transcript),
-                                                  _h(out), _h(last), _h(chal)))
-        return out, last, chal
+        return self._fused("perm3", True, (_ptr(eq), _ptr(tree), self._ptr_array(nums), self._ptr_array(dens)), N, gamma, transcript)
 
     def sumcheck_gate_wide_fs(self, tabs, length: int, transcript):
         """sumcheck_gate_wide with derived challenges -> (evals [n,8,4], last [11,4], chal [n,4])"""
         if len(tabs) != 11:
             raise ValueError("eleven tables are needed: eq, qL, qR, qM, qO, qC, qH, a, b, c, in")
-        n = max(length.bit_length() - 1, 0)
-        out, last, chal = np.zeros((n, 8, 4), dtype=np.uint64), np.zeros((11, 4), dtype=np.uint64), np.zeros((n, 4), dtype=np.uint64)
-        self._check(self.lib.zk_sumcheck_gate_wide_fs(self.h, self._ptr_array(tabs), length, self._tr(transcript), _h(out), _h(last), _h(chal)))
-        return out, last, chal
+        return self._fused("gate_wide", True, (self._ptr_array(tabs),), length, None, transcript)
 
     def sumcheck_lookup_fs(self, tabs, length: int, gamma: np.ndarray, transcript):
         """sumcheck_lookup with derived challenges -> (evals [n,4,4], last [6,4], chal [n,4])"""
         if len(tabs) != 6:
             raise ValueError("six tables are needed: E, df, dt, m, hf, ht")
-        n = max(length.bit_length() - 1, 0)
-        gamma = np.ascontiguousarray(gamma, dtype=np.uint64).reshape(4)
-        out, last, chal = np.zeros((n, 4, 4), dtype=np.uint64), np.zeros((6, 4), dtype=np.uint64), np.zeros((n, 4), dtype=np.uint64)
-        self._check(self.lib.zk_sumcheck_lookup_fs(self.h, self._ptr_array(tabs), length, _h(gamma), self._tr(transcript), _h(out), _h(last), _h(chal)))
-        return out, last, chal
+        return self._fused("lookup", True, (self._ptr_array(tabs),), length, gamma, transcript)
 
     def sumcheck_lookup_sel_fs(self, tabs, length: int, gamma: np.ndarray, transcript):
         """sumcheck_lookup_sel with derived challenges -> (evals [n,4,4], last [7,4], chal [n,4])"""
         if len(tabs) != 7:
             raise ValueError("seven tables are needed: E, df, dt, m, hf, ht, qk")
-        n = max(length.bit_length() - 1, 0)
-        gamma = np.ascontiguousarray(gamma, dtype=np.uint64).reshape(4)
-        out, last, chal = np.zeros((n, 4, 4), dtype=np.uint64), np.zeros((7, 4), dtype=np.uint64), np.zeros((n, 4), dtype=np.uint64)
-        self._check(self.lib.zk_sumcheck_lookup_sel_fs(self.h, self._ptr_array(tabs), length, _h(gamma), self._tr(transcript), _h(out), _h(last), _h(chal)))
-        return out, last, chal
+        return self._fused("lookup_sel", True, (self._ptr_array(tabs),), length, gamma, transcript)
 
     def sumcheck_multi_fs(self, es, fs, length: int, transcript):
         """sumcheck_multi with derived challenges -> (triples [n,3,4], last_e [count,4], last_f [count,4], chal [n,4])"""

@@ -24,8 +24,7 @@ import hashlib
 import numpy as np
 
 from .field import R_MOD, fr_from_mont, fr_mont, int_to_limbs
-from .verify import product_round_target
-from .zerocheck import _ints, eq_eval
+from .verify import _ints, eq_eval, round_chain
 
 
 def _norm_claims(claims, n_tables: int, n: int) -> list:
@@ -125,13 +124,8 @@ def chain_value(proof: dict, claims, alpha, rho):
             return False, None
     except (KeyError, ValueError, TypeError):
         return False, None
-    target = claimed_sum(claims, alpha)
-    for i in range(len(rounds)):
-        t0, t1, t2 = _ints(rounds[i])
-        if (t0 + t1) % R_MOD != target:
-            return False, None
-        target = product_round_target(t0, t1, t2, ch[i])
-    return True, target
+    y = round_chain(rounds, ch, claimed_sum(claims, alpha))
+    return y is not None, y
 
 
 def failed_checks(n_tables: int, claims, proof: dict, alpha, rho, finals=None) -> list:

@@ -35,17 +35,12 @@ import numpy as np
 from . import batch_open as bo
 from .field import R_MOD, fr_from_mont, fr_mont, splitmix_fr
 from .transcript import HostTranscript, Transcript
-from .wiring import round_poly_at
-from .zerocheck import _ints, eq_eval
+from .verify import _ints, _u64, eq_eval, round_chain
 
 LABEL = b"lookup"
 COMMITTED = ("f", "m", "hf", "ht")    # the prover's commitments of a record
 OPENED = ("f", "t", "m", "hf", "ht")  # the five claimed values at r, and the tables of the batch instance
 FIND = "find"                         # in the place of idx: the device finds the indices (zk_lookup_find)
-
-
-def _u64(a, *shape) -> np.ndarray:
-    return np.ascontiguousarray(a, dtype=np.uint64).reshape(*shape)
 
 
 def lookup_value(E: int, f: int, t: int, m: int, hf: int, ht: int, beta: int, gamma: int) -> int:
@@ -165,12 +160,9 @@ def failed_checks(vk: dict, proof: dict, finals=None, c: dict | None = None) -> 
         return [0]
     ch = _ints(c["chal"])
     beta, gamma, lam = (_ints(c[k])[0] for k in ("beta", "gamma", "lambda"))
-    target = 0
-    for i in range(len(rounds)):
-        p = _ints(rounds[i])
-        if (p[0] + p[1]) % R_MOD != target:
-            return [1]
-        target = round_poly_at(p, ch[i])
+    target = round_chain(rounds, ch)
+    if target is None:
+        return [1]
     if target != lookup_value(lam * eq_eval(_ints(c["tau"]), ch) % R_MOD, f, t, m, hf, ht, beta, gamma):
         return [2]
     if bo.failed_checks(len(OPENED), _claims(c, proof), proof["batch"], c["b_alpha"], c["rho"], finals):

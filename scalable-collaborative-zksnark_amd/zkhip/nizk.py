@@ -27,12 +27,9 @@ from . import batch_open as bo
 from . import wiring as wr
 from . import zerocheck as zc
 from .transcript import HostTranscript, Transcript
+from .verify import _u64
 
 GATE_LABEL, WIRING_LABEL = b"gate", b"wiring"
-
-
-def _u64(a, *shape) -> np.ndarray:
-    return np.ascontiguousarray(a, dtype=np.uint64).reshape(*shape)
 
 
 def _replay_rounds(tr, rounds: np.ndarray) -> np.ndarray:

@@ -106,7 +106,8 @@ from . import wiring as wr
 from .field import R_MOD, fr_from_mont, fr_mont
 from .proof_io import check_points, parse_proof, proof_from_bytes, proof_to_bytes, verify_bytes  # noqa: F401  (proof bytes, re-exported)
 from .transcript import HostTranscript, Transcript
-from .zerocheck import _ints, eq_eval, gate_value, wide_gate_value
+from .verify import _ints, _u64, eq_eval, round_chain, round_poly_at  # noqa: F401  (round_poly_at: importable from here as before)
+from .zerocheck import gate_value, wide_gate_value
 
 LABEL = b"plonk"
 VK_TABLES = ("q1", "q2", "ssigma0", "ssigma1", "ssigma2")
@@ -156,23 +157,7 @@ def gate_of(d: dict) -> Gate:
     return GATES[kind]
 
 
-def _u64(a, *shape) -> np.ndarray:
-    return np.ascontiguousarray(a, dtype=np.uint64).reshape(*shape)
-
-
 # ---- the verifier's closed forms ----
-def round_poly_at(evals, x: int) -> int:
-    """the polynomial of degree len(evals) - 1 through (k, evals[k]) at x"""
-    n, acc = len(evals), 0
-    for k in range(n):
-        num, den = 1, 1
-        for m in range(n):
-            if m != k:
-                num, den = num * (x - m) % R_MOD, den * (k - m) % R_MOD
-        acc = (acc + evals[k] * num % R_MOD * pow(den, -1, R_MOD)) % R_MOD
-    return acc
-
-
 def in_eval(public_inputs, r) -> int:
     """in(r) for the table whose rows 0 .. l - 1 hold the public inputs (l = 2^k) and whose other rows are zero; index bit 0 is the TOP bit:
     prod_{i < mu - k} (1 - r_i) * sum_y pi[y] eq(y, r_{mu-k..}).  public_inputs, r: python ints"""
@@ -547,19 +532,8 @@ def failed_checks(vk: dict, public_inputs, proof: dict, finals=None, v_finals=No
         return [0]
     al, bt, gm = (fr_from_mont(c[k]) for k in ("alpha", "beta", "gamma"))
     r_p, r_g = _ints(c["r_p"]), _ints(c["r_g"])
-    bad = []
-    for number, rounds, r in ((1, p_rounds, r_p), (2, g_rounds, r_g)):
-        target = 0
-        for i in range(mu):
-            p = _ints(rounds[i])
-            if (p[0] + p[1]) % R_MOD != target:
-                bad.append(number)
-                break
-            target = round_poly_at(p, r[i])
-        if number == 1:
-            p_target = target
-        else:
-            g_target = target
+    p_target, g_target = round_chain(p_rounds, r_p), round_chain(g_rounds, r_g)
+    bad = [k for k, target in ((1, p_target), (2, g_target)) if target is None]
     if 2 not in bad and g_target != gate.value(eq_eval(_ints(c["tau_g"]), r_g), gv, in_eval(pi, r_g)):
         bad.append(3)
     ids = slot_eval(r_p)
@@ -573,13 +547,10 @@ def failed_checks(vk: dict, public_inputs, proof: dict, finals=None, v_finals=No
             bo.failed_checks(1, v_claims, proof["v_batch"], c["b_alpha"], c["rho_mu1"], v_finals):
         bad.append(6)
     if lookup:
-        r_l, target = _ints(c["r_l"]), 0
-        for i in range(mu):
-            p = _ints(l_rounds[i])
-            if (p[0] + p[1]) % R_MOD != target:
-                bad.append(7)
-                break
-            target = round_poly_at(p, r_l[i])
+        r_l = _ints(c["r_l"])
+        target = round_chain(l_rounds, r_l)
+        if target is None:
+            bad.append(7)
         ze, bl, gl, lam = (fr_from_mont(c[k]) for k in ("zeta", "beta_l", "gamma_l", "lambda"))
         if 7 not in bad and target != lookup3_value(lam * eq_eval(_ints(c["tau_l"]), r_l) % R_MOD, *lv, ze, bl, gl):
             bad.append(8)

@@ -6,6 +6,7 @@ hundred field elements), so they are size-independent: the same checks run at n 
 """
 from __future__ import annotations
 
+import math
 from typing import Sequence
 
 import numpy as np
@@ -17,6 +18,63 @@ _INV2 = pow(2, -1, R_MOD)
 
 def _ints(a) -> list:
     return [fr_from_mont(x) for x in np.asarray(a, dtype=np.uint64).reshape(-1, 4)]
+
+
+def _u64(a, *shape) -> np.ndarray:
+    return np.ascontiguousarray(a, dtype=np.uint64).reshape(*shape)
+
+
+# ---- the round chain of the fused-identity sumchecks: the one copy zerocheck, wiring, lookup, batch_open and plonk call ----
+def eq_eval(tau: Sequence[int], r: Sequence[int]) -> int:
+    """eq(tau, r) = prod_i (tau_i r_i + (1 - tau_i)(1 - r_i)) on python ints"""
+    assert len(tau) == len(r)
+    v = 1
+    for t, x in zip(tau, r):
+        v = v * (t * x + (1 - t) * (1 - x)) % R_MOD
+    return v
+
+
+_LAGRANGE_DEN = {}  # node count K -> [1 / prod_{m != k} (k - m) for k < K], inverted once
+
+
+def round_poly_at(evals: Sequence[int], x: int) -> int:
+    """the polynomial of degree len(evals) - 1 through (k, evals[k]) at x, for two nodes or more (three: dsumcheck.rs:562-575)"""
+    n = len(evals)
+    den = _LAGRANGE_DEN.get(n)
+    if den is None:
+        if n < 2:
+            raise ValueError("a round polynomial needs at least two nodes")
+        den = _LAGRANGE_DEN[n] = [pow(math.prod(k - m for m in range(n) if m != k) % R_MOD, -1, R_MOD) for k in range(n)]
+    acc = 0
+    for k in range(n):
+        num = 1
+        for m in range(n):
+            if m != k:
+                num = num * (x - m) % R_MOD
+        acc = (acc + evals[k] * num % R_MOD * den[k]) % R_MOD
+    return acc
+
+
+def round_chain(rounds, chal, claimed: int = 0):
+    """
+    The sumcheck verifier's chain: p_0(0) + p_0(1) == claimed, p_i(0) + p_i(1) == p_{i-1}(r_{i-1}) by interpolation on the nodes
+    0 .. K - 1.  rounds: [n, K, 4] Montgomery limbs, or n sequences of K python ints; chal: [n, 4] limbs or n ints.
+    -> the last target p_{n-1}(r_{n-1}) as a python int (claimed itself for n = 0), None at the first round that misses its target.
+    ValueError when rounds and chal disagree on n or the limbs are not [n, K, 4]: the caller's "malformed" case.
+    """
+    limbs = isinstance(rounds, np.ndarray)
+    if limbs and (rounds.ndim != 3 or rounds.shape[2] != 4):
+        raise ValueError("rounds must be [n, K, 4] Montgomery limbs")
+    ch = _ints(chal) if isinstance(chal, np.ndarray) else list(chal)
+    if len(rounds) != len(ch):
+        raise ValueError(f"{len(rounds)} rounds, {len(ch)} challenges")
+    target = claimed % R_MOD
+    for row, r in zip(rounds, ch):
+        p = _ints(row) if limbs else row
+        if (p[0] + p[1]) % R_MOD != target:
+            return None
+        target = round_poly_at(p, r)
+    return target
 
 
 def sumcheck_chain(proof, challenge, claimed: int | None = None) -> bool:

@@ -26,32 +26,14 @@ device, is zkhip.nizk.wiring_prove_ni / wiring_verify_ni.  Single party only: th
 from __future__ import annotations
 
 import hashlib
-from typing import Sequence
 
 import numpy as np
 
 from .field import R_MOD, fr_from_mont, fr_mont
-from .zerocheck import _ints, eq_eval
+from .verify import _ints, eq_eval, round_chain, round_poly_at  # noqa: F401  (round_poly_at: importable from here as before)
 
 OPENED = ("w", "sid", "ssigma")                         # the three mu-variate openings of a proof record, at r
 V_POINTS = ("(0,r)", "(1,r)", "(r,0)", "(r,1)", "(1,..,1,0)")  # the five openings of the tree's commitment
-
-
-# Lagrange basis on the nodes 0 .. 3: 1 / prod_{m != k} (k - m)
-_LAGRANGE_DEN = [pow(int(np.prod([k - m for m in range(4) if m != k])) % R_MOD, -1, R_MOD) for k in range(4)]
-
-
-def round_poly_at(evals: Sequence[int], x: int) -> int:
-    """the degree-3 polynomial through (k, evals[k]), k = 0 .. 3, at x"""
-    assert len(evals) == 4
-    acc = 0
-    for k in range(4):
-        num = 1
-        for m in range(4):
-            if m != k:
-                num = num * (x - m) % R_MOD
-        acc = (acc + evals[k] * num % R_MOD * _LAGRANGE_DEN[k]) % R_MOD
-    return acc
 
 
 def wiring_value(eq: int, v1x: int, vx0: int, vx1: int, h: int, num: int, den: int, gamma: int) -> int:
@@ -86,14 +68,8 @@ def failed_checks(proof: dict, alpha, beta, gamma, tau, chal) -> list:
     except (KeyError, ValueError, TypeError):
         return [0]
     a, b, g = (_ints(x)[0] for x in (alpha, beta, gamma))
-    bad = []
-    target = 0
-    for i in range(mu):
-        p = _ints(rounds[i])
-        if (p[0] + p[1]) % R_MOD != target:
-            bad.append(1)
-            break
-        target = round_poly_at(p, ch[i])
+    target = round_chain(rounds, ch)
+    bad = [1] if target is None else []
     num, den = (w + a * sid + b) % R_MOD, (w + a * ssigma + b) % R_MOD
     if not bad and target != wiring_value(eq_eval(tau_i, ch), v1r, vr0, vr1, v0r, num, den, g):
         bad.append(2)

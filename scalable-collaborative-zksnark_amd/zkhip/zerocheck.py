@@ -16,43 +16,13 @@ zkhip.nizk.gate_prove_ni / gate_verify_ni.  Single party only: the distributed a
 from __future__ import annotations
 
 import hashlib
-from typing import Sequence
 
 import numpy as np
 
 from .field import R_MOD, fr_from_mont
+from .verify import _ints, eq_eval, round_chain, round_poly_at  # noqa: F401  (the shared verifier pieces, importable from here as before)
 
 OPENED = ("a", "b", "c", "in", "q1", "q2")  # order of the six openings in a proof record
-
-
-def _ints(a) -> list:
-    return [fr_from_mont(x) for x in np.asarray(a, dtype=np.uint64).reshape(-1, 4)]
-
-
-def eq_eval(tau: Sequence[int], r: Sequence[int]) -> int:
-    """eq(tau, r) = prod_i (tau_i r_i + (1 - tau_i)(1 - r_i)) on python ints"""
-    assert len(tau) == len(r)
-    v = 1
-    for t, x in zip(tau, r):
-        v = v * (t * x + (1 - t) * (1 - x)) % R_MOD
-    return v
-
-
-# Lagrange basis on the nodes 0 .. 4: 1 / prod_{m != k} (k - m)
-_LAGRANGE_DEN = [pow(int(np.prod([k - m for m in range(5) if m != k])) % R_MOD, -1, R_MOD) for k in range(5)]
-
-
-def round_poly_at(evals: Sequence[int], x: int) -> int:
-    """the degree-4 polynomial through (k, evals[k]), k = 0 .. 4, at x (the degree-2 analogue: dsumcheck.rs:562-575)"""
-    assert len(evals) == 5
-    acc = 0
-    for k in range(5):
-        num = 1
-        for m in range(5):
-            if m != k:
-                num = num * (x - m) % R_MOD
-        acc = (acc + evals[k] * num % R_MOD * _LAGRANGE_DEN[k]) % R_MOD
-    return acc
 
 
 def gate_value(eq: int, q1: int, q2: int, a: int, b: int, c: int, inp: int) -> int:
@@ -77,12 +47,9 @@ def verify_rounds(proof: dict, tau, chal) -> bool:
     n = len(rounds)
     if n == 0 or len(tau_i) != n or len(ch) != n or len(proof["openings"]) != len(OPENED):
         return False
-    target = 0
-    for i in range(n):
-        p = _ints(rounds[i])
-        if (p[0] + p[1]) % R_MOD != target:
-            return False
-        target = round_poly_at(p, ch[i])
+    target = round_chain(rounds, ch)
+    if target is None:
+        return False
     val = {name: fr_from_mont(np.asarray(op[1], dtype=np.uint64).reshape(4)) for name, op in zip(OPENED, proof["openings"])}
     return target == gate_value(eq_eval(tau_i, ch), val["q1"], val["q2"], val["a"], val["b"], val["c"], val["in"])
 

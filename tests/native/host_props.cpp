@@ -12,6 +12,7 @@
 #include <cstring>
 #include <numeric>
 
+#include "zkhost/round_chain.hpp"  // the round chain and interpolation of the fused-identity verifiers
 #include "zkhost/verify.hpp"  // the shipped verifiers (check_sumcheck, check_sumcheck_product, product_round_target) + hyperplonk.hpp
 
 using namespace zkhost;
@@ -79,6 +80,58 @@ static void operator_test_transpose() {  // utils/operator.rs:42-49
     std::vector<std::vector<int>> m = {{1, 2, 3}, {4, 5, 6}, {7, 8, 9}}, e = {{1, 4, 7}, {2, 5, 8}, {3, 6, 9}};
     CHECK(transpose(m) == e);
 }
+// round_chain.hpp, the one chain of the gate / wiring / lookup / batch-opening / Plonk verifiers: honest chains of random polynomials of
+// degree K - 1 whose constant terms are fixed to meet each target are accepted with their last value; every single evaluation + 1 is
+// caught -- nodes 0 and 1 by their own round, a node >= 2 by the next round, or in the last round by a moved last value; a wrong claim is
+// refused; the interpolation gives the values back at the nodes and is dsumcheck.rs:562-575 on three of them.
+static void round_chain_accepts_and_rejects() {  // runs as part of verifier_accepts_and_rejects
+    const size_t n = 3;
+    auto poly_at = [](const FrVec &c, const Fr &x) {
+        Fr acc = Fr::zero();
+        for (size_t k = c.size(); k-- > 0;) acc = acc * x + c[k];
+        return acc;
+    };
+    const Fr half = Fr::from_u64(2).inverse();
+    for (size_t K : {size_t(3), size_t(6)})
+        for (const Fr &claimed : {Fr::zero(), Fr::from_u64(0x1234567)}) {
+            const FrVec ch = random_vec(n, 900 + K);
+            std::vector<FrVec> rows;
+            Fr target = claimed;
+            for (size_t i = 0; i < n; ++i) {
+                FrVec c = random_vec(K, 910 + 10 * K + i);  // p(0) + p(1) = 2 c_0 + c_1 + .. + c_{K-1}
+                c[0] = (target - (sum(c) - c[0])) * half;
+                FrVec e(K);
+                for (size_t k = 0; k < K; ++k) e[k] = poly_at(c, Fr::from_u64(k));
+                for (size_t k = 0; k < K; ++k) CHECK(round_poly_nodes(e.data(), K, Fr::from_u64(k)) == e[k]);
+                CHECK(round_poly_nodes(e.data(), K, ch[i]) == poly_at(c, ch[i]));
+                if (K == 3) CHECK(round_poly_nodes(e.data(), K, ch[i]) == product_round_target(Triple{e[0], e[1], e[2]}, ch[i]));
+                if (K == 3) CHECK(round_poly_nodes(Triple{e[0], e[1], e[2]}, ch[i]) == round_poly_nodes(e.data(), K, ch[i]));  // the std::array overload
+                rows.push_back(e);
+                target = poly_at(c, ch[i]);
+            }
+            Fr last = Fr::zero(), got = Fr::zero();
+            CHECK(round_chain(rows, K, ch, claimed, &last) && last == target);
+            CHECK(round_chain(rows, K, ch, claimed, nullptr));
+            CHECK(!round_chain(rows, K, ch, claimed + Fr::one(), &got));
+            for (size_t i = 0; i < n; ++i)
+                for (size_t k = 0; k < K; ++k) {
+                    std::vector<FrVec> bad = rows;
+                    bad[i][k] += Fr::one();
+                    const bool ok = round_chain(bad, K, ch, claimed, &got);
+                    if (k < 2 || i + 1 < n)
+                        CHECK(!ok);
+                    else
+                        CHECK(ok && got != last);
+                }
+            bool threw = false;
+            try {
+                round_chain(rows, K, FrVec(ch.begin(), ch.begin() + n - 1), claimed, &got);
+            } catch (const std::invalid_argument &) {
+                threw = true;
+            }
+            CHECK(threw);
+        }
+}
 static void verifier_accepts_and_rejects() {  // dsumcheck.rs:541-588 on host-made transcripts: right ones pass, a flipped limb anywhere fails
     const size_t n = 6;
     FrVec f = random_vec(size_t(1) << n, 71), g = random_vec(size_t(1) << n, 72), ch = random_vec(n, 73);
@@ -104,6 +157,7 @@ static void verifier_accepts_and_rejects() {  // dsumcheck.rs:541-588 on host-ma
     std::vector<Pair> badp = pp_;
     badp[n][1].v[0] ^= 1;  // the closing (0, last) row is the evaluation the reference's comment leaves out
     CHECK(!check_sumcheck(claim_plain, badp, ch, n));
+    round_chain_accepts_and_rejects();  // the chain of the fused-identity verifiers, beside the reference's
 }
 static void dacc_product_sub_index_test() {  // dacc_product.rs:442-448
     CHECK(sub_index(26) == std::make_pair(size_t(20), size_t(21)));
