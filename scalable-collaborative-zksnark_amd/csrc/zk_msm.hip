@@ -1023,6 +1023,7 @@ static __global__ void __launch_bounds__(kSortThreads) k_l2_scatter(const u32* _
 }
 
 // host dispatch of the fused level 1 over the table widths that occur on long rows (any other width: the run-time layout, C = 0)
+// (23 and 24 are instantiated but unreachable: zk_srs_precompute refuses tables wider than kMaxTableBits = 22)
 #define ZK_TAB_WIDTHS(X) X(16) X(17) X(18) X(19) X(20) X(21) X(22) X(23) X(24)
 static int tab_width_known(int c) {
 #define X(Cc) if (c == Cc) return Cc;
@@ -2138,8 +2139,8 @@ static int msm_enqueue(zk_ctx* ctx, MsmRun& run) {
         for (auto& cl : classes) {
             size_t nmin = ~(size_t)0, nmax2 = 0, tot = 0;
             for (size_t k : cl.idx) nmin = std::min(nmin, items[k].n), nmax2 = std::max(nmax2, items[k].n), tot += items[k].n;
-            fprintf(stderr, "zk-class key_c=%d c=%d W=%d items=%zu n=[%zu..%zu] sum=%zu ns=%zu rows=%zu nb=%zu buckets=%zu T=%u tiles=%zu np=%u\n", cl.key_c, cl.c, cl.wc,
-                    cl.idx.size(), nmin, nmax2, tot, cl.ns, cl.rows, cl.nb, cl.total, cl.T, cl.total_tiles, cl.np);
+            fprintf(stderr, "zk-class key_c=%d c=%d W=%d items=%zu n=[%zu..%zu] sum=%zu ns=%zu rows=%zu nb=%zu buckets=%zu T=%u tiles=%zu np=%u fused=%d tab_c=%d tiled_l2=%d\n", cl.key_c, cl.c, cl.wc,
+                    cl.idx.size(), nmin, nmax2, tot, cl.ns, cl.rows, cl.nb, cl.total, cl.T, cl.total_tiles, cl.np, (int)cl.fused_tab, cl.fused_tab ? cl.tab_c : 0, (int)cl.tiled_l2);
         }
     // allocate every arena once, before anything is enqueued (no reallocation between classes)
     static const int slot[10] = {0, 1, 2, 3, 4, 5, 6, 9, 8, 11};
