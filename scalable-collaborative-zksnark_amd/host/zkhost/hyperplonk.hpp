@@ -174,105 +174,34 @@ struct Transcript {
 };
 
 namespace detail {
-// step 2 of dhyperplonk (:262-514) == the body of dpermcheck (:992-1245), up to (not including) its one batched MSM pass:
-// every sumcheck / fold / open-round kernel has run, every MSM of the step sits in `q`.  -> finalize(): the exchanges of the
-// MSM results, filling the wiring lists in the reference's order.
-inline std::function<void(Transcript &)> wiring_enqueue(size_t n, const PackedProvingParameters &pk, const PackedSharingParams &pp, Ctx &be, Net &net, MsmQueue &q,
-                                                        bool data_parallel, Timers *tm = nullptr) {
-    auto mark = [tm](const char *w) {
-        if (tm) tm->mark(w);
-    };
-    size_t l = pp.l, np = net.n_parties, M = size_t(1) << n, sbits = log2_floor(np);
-    const PowersOfG &cc = pk.c_commitment, &dc = pk.d_commitment;
-    const DevPtr &local_s_p = pk.T("local_s_p"), &local_s_l = pk.T("local_s_l");
-    auto tr = std::make_shared<Transcript>();
-    // 2.a (:268-294): every party broadcasts local_s; s = concatenation over parties (an all-gather that stays in HBM over RCCL)
-    mark("wiring: begin");
-    DevPtr s_dev = data_parallel ? pk.T("s_data_parallel") : net.all_gather_device(be, local_s_l, 32 * (4 * M / np / l));
-    mark("2.a all-gather done");
-    tr->wiring_proofs.push_back(c_sumcheck_product(be, s_dev, pk.T("V"), 4 * M / l, pk.challenge_r1, pp, net));  // 2.c
-    mark("2.c c_sumcheck_product done");
-    // 2.d: the two opens of V are independent -> their q_i commitments share one d_msm
-    auto f_copen = c_open_many_q(be, q, cc, {pk.T("V"), pk.T("V")}, {4 * M / l, 4 * M / l}, {pk.challenge_r1, pk.challenge_r2}, pp, net);
-    mark("2.d c_open_many_q (kernels) done");
-    // 2.e (:322-340)
-    size_t hlen = 4 * M / np;
-    DevPtr num = be.fr_axpb(local_s_p, pk.T("sid_p"), pk.alpha, pk.beta, hlen);
-    DevPtr den = be.fr_axpb(pk.T("eq_r1_p"), pk.T("ssigma_p"), pk.alpha, pk.beta, hlen);
-    DevPtr h_p = be.fr_batch_div(num, den, hlen);
-    mark("2.e num / den / h done");
-    auto [sub, top] = d_acc_product(be, h_p, hlen, net);  // :342
-    mark("2.e d_acc_product done");
-    q.keep.push_back(sub.tree);  // v1x and the layer slices below are views into it
-    DevPtr v1x = sub.tree.fr(hlen);
-    auto [vx0, vx1] = be.fr_deinterleave(sub.tree, hlen);  // :344-359
-    // :363-380 / :383-407: independent commits / opens
-    std::vector<DevPtr> tabs8 = {pk.T("ssigma_p"), pk.T("sid_p"), h_p, num, den, v1x, vx0, vx1};
-    std::vector<DevPtr> com_tabs = {local_s_p};
-    com_tabs.insert(com_tabs.end(), tabs8.begin(), tabs8.end());
-    std::vector<size_t> com_lens(9, hlen);
-    auto f_dcommit = d_commit_many_q(be, q, dc, com_tabs, com_lens, net);  // 2.b, then :363-380
-    std::vector<DevPtr> lay_tabs(com_tabs.begin(), com_tabs.begin() + 6);   // 2.d, then :383-407
-    std::vector<size_t> lay_lens(6, hlen);
-    std::vector<FrVec> lay_pts(6, pk.challenge_r2);
-    // the 3 + 3 (n - s) d_sumcheck_products of 2.e are independent of each other: one batched local phase, one exchange
-    std::vector<DsumcheckItem> dsp = {{den, pk.T("eq_r2_p"), hlen, pk.challenge_r2}, {h_p, den, hlen, pk.challenge_r2}, {num, pk.T("eq_r2_p"), hlen, pk.challenge_r2}};  // :411-413
-    // 2.e.2 layered sumcheck + opens on halving slices (:417-478)
-    DevPtr cur[4] = {v1x, vx0, vx1, pk.T("eq_r2_p")};
-    size_t clen = hlen / 2;  // current_* = first half
-    for (size_t i = 1; i + sbits <= n; ++i) {
-        FrVec ch(pk.challenge_r2.begin() + i, pk.challenge_r2.end());
-        dsp.push_back({cur[3], cur[0], clen, ch}), dsp.push_back({cur[3], cur[1], clen, ch}), dsp.push_back({cur[1], cur[2], clen, ch});
-        for (int k = 0; k < 3; ++k) lay_tabs.push_back(cur[k]), lay_lens.push_back(clen), lay_pts.push_back(ch);
-        for (auto &c : cur) c = c.fr(clen / 2);  // current = current[len/2..]
-        clen /= 2;
+// Where the sumcheck-family kernels of a step's primitives go (pipeline.hpp).  With the step's shared ScQueue they wait for the caller's
+// run(): the one-batch schedule.  Without one every primitive's kernels are a batch of their own, run at once: the batch-per-call
+// schedule.  `add(queue)` is the primitive's *_sq form.
+struct Kernels {
+    Ctx &be;
+    ScQueue *shared;
+    // a form without phase B -> what it returned (a closure that reads the batch when the transcript is assembled)
+    template <class Add>
+    auto queued(Add &&add) const {
+        return shared ? add(*shared) : own_batch(be, add);
     }
-    mark("2.e lists built");
-    auto f_dsp = d_sumcheck_product_many_q(be, dsp, net);
-    mark("2.e d_sumcheck_product_many_q (kernels) done");
-    auto f_dopen = d_open_many_q(be, q, dc, lay_tabs, lay_lens, lay_pts, net);
-    mark("2.e d_open_many_q (kernels) done");
-    // leader-only tail on the N_p-leaf top tree (:480-511)
-    auto top_commits = std::make_shared<std::vector<std::function<G1()>>>();
-    auto top_opens = std::make_shared<OpensInFlight>();
-    auto top_proofs = std::make_shared<std::vector<std::vector<Triple>>>();
-    bool has_top = top.has_value();
-    if (has_top) {
-        const FrVec &tt = *top;
-        size_t half = tt.size() / 2;
-        FrVec lv1x(tt.begin() + half, tt.end()), lvx0, lvx1;
-        for (size_t i = 0; i < tt.size(); ++i) (i % 2 ? lvx1 : lvx0).push_back(tt[i]);
-        FrVec chs(pk.challenge_r2.begin(), pk.challenge_r2.begin() + sbits);
-        DevPtr d0 = be.to_device(lvx0), dd1 = be.to_device(lvx1), d1 = be.to_device(lv1x);
-        for (auto &d : {d0, dd1, d1}) top_commits->push_back(commit_q(q, dc, d, half)), q.keep.push_back(d);
-        *top_opens = open_many_q(be, q, dc, {d0, dd1, d1}, {half, half, half}, {chs, chs, chs});
-        top_proofs->push_back(sumcheck_product(be, pk.T("eq_top"), d1, half, chs));
-        top_proofs->push_back(sumcheck_product(be, pk.T("eq_top"), d0, half, chs));
-        top_proofs->push_back(sumcheck_product(be, d0, dd1, half, chs));
+    // a form that returns its phase B: with a batch of its own phase B follows at once -> a closure over its result, so that both
+    // schedules read alike
+    template <class Add>
+    auto staged(Add &&add) const -> decltype(add(*shared)) {
+        if (shared) return add(*shared);
+        auto res = own_batch(be, add)();
+        return [res] { return res; };
     }
-    mark("wiring: leader tail done");
-    return [tr, f_dsp, f_copen, f_dcommit, f_dopen, top_commits, top_opens, top_proofs, has_top](Transcript &out) {
-        out.wiring_proofs = tr->wiring_proofs;
-        for (auto &p : f_dsp()) out.wiring_proofs.push_back(p);  // 2.e: after 2.c, before the leader-tree sumchecks (the reference's order)
-        out.wiring_opens = f_copen();                           // 2.d
-        out.wiring_commits = f_dcommit();                       // 2.b, then :363-380
-        for (auto &o : f_dopen()) out.wiring_opens.push_back(o);
-        if (has_top) {
-            std::vector<Opening> to = top_opens->finish();
-            for (size_t i = 0; i < 3; ++i) {  // (commit, open) per table, in the reference's order
-                out.wiring_commits.push_back((*top_commits)[i]());
-                out.wiring_opens.push_back(to[i]);
-            }
-            for (auto &p : *top_proofs) out.wiring_proofs.push_back(p);
-        }
-    };
-}
+};
 
-// The same step with ALL its sumcheck-family kernels in the caller's batch (pipeline.hpp, ScQueue): phase A enqueues -- the
-// exchanges that need no kernel result (2.a, the roots of the product tree) happen here --, the caller runs the batch, phase B
-// (the returned function) performs the exchanges that need one and returns the finishing closure of wiring_enqueue.
-inline AfterBatch<std::function<void(Transcript &)>> wiring_enqueue_sq(size_t n, const PackedProvingParameters &pk, const PackedSharingParams &pp, Ctx &be, Net &net,
-                                                                       MsmQueue &q, ScQueue &sq, bool data_parallel, Timers *tm = nullptr) {
+// step 2 of dhyperplonk (:262-514) == the body of dpermcheck (:992-1245), up to (not including) its one batched MSM pass: every
+// sumcheck / fold / open-round kernel is in the batch `k` names (or has run), every MSM that needs no kernel result sits in `q`; the
+// exchanges that need no kernel result (2.a, the roots of the product tree) have happened.  The caller runs the shared batch, if any;
+// phase B (the returned function) performs the exchanges that need a kernel result -- with a batch per call they are done already --
+// and returns finalize(): the exchanges of the MSM results, filling the wiring lists in the reference's order.
+inline AfterBatch<std::function<void(Transcript &)>> wiring_enqueue(size_t n, const PackedProvingParameters &pk, const PackedSharingParams &pp, Ctx &be, Net &net,
+                                                                    MsmQueue &q, const Kernels &k, bool data_parallel, Timers *tm = nullptr) {
     auto mark = [tm](const char *w) {
         if (tm) tm->mark(w);
     };
@@ -280,35 +209,41 @@ inline AfterBatch<std::function<void(Transcript &)>> wiring_enqueue_sq(size_t n,
     const PowersOfG &cc = pk.c_commitment, &dc = pk.d_commitment;
     const DevPtr &local_s_p = pk.T("local_s_p"), &local_s_l = pk.T("local_s_l");
     mark("wiring: begin");
-    DevPtr s_dev = data_parallel ? pk.T("s_data_parallel") : net.all_gather_device(be, local_s_l, 32 * (4 * M / np / l));  // 2.a
-    auto a_2c = c_sumcheck_product_many_sq(be, sq, {{s_dev, pk.T("V")}}, 4 * M / l, pk.challenge_r1, pp, net);              // 2.c
-    auto a_copen = c_open_many_sq(be, sq, q, cc, {pk.T("V"), pk.T("V")}, {4 * M / l, 4 * M / l}, {pk.challenge_r1, pk.challenge_r2}, pp, net);  // 2.d
+    // 2.a (:268-294): every party broadcasts local_s; s = concatenation over parties (an all-gather that stays in HBM over RCCL)
+    DevPtr s_dev = data_parallel ? pk.T("s_data_parallel") : net.all_gather_device(be, local_s_l, 32 * (4 * M / np / l));
+    auto a_2c = k.staged([&](ScQueue &sq) { return c_sumcheck_product_many_sq(be, sq, {{s_dev, pk.T("V")}}, 4 * M / l, pk.challenge_r1, pp, net); });  // 2.c
+    // 2.d: the two opens of V are independent -> their q_i commitments share one d_msm
+    auto a_copen = k.staged([&](ScQueue &sq) {
+        return c_open_many_sq(be, sq, q, cc, {pk.T("V"), pk.T("V")}, {4 * M / l, 4 * M / l}, {pk.challenge_r1, pk.challenge_r2}, pp, net);
+    });
     size_t hlen = 4 * M / np;  // 2.e (:322-340)
     DevPtr num = be.fr_axpb(local_s_p, pk.T("sid_p"), pk.alpha, pk.beta, hlen);
     DevPtr den = be.fr_axpb(pk.T("eq_r1_p"), pk.T("ssigma_p"), pk.alpha, pk.beta, hlen);
     DevPtr h_p = be.fr_batch_div(num, den, hlen);
     auto [sub, top] = d_acc_product(be, h_p, hlen, net);  // :342
     mark("2.e product tree done");
-    q.keep.push_back(sub.tree);
+    q.keep.push_back(sub.tree);  // v1x and the layer slices below are views into it
     DevPtr v1x = sub.tree.fr(hlen);
     auto [vx0, vx1] = be.fr_deinterleave(sub.tree, hlen);  // :344-359
+    // :363-380 / :383-407: independent commits / opens
     std::vector<DevPtr> com_tabs = {local_s_p, pk.T("ssigma_p"), pk.T("sid_p"), h_p, num, den, v1x, vx0, vx1};
     auto f_dcommit = d_commit_many_q(be, q, dc, com_tabs, std::vector<size_t>(9, hlen), net);  // 2.b, then :363-380
     std::vector<DevPtr> lay_tabs(com_tabs.begin(), com_tabs.begin() + 6);                      // 2.d, then :383-407
     std::vector<size_t> lay_lens(6, hlen);
     std::vector<FrVec> lay_pts(6, pk.challenge_r2);
+    // the 3 + 3 (n - s) d_sumcheck_products of 2.e are independent of each other: one batched local phase, one exchange
     std::vector<DsumcheckItem> dsp = {{den, pk.T("eq_r2_p"), hlen, pk.challenge_r2}, {h_p, den, hlen, pk.challenge_r2}, {num, pk.T("eq_r2_p"), hlen, pk.challenge_r2}};  // :411-413
     DevPtr cur[4] = {v1x, vx0, vx1, pk.T("eq_r2_p")};
-    size_t clen = hlen / 2;
+    size_t clen = hlen / 2;  // current_* = first half
     for (size_t i = 1; i + sbits <= n; ++i) {  // 2.e.2 layered sumcheck + opens on halving slices (:417-478)
         FrVec ch(pk.challenge_r2.begin() + i, pk.challenge_r2.end());
         dsp.push_back({cur[3], cur[0], clen, ch}), dsp.push_back({cur[3], cur[1], clen, ch}), dsp.push_back({cur[1], cur[2], clen, ch});
-        for (int k = 0; k < 3; ++k) lay_tabs.push_back(cur[k]), lay_lens.push_back(clen), lay_pts.push_back(ch);
-        for (auto &c : cur) c = c.fr(clen / 2);
+        for (int t = 0; t < 3; ++t) lay_tabs.push_back(cur[t]), lay_lens.push_back(clen), lay_pts.push_back(ch);
+        for (auto &c : cur) c = c.fr(clen / 2);  // current = current[len/2..]
         clen /= 2;
     }
-    auto f_dsp = d_sumcheck_product_many_sq(be, sq, dsp, net);
-    auto a_dopen = d_open_many_sq(be, sq, q, dc, lay_tabs, lay_lens, lay_pts, net);
+    auto f_dsp = k.queued([&](ScQueue &sq) { return d_sumcheck_product_many_sq(be, sq, dsp, net); });
+    auto a_dopen = k.staged([&](ScQueue &sq) { return d_open_many_sq(be, sq, q, dc, lay_tabs, lay_lens, lay_pts, net); });
     // leader-only tail on the N_p-leaf top tree (:480-511)
     auto top_commits = std::make_shared<std::vector<std::function<G1()>>>();
     auto top_opens = std::make_shared<OpensInFlight>();
@@ -322,10 +257,9 @@ inline AfterBatch<std::function<void(Transcript &)>> wiring_enqueue_sq(size_t n,
         FrVec chs(pk.challenge_r2.begin(), pk.challenge_r2.begin() + sbits);
         DevPtr d0 = be.to_device(lvx0), dd1 = be.to_device(lvx1), d1 = be.to_device(lv1x);
         for (auto &d : {d0, dd1, d1}) top_commits->push_back(commit_q(q, dc, d, half)), q.keep.push_back(d);
-        *top_opens = open_many_sq(sq, q, dc, {d0, dd1, d1}, {half, half, half}, {chs, chs, chs});
-        top_proofs->push_back(sumcheck_product_sq(be, sq, pk.T("eq_top"), d1, half, chs));
-        top_proofs->push_back(sumcheck_product_sq(be, sq, pk.T("eq_top"), d0, half, chs));
-        top_proofs->push_back(sumcheck_product_sq(be, sq, d0, dd1, half, chs));
+        *top_opens = k.queued([&](ScQueue &sq) { return open_many_sq(sq, q, dc, {d0, dd1, d1}, {half, half, half}, {chs, chs, chs}); });
+        for (auto &fg : {std::make_pair(pk.T("eq_top"), d1), std::make_pair(pk.T("eq_top"), d0), std::make_pair(d0, dd1)})
+            top_proofs->push_back(k.queued([&](ScQueue &sq) { return sumcheck_product_sq(be, sq, fg.first, fg.second, half, chs); }));
     }
     mark("wiring: everything enqueued");
     return [a_2c, a_copen, a_dopen, f_dsp, f_dcommit, top_commits, top_opens, top_proofs, has_top]() -> std::function<void(Transcript &)> {
@@ -334,13 +268,13 @@ inline AfterBatch<std::function<void(Transcript &)>> wiring_enqueue_sq(size_t n,
         auto f_dopen = a_dopen();                                              // the local open values, the leader's root opens
         return [p2c, f_dsp, f_copen, f_dcommit, f_dopen, top_commits, top_opens, top_proofs, has_top](Transcript &out) {
             out.wiring_proofs = *p2c;
-            for (auto &p : f_dsp()) out.wiring_proofs.push_back(p);
-            out.wiring_opens = f_copen();
-            out.wiring_commits = f_dcommit();
+            for (auto &p : f_dsp()) out.wiring_proofs.push_back(p);  // 2.e: after 2.c, before the leader-tree sumchecks (the reference's order)
+            out.wiring_opens = f_copen();                           // 2.d
+            out.wiring_commits = f_dcommit();                       // 2.b, then :363-380
             for (auto &o : f_dopen()) out.wiring_opens.push_back(o);
             if (has_top) {
                 std::vector<Opening> to = top_opens->finish();
-                for (size_t i = 0; i < 3; ++i) {
+                for (size_t i = 0; i < 3; ++i) {  // (commit, open) per table, in the reference's order
                     out.wiring_commits.push_back((*top_commits)[i]());
                     out.wiring_opens.push_back(to[i]);
                 }
@@ -381,113 +315,77 @@ inline Transcript dhyperplonk(size_t n, const PackedProvingParameters &pk, const
         com.insert(com.end(), com_d.begin(), com_d.end());
     };
     std::vector<FrVec> pts3(3, pk.challenge);
-    std::vector<Opening> ops;
+    // The schedules differ in data only: whether the sumcheck-family kernels of steps 2-4 share ONE batch (pipeline.hpp ScQueue;
+    // ZKHOST_ONE_BATCH=0: a batch per call), and where each of the three MSM passes is started, run or finished.
+    static const bool one_batch_env = [] {
+        const char *e = std::getenv("ZKHOST_ONE_BATCH");
+        return !e || std::atoi(e) != 0;
+    }();
+    // serial_steps: every MSM pass runs to completion inside the step that owns it, a batch per call: the timers cover what the
+    // reference's labels cover (same transcript; the measurement form, `hyperplonk --serial-rep`).  Otherwise the labels are OVERLAPPED
+    // sections, not the reference's steps: only the total is comparable.
+    const bool one_batch = one_batch_env && !serial_steps;
     // Where the commit pass is started.  2 (default, one-batch schedule): right after the kernel batch of steps 2-4 -- the product tree
     // and the batch then run on an empty chip instead of queueing behind the pass, and the GPU works on the pass during the hand-offs
     // (n = 18: 27.5 -> 24.5 ms, 64 parties at n = 20: 22.8 -> 20.5 ms, neutral at n = 12, 16, 20 .. 24: profiles/r05z_late_commit2_ab.txt);
-    // 0: at step 1, as the reference orders it; 1: together with the two long passes (ZKHOST_LATE_COMMIT)
-    static const int late_commit = [] {
+    // 0: at step 1, as the reference orders it; 1: together with the two long passes (ZKHOST_LATE_COMMIT).  With a batch per call
+    // there is no "after the batch": 2 is step 1 there.
+    static const int late_commit_env = [] {
         const char *e = std::getenv("ZKHOST_LATE_COMMIT");
         const int v = e ? std::atoi(e) : 2;
         return (v == 0 || v == 1) ? v : 2;  // anything else is the default (an unknown value must not leave the commit pass unstarted)
     }();
-    static const bool one_batch = [] {  // the sumcheck-family kernels of steps 2-4 as ONE batch (pipeline.hpp ScQueue); ZKHOST_ONE_BATCH=0: a batch per call
-        const char *e = std::getenv("ZKHOST_ONE_BATCH");
-        return !e || std::atoi(e) != 0;
-    }();
-    const bool commit_at_step_1 = late_commit == 0 || (late_commit == 2 && !one_batch);
+    const int late_commit = (late_commit_env == 2 && !one_batch) ? 0 : late_commit_env;
     if (serial_steps) {
         q.run();
         collect_commit();
-    } else if (commit_at_step_1) {
+    } else if (late_commit == 0) {
         q.start();
     }
     tm.mark("commit pass started");
     tm.end();
 
-    if (one_batch && !serial_steps) {
-        ScQueue sq(be);
-        MsmQueue q_w(be), q_o(be);
-        tm.start("Gate identity");
-        DevPtr sum_ab = be.fr_add(pk.T("a_evals"), pk.T("b_evals"), Ml);  // :233-238
-        DevPtr sum_ci = be.fr_sub(pk.T("I"), pk.T("c_evals"), Ml);        // -c + I  :251-256
-        auto a_gate = c_sumcheck_product_many_sq(be, sq, {{pk.T("eq"), pk.T("S1")}, {pk.T("S1"), sum_ab}, {pk.T("eq"), pk.T("S2")}, {pk.T("a_evals"), pk.T("b_evals")},
-                                                          {pk.T("S2"), pk.T("a_evals")}, {pk.T("eq"), sum_ci}}, Ml, pk.challenge, pp, net);
-        tm.end();
-        tm.start("Wire identity");
-        auto b_wiring = detail::wiring_enqueue_sq(n, pk, pp, be, net, q_w, sq, data_parallel, &tm);
-        auto a_co = c_open_many_sq(be, sq, q_o, cc, tc, lc, pts3, pp, net);  // the kernel phase of step 4 (:517-553) rides in the same batch
-        auto a_do = d_open_many_sq(be, sq, q_o, dc, td, ld, pts3, net);
-        sq.run();
-        tm.mark("the batch ran");
-        if (late_commit == 2) q.start();
-        out.gate_proofs = a_gate();
-        auto finalize_wiring = b_wiring();
-        auto f_co = a_co();
-        auto f_do = a_do();
-        tm.mark("hand-offs done");
-        if (late_commit == 1) q.start();
-        q_w.start();
-        tm.mark("wiring pass started");
-        q_o.start();
-        tm.mark("open pass started");
-        q.finish();
-        collect_commit();
-        tm.mark("commit pass collected");
-        tm.end();
-        tm.start("Open");
-        q_w.finish();
-        tm.mark("wiring pass finished");
-        finalize_wiring(out);
-        tm.mark("wiring finalized");
-        q_o.finish();
-        tm.mark("open pass finished");
-        ops = f_co();
-        std::vector<Opening> ops_d = f_do();
-        ops.insert(ops.end(), ops_d.begin(), ops_d.end());
-        tm.end();
-        for (size_t i = 0; i < 6; ++i) out.gate_commitments.push_back({com[i], ops[i]});
-        tm.end();
-        if (tm_out) *tm_out = tm;
-        return out;
-    }
-
+    ScQueue sq(be);
+    const detail::Kernels k{be, one_batch ? &sq : nullptr};
+    MsmQueue q_w(be), q_o(be);
     // Step 3: gate identity (:223-260): the six sumchecks are independent -- one batched phase 1, then the hand-offs in order
     tm.start("Gate identity");
     DevPtr sum_ab = be.fr_add(pk.T("a_evals"), pk.T("b_evals"), Ml);  // :233-238
     DevPtr sum_ci = be.fr_sub(pk.T("I"), pk.T("c_evals"), Ml);        // -c + I  :251-256
-    out.gate_proofs = c_sumcheck_product_many(be, {{pk.T("eq"), pk.T("S1")}, {pk.T("S1"), sum_ab}, {pk.T("eq"), pk.T("S2")}, {pk.T("a_evals"), pk.T("b_evals")},
-                                                   {pk.T("S2"), pk.T("a_evals")}, {pk.T("eq"), sum_ci}}, Ml, pk.challenge, pp, net);
-    tm.mark("gate sumchecks done");
+    auto a_gate = k.staged([&](ScQueue &s) {
+        return c_sumcheck_product_many_sq(be, s, {{pk.T("eq"), pk.T("S1")}, {pk.T("S1"), sum_ab}, {pk.T("eq"), pk.T("S2")}, {pk.T("a_evals"), pk.T("b_evals")},
+                                                  {pk.T("S2"), pk.T("a_evals")}, {pk.T("eq"), sum_ci}}, Ml, pk.challenge, pp, net);
+    });
     tm.end();
 
-    MsmQueue q_w(be), q_o(be);
+    // Step 2: wiring identity (shared with dpermcheck).  The kernel phase of the Open step (:517-553) depends on nothing the wiring
+    // step produces, so it runs BEFORE the wiring pass is started: both passes are then in flight back to back.
+    tm.start("Wire identity");
+    auto b_wiring = detail::wiring_enqueue(n, pk, pp, be, net, q_w, k, data_parallel, serial_steps ? nullptr : &tm);
+    std::function<void(Transcript &)> finalize_wiring;
     if (serial_steps) {
-        // every MSM pass runs to completion inside the step that owns it: the timers cover what the reference's labels cover
-        // (same transcript; the measurement form, `hyperplonk --serial-rep`)
-        tm.start("Wire identity");
-        auto finalize_wiring = detail::wiring_enqueue(n, pk, pp, be, net, q_w, data_parallel);
+        finalize_wiring = b_wiring();
         q_w.run();
         finalize_wiring(out);
         tm.end();
         tm.start("Open");
-        auto f_co = c_open_many_q(be, q_o, cc, tc, lc, pts3, pp, net);
-        auto f_do = d_open_many_q(be, q_o, dc, td, ld, pts3, net);
+    }
+    auto a_co = k.staged([&](ScQueue &s) { return c_open_many_sq(be, s, q_o, cc, tc, lc, pts3, pp, net); });  // step 4 (:517-553)
+    auto a_do = k.staged([&](ScQueue &s) { return d_open_many_sq(be, s, q_o, dc, td, ld, pts3, net); });
+    if (one_batch) {
+        sq.run();
+        tm.mark("the batch ran");
+        if (late_commit == 2) q.start();
+    }
+    out.gate_proofs = a_gate();
+    if (!serial_steps) finalize_wiring = b_wiring();
+    auto f_co = a_co();
+    auto f_do = a_do();
+    if (serial_steps) {
         q_o.run();
-        ops = f_co();
-        std::vector<Opening> ops_d = f_do();
-        ops.insert(ops.end(), ops_d.begin(), ops_d.end());
-        tm.end();
     } else {
-        // Step 2: wiring identity (shared with dpermcheck).  The kernel phase of the Open step (:517-553) depends on nothing the
-        // wiring step produces, so it runs BEFORE the wiring pass is started: both passes are then in flight back to back.
-        // (The labels below are therefore OVERLAPPED sections, not the reference's steps: only the total is comparable.)
-        tm.start("Wire identity");
-        auto finalize_wiring = detail::wiring_enqueue(n, pk, pp, be, net, q_w, data_parallel, &tm);
-        auto f_co = c_open_many_q(be, q_o, cc, tc, lc, pts3, pp, net);
-        auto f_do = d_open_many_q(be, q_o, dc, td, ld, pts3, net);
-        tm.mark("open-step kernels done");
-        if (!commit_at_step_1) q.start();
+        tm.mark("hand-offs done");
+        if (late_commit == 1) q.start();
         q_w.start();
         tm.mark("wiring pass started");
         q_o.start();
@@ -505,11 +403,11 @@ inline Transcript dhyperplonk(size_t n, const PackedProvingParameters &pk, const
         tm.mark("wiring finalized");
         q_o.finish();
         tm.mark("open pass finished");
-        ops = f_co();
-        std::vector<Opening> ops_d = f_do();
-        ops.insert(ops.end(), ops_d.begin(), ops_d.end());
-        tm.end();
     }
+    std::vector<Opening> ops = f_co();
+    std::vector<Opening> ops_d = f_do();
+    ops.insert(ops.end(), ops_d.begin(), ops_d.end());
+    tm.end();
     for (size_t i = 0; i < 6; ++i) out.gate_commitments.push_back({com[i], ops[i]});
     tm.end();
     if (tm_out) *tm_out = tm;
@@ -524,7 +422,7 @@ inline Transcript dpermcheck(size_t n, const PackedProvingParameters &pk, const 
     tm.start("Distributed Permcheck");
     MsmQueue q(be);
     ScQueue sq(be);  // the step's sumcheck-family kernels as one batch (pipeline.hpp)
-    auto after = detail::wiring_enqueue_sq(n, pk, pp, be, net, q, sq, false);
+    auto after = detail::wiring_enqueue(n, pk, pp, be, net, q, detail::Kernels{be, &sq}, false);
     sq.run();
     auto fin = after();
     q.run();

@@ -3,8 +3,9 @@
 // Nothing on the reference's path consumes an MSM result on the device (challenges are pre-sampled, hyperplonk/src/
 // dhyperplonk.rs:159-186), so every commit / open of a protocol step can QUEUE its MSMs, run them in ONE pipeline pass
 // (zk_msm_g1_batch, or zk_msm_g1_batch_async beside the next step's kernels) and finish -- exchange + public map -- later.
-// The `*_q` functions below run their kernels now, queue their MSMs and return a closure that produces the reference's
-// return value once the queue has run; every party calls them, the queue and the closures in the same order.  Every output
+// The `*_q` functions below queue their MSMs (those that have sumcheck-family kernels run them now; their bodies are the `*_sq`
+// forms further down) and return a closure that produces the reference's return value once the queue has run; every party
+// calls them, the queue and the closures in the same order.  Every output
 // is bit-identical to the one-call-at-a-time forms of dist_primitive.hpp (same field / group elements).
 // Lifetimes: a closure OWNS what it reads of the queue -- a shared handle on the pass its items were added to (MsmPass), so it
 // stays valid after the MsmQueue object is gone or has been re-armed by a later pass, and it throws (instead of reading someone
@@ -165,235 +166,19 @@ inline std::function<G1Vec()> d_commit_many_q(Ctx &be, MsmQueue &q, const Powers
     };
 }
 
-// several independent opens (dpoly_comm.rs:299-325 each): the fold rounds run now as one batched call, the commitments of
-// all q_i are queued.  Opens of the SAME table share their first quotient q_0 = hi - lo (it does not depend on the point):
-// with the queue's duplicate detection its commitment is one MSM for all of them.
-struct OpensInFlight {
-    std::vector<Fr> values;  // known as soon as the fold rounds ran (before the MSMs)
-    std::function<std::vector<Opening>()> finish;
-};
-inline OpensInFlight open_many_q(Ctx &be, MsmQueue &q, const PowersOfG &pg, const std::vector<DevPtr> &pevals, const std::vector<size_t> &lens,
-                                 const std::vector<FrVec> &points, size_t l = 1) {
-    std::vector<ScRequest> reqs;
-    for (size_t i = 0; i < lens.size(); ++i) {
-        size_t n = Ctx::log2_exact(lens[i]);
-        if (points[i].size() < n) throw ZkError(ZK_ERR_INVALID, "open: the point is shorter than the polynomial's variables");
-        reqs.push_back({ScRequest::Open, pevals[i], DevPtr(), lens[i], FrVec(points[i].begin(), points[i].begin() + n), DevPtr()});
-    }
-    std::vector<ScResult> rounds = be.sumcheck_batch(reqs);  // :309-323, all items at once
-    std::map<std::pair<const void *, size_t>, DevPtr> first;
-    OpensInFlight out;
-    auto cuts = std::make_shared<std::vector<std::vector<size_t>>>();
-    for (size_t i = 0; i < lens.size(); ++i) {
-        DevPtr q0 = first.emplace(std::make_pair((const void *)pevals[i].get(), lens[i]), rounds[i].out).first->second;
-        std::vector<SrsPtr> srs;
-        std::vector<DevPtr> bufs;
-        std::vector<size_t> ls;
-        detail::open_items(pg, rounds[i].out, lens[i], l, srs, bufs, ls);
-        if (!bufs.empty()) bufs[0] = q0;
-        out.values.push_back(rounds[i].last_f);
-        cuts->push_back(q.add(srs, bufs, ls));
-        q.keep.push_back(rounds[i].out);  // the q buffers must outlive the batched MSM
-    }
-    std::vector<Fr> vals = out.values;
-    out.finish = [pass = q.ticket(), cuts, vals] {
-        std::vector<Opening> res;
-        for (size_t i = 0; i < vals.size(); ++i) res.push_back({vals[i], detail::pick(pass, (*cuts)[i])});
-        return res;
-    };
-    return out;
-}
-
-// several d_open (dpoly_comm.rs:355-398): local fold rounds and the exchange of the local VALUES happen now; the commitments
-// of the local opens and (leader) of the root opens on the gathered values are queued
-inline std::function<std::vector<Opening>()> d_open_many_q(Ctx &be, MsmQueue &q, const PowersOfG &pg, const std::vector<DevPtr> &pevals, const std::vector<size_t> &lens,
-                                                           const std::vector<FrVec> &points, Net &net) {
-    size_t k = lens.size(), plog = log2_floor(net.n_parties), np = net.n_parties;
-    if (!k) return [] { return std::vector<Opening>{}; };
-    std::vector<FrVec> lo, hi;
-    for (auto &pt : points) {
-        if (pt.size() < plog) throw ZkError(ZK_ERR_INVALID, "d_open: the point is shorter than the party bits");
-        hi.emplace_back(pt.begin() + plog, pt.end());
-        lo.emplace_back(pt.begin(), pt.begin() + plog);
-    }
-    auto local = std::make_shared<OpensInFlight>(open_many_q(be, q, pg, pevals, lens, hi));
-    std::vector<FrVec> vals = net.all_gather_fr(local->values);  // [party][k]
-    auto root = std::make_shared<OpensInFlight>();
-    if (net.is_leader()) {
-        FrVec tab;  // [k][party]
-        for (size_t i = 0; i < k; ++i)
-            for (size_t p = 0; p < np; ++p) tab.push_back(vals[p][i]);
-        DevPtr d = be.to_device(tab);
-        std::vector<DevPtr> roots;
-        for (size_t i = 0; i < k; ++i) roots.push_back(d.fr(np * i));
-        *root = open_many_q(be, q, pg, roots, std::vector<size_t>(k, np), lo);
-        q.keep.push_back(d);
-    }
-    return [&be, &net, local, root, k, np] {
-        std::vector<Opening> loc = local->finish();
-        G1Vec flat;
-        std::vector<size_t> cuts{0};
-        for (auto &o : loc) {
-            flat.insert(flat.end(), o.proofs.begin(), o.proofs.end());
-            cuts.push_back(flat.size());
-        }
-        std::vector<G1Vec> prfs = net.all_gather_g1(flat);
-        std::vector<Opening> out(k, Opening{Fr::zero(), {}});
-        if (!net.is_leader()) return out;
-        G1Vec pi = be.g1_lincomb_batch(detail::by_item(prfs), FrVec(np, Fr{{1, 0, 0, 0}}), flat.size());
-        std::vector<Opening> roots = root->finish();
-        for (size_t i = 0; i < k; ++i) {
-            out[i] = roots[i];  // root proofs FIRST (:379-384)
-            out[i].proofs.insert(out[i].proofs.end(), pi.begin() + cuts[i], pi.begin() + cuts[i + 1]);
-        }
-        return out;
-    };
-}
-
-// several c_open (dpoly_comm.rs:401-464) whose q_i commitments share ONE queued d_msm
-inline std::function<std::vector<Opening>()> c_open_many_q(Ctx &be, MsmQueue &q, const PowersOfG &pg, const std::vector<DevPtr> &pevals, const std::vector<size_t> &lens,
-                                                           const std::vector<FrVec> &points, const PackedSharingParams &pp, Net &net) {
-    size_t k = lens.size();
-    std::vector<ScRequest> reqs;
-    for (size_t i = 0; i < k; ++i) {
-        size_t n = Ctx::log2_exact(lens[i]);
-        if (points[i].size() < n) throw ZkError(ZK_ERR_INVALID, "c_open: the point is shorter than the polynomial's variables");
-        reqs.push_back({ScRequest::Open, pevals[i], DevPtr(), lens[i], FrVec(points[i].begin(), points[i].begin() + n), DevPtr()});
-    }
-    std::vector<ScResult> rounds = be.sumcheck_batch(reqs);  // :418-432
-    std::map<std::pair<const void *, size_t>, DevPtr> first;
-    std::vector<SrsPtr> srs;
-    std::vector<DevPtr> bufs;
-    std::vector<size_t> ms, cuts{0};
-    for (size_t i = 0; i < k; ++i) {
-        DevPtr q0 = first.emplace(std::make_pair((const void *)pevals[i].get(), lens[i]), rounds[i].out).first->second;
-        size_t at = bufs.size();
-        detail::open_items(pg, rounds[i].out, lens[i], pp.l, srs, bufs, ms);
-        if (bufs.size() > at) bufs[at] = q0;
-        q.keep.push_back(rounds[i].out);
-        cuts.push_back(ms.size());
-    }
-    std::function<G1Vec()> f_com = ms.empty() ? std::function<G1Vec()>([] { return G1Vec{}; }) : d_msm_q(be, q, srs, bufs, ms, pp, net);
-    // phase 2 (:440-462): pss2ss of the last value, log2(l) more rounds on the l-vector; its MSMs are queued too
-    struct Tail {
-        Fr value;
-        std::vector<size_t> items;
-    };
-    auto tails = std::make_shared<std::vector<Tail>>();
-    for (size_t i = 0; i < k; ++i) {
-        FrVec cur = pss2ss(rounds[i].last_f, pp, net);
-        Tail t;
-        for (size_t r = 0; r < log2_floor(pp.l); ++r) {
-            size_t h = cur.size() / 2;
-            FrVec qi(h), nx(h);
-            for (size_t j = 0; j < h; ++j) {
-                qi[j] = cur[j + h] - cur[j];
-                nx[j] = cur[j] + points[i].at(r) * (cur[j + h] - cur[j]);
-            }
-            t.items.push_back(q.add({detail::level_for(pg, h * pp.l)}, {be.to_device(qi)}, {h})[0]);  // :457 (a plain local G::msm)
-            cur = nx;
-        }
-        t.value = cur[0];
-        tails->push_back(t);
-    }
-    return [pass = q.ticket(), f_com, tails, cuts, k] {
-        G1Vec com = f_com();
-        std::vector<Opening> out;
-        for (size_t i = 0; i < k; ++i) {
-            Opening o{(*tails)[i].value, G1Vec(com.begin() + cuts[i], com.begin() + cuts[i + 1])};
-            for (size_t it : (*tails)[i].items) o.proofs.push_back(pass->at(it));
-            out.push_back(o);
-        }
-        return out;
-    };
-}
-
-// several independent c_sumcheck_product (dsumcheck.rs:148-285) on tables of one length: their phase-1 loops run as ONE
-// batched call, the pss2ss hand-offs (:224-225) and phase 2 follow item by item in the reference's order
-inline std::vector<std::vector<Triple>> c_sumcheck_product_many(Ctx &be, const std::vector<std::pair<DevPtr, DevPtr>> &pairs, size_t len, const FrVec &challenge,
-                                                                const PackedSharingParams &pp, Net &net) {
-    size_t n = Ctx::log2_exact(len);
-    std::vector<ScRequest> reqs;
-    for (auto &fg : pairs) {
-        detail::trace(be, 'c', fg.first, fg.second, len, challenge, n);
-        reqs.push_back({ScRequest::Product, fg.first, fg.second, len, FrVec(challenge.begin(), challenge.begin() + n), DevPtr()});
-    }
-    std::vector<std::vector<Triple>> out;
-    for (ScResult &r : be.sumcheck_batch(reqs)) {
-        std::vector<Triple> tr = detail::triples_of(r.sums);
-        FrVec vf = pss2ss(r.last_f, pp, net), vg = pss2ss(r.last_g, pp, net);
-        for (size_t i = 0; i < log2_floor(pp.l); ++i) tr.push_back(detail::round_product(vf, vg, challenge.at(i)));
-        tr.push_back({Fr::zero(), vf[0] * vg[0], Fr::zero()});
-        out.push_back(tr);
-    }
-    return out;
-}
-
-// several independent d_sumcheck_product (dsumcheck.rs:359-512).  The local phases run NOW as one batched call; the closure
-// performs the exchange -- the per-item gathers of the round tuples (:437) as ONE all-gather of the concatenated payloads --
-// and the leader rounds (:440-507).  A protocol step calls it after it has started its MSM pass.
-struct DsumcheckItem {
-    DevPtr f, g;
-    size_t len;
-    FrVec challenge;
-};
-inline std::function<std::vector<std::vector<Triple>>()> d_sumcheck_product_many_q(Ctx &be, const std::vector<DsumcheckItem> &items, Net &net) {
-    if (items.empty()) return [] { return std::vector<std::vector<Triple>>{}; };
-    size_t s = log2_floor(net.n_parties);
-    std::vector<ScRequest> reqs;
-    auto ns = std::make_shared<std::vector<size_t>>();
-    auto chals = std::make_shared<std::vector<FrVec>>();
-    for (auto &it : items) {
-        size_t n = Ctx::log2_exact(it.len);
-        if (it.challenge.size() < n + s) throw ZkError(ZK_ERR_INVALID, "d_sumcheck_product: fewer challenges than local + party rounds");
-        detail::trace(be, 'd', it.f, it.g, it.len, it.challenge, n + s);
-        ns->push_back(n);
-        chals->push_back(it.challenge);
-        reqs.push_back({ScRequest::Product, it.f, it.g, it.len, FrVec(it.challenge.begin(), it.challenge.begin() + n), DevPtr()});
-    }
-    auto phase1 = std::make_shared<std::vector<ScResult>>(be.sumcheck_batch(reqs));
-    return [&net, phase1, ns, chals, s] {
-        FrVec local;
-        std::vector<size_t> cuts{0};
-        for (ScResult &r : *phase1) {
-            local.insert(local.end(), r.sums.begin(), r.sums.end());
-            local.push_back(r.last_g), local.push_back(r.last_f), local.push_back(Fr::zero());  // marker (g, f, 0)  :433
-            cuts.push_back(local.size());
-        }
-        std::vector<FrVec> all = net.all_gather_fr(local);
-        std::vector<std::vector<Triple>> out(ns->size());
-        if (!net.is_leader()) return out;
-        for (size_t k = 0; k < ns->size(); ++k) {
-            size_t n = (*ns)[k];
-            std::vector<Triple> tr(n, Triple{Fr::zero(), Fr::zero(), Fr::zero()});
-            FrVec f, g;
-            for (auto &a : all) {
-                const Fr *m = &a[cuts[k]];
-                for (size_t i = 0; i < n; ++i)
-                    for (size_t c = 0; c < 3; ++c) tr[i][c] += m[3 * i + c];
-                f.push_back(m[3 * n + 1]);  // :448
-                g.push_back(m[3 * n]);      // :449
-            }
-            for (size_t i = 0; i < s; ++i) tr.push_back(detail::round_product(f, g, (*chals)[k].at(n + i)));
-            out[k] = tr;
-        }
-        return out;
-    };
-}
-
-
 // =====================================================================================================================
-// One batch for the sumcheck-family kernels of a whole protocol step (round 5).
+// The product sumchecks and the opens, written ONCE against a queue of sumcheck-family kernels (ScQueue).
 //
-// The `*_q` forms above run their kernels in a batch of their own and block for it: the wiring step of a proof is then ~10
-// blocking calls (2.c, the opens of V, the 57 d_sumcheck_products, the 57 d_opens, the leader's top tree, the opens of step 4)
-// of which most are latency chains that leave the chip nearly empty -- 4.2 ms of a 68 ms proof at n = 20 (hyperplonk --marks).
-// None of them needs another one's RESULT on the device, only the tables; so they can all be enqueued first and run as ONE
-// zk_sumcheck_batch (ScQueue), after which the host parts follow in the reference's order.  The `*_sq` forms are the `*_q`
-// forms cut in two: phase A adds the requests (the output buffers of the opens are allocated now, so that their quotient
+// As a blocking batch per call the wiring step of a proof is ~10 calls (2.c, the opens of V, the 57 d_sumcheck_products, the 57
+// d_opens, the leader's top tree, the opens of step 4) of which most are latency chains that leave the chip nearly empty -- 4.2 ms
+// of a 68 ms proof at n = 20 (hyperplonk --marks).  None of them needs another one's RESULT on the device, only the tables; so
+// they can all be enqueued first and run as ONE zk_sumcheck_batch, after which the host parts follow in the reference's order.
+// Every `*_sq` form is phase A: it adds the requests (the output buffers of the opens are allocated now, so that their quotient
 // commitments can be queued in the MsmQueue at once) and returns phase B, which is called after ScQueue::run(): the exchanges that
 // need a kernel result (pss2ss of the last values, the gather of the local open values, the leader's root opens) and the MSM
-// items that depend on them.  Phase B returns the finishing closure of the `*_q` forms.  Same outputs, bit for bit.
+// items that depend on them.  Phase B returns the finishing closure.  The per-call names at the end of this file (open_many_q,
+// d_open_many_q, c_open_many_q, c_sumcheck_product_many, d_sumcheck_product_many_q) are the same forms on a queue of their own
+// (own_batch): add, run, phase B.  The one-call forms of dist_primitive.hpp stay what the self-check compares them with.
 // =====================================================================================================================
 struct ScPass {
     std::vector<ScResult> res;
@@ -435,7 +220,17 @@ class ScQueue {
 template <class T>
 using AfterBatch = std::function<T()>;  // phase B: call after ScQueue::run()
 
-// several c_sumcheck_product on tables of one length (c_sumcheck_product_many): A adds, B = the pss2ss hand-offs and phase 2
+// a primitive's kernels as a batch of their own: `add(queue)` is its *_sq form; the queue runs at once; -> what the form returned
+template <class Add>
+auto own_batch(Ctx &be, Add &&add) {
+    ScQueue sq(be);
+    auto out = add(sq);
+    sq.run();
+    return out;
+}
+
+// several independent c_sumcheck_product (dsumcheck.rs:148-285) on tables of one length: A adds their phase-1 loops, B = the pss2ss
+// hand-offs (:224-225) and phase 2, item by item in the reference's order
 inline AfterBatch<std::vector<std::vector<Triple>>> c_sumcheck_product_many_sq(Ctx &be, ScQueue &sq, const std::vector<std::pair<DevPtr, DevPtr>> &pairs, size_t len,
                                                                                const FrVec &challenge, const PackedSharingParams &pp, Net &net) {
     size_t n = Ctx::log2_exact(len);
@@ -471,38 +266,59 @@ inline AfterBatch<std::vector<Triple>> sumcheck_product_sq(Ctx &be, ScQueue &sq,
     };
 }
 
-// open_many_q: B has nothing to exchange -- the values are read when the finishing closure runs
-inline OpensInFlight open_many_sq(ScQueue &sq, MsmQueue &q, const PowersOfG &pg, const std::vector<DevPtr> &pevals, const std::vector<size_t> &lens,
-                                  const std::vector<FrVec> &points, size_t l = 1) {
+// several independent opens (dpoly_comm.rs:299-325 each): their fold rounds (:309-323) are added to the batch, the commitments of all
+// q_i are queued.  There is nothing to exchange, so no phase B: the values are read when the finishing closure runs.
+struct OpensInFlight {
+    std::vector<size_t> idx;  // the opens' requests in the batch: open i's value is ScPass::at(idx[i]).last_f
+    std::function<std::vector<Opening>()> finish;
+};
+namespace detail {
+// The quotient buffers of several opens as MSM items: the log2(len) commitments of every open (open_items) one after the other, open i's
+// being items cuts[i] .. cuts[i + 1].  Opens of the SAME table share their first quotient q_0 = hi - lo (it does not depend on the
+// point): they name the first such open's buffer, and with the queue's duplicate detection its commitment is one MSM for all of them.
+struct OpenWalk {
+    std::vector<SrsPtr> srs;
+    std::vector<DevPtr> bufs;
+    std::vector<size_t> lens, cuts{0};
+};
+inline OpenWalk open_walk(const PowersOfG &pg, const std::vector<DevPtr> &pevals, const std::vector<size_t> &lens, const std::vector<DevPtr> &qbufs, size_t l) {
+    OpenWalk w;
     std::map<std::pair<const void *, size_t>, DevPtr> first;
-    auto cuts = std::make_shared<std::vector<std::vector<size_t>>>();
-    auto idx = std::make_shared<std::vector<size_t>>();
+    for (size_t i = 0; i < lens.size(); ++i) {
+        DevPtr q0 = first.emplace(std::make_pair((const void *)pevals[i].get(), lens[i]), qbufs[i]).first->second;
+        size_t at = w.bufs.size();
+        open_items(pg, qbufs[i], lens[i], l, w.srs, w.bufs, w.lens);
+        if (w.bufs.size() > at) w.bufs[at] = q0;
+        w.cuts.push_back(w.lens.size());
+    }
+    return w;
+}
+}  // namespace detail
+inline OpensInFlight open_many_sq(ScQueue &sq, MsmQueue &q, const PowersOfG &pg, const std::vector<DevPtr> &pevals, const std::vector<size_t> &lens,
+                                  const std::vector<FrVec> &points) {
+    OpensInFlight out;
+    std::vector<DevPtr> qbufs;
     for (size_t i = 0; i < lens.size(); ++i) {
         size_t n = Ctx::log2_exact(lens[i]);
         if (points[i].size() < n) throw ZkError(ZK_ERR_INVALID, "open: the point is shorter than the polynomial's variables");
-        size_t k = sq.add({ScRequest::Open, pevals[i], DevPtr(), lens[i], FrVec(points[i].begin(), points[i].begin() + n), DevPtr()});
-        idx->push_back(k);
-        const DevPtr &qbuf = sq.out_of(k);
-        DevPtr q0 = first.emplace(std::make_pair((const void *)pevals[i].get(), lens[i]), qbuf).first->second;
-        std::vector<SrsPtr> srs;
-        std::vector<DevPtr> bufs;
-        std::vector<size_t> ls;
-        detail::open_items(pg, qbuf, lens[i], l, srs, bufs, ls);
-        if (!bufs.empty()) bufs[0] = q0;
-        cuts->push_back(q.add(srs, bufs, ls));
-        q.keep.push_back(qbuf);
+        out.idx.push_back(sq.add({ScRequest::Open, pevals[i], DevPtr(), lens[i], FrVec(points[i].begin(), points[i].begin() + n), DevPtr()}));
+        qbufs.push_back(sq.out_of(out.idx.back()));
+        q.keep.push_back(qbufs.back());  // the q buffers must outlive the batched MSM
     }
-    OpensInFlight out;  // (values: filled by the caller's phase B where an exchange needs them; the closure reads the batch itself)
-    out.finish = [mpass = q.ticket(), spass = sq.ticket(), cuts, idx] {
+    detail::OpenWalk w = detail::open_walk(pg, pevals, lens, qbufs, 1);
+    std::vector<size_t> items = q.add(w.srs, w.bufs, w.lens);
+    out.finish = [mpass = q.ticket(), spass = sq.ticket(), idx = out.idx, items, cuts = w.cuts] {
         std::vector<Opening> res;
-        for (size_t i = 0; i < idx->size(); ++i) res.push_back({spass->at((*idx)[i]).last_f, detail::pick(mpass, (*cuts)[i])});
+        for (size_t i = 0; i < idx.size(); ++i)
+            res.push_back({spass->at(idx[i]).last_f, detail::pick(mpass, std::vector<size_t>(items.begin() + cuts[i], items.begin() + cuts[i + 1]))});
         return res;
     };
     return out;
 }
 
-// d_open_many_q in two halves: A = the local opens' kernels and quotient commitments; B = the gather of the local values and, on the
-// leader, the root opens (their tables are 8 l elements: a batch of their own, run inside B)
+// several d_open (dpoly_comm.rs:355-398): A = the local opens' kernels and quotient commitments; B = the gather of the local VALUES and, on
+// the leader, the root opens on the gathered values, whose commitments are queued too; B -> the finishing closure: the exchange of the
+// local proofs and (leader) root proofs ++ summed local proofs
 inline AfterBatch<std::function<std::vector<Opening>()>> d_open_many_sq(Ctx &be, ScQueue &sq, MsmQueue &q, const PowersOfG &pg, const std::vector<DevPtr> &pevals,
                                                                         const std::vector<size_t> &lens, const std::vector<FrVec> &points, Net &net) {
     size_t k = lens.size(), plog = log2_floor(net.n_parties), np = net.n_parties;
@@ -513,40 +329,18 @@ inline AfterBatch<std::function<std::vector<Opening>()>> d_open_many_sq(Ctx &be,
         hi.emplace_back(pt.begin() + plog, pt.end());
         lo.emplace_back(pt.begin(), pt.begin() + plog);
     }
-    // (the local opens are added one by one so that their batch indices are known for the gather of the values)
-    auto idx = std::make_shared<std::vector<size_t>>();
-    auto cuts = std::make_shared<std::vector<std::vector<size_t>>>();
-    {
-        std::map<std::pair<const void *, size_t>, DevPtr> first;
-        for (size_t i = 0; i < k; ++i) {
-            size_t n = Ctx::log2_exact(lens[i]);
-            if (hi[i].size() < n) throw ZkError(ZK_ERR_INVALID, "open: the point is shorter than the polynomial's variables");
-            size_t j = sq.add({ScRequest::Open, pevals[i], DevPtr(), lens[i], FrVec(hi[i].begin(), hi[i].begin() + n), DevPtr()});
-            idx->push_back(j);
-            const DevPtr &qbuf = sq.out_of(j);
-            DevPtr q0 = first.emplace(std::make_pair((const void *)pevals[i].get(), lens[i]), qbuf).first->second;
-            std::vector<SrsPtr> srs;
-            std::vector<DevPtr> bufs;
-            std::vector<size_t> ls;
-            detail::open_items(pg, qbuf, lens[i], 1, srs, bufs, ls);
-            if (!bufs.empty()) bufs[0] = q0;
-            cuts->push_back(q.add(srs, bufs, ls));
-            q.keep.push_back(qbuf);
-        }
-    }
-    ScPassRef spass = sq.ticket();
-    MsmPassRef mpass = q.ticket();
-    return [&be, &q, &net, &pg, spass, mpass, idx, cuts, lo, k, np]() -> std::function<std::vector<Opening>()> {
+    OpensInFlight local = open_many_sq(sq, q, pg, pevals, lens, hi);
+    return [&be, &q, &net, &pg, spass = sq.ticket(), local, lo, k, np]() -> std::function<std::vector<Opening>()> {
         FrVec mine;
-        for (size_t j : *idx) mine.push_back(spass->at(j).last_f);
+        for (size_t j : local.idx) mine.push_back(spass->at(j).last_f);
         std::vector<FrVec> vals = net.all_gather_fr(mine);  // [party][k]
-        auto root = std::make_shared<OpensInFlight>();
+        auto roots = std::make_shared<std::vector<Opening>>();  // (value, no proofs yet)
+        auto rcuts = std::make_shared<std::vector<std::vector<size_t>>>(k);
         if (net.is_leader()) {
             // the root opens (dpoly_comm.rs:372-378: `open` of the N_p gathered values) are tables of 8 l elements: their fold rounds run
             // here on the host -- the same q = hi - lo, lo + r (hi - lo) -- and only the quotients go to the device for their commitments
             // (as a batch of their own the k of them were a blocking launch chain of ~0.3 ms)
             FrVec qall;
-            auto rvals = std::make_shared<std::vector<Fr>>(k);
             for (size_t i = 0; i < k; ++i) {
                 FrVec cur;
                 for (size_t p = 0; p < np; ++p) cur.push_back(vals[p][i]);
@@ -560,9 +354,8 @@ inline AfterBatch<std::function<std::vector<Opening>()>> d_open_many_sq(Ctx &be,
                     }
                     cur = nx;
                 }
-                (*rvals)[i] = cur[0];
+                roots->push_back({cur[0], {}});
             }
-            auto rcuts = std::make_shared<std::vector<std::vector<size_t>>>();
             if (np > 1) {
                 DevPtr dq = be.to_device(qall);  // [k][N_p - 1]
                 q.keep.push_back(dq);
@@ -571,32 +364,23 @@ inline AfterBatch<std::function<std::vector<Opening>()>> d_open_many_sq(Ctx &be,
                     std::vector<DevPtr> bufs;
                     std::vector<size_t> ls;
                     detail::open_items(pg, dq.fr((np - 1) * i), np, 1, srs, bufs, ls);
-                    rcuts->push_back(q.add(srs, bufs, ls));
+                    (*rcuts)[i] = q.add(srs, bufs, ls);
                 }
-            } else {
-                rcuts->assign(k, {});
             }
-            root->finish = [rpass = q.ticket(), rcuts, rvals, k] {
-                std::vector<Opening> res;
-                for (size_t i = 0; i < k; ++i) res.push_back({(*rvals)[i], detail::pick(rpass, (*rcuts)[i])});
-                return res;
-            };
         }
-        return [&be, &net, spass, mpass, idx, cuts, root, k, np] {
+        return [&be, &net, rpass = q.ticket(), local, roots, rcuts, k, np] {
             G1Vec flat;
             std::vector<size_t> ends{0};
-            for (size_t i = 0; i < k; ++i) {
-                G1Vec pr = detail::pick(mpass, (*cuts)[i]);
-                flat.insert(flat.end(), pr.begin(), pr.end());
+            for (const Opening &o : local.finish()) {
+                flat.insert(flat.end(), o.proofs.begin(), o.proofs.end());
                 ends.push_back(flat.size());
             }
             std::vector<G1Vec> prfs = net.all_gather_g1(flat);
             std::vector<Opening> out(k, Opening{Fr::zero(), {}});
             if (!net.is_leader()) return out;
             G1Vec pi = be.g1_lincomb_batch(detail::by_item(prfs), FrVec(np, Fr{{1, 0, 0, 0}}), flat.size());
-            std::vector<Opening> roots = root->finish();
             for (size_t i = 0; i < k; ++i) {
-                out[i] = roots[i];  // root proofs FIRST (:379-384)
+                out[i] = {(*roots)[i].value, detail::pick(rpass, (*rcuts)[i])};  // root proofs FIRST (:379-384)
                 out[i].proofs.insert(out[i].proofs.end(), pi.begin() + ends[i], pi.begin() + ends[i + 1]);
             }
             return out;
@@ -604,19 +388,15 @@ inline AfterBatch<std::function<std::vector<Opening>()>> d_open_many_sq(Ctx &be,
     };
 }
 
-// c_open_many_q in two halves: A = fold rounds + the ONE queued d_msm over all quotients; B = pss2ss of the last values and the
-// log2(l) extra rounds, whose small MSMs are queued too
+// several c_open (dpoly_comm.rs:401-464) whose q_i commitments share ONE queued d_msm: A = the fold rounds (:418-432); B = that d_msm
+// (:436), pss2ss of the last values (:440) and the log2(l) extra rounds, whose small MSMs are queued too; B -> the finishing closure
 inline AfterBatch<std::function<std::vector<Opening>()>> c_open_many_sq(Ctx &be, ScQueue &sq, MsmQueue &q, const PowersOfG &pg, const std::vector<DevPtr> &pevals,
                                                                         const std::vector<size_t> &lens, const std::vector<FrVec> &points,
                                                                         const PackedSharingParams &pp, Net &net) {
     size_t k = lens.size();
-    std::map<std::pair<const void *, size_t>, DevPtr> first;
     std::map<std::tuple<const void *, size_t, std::vector<uint64_t>>, size_t> same;
-    std::vector<SrsPtr> srs;
-    std::vector<DevPtr> bufs;
-    std::vector<size_t> ms;
-    auto cuts = std::make_shared<std::vector<size_t>>(1, 0);
-    auto idx = std::make_shared<std::vector<size_t>>();
+    std::vector<size_t> idx;
+    std::vector<DevPtr> qbufs;
     for (size_t i = 0; i < k; ++i) {
         size_t n = Ctx::log2_exact(lens[i]);
         if (points[i].size() < n) throw ZkError(ZK_ERR_INVALID, "c_open: the point is shorter than the polynomial's variables");
@@ -629,28 +409,23 @@ inline AfterBatch<std::function<std::vector<Opening>()>> c_open_many_sq(Ctx &be,
         auto seen = same.find(same_key);
         size_t j = seen != same.end() ? seen->second : sq.add({ScRequest::Open, pevals[i], DevPtr(), lens[i], pt, DevPtr()});
         same.emplace(same_key, j);
-        idx->push_back(j);
-        const DevPtr &qbuf = sq.out_of(j);
-        DevPtr q0 = first.emplace(std::make_pair((const void *)pevals[i].get(), lens[i]), qbuf).first->second;
-        size_t at = bufs.size();
-        detail::open_items(pg, qbuf, lens[i], pp.l, srs, bufs, ms);
-        if (bufs.size() > at) bufs[at] = q0;
-        q.keep.push_back(qbuf);
-        cuts->push_back(ms.size());
+        idx.push_back(j);
+        qbufs.push_back(sq.out_of(j));
+        q.keep.push_back(qbufs.back());
     }
-    ScPassRef spass = sq.ticket();
+    detail::OpenWalk w = detail::open_walk(pg, pevals, lens, qbufs, pp.l);
     std::vector<FrVec> pts = points;
-    return [&be, &q, &net, &pp, &pg, spass, idx, cuts, srs, bufs, ms, pts, k]() -> std::function<std::vector<Opening>()> {
+    return [&be, &q, &net, &pp, &pg, spass = sq.ticket(), idx, w, pts, k]() -> std::function<std::vector<Opening>()> {
         // (the d_msm over the quotients is queued HERE, after the batch: with real parties d_msm_q pre-scales its scalars by lambda_p on
         // the device when it is called, and the quotient buffers are filled by the batch)
-        std::function<G1Vec()> f_com = ms.empty() ? std::function<G1Vec()>([] { return G1Vec{}; }) : d_msm_q(be, q, srs, bufs, ms, pp, net);
+        std::function<G1Vec()> f_com = d_msm_q(be, q, w.srs, w.bufs, w.lens, pp, net);
         struct Tail {
             Fr value;
             std::vector<size_t> items;
         };
         auto tails = std::make_shared<std::vector<Tail>>();
         for (size_t i = 0; i < k; ++i) {
-            FrVec cur = pss2ss(spass->at((*idx)[i]).last_f, pp, net);
+            FrVec cur = pss2ss(spass->at(idx[i]).last_f, pp, net);
             Tail t;
             for (size_t r = 0; r < log2_floor(pp.l); ++r) {
                 size_t h = cur.size() / 2;
@@ -665,11 +440,11 @@ inline AfterBatch<std::function<std::vector<Opening>()>> c_open_many_sq(Ctx &be,
             t.value = cur[0];
             tails->push_back(t);
         }
-        return [mpass = q.ticket(), f_com, tails, cuts, k] {
+        return [mpass = q.ticket(), f_com, tails, cuts = w.cuts, k] {
             G1Vec com = f_com();
             std::vector<Opening> out;
             for (size_t i = 0; i < k; ++i) {
-                Opening o{(*tails)[i].value, G1Vec(com.begin() + (*cuts)[i], com.begin() + (*cuts)[i + 1])};
+                Opening o{(*tails)[i].value, G1Vec(com.begin() + cuts[i], com.begin() + cuts[i + 1])};
                 for (size_t it : (*tails)[i].items) o.proofs.push_back(mpass->at(it));
                 out.push_back(o);
             }
@@ -678,8 +453,14 @@ inline AfterBatch<std::function<std::vector<Opening>()>> c_open_many_sq(Ctx &be,
     };
 }
 
-// d_sumcheck_product_many_q with its local phases in the batch: the returned closure (exchange + leader rounds) is called when
-// the transcript is assembled, long after ScQueue::run()
+// several independent d_sumcheck_product (dsumcheck.rs:359-512): their local phases are added to the batch; the returned closure performs
+// the exchange -- the per-item gathers of the round tuples (:437) as ONE all-gather of the concatenated payloads -- and the leader rounds
+// (:440-507).  It is called when the transcript is assembled, long after ScQueue::run(): a protocol step has started its MSM pass by then.
+struct DsumcheckItem {
+    DevPtr f, g;
+    size_t len;
+    FrVec challenge;
+};
 inline std::function<std::vector<std::vector<Triple>>()> d_sumcheck_product_many_sq(Ctx &be, ScQueue &sq, const std::vector<DsumcheckItem> &items, Net &net) {
     if (items.empty()) return [] { return std::vector<std::vector<Triple>>{}; };
     size_t s = log2_floor(net.n_parties);
@@ -722,6 +503,30 @@ inline std::function<std::vector<std::vector<Triple>>()> d_sumcheck_product_many
         }
         return out;
     };
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The per-call forms: the same primitives with their kernels as a batch of their own, run inside the call, and phase B right behind it.
+// What they return is what the *_sq form's phase B returns (or, where it has none, its finishing closure).
+// ---------------------------------------------------------------------------------------------------------------------
+inline OpensInFlight open_many_q(Ctx &be, MsmQueue &q, const PowersOfG &pg, const std::vector<DevPtr> &pevals, const std::vector<size_t> &lens,
+                                 const std::vector<FrVec> &points) {
+    return own_batch(be, [&](ScQueue &sq) { return open_many_sq(sq, q, pg, pevals, lens, points); });
+}
+inline std::function<std::vector<Opening>()> d_open_many_q(Ctx &be, MsmQueue &q, const PowersOfG &pg, const std::vector<DevPtr> &pevals, const std::vector<size_t> &lens,
+                                                           const std::vector<FrVec> &points, Net &net) {
+    return own_batch(be, [&](ScQueue &sq) { return d_open_many_sq(be, sq, q, pg, pevals, lens, points, net); })();
+}
+inline std::function<std::vector<Opening>()> c_open_many_q(Ctx &be, MsmQueue &q, const PowersOfG &pg, const std::vector<DevPtr> &pevals, const std::vector<size_t> &lens,
+                                                           const std::vector<FrVec> &points, const PackedSharingParams &pp, Net &net) {
+    return own_batch(be, [&](ScQueue &sq) { return c_open_many_sq(be, sq, q, pg, pevals, lens, points, pp, net); })();
+}
+inline std::vector<std::vector<Triple>> c_sumcheck_product_many(Ctx &be, const std::vector<std::pair<DevPtr, DevPtr>> &pairs, size_t len, const FrVec &challenge,
+                                                                const PackedSharingParams &pp, Net &net) {
+    return own_batch(be, [&](ScQueue &sq) { return c_sumcheck_product_many_sq(be, sq, pairs, len, challenge, pp, net); })();
+}
+inline std::function<std::vector<std::vector<Triple>>()> d_sumcheck_product_many_q(Ctx &be, const std::vector<DsumcheckItem> &items, Net &net) {
+    return own_batch(be, [&](ScQueue &sq) { return d_sumcheck_product_many_sq(be, sq, items, net); });
 }
 
 }  // namespace zkhost

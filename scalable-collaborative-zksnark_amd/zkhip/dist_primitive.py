@@ -245,15 +245,6 @@ def sumcheck(be, evaluation, length: int, challenge: np.ndarray) -> np.ndarray:
     return np.concatenate([pairs, np.stack([ZERO, last])[None]])
 
 
-def sumcheck_product(be, ef, eg, length: int, challenge: np.ndarray) -> np.ndarray:
-    """dsumcheck.rs:28-90 -> [n+1, 3, 4]; last entry (0, f*g, 0)"""
-    n = length.bit_length() - 1
-    _trace(be, "plain", ef, eg, length, challenge[:n])
-    tr, lf, lg = be.sumcheck_product(ef, eg, length, challenge[:n])
-    prod = fr_mont(fr_from_mont(lf) * fr_from_mont(lg) % R_MOD)
-    return np.concatenate([tr, np.stack([ZERO, prod, ZERO])[None]])
-
-
 def c_sumcheck(be, shares, length: int, challenge: np.ndarray, pp: PackedSharingParams, net: Net) -> np.ndarray:
     """dsumcheck.rs:92-146 -> [n + log2(l) + 1, 2, 4]"""
     n = length.bit_length() - 1
@@ -266,45 +257,6 @@ def c_sumcheck(be, shares, length: int, challenge: np.ndarray, pp: PackedSharing
         extra.append(s)
     extra.append((0, v[0]))
     return np.concatenate([pairs, _ints_to_fr([x for p in extra for x in p]).reshape(-1, 2, 4)])
-
-
-def c_sumcheck_product(be, shares_f, shares_g, length: int, challenge: np.ndarray, pp: PackedSharingParams, net: Net) -> np.ndarray:
-    """dsumcheck.rs:148-285 -> [n + log2(l) + 1, 3, 4]"""
-    n = length.bit_length() - 1
-    _trace(be, "c", shares_f, shares_g, length, challenge[:n])
-    tr, lf, lg = be.sumcheck_product(shares_f, shares_g, length, challenge[:n])
-    vf = _fr_vec_to_ints(pss2ss(lf, pp, net))  # :224
-    vg = _fr_vec_to_ints(pss2ss(lg, pp, net))  # :225
-    ch = _fr_vec_to_ints(challenge)
-    extra = []
-    for i in range(pp.l.bit_length() - 1):
-        t, vf, vg = _round_product(vf, vg, ch[i])
-        extra.append(t)
-    extra.append((0, vf[0] * vg[0] % R_MOD, 0))  # :282
-    return np.concatenate([tr, _ints_to_fr([x for t in extra for x in t]).reshape(-1, 3, 4)])
-
-
-def c_sumcheck_product_many(be, pairs: Sequence, length: int, challenge: np.ndarray, pp: PackedSharingParams, net: Net) -> List[np.ndarray]:
-    """
-    several independent c_sumcheck_product (dsumcheck.rs:148-285) on tables of one length: their phase-1 loops run as ONE
-    batched call, the pss2ss hand-offs (:224-225) and phase 2 follow item by item in the reference's order.
-    """
-    n = length.bit_length() - 1
-    for f, g in pairs:
-        _trace(be, "c", f, g, length, challenge[:n])
-    phase1 = _sc_batch(be, [("product", f, g, length, challenge[:n]) for f, g in pairs])
-    ch = _fr_vec_to_ints(challenge)
-    out = []
-    for tr, lf, lg in phase1:
-        vf = _fr_vec_to_ints(pss2ss(lf, pp, net))  # :224
-        vg = _fr_vec_to_ints(pss2ss(lg, pp, net))  # :225
-        extra = []
-        for i in range(pp.l.bit_length() - 1):
-            t, vf, vg = _round_product(vf, vg, ch[i])
-            extra.append(t)
-        extra.append((0, vf[0] * vg[0] % R_MOD, 0))  # :282
-        out.append(np.concatenate([tr, _ints_to_fr([x for t in extra for x in t]).reshape(-1, 3, 4)]))
-    return out
 
 
 def d_sumcheck(be, partial_poly, length: int, challenge: np.ndarray, net: Net) -> np.ndarray:
@@ -324,47 +276,6 @@ def d_sumcheck(be, partial_poly, length: int, challenge: np.ndarray, net: Net) -
         sm, v = _round_plain(v, ch[i])
         res.append(sm)
     return np.concatenate([head.reshape(-1, 2, 4), _ints_to_fr([x for p in res for x in p]).reshape(-1, 2, 4)])
-
-
-def d_sumcheck_product(be, partial_f, partial_g, length: int, challenge: np.ndarray, net: Net) -> np.ndarray:
-    """dsumcheck.rs:359-512.  Leader: [n'+s, 3, 4]; workers: empty.  Marker tuple is (g, f, 0) (:433)"""
-    n = length.bit_length() - 1
-    s = net.n_parties.bit_length() - 1
-    _trace(be, "d", partial_f, partial_g, length, challenge[: n + s])
-    tr, lf, lg = be.sumcheck_product(partial_f, partial_g, length, challenge[:n])
-    local = np.concatenate([tr, np.stack([lg, lf, ZERO])[None]])
-    allp = net.all_gather(local)
-    if not net.is_leader:
-        return np.zeros((0, 3, 4), dtype=np.uint64)
-    head = fr_sum_mont([np.asarray(allp[p])[:n] for p in range(net.n_parties)])  # [n, 3, 4]
-    res = []
-    f = [fr_from_mont(allp[p][n][1]) for p in range(net.n_parties)]  # :448
-    g = [fr_from_mont(allp[p][n][0]) for p in range(net.n_parties)]  # :449
-    ch = _fr_vec_to_ints(challenge[n : n + s])
-    for i in range(s):
-        t, f, g = _round_product(f, g, ch[i])
-        res.append(t)
-    return np.concatenate([head.reshape(-1, 3, 4), _ints_to_fr([x for t in res for x in t]).reshape(-1, 3, 4)])
-
-
-def d_sumcheck_product_many_q(be, items: Sequence, net: Net):
-    """
-    several independent d_sumcheck_product (dsumcheck.rs:359-512); items = [(partial_f, partial_g, length, challenge)].
-    The local phases run NOW as ONE batched call; -> closure that performs the exchange and the leader part: the per-item
-    gathers of the round tuples (:437) travel as ONE all-gather of the concatenated payloads (same bytes, one exchange instead
-    of len(items)), the leader rounds (:440-507, host arithmetic on a few hundred field elements) are unchanged per item.  A
-    protocol step calls the closure after it has started its MSM pass: the host work then runs beside the GPU's.
-    """
-    if not len(items):
-        return lambda: []
-    s = net.n_parties.bit_length() - 1
-    ns = [length.bit_length() - 1 for _, _, length, _ in items]
-    for (f, g, length, ch), n in zip(items, ns):
-        _trace(be, "d", f, g, length, ch[: n + s])
-    phase1 = _sc_batch(be, [("product", f, g, length, ch[:n]) for (f, g, length, ch), n in zip(items, ns)])
-    chals = [np.array(ch, copy=True) for _, _, _, ch in items]
-
-    return lambda: _d_sumcheck_leader_rounds(phase1, chals, ns, s, net)
 
 
 def _d_sumcheck_leader_rounds(phase1, chals, ns, s, net):
@@ -389,18 +300,15 @@ def _d_sumcheck_leader_rounds(phase1, chals, ns, s, net):
     return out
 
 
-def d_sumcheck_product_many(be, items: Sequence, net: Net) -> List[np.ndarray]:
-    """several independent d_sumcheck_product (dsumcheck.rs:359-512) at once: the local phases as one batched call, one exchange"""
-    return d_sumcheck_product_many_q(be, items, net)()
-
-
 # =======================================================================================
-# ONE batch for the sumcheck-family kernels of a whole protocol step (the mirror of zkhost/pipeline.hpp ScQueue and its *_sq forms).
-# The *_q forms above run the kernels of one primitive, then do the exchange that depends on them; a step that calls several of them
-# pays a blocking launch chain per call with the chip nearly empty.  Nothing in those chains needs another call's result ON THE
-# DEVICE: every *_sq form splits into phase A -- add the requests (the opens' quotient buffers are allocated at once, so their
-# commitments can be queued) -- and phase B, called after ScQueue.run(), which performs the exchanges that need a kernel result
-# and returns what the *_q form returns.  Same outputs, bit for bit.
+# The product sumchecks and the opens are written ONCE, against a queue of sumcheck-family kernels (ScQueue, the mirror of
+# zkhost/pipeline.hpp): every *_sq form is phase A -- add the requests (the opens' quotient buffers are allocated at once, so their
+# commitments can be queued) -- and returns phase B, called after ScQueue.run(), which performs the exchanges that need a kernel
+# result (pss2ss of the last values, the gather of the local open values, the leader's root opens), queues the MSM items that depend
+# on them and returns the finishing closure.  A protocol step adds all its primitives to ONE queue: nothing in them needs another's
+# result ON THE DEVICE, and as a blocking launch chain per call they leave the chip nearly empty.  The per-call names (sumcheck_product,
+# c_sumcheck_product_many, d_sumcheck_product_many_q, open_many_q, d_open_many_q, c_open_many_q and their wrappers) are the same
+# forms on a queue of their own (own_batch): add, run, phase B.
 # =======================================================================================
 class ScQueue:
     def __init__(self, be):
@@ -423,6 +331,14 @@ class ScQueue:
         if self.res is None:
             raise RuntimeError("ScQueue: a result was read before the batch ran")
         return self.res[i]
+
+
+def own_batch(be, add):
+    """a primitive's kernels as a batch of their own: `add(queue)` is its *_sq form; the queue runs at once; -> what the form returned"""
+    sq = ScQueue(be)
+    out = add(sq)
+    sq.run()
+    return out
 
 
 def c_sumcheck_product_many_sq(be, sq: ScQueue, pairs: Sequence, length: int, challenge: np.ndarray, pp: PackedSharingParams, net: Net):
@@ -466,7 +382,8 @@ def sumcheck_product_sq(be, sq: ScQueue, ef, eg, length: int, challenge: np.ndar
 
 
 def open_many_sq(be, sq: ScQueue, q: MsmQueue, powers_of_g, pevals: Sequence, lens: Sequence[int], points: Sequence[np.ndarray]):
-    """open_many_q: nothing to exchange -- the values are read when the finishing closure runs"""
+    """several independent opens (dpoly_comm.rs:299-325 each): their fold rounds (:309-323) are added to the batch, the commitments of
+    all q_i are queued; nothing to exchange, so there is no phase B -- the values are read when the finishing closure runs"""
     pts = [np.asarray(pt, dtype=np.uint64).reshape(-1, 4) for pt in points]
     idx = [sq.add(("open", pe, length, pt[: length.bit_length() - 1])) for pe, length, pt in zip(pevals, lens, pts)]
     qbufs = [sq.out_of(i) for i in idx]
@@ -484,9 +401,9 @@ def open_many_sq(be, sq: ScQueue, q: MsmQueue, powers_of_g, pevals: Sequence, le
 
 
 def d_open_many_sq(be, sq: ScQueue, q: MsmQueue, powers_of_g, pevals: Sequence, lens: Sequence[int], points: Sequence[np.ndarray], net: Net):
-    """d_open_many_q in two halves: A = the local opens' kernels and quotient commitments; B = the gather of the local values and, on
-    the leader, the root opens (dpoly_comm.rs:372-378: tables of N_p values -- their fold rounds run on the host, only the quotients
-    go to the device for their commitments); B -> the finishing closure"""
+    """several d_open (dpoly_comm.rs:355-398): A = the local opens' kernels and quotient commitments; B = the gather of the local values
+    and, on the leader, the root opens (:372-378: tables of N_p values -- their fold rounds run on the host, only the quotients go to
+    the device for their commitments); B -> the finishing closure: the exchange of the proofs, root proofs ++ summed local proofs"""
     k = len(lens)
     if not k:
         return lambda: (lambda: [])
@@ -542,34 +459,31 @@ def d_open_many_sq(be, sq: ScQueue, q: MsmQueue, powers_of_g, pevals: Sequence, 
 
 
 def c_open_many_sq(be, sq: ScQueue, q: MsmQueue, powers_of_g, pevals: Sequence, lens: Sequence[int], points: Sequence[np.ndarray], pp: PackedSharingParams, net: Net):
-    """c_open_many_q in two halves: A = the fold rounds; B = the ONE queued d_msm over all quotients (with real parties d_msm_q pre-scales
-    its scalars on the device when it is called, and the quotient buffers are filled by the batch), pss2ss of the last values and the
-    log2(l) extra rounds, whose small MSMs are queued too; B -> the finishing closure"""
+    """several c_open (dpoly_comm.rs:401-464) whose q_i commitments share ONE queued d_msm.  A = the fold rounds (:418-432); B = that
+    d_msm over all quotients (:436; with real parties d_msm_q pre-scales its scalars on the device when it is called, and the quotient
+    buffers are filled by the batch), pss2ss of the last values (:440) and the log2(l) extra rounds, whose small MSMs are queued too;
+    B -> the finishing closure"""
     k = len(lens)
     pts = [np.asarray(p, dtype=np.uint64).reshape(-1, 4) for p in points]
+    # the same table at the same point again (cpermcheck opens num / den twice, dhyperplonk.rs:1324 and :1371) is the same request: its
+    # kernels run once and its MSM items name the same quotient buffers, which the MsmQueue computes once
     keys = [(_addr(pe), length, pt[: length.bit_length() - 1].tobytes()) for pe, length, pt in zip(pevals, lens, pts)]
     seen, idx = {}, []
-    for i, key in enumerate(keys):  # (the same table at the same point again is the same request: see c_open_many_q)
+    for i, key in enumerate(keys):
         if key not in seen:
             seen[key] = sq.add(("open", pevals[i], lens[i], pts[i][: lens[i].bit_length() - 1]))
         idx.append(seen[key])
     qbufs = [sq.out_of(i) for i in idx]
     q0s = _first_quotient_sources(pevals, lens, qbufs)
-    bufs, ms, cuts = [], [], [0]
+    srs, bufs, ms, cuts = [], [], [], [0]
     for qb, length, q0 in zip(qbufs, lens, q0s):
-        n = length.bit_length() - 1
+        s_, b_, l_ = _open_msm_items(powers_of_g, qb, length, q0, pp.l)
+        srs, bufs, ms = srs + s_, bufs + b_, ms + l_
         q.keep.append(qb)
-        off, m = 0, length
-        for r_ in range(n):
-            h = m // 2
-            bufs.append((q0 if r_ == 0 else qb).at(32 * off))
-            ms.append(h)
-            off += h
-            m = h
         cuts.append(len(ms))
 
     def phase_b():
-        f_com = c_commit_q(be, q, powers_of_g, bufs, ms, pp, net) if ms else (lambda: np.zeros((0, 18), dtype=np.uint64))
+        f_com = d_msm_q(be, q, srs, bufs, ms, pp, net)
         tails = []
         for i in range(k):
             cur = _fr_vec_to_ints(pss2ss(sq.at(idx[i])[1], pp, net))
@@ -598,8 +512,9 @@ def c_open_many_sq(be, sq: ScQueue, q: MsmQueue, powers_of_g, pevals: Sequence, 
 
 
 def d_sumcheck_product_many_sq(be, sq: ScQueue, items: Sequence, net: Net):
-    """d_sumcheck_product_many_q with its local phases in the batch: the returned closure (exchange + leader rounds) is called when
-    the transcript is assembled, after ScQueue.run()"""
+    """several independent d_sumcheck_product (dsumcheck.rs:359-512); items = [(partial_f, partial_g, length, challenge)].  Their local
+    phases are added to the batch; -> closure (exchange + leader rounds, _d_sumcheck_leader_rounds), called when the transcript is
+    assembled, after ScQueue.run(): a protocol step calls it after it has started its MSM pass, the host work then runs beside the GPU's"""
     if not len(items):
         return lambda: []
     s = net.n_parties.bit_length() - 1
@@ -615,6 +530,37 @@ def d_sumcheck_product_many_sq(be, sq: ScQueue, items: Sequence, net: Net):
         return _d_sumcheck_leader_rounds(phase1, chals, ns, s, net)
 
     return fin
+
+
+# the per-call forms of the product sumchecks: each a batch of its own, phase B at once
+def sumcheck_product(be, ef, eg, length: int, challenge: np.ndarray) -> np.ndarray:
+    """dsumcheck.rs:28-90 -> [n+1, 3, 4]; last entry (0, f*g, 0)"""
+    return own_batch(be, lambda sq: sumcheck_product_sq(be, sq, ef, eg, length, challenge))()
+
+
+def c_sumcheck_product_many(be, pairs: Sequence, length: int, challenge: np.ndarray, pp: PackedSharingParams, net: Net) -> List[np.ndarray]:
+    """several independent c_sumcheck_product on tables of one length: their phase-1 loops as ONE batched call, then the hand-offs"""
+    return own_batch(be, lambda sq: c_sumcheck_product_many_sq(be, sq, pairs, length, challenge, pp, net))()
+
+
+def c_sumcheck_product(be, shares_f, shares_g, length: int, challenge: np.ndarray, pp: PackedSharingParams, net: Net) -> np.ndarray:
+    """dsumcheck.rs:148-285 -> [n + log2(l) + 1, 3, 4]"""
+    return c_sumcheck_product_many(be, [(shares_f, shares_g)], length, challenge, pp, net)[0]
+
+
+def d_sumcheck_product_many_q(be, items: Sequence, net: Net):
+    """the local phases of several d_sumcheck_product run NOW as one batched call; -> closure: the exchange and the leader part"""
+    return own_batch(be, lambda sq: d_sumcheck_product_many_sq(be, sq, items, net))
+
+
+def d_sumcheck_product_many(be, items: Sequence, net: Net) -> List[np.ndarray]:
+    """several independent d_sumcheck_product (dsumcheck.rs:359-512) at once: the local phases as one batched call, one exchange"""
+    return d_sumcheck_product_many_q(be, items, net)()
+
+
+def d_sumcheck_product(be, partial_f, partial_g, length: int, challenge: np.ndarray, net: Net) -> np.ndarray:
+    """dsumcheck.rs:359-512.  Leader: [n'+s, 3, 4]; workers: empty.  Marker tuple is (g, f, 0) (:433)"""
+    return d_sumcheck_product_many(be, [(partial_f, partial_g, length, challenge)], net)[0]
 
 
 # ---------------------------------------------------------------------------------------
@@ -709,13 +655,14 @@ def _first_quotient_sources(pevals, lens, qbufs):
     return out
 
 
-def _open_msm_items(powers_of_g, q, length: int, q0=None):
-    """the n commitments of one open (:318-321) as MSM items over the quotient buffer q: (srs list, scalar views, lens)"""
+def _open_msm_items(powers_of_g, q, length: int, q0=None, l: int = 1):
+    """the n commitments of one open (:318-321) as MSM items over the quotient buffer q: (srs list, scalar views, lens); l: the packing
+    factor of a c_open, whose h shares are committed on the level of h l points (:256-257)"""
     n = length.bit_length() - 1
     srs, bufs, lens, off, m = [], [], [], 0, length
     for i in range(n):
         h = m // 2
-        srs.append(powers_of_g[h.bit_length() - 1])
+        srs.append(powers_of_g[(h * l).bit_length() - 1])
         bufs.append((q0 if (i == 0 and q0 is not None) else q).at(32 * off))
         lens.append(h)
         off += h
@@ -724,20 +671,8 @@ def _open_msm_items(powers_of_g, q, length: int, q0=None):
 
 
 def open_many_q(be, q: MsmQueue, powers_of_g, pevals: Sequence, lens: Sequence[int], points: Sequence[np.ndarray]):
-    """several independent opens: the fold rounds run now, the commitments of all q_i are queued; -> closure"""
-    vals, cuts = [], []
-    pts = [np.asarray(pt, dtype=np.uint64).reshape(-1, 4) for pt in points]
-    rounds = _sc_batch(be, [("open", pe, length, pt[: length.bit_length() - 1]) for pe, length, pt in zip(pevals, lens, pts)])  # :309-323, all items at once
-    q0s = _first_quotient_sources(pevals, lens, [qb for qb, _ in rounds])
-    for (qb, v), length, q0 in zip(rounds, lens, q0s):
-        s_, b_, l_ = _open_msm_items(powers_of_g, qb, length, q0)
-        vals.append(v)
-        cuts.append(q.add(s_, b_, l_, keep=[qb]))  # the q buffers must outlive the batched MSM
-    def fin():
-        return [(vals[k], q.res[cuts[k]]) for k in range(len(vals))]
-
-    fin.values = vals  # known as soon as the fold rounds ran (before the MSMs)
-    return fin
+    """open_many_sq with the fold rounds run now; -> closure"""
+    return own_batch(be, lambda sq: open_many_sq(be, sq, q, powers_of_g, pevals, lens, points))
 
 
 def open_many(be, powers_of_g, pevals: Sequence, lens: Sequence[int], points: Sequence[np.ndarray]):
@@ -808,45 +743,8 @@ def c_commit(be, powers_of_g, pevals: Sequence, lens: Sequence[int], pp: PackedS
 
 
 def d_open_many_q(be, q: MsmQueue, powers_of_g, pevals: Sequence, lens: Sequence[int], points: Sequence[np.ndarray], net: Net):
-    """
-    several d_open (dpoly_comm.rs:355-398): local fold rounds and the exchange of the local VALUES happen now; the
-    commitments of the local opens and (leader) of the root opens on the gathered values are queued; -> closure
-    """
-    k = len(lens)
-    if not k:
-        return lambda: []
-    plog = net.n_parties.bit_length() - 1
-    pts = [np.asarray(p, dtype=np.uint64).reshape(-1, 4) for p in points]
-    f_local = open_many_q(be, q, powers_of_g, pevals, lens, [p[plog:] for p in pts])
-    # the local values are known once the fold rounds ran: gather them now, queue the root opens with them
-    vals_mine = np.stack([np.asarray(v, dtype=np.uint64).reshape(4) for v in f_local.values])
-    vals = net.all_gather(vals_mine)  # [party][k, 4]
-    f_root = None
-    if net.is_leader:
-        root_tab = be.to_device(np.ascontiguousarray(np.stack([np.asarray(v).reshape(-1, 4) for v in vals], axis=1)))  # [k][party][4]
-        f_root = open_many_q(be, q, powers_of_g, [root_tab.at(32 * net.n_parties * i) for i in range(k)], [net.n_parties] * k, [p[:plog] for p in pts])
-        q.keep.append(root_tab)
-
-    def fin():
-        local = f_local()
-        cuts = [0]
-        for _, prf in local:
-            cuts.append(cuts[-1] + len(prf))
-        prfs = net.all_gather(np.concatenate([prf for _, prf in local]) if cuts[-1] else np.zeros((0, 18), dtype=np.uint64))
-        if not net.is_leader:
-            return [(ZERO.copy(), np.zeros((0, 18), dtype=np.uint64)) for _ in range(k)]
-        ones = np.tile(int_to_limbs(1, 4), (net.n_parties, 1))
-        total = cuts[-1]
-        pi = be.g1_lincomb_batch(np.stack([np.asarray(g).reshape(-1, 18) for g in prfs], axis=1), ones) if total else np.zeros((0, 18), dtype=np.uint64)
-        roots = f_root()
-        out = []
-        for i in range(k):
-            root_val, root_proofs = roots[i]
-            allp = list(root_proofs) + list(pi[cuts[i] : cuts[i + 1]])  # root proofs FIRST (:379-384)
-            out.append((root_val, np.stack(allp) if allp else np.zeros((0, 18), dtype=np.uint64)))
-        return out
-
-    return fin
+    """d_open_many_sq with the local fold rounds, the exchange of the local VALUES and the leader's root opens done now; -> closure"""
+    return own_batch(be, lambda sq: d_open_many_sq(be, sq, q, powers_of_g, pevals, lens, points, net))()
 
 
 def d_open_many(be, powers_of_g, pevals: Sequence, lens: Sequence[int], points: Sequence[np.ndarray], net: Net):
@@ -870,59 +768,8 @@ def d_open(be, powers_of_g, peval, length: int, point: np.ndarray, net: Net):
 
 
 def c_open_many_q(be, q: MsmQueue, powers_of_g, pevals: Sequence, lens: Sequence[int], points: Sequence[np.ndarray], pp: PackedSharingParams, net: Net):
-    """several c_open (dpoly_comm.rs:401-464) whose q_i commitments share ONE queued d_msm; -> closure"""
-    k = len(lens)
-    pts = [np.asarray(p, dtype=np.uint64).reshape(-1, 4) for p in points]
-    vals, bufs, ms, cuts = [], [], [], [0]
-    # the same table at the same point again (cpermcheck opens num / den twice, dhyperplonk.rs:1324 and :1371) is the same request: its
-    # kernels run once and its MSM items name the same quotient buffers, which the MsmQueue computes once
-    keys = [(_addr(pe), length, pt[: length.bit_length() - 1].tobytes()) for pe, length, pt in zip(pevals, lens, pts)]
-    uniq = {}
-    for i, key in enumerate(keys):
-        uniq.setdefault(key, i)
-    order = sorted(set(uniq.values()))
-    rounds_u = _sc_batch(be, [("open", pevals[i], lens[i], pts[i][: lens[i].bit_length() - 1]) for i in order])  # :418-432
-    at = {i: j for j, i in enumerate(order)}
-    rounds = [rounds_u[at[uniq[key]]] for key in keys]
-    q0s = _first_quotient_sources(pevals, lens, [qb for qb, _ in rounds])
-    for (qb, value), length, q0 in zip(rounds, lens, q0s):
-        n = length.bit_length() - 1
-        q.keep.append(qb)
-        vals.append(value)
-        off, m = 0, length
-        for r_ in range(n):
-            h = m // 2
-            bufs.append((q0 if r_ == 0 else qb).at(32 * off))
-            ms.append(h)
-            off += h
-            m = h
-        cuts.append(len(ms))
-    f_com = c_commit_q(be, q, powers_of_g, bufs, ms, pp, net) if ms else (lambda: np.zeros((0, 18), dtype=np.uint64))
-    # phase 2 (:440-462): pss2ss of the last value, log2(l) more rounds on the l-vector; its MSMs are queued too
-    tails = []
-    for i in range(k):
-        cur = _fr_vec_to_ints(pss2ss(vals[i], pp, net))
-        pt = _fr_vec_to_ints(pts[i])
-        fins = []
-        for r in range(pp.l.bit_length() - 1):
-            h = len(cur) // 2
-            qi = [(cur[j + h] - cur[j]) % R_MOD for j in range(h)]
-            level = (len(qi) * pp.l).bit_length() - 1
-            d_qi = be.to_device(_ints_to_fr(qi))
-            sl = q.add([powers_of_g[level]], [d_qi], [len(qi)], keep=[d_qi])
-            fins.append(sl)
-            cur = [(cur[j] * (1 - pt[r]) + cur[j + h] * pt[r]) % R_MOD for j in range(h)]
-        tails.append((fr_mont(cur[0]), fins))
-
-    def fin():
-        com = f_com()
-        out = []
-        for i in range(k):
-            res = list(com[cuts[i] : cuts[i + 1]]) + [q.res[sl][0] for sl in tails[i][1]]
-            out.append((tails[i][0], np.stack(res) if res else np.zeros((0, 18), dtype=np.uint64)))
-        return out
-
-    return fin
+    """c_open_many_sq with the fold rounds and the pss2ss hand-offs done now, the d_msm and the tail's MSMs queued; -> closure"""
+    return own_batch(be, lambda sq: c_open_many_sq(be, sq, q, powers_of_g, pevals, lens, points, pp, net))()
 
 
 def c_open_many(be, powers_of_g, pevals: Sequence, lens: Sequence[int], points: Sequence[np.ndarray], pp: PackedSharingParams, net: Net):

@@ -177,9 +177,20 @@ def _halves(buf, length):
     return buf, _at(buf, 32 * (length // 2))
 
 
-def _done(value):
-    """a phase-B / finishing closure for work that has already run (the batch-per-call forms next to the *_sq ones)"""
-    return lambda: value
+def _stage(be, sq, add, phase_b=True):
+    """
+    Where one primitive's sumcheck-family kernels go.  add(queue) is its dp.*_sq form.  sq = the step's shared dp.ScQueue: the
+    kernels wait for the caller's sq.run(), and what the form returned (its phase B, or its finishing closure where it has none:
+    phase_b=False) is handed back.  sq = None, the batch-per-call schedule: a queue of its own, run at once, phase B right behind it;
+    -> a closure over phase B's result, so the caller reads both schedules the same way.
+    """
+    if sq is not None:
+        return add(sq)
+    out = dp.own_batch(be, add)
+    if not phase_b:
+        return out
+    res = out()
+    return lambda: res
 
 
 def _at(buf, byte_off):
@@ -202,12 +213,12 @@ def _wiring_enqueue(n, pk, pp, be, net, seed, data_parallel, local_s_p, local_s_
     the step up to (not including) its one batched MSM pass.  -> (queue, phase_b); finalize = phase_b(); run (or start / finish) the
     queue, then finalize() performs the exchanges of the MSM results and returns (wiring_proofs, wiring_commits, wiring_opens) in the
     reference's order.
-    sq = None: every sumcheck / fold / open-round kernel runs inside the call that owns it (a blocking batch per call), phase_b()
-    has nothing left to do.  sq = a dp.ScQueue (the mirror of zkhost/hyperplonk.hpp wiring_enqueue_sq): the calls only ADD their
-    kernels; the caller runs the batch, and phase_b() performs the exchanges that need a kernel result (pss2ss of 2.c and of the
-    opens of V, the gather of the local open values, the leader's root opens).  Same outputs.
+    sq = a dp.ScQueue (the mirror of zkhost/hyperplonk.hpp wiring_enqueue): the primitives only ADD their kernels; the caller runs the
+    batch, and phase_b() performs the exchanges that need a kernel result (pss2ss of 2.c and of the opens of V, the gather of the
+    local open values, the leader's root opens).  sq = None: every primitive's kernels are a batch of their own with its phase B right
+    behind it (_stage), phase_b() has nothing left to do.  Same outputs.
     """
-    one = sq is not None
+    stage = lambda add, phase_b=True: _stage(be, sq, add, phase_b)
     T, L = pk.tables, pk.lens
     l, npar = pp.l, net.n_parties
     M = 1 << n
@@ -234,13 +245,9 @@ def _wiring_enqueue(n, pk, pp, be, net, seed, data_parallel, local_s_p, local_s_
     # every MSM of the step is queued and runs in ONE batched pass at its end (dp.MsmQueue); the closures below put
     # the results at the reference's positions.  Exchanges keep the reference's order on every party.
     q = dp.MsmQueue(be)
-    if one:
-        a_2c = dp.c_sumcheck_product_many_sq(be, sq, [(s_dev, T["V"])], 4 * M // l, pk.challenge_r1, pp, net)  # 2.c
-        a_copen = dp.c_open_many_sq(be, sq, q, cc, [T["V"], T["V"]], [4 * M // l] * 2, [pk.challenge_r1, pk.challenge_r2], pp, net)  # 2.d
-    else:
-        a_2c = _done([dp.c_sumcheck_product(be, s_dev, T["V"], 4 * M // l, pk.challenge_r1, pp, net)])  # 2.c
-        # 2.d: the two opens of V are independent -> their q_i commitments share one d_msm
-        a_copen = _done(dp.c_open_many_q(be, q, cc, [T["V"], T["V"]], [4 * M // l] * 2, [pk.challenge_r1, pk.challenge_r2], pp, net))
+    a_2c = stage(lambda s: dp.c_sumcheck_product_many_sq(be, s, [(s_dev, T["V"])], 4 * M // l, pk.challenge_r1, pp, net))  # 2.c
+    # 2.d: the two opens of V are independent -> their q_i commitments share one d_msm
+    a_copen = stage(lambda s: dp.c_open_many_sq(be, s, q, cc, [T["V"], T["V"]], [4 * M // l] * 2, [pk.challenge_r1, pk.challenge_r2], pp, net))
     # 2.e (:322-340)
     hlen = 4 * M // npar
     num = be.fr_axpb(local_s_p, T["sid_p"], pk.alpha, pk.beta, hlen)
@@ -273,9 +280,9 @@ def _wiring_enqueue(n, pk, pp, be, net, seed, data_parallel, local_s_p, local_s_
             cur[k] = _at(cur[k], 32 * (clen // 2))
         clen //= 2
     # (local phases now; the exchange and the leader rounds -- host arithmetic -- in finalize(), beside the step's MSM pass)
-    f_dsp = dp.d_sumcheck_product_many_sq(be, sq, dsp_items, net) if one else dp.d_sumcheck_product_many_q(be, dsp_items, net)
+    f_dsp = stage(lambda s: dp.d_sumcheck_product_many_sq(be, s, dsp_items, net), phase_b=False)
     # the opens of local_s, of the five tables and of all layers are independent of each other
-    a_dopen = dp.d_open_many_sq(be, sq, q, dc, lay_tabs, lay_lens, lay_pts, net) if one else _done(dp.d_open_many_q(be, q, dc, lay_tabs, lay_lens, lay_pts, net))
+    a_dopen = stage(lambda s: dp.d_open_many_sq(be, s, q, dc, lay_tabs, lay_lens, lay_pts, net))
     f_top_commits, f_top_opens, top_proofs = [], None, []
     if top is not None:  # leader-only tail on the N_p-leaf top tree (:480-511)
         tt = np.asarray(top, dtype=np.uint64).reshape(-1, 4)
@@ -284,12 +291,11 @@ def _wiring_enqueue(n, pk, pp, be, net, seed, data_parallel, local_s_p, local_s_
         chs = pk.challenge_r2[:sbits]
         dv = [be.to_device(np.ascontiguousarray(v)) for v in (lvx0, lvx1, lv1x)]
         f_top_commits = [dp.commit_q(q, dc, d, len(v)) for d, v in zip(dv, (lvx0, lvx1, lv1x))]
-        f_top_opens = (dp.open_many_sq(be, sq, q, dc, dv, [len(lvx0), len(lvx1), len(lv1x)], [chs] * 3) if one
-                       else dp.open_many_q(be, q, dc, dv, [len(lvx0), len(lvx1), len(lv1x)], [chs] * 3))
+        f_top_opens = stage(lambda s: dp.open_many_sq(be, s, q, dc, dv, [len(lvx0), len(lvx1), len(lv1x)], [chs] * 3), phase_b=False)
         q.keep += dv
         d0, dd1, d1 = dv
         for f_, g_, m_ in ((eq_top, d1, len(lv1x)), (eq_top, d0, len(lvx0)), (d0, dd1, len(lvx0))):
-            top_proofs.append(dp.sumcheck_product_sq(be, sq, f_, g_, m_, chs) if one else _done(dp.sumcheck_product(be, f_, g_, m_, chs)))
+            top_proofs.append(stage(lambda s: dp.sumcheck_product_sq(be, s, f_, g_, m_, chs), phase_b=False))
 
     def phase_b():
         wiring_proofs.extend(a_2c())  # (one batch: pss2ss of 2.c)
@@ -363,53 +369,33 @@ def dhyperplonk(n: int, pk: PackedProvingParameters, pp: PackedSharingParams, be
     sum_ab = be.fr_add(T["a_evals"], T["b_evals"], Ml)  # :233-238
     sum_ci = be.fr_sub(T["I"], T["c_evals"], Ml)  # -c + I  :251-256
     gate_pairs = [(T["eq"], T["S1"]), (T["S1"], sum_ab), (T["eq"], T["S2"]), (T["a_evals"], T["b_evals"]), (T["S2"], T["a_evals"]), (T["eq"], sum_ci)]
-    if ONE_BATCH and dp.PIPELINE_MSM:
-        # The sumcheck-family kernels of steps 2-4 as ONE batch (dp.ScQueue; zkhost/hyperplonk.hpp does the same): the six gate
-        # sumchecks, everything of the wiring step, the fold rounds of the Open step.  None needs another's result on the device; as
-        # ~10 blocking calls they were launch chains on a nearly empty chip.  Phase B of every primitive (the exchanges that need a
-        # kernel result) follows in the reference's order; then the two long MSM passes start.
-        sq = dp.ScQueue(be)
-        a_gate = dp.c_sumcheck_product_many_sq(be, sq, gate_pairs, Ml, pk.challenge, pp, net)
-        tm.end()
-        tm.start("Wire identity")
-        q_w, b_wiring = _wiring_enqueue(n, pk, pp, be, net, seed, data_parallel, local_s_p, local_s_l, eq_top, sq)
-        q_o = dp.MsmQueue(be)
-        a_co = dp.c_open_many_sq(be, sq, q_o, cc, [T[x] for x in names_c], [L[x] for x in names_c], [pk.challenge] * 3, pp, net)
-        a_do = dp.d_open_many_sq(be, sq, q_o, dc, [T[x] for x in names_d], [L[x] for x in names_d], [pk.challenge] * 3, net)
-        sq.run()
-        if late:
-            q.start()
-        gate_proofs = a_gate()
-        finalize_wiring = b_wiring()
-        f_co, f_do = a_co(), a_do()
-        q_w.start()
-        q_o.start()
-        finish_commit()
-        tm.end()
-        tm.start("Open")
-        q_w.finish()
-        wiring_proofs, wiring_commits, wiring_opens = finalize_wiring()
-        q_o.finish()
-        gate_commitments = [(com[name], op) for name, op in zip(names_c + names_d, list(f_co()) + list(f_do()))]
-        tm.end()
-        tm.end()
-        return ((gate_proofs, gate_commitments), (wiring_proofs, wiring_commits, wiring_opens)), tm.t
-    # the six sumchecks are independent: one batched phase 1, then the hand-offs in the reference's order
-    gate_proofs = dp.c_sumcheck_product_many(be, gate_pairs, Ml, pk.challenge, pp, net)
+    # The sumcheck-family kernels of steps 2-4 as ONE batch (dp.ScQueue; zkhost/hyperplonk.hpp does the same): the six gate
+    # sumchecks, everything of the wiring step, the fold rounds of the Open step.  None needs another's result on the device; as
+    # ~10 blocking calls they were launch chains on a nearly empty chip.  Phase B of every primitive (the exchanges that need a
+    # kernel result) follows in the reference's order; then the two long MSM passes start.  Without the shared queue (ONE_BATCH =
+    # False, and the serial-steps form PIPELINE_MSM = False) every primitive is a batch of its own with its phase B behind it (_stage).
+    sq = dp.ScQueue(be) if ONE_BATCH and dp.PIPELINE_MSM else None
+    stage = lambda add: _stage(be, sq, add)
+    a_gate = stage(lambda s: dp.c_sumcheck_product_many_sq(be, s, gate_pairs, Ml, pk.challenge, pp, net))
     tm.end()
 
     # Step 2: wiring identity (shared with dpermcheck)
     tm.start("Wire identity")
-    q_w, b_wiring = _wiring_enqueue(n, pk, pp, be, net, seed, data_parallel, local_s_p, local_s_l, eq_top)
-    finalize_wiring = b_wiring()
+    q_w, b_wiring = _wiring_enqueue(n, pk, pp, be, net, seed, data_parallel, local_s_p, local_s_l, eq_top, sq)
     # The kernel phase of the Open step (:517-553: fold rounds and quotients of a, b, c, I, S1, S2) depends on nothing the wiring step
     # produces, so it runs BEFORE the wiring pass is started: behind a running pass its ~0.5 ms of kernels would wait for the pass to
     # drain (they share the runtime's hardware queues), the Open pass could only be enqueued after that, and the GPU would idle between
-    # the two passes while the host prepares the second.  Both passes are now in flight back to back; outputs keep their positions.
-    gate_commitments = []
+    # the two passes while the host prepares the second.  Both passes are then in flight back to back; outputs keep their positions.
     q_o = dp.MsmQueue(be)
-    f_co = dp.c_open_many_q(be, q_o, cc, [T[x] for x in names_c], [L[x] for x in names_c], [pk.challenge] * 3, pp, net)
-    f_do = dp.d_open_many_q(be, q_o, dc, [T[x] for x in names_d], [L[x] for x in names_d], [pk.challenge] * 3, net)
+    a_co = stage(lambda s: dp.c_open_many_sq(be, s, q_o, cc, [T[x] for x in names_c], [L[x] for x in names_c], [pk.challenge] * 3, pp, net))
+    a_do = stage(lambda s: dp.d_open_many_sq(be, s, q_o, dc, [T[x] for x in names_d], [L[x] for x in names_d], [pk.challenge] * 3, net))
+    if sq is not None:
+        sq.run()
+    if late:
+        q.start()
+    gate_proofs = a_gate()
+    finalize_wiring = b_wiring()
+    f_co, f_do = a_co(), a_do()
     q_w.start()
     q_o.start()
     finish_commit()  # (host: exchange + point combinations of step 1, beside the passes on the GPU)
@@ -420,10 +406,7 @@ def dhyperplonk(n: int, pk: PackedProvingParameters, pp: PackedSharingParams, be
     q_w.finish()
     wiring_proofs, wiring_commits, wiring_opens = finalize_wiring()
     q_o.finish()
-    for name, op in zip(names_c, f_co()):
-        gate_commitments.append((com[name], op))
-    for name, op in zip(names_d, f_do()):
-        gate_commitments.append((com[name], op))
+    gate_commitments = [(com[name], op) for name, op in zip(names_c + names_d, list(f_co()) + list(f_do()))]
     tm.end()
     tm.end()
     return ((gate_proofs, gate_commitments), (wiring_proofs, wiring_commits, wiring_opens)), tm.t

@@ -539,6 +539,33 @@ def test_cpp_cpermcheck_pipelined_equals_the_call_by_call_form():
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("args,parties", [
+    (["--l", "1", "--n", "10"], 1),                                       # leader: no root opens
+    (["--l", "1", "--n", "8", "--mode", "threads"], 8),                   # 8 parties: root opens, pss2ss and the top tree all run
+    (["--l", "1", "--n", "8", "--which", "data-parallel"], 0),            # (digest only)
+    (["--l", "1", "--n", "8", "--mode", "threads", "--which", "dpermcheck"], 0),
+])
+def test_cpp_one_batch_schedule_equals_the_batch_per_call_form(args, parties):
+    """ZKHOST_ONE_BATCH=0 gives every primitive's sumcheck-family kernels a batch of their own (the same *_sq forms on private queues),
+    and --serial-rep adds the serial-steps schedule: every printed digest is the same one, every party's self-check passes, and the
+    Comm totals of the two settings are equal"""
+    seen = []
+    for one in ("1", "0"):
+        r = subprocess.run([_example()] + args + ["--reps", "1", "--digest", "--serial-rep"] + (["--check"] if parties else []), capture_output=True, text=True,
+                           timeout=900, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", ZKHOST_ONE_BATCH=one))
+        assert r.returncode == 0, r.stdout[-2500:] + r.stderr[-1500:]
+        digests = [l.split()[-1] for l in r.stdout.splitlines() if l.startswith("transcript sha256")]
+        assert len(digests) == (1 if "dpermcheck" in args else 2) and len(set(digests)) == 1, digests  # the timed rep and the serial-steps rep
+        if parties:
+            lines = _check_lines(r)
+            assert len(lines) == parties and all(" ok -- anchored" in l for l in lines), r.stdout[-2500:]
+        comms = [l for l in r.stdout.splitlines() if l.startswith("Comm:")]
+        assert len(comms) == 1
+        seen.append((digests[0], comms[0]))
+    assert seen[0] == seen[1], (args, seen)
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("args", [["--l", "1", "--n", "12"], ["--l", "1", "--n", "10", "--mode", "threads"]])
 def test_cpp_example_rejects_a_flipped_limb(args):
     """--tamper: one limb of one t2 of the transcript under test is flipped; the self-check must fail (exit code 3) on every party"""

@@ -354,3 +354,105 @@ def test_sumcheck_product_many_forms_equal_the_single_calls():
         exp = po.c_sumcheck_product_all(cf, cg[k], cch, opp)
         for p in range(W):
             assert [tuple(ints(t)) for t in res[p][2][k]] == exp[p]
+
+
+# ---------------------------------------------------------------------------------------
+# the per-call forms are the *_sq forms on a queue of their own: add, run(), phase B
+# ---------------------------------------------------------------------------------------
+def _same(a, b):
+    if isinstance(a, (list, tuple)):
+        return isinstance(b, (list, tuple)) and len(a) == len(b) and all(_same(x, y) for x, y in zip(a, b))
+    a, b = np.asarray(a), np.asarray(b)
+    return a.shape == b.shape and bool((a == b).all())
+
+
+def _trace_key(trace):
+    return [(kind, int(length), np.asarray(ch, dtype=np.uint64).tobytes()) for kind, _f, _g, length, ch in trace]
+
+
+def _per_call_and_by_hand(name, be, net, pp, rng_seed):
+    """-> (per-call output, by-hand output, MSM items of the per-call form, of the by-hand form); both forms on the same tables"""
+    rng = po.SplitMix64(rng_seed + net.party_id)
+    dev = lambda m: be.to_device(to_m(rng.fr_vec(m)))
+    s = net.n_parties.bit_length() - 1
+    f16, g16, f8, g8 = dev(16), dev(16), dev(8), dev(8)
+    ch = to_m(po.SplitMix64(rng_seed).fr_vec(4 + s + 2))  # public: the same on every party
+    cpg = dp.PolynomialCommitmentCub.new_single(be, 5, pp, seed=7).powers_of_g
+    dpg = dp.PolynomialCommitmentCub.new_random(be, 4 + s, net.n_parties, seed=8).powers_of_g
+    sq, q, q2 = dp.ScQueue(be), dp.MsmQueue(be), dp.MsmQueue(be)
+
+    def with_msm(queue, fin):
+        items = len(queue.lens)
+        queue.run()
+        return fin(), items
+
+    if name == "sumcheck_product":
+        got = dp.sumcheck_product(be, f16, g16, 16, ch), 0
+        fin = dp.sumcheck_product_sq(be, sq, f16, g16, 16, ch)
+        sq.run()
+        exp = fin(), 0
+    elif name == "c_sumcheck_product_many":
+        pairs = [(f16, g16), (g16, f16)]
+        got = dp.c_sumcheck_product_many(be, pairs, 16, ch, pp, net), 0
+        b = dp.c_sumcheck_product_many_sq(be, sq, pairs, 16, ch, pp, net)
+        sq.run()
+        exp = b(), 0
+    elif name == "d_sumcheck_product_many_q":
+        items = [(f16, g16, 16, ch), (f8, g8, 8, ch[1:])]
+        got = dp.d_sumcheck_product_many_q(be, items, net)(), 0
+        fin = dp.d_sumcheck_product_many_sq(be, sq, items, net)
+        sq.run()
+        exp = fin(), 0
+    elif name == "open_many_q":
+        args = (dpg, [f16, f8, f16], [16, 8, 16], [ch, ch, ch[2:]])  # the same table at two points: one first quotient
+        got = with_msm(q, dp.open_many_q(be, q, *args))
+        fin = dp.open_many_sq(be, sq, q2, *args)
+        sq.run()
+        exp = with_msm(q2, fin)
+    elif name == "d_open_many_q":
+        args = (dpg, [f16, f8], [16, 8], [ch, ch[1:]], net)
+        got = with_msm(q, dp.d_open_many_q(be, q, *args))
+        b = dp.d_open_many_sq(be, sq, q2, *args)
+        sq.run()
+        exp = with_msm(q2, b())
+    else:  # c_open_many_q; "twice": the same table at the same point again
+        tabs, lens = ([f16, f8, f16], [16, 8, 16]) if name.endswith("twice") else ([f16, f8], [16, 8])
+        args = (cpg, tabs, lens, [ch] * len(tabs), pp, net)
+        got = with_msm(q, dp.c_open_many_q(be, q, *args))
+        b = dp.c_open_many_sq(be, sq, q2, *args)
+        sq.run()
+        exp = with_msm(q2, b())
+    return got, exp
+
+
+@pytest.mark.parametrize("name", ["sumcheck_product", "c_sumcheck_product_many", "d_sumcheck_product_many_q", "open_many_q", "d_open_many_q",
+                                  "c_open_many_q", "c_open_many_q twice"])
+def test_per_call_forms_equal_the_queued_forms_run_by_hand(name, monkeypatch):
+    """Every per-call form against the same call made by hand on a fresh ScQueue: the *_sq form, run(), phase B.  Same outputs, the
+    same sc_trace records (kinds, lengths, challenge slices, once per request), the same MSM items.  l = 2; the d_ and plain forms
+    run on 8 party threads, the c_ forms on the 8 l = 16 parties a packed sharing at l = 2 has."""
+    pp = PackedSharingParams(2)
+    batches = []  # the open requests of every kernel batch, all parties
+    real = dp._sc_batch
+    monkeypatch.setattr(dp, "_sc_batch", lambda be, reqs: (batches.append((be, sum(r[0] == "open" for r in reqs))), real(be, reqs))[1])
+
+    def party(net):
+        be = OracleBackend()
+        be.sc_trace = []
+        got, exp = _per_call_and_by_hand(name, be, net, pp, 5100)
+        half = len(be.sc_trace) // 2
+        opens = [n for b, n in batches if b is be and n]
+        return got, exp, _trace_key(be.sc_trace[:half]), _trace_key(be.sc_trace[half:]), opens
+
+    res = LocalTestNet.simulate_network_round(pp.n if name.startswith("c_") else 8, party)
+    for p, (got, exp, trace_got, trace_exp, opens) in enumerate(res):
+        assert _same(got[0], exp[0]), f"party {p}: outputs"
+        assert got[1] == exp[1], f"party {p}: MSM items"
+        assert trace_got == trace_exp, f"party {p}: sc_trace"
+        if "sumcheck" in name:
+            n_req = {"sumcheck_product": 1, "c_sumcheck_product_many": 2, "d_sumcheck_product_many_q": 2}[name]
+            assert len(trace_got) == n_req and {k for k, _, _ in trace_got} == {{"s": "plain", "c": "c", "d": "d"}[name[0]]}
+        if name == "c_open_many_q twice":
+            # one request and one set of MSM items for the repeated open: 4 + 3 quotient commitments, and log2(l) = 1 tail item per opening
+            assert opens == [2, 2] and got[1] == (4 + 3) + 3
+            assert _same(got[0][0], got[0][2])
