@@ -667,6 +667,39 @@ int zk_g1_decompress_check(zk_ctx *ctx, size_t count, const void *h_in48, uint64
  * in zk_pcs_verify_batch).  The curve equation is checked as Y^2 == X^3 + 4 Z^6: no inversion. */
 int zk_g1_check(zk_ctx *ctx, size_t count, const uint64_t *h_points18, uint8_t *h_status);
 
+/* ---- aggregated PCS verification: many openings, one pairing check (csrc/zk_g1seg.hip, csrc/zk_pairing.hip) ----------------------
+ * The G2 arguments of PolynomialCommitment::verify are the fixed keys g2, s_0 g2, ..., so any number of openings of mixed variable
+ * counts folds into one product of n_g2 pairings with one final exponentiation.  With weights rho_k:
+ *     L   = sum_k rho_k ( sum_j e_kj C_kj  -  v_k g1  +  sum_i u_ki pi_ki )
+ *     M_j = sum_{k uses key j} rho_k pi_{k, j-1-skip_k}                           j = 1 .. n_g2 - 1
+ *     accept  <=>  e(L, g2) prod_j e(-M_j, powers_g2[j]) == 1.
+ * The aggregate accepts when every opening holds; when one fails it rejects except with probability about count / 2^128. */
+/* out[s] = sum over t in [h_start[s], h_start[s+1]) of k_t * P_t, entirely on the device (h_start: segments + 1 non-decreasing
+ * offsets from 0).  h_points18: Jacobian, Montgomery, any representative, Z = 0 is infinity (as zk_g1_check); h_scalars: CANONICAL
+ * 4 x u64 (as zk_g1_lincomb); h_out18: normalised Jacobian, (1,1,0) for infinity and for an empty segment (what zk_msm_g1 returns).
+ * A term that is not canonical or not on the curve: ZK_ERR_INVALID naming the smallest such term; nothing else is returned.
+ * One lane per term (a double-and-add over the bit length of the call's largest scalar, complete additions), a tree in LDS per
+ * workgroup of 256 terms, a second launch for segments longer than that; one synchronisation of the ctx stream. */
+int zk_g1_lincomb_seg(zk_ctx *ctx, size_t segments, const size_t *h_start, const uint64_t *h_points18, const uint64_t *h_scalars,
+                      uint64_t *h_out18);
+/* h_ok[0] = 1 iff the aggregate equation above holds.  Opening k: nvars_k variables, proof point i pairs with
+ * powers_g2[1 + skip_k + i] (1 + skip_k + nvars_k <= n_g2, else ZK_ERR_INVALID); its commitment is sum_j e_kj C_kj over terms
+ * [h_cstart[k], h_cstart[k+1]) (one term with e = 1 is a plain commitment).  Values, points, e: Fr Montgomery as in
+ * zk_pcs_verify_batch; proofs / points are the openings' rows one after another.  h_rho: count x 2 u64 (128-bit weights), or NULL:
+ * derived by zk_pcs_agg_weights.  count = 0: h_ok[0] = 1, nothing launched.  Points are checked as in zk_pcs_verify_batch (canonical,
+ * on the curve; not the subgroup).  One zk_g1_lincomb_seg call and one pairing call: two synchronisations of the ctx stream. */
+int zk_pcs_verify_agg(zk_ctx *ctx, const zk_pcs_vk *vk, size_t count, const size_t *h_nvars, const size_t *h_skip,
+                      const size_t *h_cstart, const uint64_t *h_cpoints18, const uint64_t *h_cscalars, const uint64_t *h_values,
+                      const uint64_t *h_proofs18, const uint64_t *h_points, const uint64_t *h_rho, uint8_t *h_ok);
+/* host only, no ctx: the derived weights (Fiat-Shamir over the batch, deterministic).
+ *   seed  = SHA-256("zkhip-pcs-agg-v1" || u64le(count) || for each k: u64le(nvars_k) || u64le(skip_k) || u64le(J_k) || its commitment
+ *           points || its commitment scalars || value || proof points || point),  every array as the little-endian words given;
+ *   rho_k = the first 16 bytes of SHA-256(seed || u64le(k)) as two little-endian u64.
+ * ZK_ERR_INVALID: a null array that is read, or commitment offsets that do not start at 0 or decrease. */
+int zk_pcs_agg_weights(size_t count, const size_t *h_nvars, const size_t *h_skip, const size_t *h_cstart,
+                       const uint64_t *h_cpoints18, const uint64_t *h_cscalars, const uint64_t *h_values, const uint64_t *h_proofs18,
+                       const uint64_t *h_points, uint64_t *h_rho);
+
 /* (the zk_dbg_* test hooks of the library are declared in include/zkhip_test.h: they are not part of this surface) */
 
 #ifdef __cplusplus

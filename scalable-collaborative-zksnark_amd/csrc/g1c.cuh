@@ -1,0 +1,105 @@
+// g1c.cuh -- what the one-lane-per-point G1 kernels share (zk_g1check.hip: validation; zk_g1seg.hip: segmented linear combination):
+// the curve constant, the canonical-coordinate tests and the complete XYZZ doubling / addition with the doubling inlined.
+#pragma once
+#include "curve30.cuh"
+
+namespace zk {
+
+namespace g1c {
+__host__ __device__ constexpr u32 FOUR(int i) {  // 4 (the curve's b), internal form
+    constexpr u32 t[13] = {0x0347fcb8u, 0x27600000u, 0x12002b11u, 0x3803379bu, 0x090c7212u, 0x1a7e0e88u, 0x373e0376u, 0x26d0b683u, 0x17bb09b0u, 0x17663c4au, 0x12ca7c51u, 0x167f3e80u, 0x000577a6u};
+    return t[i];
+}
+enum : unsigned char { kOk = 0, kBadEncoding = 1, kNotOnCurve = 2, kNotInG1 = 3 };
+}  // namespace g1c
+
+#define ZK_G1C_CONST(name, T)                                    \
+    __device__ __forceinline__ Fq30 name() {                     \
+        Fq30 r;                                                  \
+        _Pragma("unroll") for (int i = 0; i < 13; i++) r.l[i] = T(i); \
+        return r;                                                \
+    }
+ZK_G1C_CONST(g1c_four, g1c::FOUR)
+
+// v < q for a normalised v < 2^384
+__device__ __forceinline__ bool g1c_lt_q(const Fq30& v) {
+    u32 bw = 0;
+#pragma unroll
+    for (int i = 0; i < 13; i++) bw = (v.l[i] - Q30::Q(i) - bw) >> 31;
+    return bw != 0;
+}
+__device__ __forceinline__ bool g1c_same(const Fq30& a, const Fq30& b) {  // canonical operands
+    u32 o = 0;
+#pragma unroll
+    for (int i = 0; i < 13; i++) o |= a.l[i] ^ b.l[i];
+    return o == 0;
+}
+
+// 2p (dbl-2008-s-1, a = 0) and a + b below: the formulas of xyzz30_dbl / xyzz30_add of curve30.cuh, inlined.  There the doubling is a rare
+// path behind a call (__noinline__); here it IS the hot path.  k_g1_subgroup built on the curve30.cuh pair takes 255 VGPRs + 105 AGPRs
+// and 640 bytes of scratch per lane (the call's stack frame); with these two it takes 256 + 21 and none.  A change of either
+// formula must be made in both files; tests/test_gpu_g1check.py (this copy) and tests/test_gpu_xyzz.py (that one) check each against a model.
+__device__ __forceinline__ Xyzz30 g1c_dbl(const Xyzz30& p) {
+    if (xyzz30_is_inf(p)) return p;
+    Xyzz30 r;
+    const Fq30 U = f30_add(p.y, p.y);               // < 8q
+    const Fq30 V = f30_sqr(U);
+    const Fq30 W = f30_mul(U, V);
+    const Fq30 S = f30_mul(p.x, V);                 // 8q * 2q
+    const Fq30 xx = f30_sqr(p.x);                   // 64 q^2
+    const Fq30 M = f30_add(f30_add(xx, xx), xx);    // < 6q
+    const Fq30 X3 = f30_sub4(f30_sqr(M), f30_add(S, S));  // < 6q
+    r.y = f30_sub2(f30_mul(M, f30_sub8(S, X3)), f30_mul(W, p.y));  // < 4q
+    r.x = X3;
+    r.zz = f30_mul(V, p.zz);
+    r.zzz = f30_mul(W, p.zzz);
+    return r;
+}
+// a + b (add-2008-s), complete: xyzz30_add of curve30.cuh with the doubling inlined
+__device__ __forceinline__ Xyzz30 g1c_add(const Xyzz30& a, const Xyzz30& b) {
+    if (xyzz30_is_inf(a)) return b;
+    if (xyzz30_is_inf(b)) return a;
+    const Fq30 U1 = f30_mul(a.x, b.zz);       // 8q * 2q
+    const Fq30 U2 = f30_mul(b.x, a.zz);
+    const Fq30 S1 = f30_mul(a.y, b.zzz);      // 4q * 2q
+    const Fq30 S2 = f30_mul(b.y, a.zzz);
+    const Fq30 P = f30_sub2(U2, U1);          // < 4q
+    const Fq30 R = f30_sub2(S2, S1);          // < 4q
+    const Fq30 PP = f30_sqr(P);
+    const Fq30 PPP = f30_mul(P, PP);
+    const Fq30 Q = f30_mul(U1, PP);
+    const Fq30 ZZ3 = f30_mul(f30_mul(a.zz, b.zz), PP);
+    Xyzz30 r;
+    if (f30_is_zero_2q(ZZ3)) {  // same x: the same point or its opposite
+        if (f30_all_zero(f30_canon8(R))) r = g1c_dbl(a);
+        else xyzz30_set_inf(r);
+        return r;
+    }
+    r.x = f30_sub6(f30_sqr(R), f30_add2x(PPP, Q));                          // < 8q
+    r.y = f30_mul2add(R, f30_sub8(Q, r.x), f30_sub2(f30_zero(), S1), PPP);  // 4q*10q + 2q*2q -> < 2q
+    r.zz = ZZ3;
+    r.zzz = f30_mul(f30_mul(a.zzz, b.zzz), PPP);
+    return r;
+}
+
+// One 18-word Jacobian record (X, Y, Z), reference Montgomery form, any representative, as XYZZ: canonical coordinates and
+// Y^2 == X^3 + 4 Z^6 (no inversion).  Z = 0 is infinity whatever X and Y are.  Returns the status; p is set for g1c::kOk only.
+__device__ __forceinline__ unsigned char g1c_load_jac(const void* in18, size_t i, Xyzz30& p) {
+    const Fq30 xr = f30_load(in18, i * 144), yr = f30_load(in18, i * 144 + 48), zr = f30_load(in18, i * 144 + 96);
+    if (!g1c_lt_q(xr) || !g1c_lt_q(yr) || !g1c_lt_q(zr)) return g1c::kBadEncoding;
+    if (f30_all_zero(zr)) {
+        xyzz30_set_inf(p);
+        return g1c::kOk;
+    }
+    const Fq30 X = f30_from_ref(xr), Y = f30_from_ref(yr), Z = f30_from_ref(zr);  // canonical
+    const Fq30 ZZ = f30_sqr(Z), ZZZ = f30_mul(ZZ, Z);                            // < 2q
+    const Fq30 rhs = f30_mul2add(f30_sqr(X), X, f30_sqr(ZZZ), g1c_four());
+    if (!g1c_same(f30_canon8(f30_sqr(Y)), f30_canon8(rhs))) return g1c::kNotOnCurve;
+    p.x = X;  // (X, Y, Z^2, Z^3) is the XYZZ form of the same point
+    p.y = Y;
+    p.zz = ZZ;
+    p.zzz = ZZZ;
+    return g1c::kOk;
+}
+
+}  // namespace zk

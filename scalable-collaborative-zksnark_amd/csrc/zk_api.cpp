@@ -760,6 +760,25 @@ int zk_g1_check(zk_ctx* ctx, size_t count, const uint64_t* h_points18, uint8_t* 
     NEED(ctx, count == 0 || (h_points18 && h_status));
     return g1_check(ctx, count, h_points18, h_status);
 }
+int zk_g1_lincomb_seg(zk_ctx* ctx, size_t segments, const size_t* h_start, const uint64_t* h_points18, const uint64_t* h_scalars, uint64_t* h_out18) {
+    NEED(ctx, segments == 0 || (h_start && h_out18));
+    return g1_lincomb_seg(ctx, segments, h_start, h_points18, h_scalars, h_out18);
+}
+int zk_pcs_verify_agg(zk_ctx* ctx, const zk_pcs_vk* vk, size_t count, const size_t* h_nvars, const size_t* h_skip, const size_t* h_cstart,
+                      const uint64_t* h_cpoints18, const uint64_t* h_cscalars, const uint64_t* h_values, const uint64_t* h_proofs18,
+                      const uint64_t* h_points, const uint64_t* h_rho, uint8_t* h_ok) {
+    NEED(ctx, vk && h_ok && (count == 0 || (h_nvars && h_skip && h_cstart && h_values)));
+    return pcs_verify_agg(ctx, vk, count, h_nvars, h_skip, h_cstart, h_cpoints18, h_cscalars, h_values, h_proofs18, h_points, h_rho, h_ok);
+}
+int zk_pcs_agg_weights(size_t count, const size_t* h_nvars, const size_t* h_skip, const size_t* h_cstart, const uint64_t* h_cpoints18,
+                       const uint64_t* h_cscalars, const uint64_t* h_values, const uint64_t* h_proofs18, const uint64_t* h_points, uint64_t* h_rho) {
+    if (count == 0) return ZK_OK;
+    if (!h_nvars || !h_skip || !h_cstart || !h_values || !h_rho) return ZK_ERR_INVALID;
+    size_t rows = 0;
+    for (size_t k = 0; k < count; k++) rows += h_nvars[k];
+    if ((h_cstart[count] && (!h_cpoints18 || !h_cscalars)) || (rows && (!h_proofs18 || !h_points))) return ZK_ERR_INVALID;
+    return pcs_agg_weights(count, h_nvars, h_skip, h_cstart, h_cpoints18, h_cscalars, h_values, h_proofs18, h_points, h_rho);
+}
 int zk_msm_window(size_t n) { return msm_pick_window(n); }
 int zk_msm_set_window(zk_ctx* ctx, int c) {
     if (!ctx || c < 0 || c > 20) return ZK_ERR_INVALID;

@@ -354,9 +354,18 @@ int pcs_vk_create(zk_ctx* ctx, const void* h_g1_96, const void* h_powers_g2, siz
 void pcs_vk_free(zk_pcs_vk* vk);
 int pcs_verify_batch(zk_ctx* ctx, const zk_pcs_vk* vk, size_t nvars, size_t count, const uint64_t* h_comm, const uint64_t* h_values,
                      const uint64_t* h_proofs, const uint64_t* h_points, uint8_t* h_ok);
+int pcs_agg_weights(size_t count, const size_t* h_nvars, const size_t* h_skip, const size_t* h_cstart, const uint64_t* h_cpoints18,
+                    const uint64_t* h_cscalars, const uint64_t* h_values, const uint64_t* h_proofs18, const uint64_t* h_points, uint64_t* h_rho);
+int pcs_verify_agg(zk_ctx* ctx, const zk_pcs_vk* vk, size_t count, const size_t* h_nvars, const size_t* h_skip, const size_t* h_cstart,
+                   const uint64_t* h_cpoints18, const uint64_t* h_cscalars, const uint64_t* h_values, const uint64_t* h_proofs18,
+                   const uint64_t* h_points, const uint64_t* h_rho, uint8_t* h_ok);
 // ---- zk_g1check.hip ----
 int g1_decompress_check(zk_ctx* ctx, size_t count, const void* h_in48, uint64_t* h_out18, uint8_t* h_status);
 int g1_check(zk_ctx* ctx, size_t count, const uint64_t* h_points18, uint8_t* h_status);
+// ---- zk_g1seg.hip ----
+// h_bad, h_why (optional): the term a ZK_ERR_INVALID names (~0 otherwise) and what is wrong with it
+int g1_lincomb_seg(zk_ctx* ctx, size_t segments, const size_t* h_start, const uint64_t* h_points18, const uint64_t* h_scalars, uint64_t* h_out18,
+                   size_t* h_bad = nullptr, const char** h_why = nullptr);
 // ---- zk_pairing.hip: test hooks ----
 int dbg_fq30_op(zk_ctx* ctx, int mode, const void* d_x, const void* d_kx, const void* d_y, const void* d_ky, void* d_out, void* d_flags,
                 size_t n);

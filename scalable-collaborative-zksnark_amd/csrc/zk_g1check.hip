@@ -15,7 +15,7 @@
 // those cases in the first steps of the ladder.
 #include <hip/hip_runtime.h>
 
-#include "curve30.cuh"
+#include "g1c.cuh"
 #include "zk_ctx.hpp"
 
 namespace zk {
@@ -23,10 +23,6 @@ namespace zk {
 namespace g1c {
 __host__ __device__ constexpr u32 R2(int i) {  // 2^780 mod q: canonical integer -> internal form (x 2^390)
     constexpr u32 t[13] = {0x0510070fu, 0x3b19070du, 0x0132243au, 0x299bb0e8u, 0x3507af6eu, 0x3b81ec77u, 0x21b145efu, 0x0a487bb4u, 0x370a4144u, 0x05dcb4cbu, 0x18c97900u, 0x3812b364u, 0x000f696eu};
-    return t[i];
-}
-__host__ __device__ constexpr u32 FOUR(int i) {  // 4 (the curve's b), internal form
-    constexpr u32 t[13] = {0x0347fcb8u, 0x27600000u, 0x12002b11u, 0x3803379bu, 0x090c7212u, 0x1a7e0e88u, 0x373e0376u, 0x26d0b683u, 0x17bb09b0u, 0x17663c4au, 0x12ca7c51u, 0x167f3e80u, 0x000577a6u};
     return t[i];
 }
 // beta = 0x5f19672fdf76ce51ba69c6076a0f77eaddb3a93be6f89688de17d813620a00022e01fffffffefffe, internal form: the cube root of unity whose
@@ -44,40 +40,19 @@ __device__ const u32 kSqrtExp[12] = {0xffffeaabu, 0xee7fbfffu, 0xac54ffffu, 0x07
 constexpr int kSqrtBits = 379;
 constexpr unsigned long long kXAbs = 0xd201000000010000ULL;
 constexpr int kBlk = 64;
-enum : unsigned char { kOk = 0, kBadEncoding = 1, kNotOnCurve = 2, kNotInG1 = 3 };
 }  // namespace g1c
 
-#define ZK_G1C_CONST(name, T)                                    \
-    __device__ __forceinline__ Fq30 name() {                     \
-        Fq30 r;                                                  \
-        _Pragma("unroll") for (int i = 0; i < 13; i++) r.l[i] = T(i); \
-        return r;                                                \
-    }
 ZK_G1C_CONST(g1c_r2, g1c::R2)
-ZK_G1C_CONST(g1c_four, g1c::FOUR)
 ZK_G1C_CONST(g1c_beta, g1c::BETA)
 ZK_G1C_CONST(g1c_one_ref, Q30::C384)  // 2^384 mod q: the reference form of 1
 #undef ZK_G1C_CONST
 
-// v < q for a normalised v < 2^384
-__device__ __forceinline__ bool g1c_lt_q(const Fq30& v) {
-    u32 bw = 0;
-#pragma unroll
-    for (int i = 0; i < 13; i++) bw = (v.l[i] - Q30::Q(i) - bw) >> 31;
-    return bw != 0;
-}
 // v > (q - 1) / 2 for a canonical plain integer v
 __device__ __forceinline__ bool g1c_is_larger(const Fq30& v) {
     u32 bw = 0;
 #pragma unroll
     for (int i = 0; i < 13; i++) bw = (g1c::HALF(i) - v.l[i] - bw) >> 31;
     return bw != 0;
-}
-__device__ __forceinline__ bool g1c_same(const Fq30& a, const Fq30& b) {  // canonical operands
-    u32 o = 0;
-#pragma unroll
-    for (int i = 0; i < 13; i++) o |= a.l[i] ^ b.l[i];
-    return o == 0;
 }
 __device__ __forceinline__ void g1c_store_words(void* base, size_t byte_off, int nwords16, u32 v) {  // nwords16 x 16 bytes of v
     uint4* p = reinterpret_cast<uint4*>(reinterpret_cast<char*>(base) + byte_off);
@@ -91,52 +66,8 @@ __device__ __forceinline__ void g1c_store_jac(void* out, size_t i, const Fq30& x
     f30_store(out, i * 144 + 96, inf ? f30_zero() : one);
 }
 
-// 2p (dbl-2008-s-1, a = 0) and a + b below: the formulas of xyzz30_dbl / xyzz30_add of curve30.cuh, inlined.  There the doubling is a rare
-// path behind a call (__noinline__); here it IS the hot path.  k_g1_subgroup built on the curve30.cuh pair takes 255 VGPRs + 105 AGPRs
-// and 640 bytes of scratch per lane (the call's stack frame); with these two it takes 256 + 21 and none.  A change of either
-// formula must be made in both files; tests/test_gpu_g1check.py (this copy) and tests/test_gpu_xyzz.py (that one) check each against a model.
-__device__ __forceinline__ Xyzz30 g1c_dbl(const Xyzz30& p) {
-    if (xyzz30_is_inf(p)) return p;
-    Xyzz30 r;
-    const Fq30 U = f30_add(p.y, p.y);               // < 8q
-    const Fq30 V = f30_sqr(U);
-    const Fq30 W = f30_mul(U, V);
-    const Fq30 S = f30_mul(p.x, V);                 // 8q * 2q
-    const Fq30 xx = f30_sqr(p.x);                   // 64 q^2
-    const Fq30 M = f30_add(f30_add(xx, xx), xx);    // < 6q
-    const Fq30 X3 = f30_sub4(f30_sqr(M), f30_add(S, S));  // < 6q
-    r.y = f30_sub2(f30_mul(M, f30_sub8(S, X3)), f30_mul(W, p.y));  // < 4q
-    r.x = X3;
-    r.zz = f30_mul(V, p.zz);
-    r.zzz = f30_mul(W, p.zzz);
-    return r;
-}
-// a + b (add-2008-s), complete: xyzz30_add of curve30.cuh with the doubling inlined
-__device__ __forceinline__ Xyzz30 g1c_add(const Xyzz30& a, const Xyzz30& b) {
-    if (xyzz30_is_inf(a)) return b;
-    if (xyzz30_is_inf(b)) return a;
-    const Fq30 U1 = f30_mul(a.x, b.zz);       // 8q * 2q
-    const Fq30 U2 = f30_mul(b.x, a.zz);
-    const Fq30 S1 = f30_mul(a.y, b.zzz);      // 4q * 2q
-    const Fq30 S2 = f30_mul(b.y, a.zzz);
-    const Fq30 P = f30_sub2(U2, U1);          // < 4q
-    const Fq30 R = f30_sub2(S2, S1);          // < 4q
-    const Fq30 PP = f30_sqr(P);
-    const Fq30 PPP = f30_mul(P, PP);
-    const Fq30 Q = f30_mul(U1, PP);
-    const Fq30 ZZ3 = f30_mul(f30_mul(a.zz, b.zz), PP);
-    Xyzz30 r;
-    if (f30_is_zero_2q(ZZ3)) {  // same x: the same point or its opposite
-        if (f30_all_zero(f30_canon8(R))) r = g1c_dbl(a);
-        else xyzz30_set_inf(r);
-        return r;
-    }
-    r.x = f30_sub6(f30_sqr(R), f30_add2x(PPP, Q));                          // < 8q
-    r.y = f30_mul2add(R, f30_sub8(Q, r.x), f30_sub2(f30_zero(), S1), PPP);  // 4q*10q + 2q*2q -> < 2q
-    r.zz = ZZ3;
-    r.zzz = f30_mul(f30_mul(a.zzz, b.zzz), PPP);
-    return r;
-}
+// (the complete doubling and addition g1c_dbl / g1c_add are in g1c.cuh: zk_g1seg.hip uses them too.  Its g1c_load_jac is the rule of
+// k_g1_load_jac below for a lane that keeps the point in registers; this kernel stores as it goes and keeps its own text.)
 
 // in48: count x 48 bytes.  pts: count flat XYZZ records (written for status 0 and 3).  out18: count x 144 bytes (zero for status 1, 2).
 static __global__ void __launch_bounds__(g1c::kBlk) k_g1_decompress(size_t count, const void* __restrict__ in48, void* __restrict__ pts,

@@ -19,6 +19,8 @@
 // (host, threads over openings), the nvars + 1 Miller loops and the final exponentiation run here.
 #include "fq12.cuh"
 #include "host_curve.hpp"
+#include "host_fr.hpp"
+#include "host_sha256.hpp"
 #include "zk_ctx.hpp"
 
 #include <algorithm>
@@ -433,6 +435,156 @@ int pcs_verify_batch(zk_ctx* ctx, const zk_pcs_vk* vk, size_t nvars, size_t coun
     }
     start[count] = count * per;
     return pairing_run(ctx, count * per, g1.data(), g2.data(), count, start.data(), h_ok);
+}
+
+// ---- aggregated verification: any number of openings of mixed variable counts, one product of n_g2 pairings -------------------------
+// The G2 arguments of every opening are the fixed keys, so with weights rho_k
+//     L   = sum_k rho_k (sum_j e_kj C_kj - v_k g1 + sum_i u_ki pi_ki)
+//     M_j = sum_{k uses key j} rho_k pi_{k, j-1-skip_k}                      j = 1 .. n_g2 - 1
+//     accept  <=>  e(L, g2) prod_j e(-M_j, powers_g2[j]) == 1.
+// When every opening holds the product is 1; when one does not it is 1 with probability about count / 2^128 over the weights, which
+// are Fiat-Shamir over the whole batch (pcs_agg_weights): the caller cannot choose the openings after the weights.
+// L and the M_j are the segments of ONE zk_g1_lincomb_seg call; the host builds its term list with plain Fr arithmetic.
+
+// the offsets of the commitment terms: from 0, non-decreasing
+static bool agg_cstart_ok(size_t count, const size_t* h_cstart) {
+    if (h_cstart[0] != 0) return false;
+    for (size_t k = 0; k < count; k++)
+        if (h_cstart[k + 1] < h_cstart[k]) return false;
+    return true;
+}
+
+int pcs_agg_weights(size_t count, const size_t* h_nvars, const size_t* h_skip, const size_t* h_cstart, const uint64_t* h_cpoints18,
+                    const uint64_t* h_cscalars, const uint64_t* h_values, const uint64_t* h_proofs18, const uint64_t* h_points, uint64_t* h_rho) {
+    if (count && !agg_cstart_ok(count, h_cstart)) return ZK_ERR_INVALID;
+    H::Sha256 seed;
+    seed.update("zkhip-pcs-agg-v1", 16);
+    seed.update_u64le(count);
+    size_t row = 0;  // proof points / point coordinates before opening k
+    for (size_t k = 0; k < count; k++) {
+        const size_t c0 = h_cstart[k], J = h_cstart[k + 1] - c0, nv = h_nvars[k];
+        seed.update_u64le(nv);
+        seed.update_u64le(h_skip[k]);
+        seed.update_u64le(J);
+        if (J) {
+            seed.update(h_cpoints18 + 18 * c0, J * 144);
+            seed.update(h_cscalars + 4 * c0, J * 32);
+        }
+        seed.update(h_values + 4 * k, 32);
+        if (nv) {
+            seed.update(h_proofs18 + 18 * row, nv * 144);
+            seed.update(h_points + 4 * row, nv * 32);
+        }
+        row += nv;
+    }
+    uint8_t s32[32], d[32];
+    seed.digest(s32);
+    for (size_t k = 0; k < count; k++) {
+        H::Sha256 h;
+        h.update(s32, 32);
+        h.update_u64le(k);
+        h.digest(d);
+        for (int w = 0; w < 2; w++) {
+            uint64_t v = 0;
+            for (int b = 7; b >= 0; b--) v = v << 8 | d[8 * w + b];
+            h_rho[2 * k + w] = v;
+        }
+    }
+    return ZK_OK;
+}
+
+int pcs_verify_agg(zk_ctx* ctx, const zk_pcs_vk* vk, size_t count, const size_t* h_nvars, const size_t* h_skip, const size_t* h_cstart,
+                   const uint64_t* h_cpoints18, const uint64_t* h_cscalars, const uint64_t* h_values, const uint64_t* h_proofs18,
+                   const uint64_t* h_points, const uint64_t* h_rho, uint8_t* h_ok) {
+    if (count == 0) {
+        h_ok[0] = 1;
+        return ZK_OK;
+    }
+    if (!agg_cstart_ok(count, h_cstart)) return fail(ctx, ZK_ERR_INVALID, "commitment term offsets must start at 0 and not decrease");
+    const size_t n_g2 = vk->n_g2;
+    size_t rows = 0;
+    for (size_t k = 0; k < count; k++) {
+        if (h_skip[k] >= n_g2 || h_nvars[k] >= n_g2 || 1 + h_skip[k] + h_nvars[k] > n_g2)
+            return fail(ctx, ZK_ERR_INVALID, "opening %zu: 1 + skip + nvars = 1 + %zu + %zu > %zu powers of g2", k, h_skip[k], h_nvars[k], n_g2);
+        rows += h_nvars[k];
+    }
+    const size_t cterms = h_cstart[count];
+    if ((cterms && (!h_cpoints18 || !h_cscalars)) || (rows && (!h_proofs18 || !h_points))) return fail(ctx, ZK_ERR_INVALID, "null argument");
+    std::vector<uint64_t> rho_buf;
+    if (!h_rho) {
+        rho_buf.resize(2 * count);
+        pcs_agg_weights(count, h_nvars, h_skip, h_cstart, h_cpoints18, h_cscalars, h_values, h_proofs18, h_points, rho_buf.data());
+        h_rho = rho_buf.data();
+    }
+    // the term list: segment 0 is L (every G1 point of the input once, then g1), segment j is M_j
+    const size_t l_terms = cterms + rows + 1, terms = l_terms + rows;
+    std::vector<uint64_t> pts(terms * 18), ks(terms * 4);
+    std::vector<size_t> seg(n_g2 + 1, 0), row0(count);
+    for (size_t k = 0, row = 0; k < count; row += h_nvars[k], k++) {
+        row0[k] = row;
+        for (size_t i = 0; i < h_nvars[k]; i++) seg[1 + h_skip[k] + i + 1]++;  // (counts of segment j at seg[j + 1])
+    }
+    seg[1] = l_terms;
+    for (size_t j = 2; j <= n_g2; j++) seg[j] += seg[j - 1];
+    std::vector<size_t> fill(seg.begin(), seg.end() - 1);  // the next free term of every segment
+    uint64_t vsum[4] = {0, 0, 0, 0};
+    for (size_t k = 0; k < count; k++) {
+        const uint64_t rho[4] = {h_rho[2 * k], h_rho[2 * k + 1], 0, 0};
+        for (size_t c = h_cstart[k]; c < h_cstart[k + 1]; c++) {
+            const size_t t = fill[0]++;
+            std::memcpy(&pts[18 * t], h_cpoints18 + 18 * c, 144);
+            H::fr::mont_mul(rho, h_cscalars + 4 * c, &ks[4 * t]);
+        }
+        for (size_t i = 0; i < h_nvars[k]; i++) {
+            const uint64_t* pi = h_proofs18 + 18 * (row0[k] + i);
+            size_t t = fill[0]++;
+            std::memcpy(&pts[18 * t], pi, 144);
+            H::fr::mont_mul(rho, h_points + 4 * (row0[k] + i), &ks[4 * t]);
+            t = fill[1 + h_skip[k] + i]++;
+            std::memcpy(&pts[18 * t], pi, 144);
+            std::memcpy(&ks[4 * t], rho, 32);
+        }
+        uint64_t rv[4];
+        H::fr::mont_mul(rho, h_values + 4 * k, rv);
+        H::fr::add_canon(vsum, rv, vsum);
+    }
+    {
+        const size_t t = fill[0]++;
+        H::put_fe(vk->g1.x, &pts[18 * t]);
+        H::put_fe(vk->g1.y, &pts[18 * t + 6]);
+        H::put_fe(H::aff_inf(vk->g1) ? H::ZERO : H::ONE, &pts[18 * t + 12]);
+        fr_neg_canon(vsum, &ks[4 * t]);
+    }
+    std::vector<uint64_t> sums(n_g2 * 18);
+    size_t bad = 0;
+    const char* why = "";
+    const int rc = g1_lincomb_seg(ctx, n_g2, seg.data(), pts.data(), ks.data(), sums.data(), &bad, &why);
+    if (rc == ZK_ERR_INVALID && bad == cterms + rows) return fail(ctx, ZK_ERR_INVALID, "the key's g1: %s", why);
+    if (rc == ZK_ERR_INVALID && bad < cterms + rows) {  // every input point is a term of L, in the caller's order within each opening
+        size_t k = 0, t0 = 0;
+        for (;; k++) {
+            const size_t n = (h_cstart[k + 1] - h_cstart[k]) + h_nvars[k];
+            if (bad < t0 + n) break;
+            t0 += n;
+        }
+        const size_t J = h_cstart[k + 1] - h_cstart[k];
+        if (bad - t0 < J) return fail(ctx, ZK_ERR_INVALID, "commitment term %zu of opening %zu: %s", bad - t0, k, why);
+        return fail(ctx, ZK_ERR_INVALID, "proof point %zu of opening %zu: %s", bad - t0 - J, k, why);
+    }
+    if (rc) return rc;
+    // pairs: (L, g2), (-M_j, powers_g2[j])
+    std::vector<uint64_t> g1(n_g2 * 12, 0);
+    for (size_t j = 0; j < n_g2; j++) {
+        const uint64_t* p = &sums[18 * j];
+        H::Fq z, y;
+        H::get_fe(z, p + 12);
+        if (H::is_zero(z)) continue;  // infinity: x = y = 0, a factor 1
+        H::get_fe(y, p + 6);
+        std::memcpy(&g1[12 * j], p, 48);
+        H::put_fe(j ? H::neg(y) : y, &g1[12 * j + 6]);
+    }
+    const size_t start[2] = {0, n_g2};
+    return pairing_run(ctx, n_g2, g1.data(), vk->g2.data(), 1, start, h_ok);
 }
 
 }  // namespace zk

@@ -6,7 +6,16 @@
 //     bin/plonk_check --mu M [--seed S] [--gate wide] [--witness] [--lookup | --lookup-fn [--find] [--break-lookup K]] [--break-gate K | --break-wire K | --bad-input | --break K|all]
 //                     [--circuit-only | --sample-only [--time-sample R]] [--bytes [--dump-proof FILE] [--torsion K]]
 //     bin/plonk_check --g1check-time K [--reps R]
+//     bin/plonk_check --mu M [--seed S] [--gate wide] [--lookup] --verify-many K [--break-one J]
 //
+// --verify-many K verifies K proofs under ONE key with ONE pairing check (plonk_verify_many: zk_pcs_verify_agg).  The key, and with it the
+// SRS, is the one of seed S -- the aggregate needs one set of G2 keys, and every seed has its own trapdoor -- and proof k is a proof of
+// that circuit for the public inputs of seed S + k: proof 0 from the sampler's wires, the others from wires the device generates
+// (plonk_witness).  With --lookup the proof of seed S is repeated K times instead (the sampler's lookup rows must hit the table; the
+// aggregate does not care).  --break-one J moves a point of proof J's first opening (opening[0] = opening[last]): its field checks hold,
+// its pairing does not, the aggregate rejects and the one-by-one pass names it.  Prints one digest per proof and the line
+// "verify-many K=.. verdicts 1,0,.. weights sha256 .." -- the verdicts and the SHA-256 of the weights zk_pcs_agg_weights derives from the
+// aggregate's input arrays (count x 2 little-endian u64; computed on the host beside the call, which derives the same bits itself), identical to the Python host's for the same arguments (tests/test_host_plonk_agg.py).  Exit 0 when every verdict is 1.
 // --bytes proves, encodes the record (zkhost/proof_io.hpp: the byte format of zkhip/proof_io.py) and verifies THE BYTES with verify_bytes:
 // one device call validates every G1 point (canonical encoding, on the curve, in the prime-order subgroup) before plonk_verify runs.  Prints
 // the SHA-256 of the bytes -- one digest for one seed in both hosts -- and the verdict; --dump-proof FILE writes the bytes.  --torsion K adds
@@ -63,7 +72,7 @@ static bool number(const char *s, long long &out) {
 
 struct Options {
     long long mu = -1, seed = 7, break_gate = -1, break_wire = -1, break_lookup = -1, break_part = -1;
-    long long time_sample = 0, torsion = -1, g1check_time = 0, reps = 20;
+    long long time_sample = 0, torsion = -1, g1check_time = 0, reps = 20, verify_many = 0, break_one = -1;
     bool bytes = false;
     std::string dump_proof;
     bool bad_input = false, wide = false, lookup = false, break_all = false, find = false, witness = false, lookup_fn = false;
@@ -164,6 +173,40 @@ static void flip(PlonkProof &p, int k) {
     w[k][0] ^= 1;
 }
 
+// --verify-many K [--break-one J]: K proofs under the key of seed S, one aggregate call
+static int verify_many(Ctx &be, const Options &o, const PcsVk &vk_mu, const PcsVk &vk_mu1, const PlonkVk &vk, const PlonkPk &pk, const PowersOfG &pg,
+                       const PlonkCircuit &good, const PlonkProof &first) {
+    const size_t K = (size_t)o.verify_many;
+    std::vector<PlonkItem> items{PlonkItem{good.public_inputs, first}};
+    std::shared_ptr<WitnessPlan> plan;
+    for (size_t k = 1; k < K; ++k) {
+        if (o.lookup) {
+            items.push_back(items[0]);
+            continue;
+        }
+        if (!plan) plan = witness_plan(be, good, false);
+        Options ok = o;
+        ok.seed = o.seed + (long long)k;
+        const FrVec pi = sample(ok, false).public_inputs;
+        const std::array<DevPtr, 3> w = plonk_witness(be, pk, *plan, pi, nullptr);
+        items.push_back(PlonkItem{pi, plonk_prove(be, pg, pk, w[0], w[1], w[2], pi)});
+    }
+    if (o.break_one >= 0) {
+        G1Vec &op = items[(size_t)o.break_one].proof.batch.opening;
+        op.front() = op.back();
+    }
+    for (size_t k = 0; k < K; ++k) std::printf("proof %zu sha256 %s\n", k, proof_digest(items[k].proof).c_str());
+    std::vector<uint64_t> rho;
+    const std::vector<bool> got = plonk_verify_many(be, vk_mu, vk_mu1, vk, items, &rho);
+    Sha256 h;
+    h.update(rho.data(), 8 * rho.size());
+    std::string verdicts;
+    bool all = true;
+    for (size_t k = 0; k < K; ++k) verdicts += (k ? "," : ""), verdicts += got[k] ? "1" : "0", all = all && got[k];
+    std::printf("verify-many K=%zu verdicts %s weights sha256 %s\n", K, verdicts.c_str(), h.hex().c_str());
+    return all ? 0 : 1;
+}
+
 static int run(const Options &o) {
     Ctx be(0);
     const size_t mu = (size_t)o.mu, N = size_t(1) << mu;
@@ -209,6 +252,12 @@ static int run(const Options &o) {
     }
     FrVec pi = good.public_inputs;
     if (bad_input) pi[1] += Fr::one();
+    if (o.verify_many > 0) {
+        const int rc = verify_many(be, o, *vk_mu, *vk_mu1, vk, pk, cub.mature(), good, proof);
+        std::printf("plonk_check mu=%zu N=%zu l=%zu seed=%llu%s%s: %s\n", mu, N, good.l, (unsigned long long)seed, wide ? " gate=wide" : "", o.lookup ? " lookup" : "",
+                    rc ? "reject" : "accept");
+        return rc;
+    }
     std::printf("proof sha256 %s\n", proof_digest(proof).c_str());
     bool ok = true;
     if (o.break_all) {
@@ -249,6 +298,8 @@ int main(int argc, char **argv) {
         else if (i + 1 < argc && k == "--dump-proof") o.dump_proof = argv[++i];
         else if (i + 1 < argc && k == "--torsion") usage = !number(argv[++i], o.torsion);
         else if (i + 1 < argc && k == "--g1check-time") usage = !number(argv[++i], o.g1check_time) || o.g1check_time < 1;
+        else if (i + 1 < argc && k == "--verify-many") usage = !number(argv[++i], o.verify_many) || o.verify_many < 1 || o.verify_many > 256;
+        else if (i + 1 < argc && k == "--break-one") usage = !number(argv[++i], o.break_one);
         else if (i + 1 < argc && k == "--reps") usage = !number(argv[++i], o.reps) || o.reps < 1;
         else if (i + 1 < argc && k == "--time-sample") usage = !number(argv[++i], o.time_sample) || o.time_sample < 1;
         else if (i + 1 < argc && k == "--break-lookup") usage = !number(argv[++i], o.break_lookup);
@@ -270,11 +321,13 @@ int main(int argc, char **argv) {
             return 2;
         }
     }
+    usage = usage || (o.break_one >= 0 && o.break_one >= o.verify_many) ||
+            (o.verify_many > 0 && (o.bytes || tamper || bad_input || o.witness || o.find || o.lookup_fn || break_gate >= 0 || break_wire >= 0 || o.break_lookup >= 0 || only_circuit));
     usage = usage || o.g1check_time > 0 || ((o.torsion >= 0 || !o.dump_proof.empty()) && !o.bytes) || (o.bytes && tamper);
     if (usage || mu < 0 || (break_gate >= 0) + (break_wire >= 0) + (bad_input ? 1 : 0) + (o.break_lookup >= 0) + (tamper ? 1 : 0) > 1 ||
         (o.break_all && o.break_part >= 0) || (o.break_lookup >= 0 && !o.lookup) || (o.find && !o.lookup) || (o.lookup && (break_gate >= 0 || break_wire >= 0)) ||
         (o.witness && (break_gate >= 0 || break_wire >= 0)) || (o.time_sample > 0 && !only_circuit) || (o.lookup_fn && (!wide || o.time_sample > 0))) {
-        std::fprintf(stderr, "usage: plonk_check --mu M [--seed S] [--gate wide] [--witness] [--lookup | --gate wide --lookup-fn [--find] [--break-lookup K]] [--break-gate K | --break-wire K | --bad-input | --break K|all] [--circuit-only | --sample-only [--time-sample R]] [--bytes [--dump-proof FILE] [--torsion K]] | --g1check-time K [--reps R]\n");
+        std::fprintf(stderr, "usage: plonk_check --mu M [--seed S] [--gate wide] [--witness] [--lookup | --gate wide --lookup-fn [--find] [--break-lookup K]] [--break-gate K | --break-wire K | --bad-input | --break K|all] [--circuit-only | --sample-only [--time-sample R]] [--bytes [--dump-proof FILE] [--torsion K]] | --verify-many K [--break-one J] | --g1check-time K [--reps R]\n");
         return 2;
     }
     if (mu < 2 || mu > 24) {

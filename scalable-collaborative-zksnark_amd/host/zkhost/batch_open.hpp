@@ -132,6 +132,16 @@ inline bool batch_open_verify(Ctx &be, const PcsVk &vk, const G1Vec &commitments
     return verify_opening(be, vk, commitments, claims, proof, alpha, rho, y);
 }
 
+// what batch_open_verify hands to the pairing, without calling the device: the opening of sum_j e_j C_j at rho with the chain's value y,
+// added to `out` as one opening of verify_agg (zkhip.batch_open.opening_claim).  false, and nothing added, when the chain breaks
+inline bool opening_claim(const G1Vec &commitments, const std::vector<Claim> &claims, const BatchOpenProof &proof, const Fr &alpha, const FrVec &rho, size_t skip,
+                          AggArrays &out) {
+    Fr y;
+    if (failed_checks(commitments.size(), claims, proof, alpha, rho, &y)) return false;
+    out.add(commitments, eq_coefficients(commitments.size(), claims, alpha, rho), y, proof.opening, rho, skip);
+    return true;
+}
+
 // [(j, z)] -> claims with v = f_j(z) by zk_fold
 inline std::vector<Claim> evaluate_claims(Ctx &be, const std::vector<DevPtr> &tables, size_t N, const std::vector<std::pair<size_t, FrVec>> &points) {
     std::vector<Claim> out;

@@ -59,6 +59,41 @@ struct PcsVk {
     }
 };
 
+// the flat arrays of zk_pcs_verify_agg / zk_pcs_agg_weights (zkhip.dist_primitive.agg_arrays): opening k has nvars[k] variables, its
+// proof point i pairs with powers_g2[1 + skip[k] + i] of the FULL key, its commitment is sum_j e_j C_j over the terms cstart[k] ..
+// cstart[k+1] of cpoints / cscalars (Montgomery); proofs / points hold the openings' rows one after another
+struct AggArrays {
+    std::vector<size_t> nvars, skip, cstart{0};
+    G1Vec cpoints, proofs;
+    FrVec cscalars, values, points;
+    size_t count() const { return nvars.size(); }
+    // one opening: (C [J], e [J], value, proofs [n], point [n], skip)
+    void add(const G1Vec &c, const FrVec &e, const Fr &value, const G1Vec &pf, const FrVec &pt, size_t skip_) {
+        if (c.size() != e.size() || pf.size() != pt.size()) throw ZkError(ZK_ERR_INVALID, "AggArrays::add: list lengths differ");
+        nvars.push_back(pf.size()), skip.push_back(skip_), cstart.push_back(cstart.back() + c.size());
+        cpoints.insert(cpoints.end(), c.begin(), c.end()), cscalars.insert(cscalars.end(), e.begin(), e.end());
+        values.push_back(value), proofs.insert(proofs.end(), pf.begin(), pf.end()), points.insert(points.end(), pt.begin(), pt.end());
+    }
+    // the openings of `o` after mine
+    void append(const AggArrays &o) {
+        nvars.insert(nvars.end(), o.nvars.begin(), o.nvars.end()), skip.insert(skip.end(), o.skip.begin(), o.skip.end());
+        const size_t base = cstart.back();
+        for (size_t k = 1; k < o.cstart.size(); ++k) cstart.push_back(base + o.cstart[k]);
+        cpoints.insert(cpoints.end(), o.cpoints.begin(), o.cpoints.end()), cscalars.insert(cscalars.end(), o.cscalars.begin(), o.cscalars.end());
+        values.insert(values.end(), o.values.begin(), o.values.end());
+        proofs.insert(proofs.end(), o.proofs.begin(), o.proofs.end()), points.insert(points.end(), o.points.begin(), o.points.end());
+    }
+};
+// zk_pcs_agg_weights (host only, no ctx, no GPU): the derived 128-bit weights of pcs_verify_agg -> count x 2 u64
+inline std::vector<uint64_t> pcs_agg_weights(const AggArrays &a) {
+    std::vector<uint64_t> rho(2 * a.count());
+    const int rc = zk_pcs_agg_weights(a.count(), a.nvars.data(), a.skip.data(), a.cstart.data(), a.cpoints.empty() ? nullptr : a.cpoints[0].data(),
+                                      a.cscalars.empty() ? nullptr : a.cscalars[0].v, a.values.empty() ? nullptr : a.values[0].v,
+                                      a.proofs.empty() ? nullptr : a.proofs[0].data(), a.points.empty() ? nullptr : a.points[0].v, rho.data());
+    if (rc) throw ZkError(rc, "zk_pcs_agg_weights: the commitment offsets must start at 0 and not decrease");
+    return rho;
+}
+
 // the witness plan of one Plonk circuit held by the library (zk_witness_plan: sources, levels, launch schedule and, built with a lookup,
 // the key table of (t0, t1)); it holds its ctx
 struct WitnessPlan {
@@ -712,6 +747,33 @@ class Ctx {
             check(zk_pcs_verify_batch(h_, vk.h, nvars, count, commitments[0].data(), values[0].v, nvars ? proofs[0].data() : nullptr,
                                       nvars ? points[0].v : nullptr, ok.data()));
         return std::vector<bool>(ok.begin(), ok.begin() + count);
+    }
+
+    // out[s] = sum_{starts[s] <= t < starts[s+1]} k_t P_t on the device (zk_g1_lincomb_seg): starts = segments + 1 offsets from 0, points
+    // Jacobian in any representative, scalars CANONICAL -> one normalised point per segment.  A term that is not canonical or not on the
+    // curve: ZkError(ZK_ERR_INVALID) naming the smallest such term
+    G1Vec g1_lincomb_seg(const std::vector<size_t> &starts, const G1Vec &points, const FrVec &scalars_canonical) {
+        const size_t segments = starts.empty() ? 0 : starts.size() - 1;
+        need(!segments || (points.size() >= starts.back() && scalars_canonical.size() >= starts.back()), "g1_lincomb_seg: fewer terms than the last offset");
+        G1Vec out(segments);
+        if (segments)
+            check(zk_g1_lincomb_seg(h_, segments, starts.data(), points.empty() ? nullptr : points[0].data(),
+                                    scalars_canonical.empty() ? nullptr : scalars_canonical[0].v, out[0].data()));
+        return out;
+    }
+    // every opening of `a` in ONE pairing check (zk_pcs_verify_agg); rho: count x 2 u64 explicit weights (tests), nullptr: derived
+    bool pcs_verify_agg(const PcsVk &vk, const AggArrays &a, const uint64_t *rho = nullptr) {
+        const size_t count = a.count();
+        size_t rows = 0;
+        for (size_t n : a.nvars) rows += n;
+        need(a.skip.size() == count && a.cstart.size() == count + 1 && a.values.size() == count && a.proofs.size() == rows && a.points.size() == rows &&
+                 a.cpoints.size() == a.cscalars.size() && a.cpoints.size() >= a.cstart.back(),
+             "pcs_verify_agg: the arrays disagree on the number of openings, terms or rows");
+        uint8_t ok = 0;
+        check(zk_pcs_verify_agg(h_, vk.h, count, a.nvars.data(), a.skip.data(), a.cstart.data(), a.cpoints.empty() ? nullptr : a.cpoints[0].data(),
+                                a.cscalars.empty() ? nullptr : a.cscalars[0].v, a.values.empty() ? nullptr : a.values[0].v,
+                                a.proofs.empty() ? nullptr : a.proofs[0].data(), a.points.empty() ? nullptr : a.points[0].v, rho, &ok));
+        return ok != 0;
     }
 
     // zk_g1_decompress_check: k x 48 bytes of compressed G1 -> the normalised points and one status per point (0 ok, 1 bad encoding,

@@ -437,6 +437,9 @@ inline std::vector<bool> verify_batch(Ctx &be, const PcsVk &vk, const G1Vec &com
 inline bool verify(Ctx &be, const PcsVk &vk, const G1 &commitment, const Fr &value, const G1Vec &proof, const FrVec &point) {
     return verify_batch(be, vk, G1Vec{commitment}, FrVec{value}, {proof}, {point})[0];
 }
+// any number of openings of mixed variable counts in ONE pairing check (zk_pcs_verify_agg): true when every opening holds, false when one
+// does not (up to the soundness error count / 2^128 of the derived weights).  vk: the FULL key; rho: explicit weights (tests)
+inline bool verify_agg(Ctx &be, const PcsVk &vk, const AggArrays &openings, const uint64_t *rho = nullptr) { return be.pcs_verify_agg(vk, openings, rho); }
 
 // dpoly_comm.rs:401-464: n fold rounds producing every q_i, ONE batched d_msm over them (:436), pss2ss of the last value,
 // then log2(l) more rounds on the l-vector re-using point[0..] (:452) -> (value, n + log2 l proofs)

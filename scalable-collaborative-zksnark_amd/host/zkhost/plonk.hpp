@@ -706,6 +706,68 @@ inline bool plonk_verify(Ctx &be, const PcsVk &vk_mu, const PcsVk &vk_mu1, const
     }
 }
 
+// ---- aggregated verification: many proofs, one pairing check (zkhip.plonk.agg_openings / verify_many / verify_agg) ----
+struct PlonkItem {
+    FrVec public_inputs;
+    PlonkProof proof;
+};
+// the replay and the checks of plonk_failed_checks for every item; the batch instances of the survivors -- two each, with a lookup three --
+// as openings over the FULL key: skip = 1 for the mu-variate instances, 0 for the tree's.  alive: the indices of the survivors
+inline AggArrays plonk_agg_openings(const PlonkVk &vk, const std::vector<PlonkItem> &items, std::vector<size_t> &alive) {
+    AggArrays all;
+    alive.clear();
+    const size_t ns = gate_desc(vk.gate).selectors;
+    for (size_t n = 0; n < items.size(); ++n) {
+        const PlonkProof &p = items[n].proof;
+        PlonkChallenges c;
+        if (!plonk_challenges(vk, items[n].public_inputs, p, c) || plonk_failed_checks(vk, items[n].public_inputs, p, c)) continue;
+        std::vector<Claim> claims, v_claims, l_claims;
+        detail::plonk_claims(p, c.r_g, c.r_p, claims, v_claims);
+        if (vk.lookup) detail::lookup_claims(p, c.r_l, claims, l_claims);
+        G1Vec comms(vk.commitments.begin(), vk.commitments.begin() + ns);  // batch_tables order
+        comms.insert(comms.end(), p.commitments.begin(), p.commitments.end());
+        comms.insert(comms.end(), vk.commitments.begin() + ns, vk.commitments.begin() + ns + 3);
+        AggArrays mine;
+        bool ok = opening_claim(comms, claims, p.batch, c.b_alpha, c.rho_mu, 1, mine) &&
+                  opening_claim(G1Vec{p.v_commitment}, v_claims, p.v_batch, c.b_alpha, c.rho_mu1, 0, mine);
+        if (ok && vk.lookup) {
+            G1Vec l_comms(vk.commitments.begin() + ns + 3, vk.commitments.end());
+            l_comms.insert(l_comms.end(), p.l_commitments.begin(), p.l_commitments.end());
+            ok = opening_claim(l_comms, l_claims, p.l_batch, c.b_alpha, c.rho_l, 1, mine);
+        }
+        if (!ok) continue;
+        alive.push_back(n);
+        all.append(mine);
+    }
+    return all;
+}
+// plonk_verify for a list: ONE zk_pcs_verify_agg call for the batch instances of all surviving proofs.  When the aggregate accepts every
+// survivor is true; when it rejects -- or refuses a point that is not on the curve -- the survivors go one by one through plonk_verify,
+// so the bad one is named.  weights (optional): what zk_pcs_agg_weights derives from the aggregate's input arrays, count x 2 u64 --
+// computed here on the host for the caller, not read back from the call, which derives the same bits again
+inline std::vector<bool> plonk_verify_many(Ctx &be, const PcsVk &vk_mu, const PcsVk &vk_mu1, const PlonkVk &vk, const std::vector<PlonkItem> &items,
+                                           std::vector<uint64_t> *weights = nullptr) {
+    std::vector<size_t> alive;
+    const AggArrays openings = plonk_agg_openings(vk, items, alive);
+    if (weights) *weights = pcs_agg_weights(openings);
+    bool ok = true;
+    if (!alive.empty()) {
+        try {
+            ok = verify_agg(be, vk_mu1, openings);
+        } catch (const ZkError &e) {
+            if (e.status != ZK_ERR_INVALID) throw;
+            ok = false;
+        }
+    }
+    std::vector<bool> out(items.size(), false);
+    for (size_t n : alive) out[n] = ok || plonk_verify(be, vk_mu, vk_mu1, vk, items[n].public_inputs, items[n].proof);
+    return out;
+}
+// plonk_verify with ONE pairing call instead of two or three: plonk_verify_many of one proof
+inline bool plonk_verify_agg(Ctx &be, const PcsVk &vk_mu, const PcsVk &vk_mu1, const PlonkVk &vk, const FrVec &pi, const PlonkProof &p) {
+    return plonk_verify_many(be, vk_mu, vk_mu1, vk, {PlonkItem{pi, p}})[0];
+}
+
 // zkhip.plonk.proof_digest: the record's words in the order of the schedule
 inline std::string proof_digest(const PlonkProof &p) {
     Sha256 h;

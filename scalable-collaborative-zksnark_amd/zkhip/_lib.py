@@ -131,6 +131,9 @@ SYMBOLS = [
     ("zk_pcs_verify_batch", _i, [_vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp]),
     ("zk_g1_decompress_check", _i, [_vp, _sz, _vp, _vp, _vp]),
     ("zk_g1_check", _i, [_vp, _sz, _vp, _vp]),
+    ("zk_g1_lincomb_seg", _i, [_vp, _sz, _vp, _vp, _vp, _vp]),
+    ("zk_pcs_verify_agg", _i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("zk_pcs_agg_weights", _i, [_sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 ]
 
 # include/zkhip_test.h: the zk_dbg_* test hooks -- not part of the ABI, resolved only when a test / tool asks (test_hooks())

@@ -997,6 +997,59 @@ class Ctx:
             self._check(self.lib.zk_g1_check(self.h, len(pts), _h(pts), _h(st)))
         return st
 
+    # ---- aggregated PCS verification: many openings, one pairing check (csrc/zk_g1seg.hip, csrc/zk_pairing.hip) ----
+    def g1_lincomb_seg(self, starts, points, scalars_canon) -> np.ndarray:
+        """out[s] = sum_{starts[s] <= t < starts[s+1]} k_t P_t on the device: starts [segments + 1] offsets from 0, points [terms, 18]
+        Jacobian (any representative, Z = 0: infinity), scalars [terms, 4] canonical -> [segments, 18] normalised Jacobian.  A term that
+        is not canonical or not on the curve raises ZkError(ZK_ERR_INVALID) naming the smallest such term"""
+        st = np.ascontiguousarray(starts, dtype=np.uint64).reshape(-1)
+        segments = max(len(st) - 1, 0)
+        pts = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 18)
+        sc = np.ascontiguousarray(scalars_canon, dtype=np.uint64).reshape(-1, 4)
+        if segments and (len(pts) < int(st[-1]) or len(sc) < int(st[-1])):
+            raise ValueError("fewer terms than the last offset")
+        out = np.zeros((segments, 18), dtype=np.uint64)
+        if segments:
+            self._check(self.lib.zk_g1_lincomb_seg(self.h, segments, _h(st), _h(pts), _h(sc), _h(out)))
+        return out
+
+    @staticmethod
+    def _agg_arrays(nvars, skip, cstart, cpoints, cscalars, values, proofs, points):
+        nv = np.ascontiguousarray(nvars, dtype=np.uint64).reshape(-1)
+        count = len(nv)
+        sk = np.ascontiguousarray(skip, dtype=np.uint64).reshape(-1)
+        cs = np.ascontiguousarray(cstart, dtype=np.uint64).reshape(-1)
+        cp = np.ascontiguousarray(cpoints, dtype=np.uint64).reshape(-1, 18)
+        ce = np.ascontiguousarray(cscalars, dtype=np.uint64).reshape(-1, 4)
+        vals = np.ascontiguousarray(values, dtype=np.uint64).reshape(-1, 4)
+        pf = np.ascontiguousarray(proofs, dtype=np.uint64).reshape(-1, 18)
+        pts = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 4)
+        rows = int(nv.sum()) if count else 0
+        if len(sk) != count or len(cs) != count + 1 or len(vals) != count or len(pf) != rows or len(pts) != rows or len(cp) != len(ce) or len(cp) < int(cs[-1]):
+            raise ValueError("pcs_verify_agg: the arrays disagree on the number of openings, terms or rows")
+        return count, nv, sk, cs, cp, ce, vals, pf, pts
+
+    @staticmethod
+    def pcs_agg_weights(nvars, skip, cstart, cpoints, cscalars, values, proofs, points) -> np.ndarray:
+        """the derived weights of pcs_verify_agg (zk_pcs_agg_weights: host only, needs no ctx and no GPU) -> [count, 2] u64"""
+        count, nv, sk, cs, cp, ce, vals, pf, pts = Ctx._agg_arrays(nvars, skip, cstart, cpoints, cscalars, values, proofs, points)
+        rho = np.zeros((count, 2), dtype=np.uint64)
+        rc = _lib.lib().zk_pcs_agg_weights(count, _h(nv), _h(sk), _h(cs), _h(cp), _h(ce), _h(vals), _h(pf), _h(pts), _h(rho))
+        if rc:
+            raise ZkError(rc, "zk_pcs_agg_weights: the commitment offsets must start at 0 and not decrease")
+        return rho
+
+    def pcs_verify_agg(self, vk: "PcsVk", nvars, skip, cstart, cpoints, cscalars, values, proofs, points, rho=None) -> bool:
+        """count openings of mixed variable counts in ONE pairing check (zk_pcs_verify_agg): nvars, skip [count]; opening k's commitment
+        is sum_j e_j C_j over the terms cstart[k] .. cstart[k+1] of cpoints [*, 18] / cscalars [*, 4] (Montgomery); values [count, 4];
+        proofs [rows, 18] and points [rows, 4]: the openings' rows one after another; rho [count, 2] u64 or None (derived)"""
+        count, nv, sk, cs, cp, ce, vals, pf, pts = self._agg_arrays(nvars, skip, cstart, cpoints, cscalars, values, proofs, points)
+        ok = np.zeros(1, dtype=np.uint8)
+        r = None if rho is None else np.ascontiguousarray(rho, dtype=np.uint64).reshape(count, 2)
+        self._check(self.lib.zk_pcs_verify_agg(self.h, vk.h, count, _h(nv), _h(sk), _h(cs), _h(cp), _h(ce), _h(vals), _h(pf), _h(pts),
+                                               None if r is None else _h(r), _h(ok)))
+        return bool(ok[0])
+
     # ---- party exchanges through the C ABI (RCCL communicator inside the ctx) ----
     def comm_unique_id(self) -> bytes:
         buf = (ctypes.c_uint8 * 128)()

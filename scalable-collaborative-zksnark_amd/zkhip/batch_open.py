@@ -180,6 +180,20 @@ def batch_open_verify(be, vk, commitments, claims, proof: dict, alpha, rho) -> b
     return bool(np.all(ok))
 
 
+def opening_claim(commitments, claims, proof: dict, alpha, rho):
+    """what batch_open_verify hands to the pairing, without calling the device: the opening of sum_j e_j C_j at rho with the chain's
+    value y -> (C [J, 18], e [J, 4] Montgomery, y [4] Montgomery, opening [n, 18], rho [n, 4]), the form of one opening of
+    dist_primitive.verify_agg.  None when the chain breaks (failed_checks is not empty)"""
+    comms = np.ascontiguousarray(commitments, dtype=np.uint64).reshape(-1, 18)
+    if failed_checks(len(comms), claims, proof, alpha, rho):
+        return None
+    rho = np.ascontiguousarray(rho, dtype=np.uint64).reshape(-1, 4)
+    claims = _norm_claims(claims, len(comms), len(rho))
+    _, y = chain_value(proof, claims, alpha, rho)
+    e = eq_coefficients(len(comms), claims, alpha, rho)
+    return comms, np.stack([fr_mont(x) for x in e]), fr_mont(y), np.asarray(proof["opening"], dtype=np.uint64).reshape(len(rho), 18), rho
+
+
 def proof_digest(proof: dict) -> str:
     """SHA-256 over the record's little-endian words: rounds | opening"""
     h = hashlib.sha256()

@@ -826,6 +826,28 @@ def verify_batch(be, vk, commitments, values, proofs, points) -> np.ndarray:
     return be.pcs_verify_batch(vk, commitments, values, proofs, points)
 
 
+def agg_arrays(openings):
+    """[(C [J, 18], e [J, 4] Montgomery, value [4], proofs [nvars, 18], point [nvars, 4], skip)] -> the flat arrays of
+    zk_pcs_verify_agg / zk_pcs_agg_weights: (nvars, skip, cstart, cpoints, cscalars, values, proofs, points)"""
+    u = lambda a, w: np.ascontiguousarray(a, dtype=np.uint64).reshape(-1, w)
+    cs = [u(o[0], 18) for o in openings]
+    cat = lambda parts, w: np.concatenate(parts) if parts else np.zeros((0, w), dtype=np.uint64)
+    pfs = [u(o[3], 18) for o in openings]
+    return (np.array([len(p) for p in pfs], dtype=np.uint64), np.array([int(o[5]) for o in openings], dtype=np.uint64),
+            np.cumsum([0] + [len(c) for c in cs]).astype(np.uint64), cat(cs, 18), cat([u(o[1], 4) for o in openings], 4),
+            cat([u(o[2], 4) for o in openings], 4), cat(pfs, 18), cat([u(o[4], 4) for o in openings], 4))
+
+
+def verify_agg(be, vk, openings, rho=None) -> bool:
+    """
+    Any number of openings of mixed variable counts in ONE pairing check (zk_pcs_verify_agg): True when every opening holds, False
+    when one does not (up to the soundness error count / 2^128 of the derived weights).  openings: the tuples of agg_arrays -- the
+    commitment of an opening is sum_j e_j C_j, proof point i pairs with powers_of_g2[1 + skip + i] of the FULL key vk.
+    rho: [count, 2] u64 explicit weights (tests), None: derived from the openings.
+    """
+    return be.pcs_verify_agg(vk, *agg_arrays(openings), rho=rho)
+
+
 def verify_device(be, powers_of_g2, commitment: np.ndarray, value: np.ndarray, proof: np.ndarray, point: np.ndarray, g1=None) -> bool:
     """`verify` with the reference's arguments, on the device: one opening through verify_batch"""
     vk = powers_of_g2 if hasattr(powers_of_g2, "n_g2") else pcs_vk(be, powers_of_g2, g1)

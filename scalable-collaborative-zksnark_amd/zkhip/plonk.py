@@ -104,7 +104,7 @@ import numpy as np
 from . import batch_open as bo
 from . import wiring as wr
 from .field import R_MOD, fr_from_mont, fr_mont
-from .proof_io import check_points, parse_proof, proof_from_bytes, proof_to_bytes, verify_bytes  # noqa: F401  (proof bytes, re-exported)
+from .proof_io import check_points, parse_proof, proof_from_bytes, proof_to_bytes, verify_bytes, verify_bytes_many  # noqa: F401  (proof bytes, re-exported)
 from .transcript import HostTranscript, Transcript
 from .verify import _ints, _u64, eq_eval, round_chain, round_poly_at  # noqa: F401  (round_poly_at: importable from here as before)
 from .zerocheck import gate_value, wide_gate_value
@@ -591,6 +591,76 @@ def verify(be, vk: dict, public_inputs, proof: dict) -> bool:
         return bo.batch_open_verify(be, vk_mu, l_comms, _lookup_claims(c, proof), proof["lookup"]["batch"], c["b_alpha"], c["rho_l"])
     except (KeyError, ValueError, TypeError):
         return False
+
+
+def _agg_openings(vk: dict, c: dict, proof: dict) -> list | None:
+    """the batch instances of one proof -- two, with a lookup three -- as openings of dist_primitive.verify_agg over the full key
+    vk["pcs"][1]: skip = 1 for the mu-variate instances, 0 for the tree's.  None when a chain breaks"""
+    claims, v_claims = _claims(c, proof)
+    ns = len(gate_of(vk).selectors)
+    lookup = has_lookup(vk)
+    vkc, pc = _u64(vk["commitments"], ns + 3 + (len(LOOKUP_VK_TABLES) if lookup else 0), 18), _u64(proof["commitments"], 3, 18)
+    comms = np.concatenate([vkc[:ns], pc, vkc[ns:ns + 3]])  # batch_tables order
+    parts = [(bo.opening_claim(comms, claims, proof["batch"], c["b_alpha"], c["rho_mu"]), 1),
+             (bo.opening_claim(_u64(proof["v_commitment"], 1, 18), v_claims, proof["v_batch"], c["b_alpha"], c["rho_mu1"]), 0)]
+    if lookup:
+        l_comms = np.concatenate([vkc[ns + 3:], _u64(proof["lookup"]["commitments"], len(LOOKUP_COMMITTED), 18)])  # L_BATCH_TABLES order
+        parts.append((bo.opening_claim(l_comms, _lookup_claims(c, proof), proof["lookup"]["batch"], c["b_alpha"], c["rho_l"]), 1))
+    if any(p is None for p, _ in parts):
+        return None
+    return [p + (skip,) for p, skip in parts]
+
+
+def agg_openings(vk: dict, items) -> tuple:
+    """the host half of verify_many, without a GPU: every (public_inputs, proof) gets the replay and the checks of failed_checks; the
+    batch instances of the survivors become openings of dist_primitive.verify_agg -> (alive: the survivors' indices, openings)"""
+    alive, openings = [], []
+    for n, (public_inputs, proof) in enumerate(items):
+        try:
+            c = challenges(vk, public_inputs, proof)
+            if failed_checks(vk, public_inputs, proof, c=c):
+                continue
+            ops = _agg_openings(vk, c, proof)
+        except (KeyError, ValueError, TypeError):
+            continue
+        if ops is not None:
+            alive.append(n)
+            openings += ops
+    return alive, openings
+
+
+def verify_many(be, vk: dict, items) -> list:
+    """`verify` for a list of (public_inputs, proof): every proof gets the replay and the checks of failed_checks (agg_openings), then
+    the batch instances of all surviving proofs go into ONE zk_pcs_verify_agg call over the full key vk["pcs"][1].  When the aggregate
+    accepts every survivor is True; when it rejects -- or refuses a point that is not on the curve -- the survivors go one by one
+    through `verify`, so the bad one is named.  The verdicts are those of [verify(be, vk, pi, proof) for pi, proof in items] up to the
+    aggregate's soundness error (openings / 2^128)."""
+    from . import dist_primitive as dp
+
+    if vk.get("pcs") is None:
+        raise ValueError("the verifying key holds no pairing keys (preprocess without powers_of_g2)")
+    from .api import ZK_ERR_INVALID, ZkError
+
+    def refused_is_false(call):  # a point that is not on the curve is a refusal of the library (ZK_ERR_INVALID): a record to reject
+        try:
+            return bool(call())
+        except ZkError as e:
+            if e.code != ZK_ERR_INVALID:
+                raise
+            return False
+
+    items = list(items)
+    alive, openings = agg_openings(vk, items)
+    ok = refused_is_false(lambda: dp.verify_agg(be, vk["pcs"][1], openings)) if alive else True
+    out = [False] * len(items)
+    for n in alive:
+        out[n] = True if ok else refused_is_false(lambda: verify(be, vk, *items[n]))
+    return out
+
+
+def verify_agg(be, vk: dict, public_inputs, proof: dict) -> bool:
+    """`verify` with ONE pairing call instead of two or three: verify_many of one proof"""
+    return verify_many(be, vk, [(public_inputs, proof)])[0]
 
 
 def proof_digest(proof: dict) -> str:

@@ -210,16 +210,40 @@ def check_points(be, proof: dict) -> list:
     return [(*parts[int(i)], int(status[int(i)])) for i in np.nonzero(status)[0]]
 
 
-def verify_bytes(be, vk: dict, public_inputs, data) -> bool:
-    """proof_from_bytes, the header against the vk (gate kind, lookup, mu, l), then plonk.verify; any refusal is False"""
-    from .plonk import gate_of, has_lookup, verify
+def _record_for(be, vk: dict, data):
+    """the record of the bytes when its header agrees with the vk (gate kind, lookup, mu, l) and every point passes; None otherwise"""
+    from .plonk import gate_of, has_lookup
 
     try:
         data = bytes(data)
         hdr = parse_header(data)
         if (hdr["gate"], hdr["lookup"], hdr["mu"], hdr["l"]) != (gate_of(vk).kind, has_lookup(vk), int(vk["mu"]), int(vk["l"])):
-            return False
-        proof = _record(be, parse_proof(data, hdr))  # the body is parsed once
+            return None
+        return _record(be, parse_proof(data, hdr))  # the body is parsed once
     except (KeyError, ValueError, TypeError):
+        return None
+
+
+def verify_bytes(be, vk: dict, public_inputs, data, aggregate: bool = False) -> bool:
+    """proof_from_bytes, the header against the vk (gate kind, lookup, mu, l), then plonk.verify (aggregate=True: plonk.verify_agg, one
+    pairing call); any refusal is False"""
+    from .plonk import verify, verify_agg
+
+    proof = _record_for(be, vk, data)
+    if proof is None:
         return False
-    return verify(be, vk, public_inputs, proof)
+    return (verify_agg if aggregate else verify)(be, vk, public_inputs, proof)
+
+
+def verify_bytes_many(be, vk: dict, items) -> list:
+    """verify_bytes for a list of (public_inputs, data): each encoding is validated on its own, the records that pass go through
+    plonk.verify_many -- ONE aggregated pairing check for all of them"""
+    from .plonk import verify_many
+
+    records = [(pi, _record_for(be, vk, data)) for pi, data in items]
+    good = [n for n, (_, rec) in enumerate(records) if rec is not None]
+    verdicts = verify_many(be, vk, [records[n] for n in good])
+    out = [False] * len(records)
+    for n, v in zip(good, verdicts):
+        out[n] = bool(v)
+    return out
