@@ -614,8 +614,8 @@ int zk_d_msm(zk_ctx *ctx, size_t count, const zk_srs *const *srs, const size_t *
  * struct's stride: a nonzero flag byte at offset 192 marks infinity), G1 Jacobian 18 u64 (any representative; the library's
  * results are normalised), Fr 4 u64 Montgomery.  Before anything is launched every point is checked to be canonical and on
  * its curve (ZK_ERR_INVALID otherwise).  Membership in the prime-order subgroups is NOT checked -- as for zk_srs_register it is
- * the caller's responsibility (arkworks' G1Affine / G2Affine guarantee it); off-subgroup points give meaningless values or
- * verdicts, never a fault or a hang.  A pair with a point at infinity contributes a factor 1.  Every call ends in one
+ * the caller's responsibility (arkworks' G1Affine / G2Affine guarantee it; zk_g1_check and zk_g2_check below are that check
+ * for points from elsewhere); off-subgroup points give meaningless values or verdicts, never a fault or a hang.  A pair with a point at infinity contributes a factor 1.  Every call ends in one
  * synchronisation of the ctx stream.
  *
  * Values: e(P, Q) is the optimal ate Miller value f_{|x|,Q}(P) (|x| = 0xd201000000010000, not conjugated) after the final
@@ -666,6 +666,28 @@ int zk_g1_decompress_check(zk_ctx *ctx, size_t count, const void *h_in48, uint64
 /* h_points18: count x 18 u64 Jacobian (X, Y, Z), Montgomery form, any representative; Z = 0 is infinity whatever X and Y are (as
  * in zk_pcs_verify_batch).  The curve equation is checked as Y^2 == X^3 + 4 Z^6: no inversion. */
 int zk_g1_check(zk_ctx *ctx, size_t count, const uint64_t *h_points18, uint8_t *h_status);
+
+/* ---- G2 points from outside: decompression and subgroup membership (csrc/zk_g2check.hip) ----------------------------------------
+ * The same two calls for the twist E'(Fq2): y^2 = x^3 + 4 (1 + u), whose cofactor has about 507 bits: the keys of a verifying key
+ * that comes from a file or another host.  One status byte per point, the values of the G1 calls; ZK_OK whenever the call ran,
+ * count = 0 included.  Each call makes one synchronisation of the ctx stream.
+ * Membership is psi(P) == [x]P with psi(x, y) = (c_x conj(x), c_y conj(y)), c_x = (1 + u)^(-(q-1)/3), c_y = (1 + u)^(-(q-1)/2), and
+ * x = -0xd201000000010000 (Scott, as above): one 64-bit scalar multiplication over Fq2, complete for every input, constant trip
+ * counts.  Infinity is a member. */
+#define ZK_G2_OK 0
+#define ZK_G2_BAD_ENCODING 1
+#define ZK_G2_NOT_ON_CURVE 2
+#define ZK_G2_NOT_IN_SUBGROUP 3
+/* h_in96: count x 96 bytes, the zcash / arkworks compressed encoding: big-endian, x.c1 in bytes 0..47 and x.c0 in bytes 48..95, top
+ * three bits of byte 0 = (compressed, infinity, y is the larger of (y, -y): y.c1 > (q - 1) / 2, or y.c1 = 0 and y.c0 > (q - 1) / 2).
+ * Refused with status 1: the compressed bit clear; x.c0 >= q or x.c1 >= q; the infinity bit together with any other bit or byte.
+ * h_out24: count x 24 u64 affine records x.c0 | x.c1 | y.c0 | y.c1, Montgomery form -- what zk_pairing and zk_pcs_vk_create take;
+ * written for status 0 and 3, all zero for status 1 and 2 and for infinity. */
+int zk_g2_decompress_check(zk_ctx *ctx, size_t count, const void *h_in96, uint64_t *h_out24, uint8_t *h_status);
+/* h_g2: count affine records at g2_stride bytes as zk_pairing takes them (192, or the Rust struct's stride: a nonzero flag byte at
+ * offset 192 marks infinity; all zero is infinity).  Status 1: a coordinate >= q; 2: y^2 != x^3 + 4 (1 + u).  g2_stride < 192:
+ * ZK_ERR_INVALID. */
+int zk_g2_check(zk_ctx *ctx, size_t count, const void *h_g2, size_t g2_stride, uint8_t *h_status);
 
 /* ---- aggregated PCS verification: many openings, one pairing check (csrc/zk_g1seg.hip, csrc/zk_pairing.hip) ----------------------
  * The G2 arguments of PolynomialCommitment::verify are the fixed keys g2, s_0 g2, ..., so any number of openings of mixed variable

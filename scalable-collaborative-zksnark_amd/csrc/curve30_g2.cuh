@@ -145,7 +145,9 @@ __device__ __forceinline__ Xyzz2 xyzz2_dbl_affine(const Fq2x& x, const Fq2x& y) 
     return xyzz2_dbl(p);
 }
 
-// acc += p (affine; `neg`: -p), madd-2008-s with the bounds of curve30.cuh
+// acc += p (affine; `neg`: -p), madd-2008-s with the bounds of curve30.cuh.  COMPLETE, and it has to stay so: infinity on either side,
+// equal operands (doubling) and opposite operands (cancellation) are handled below, and the membership ladder of zk_g2check.hip, which
+// meets all of them on points of small order, relies on it (as on xyzz2_dbl passing infinity through).
 __device__ __forceinline__ void xyzz2_madd(Xyzz2& acc, const Aff2& p, bool neg) {
     if (aff2_is_inf(p)) return;
     if (xyzz2_is_inf(acc)) {

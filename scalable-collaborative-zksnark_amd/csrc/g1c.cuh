@@ -1,5 +1,5 @@
-// g1c.cuh -- what the one-lane-per-point G1 kernels share (zk_g1check.hip: validation; zk_g1seg.hip: segmented linear combination):
-// the curve constant, the canonical-coordinate tests and the complete XYZZ doubling / addition with the doubling inlined.
+// g1c.cuh -- what the one-lane-per-point kernels share (zk_g1check.hip, zk_g2check.hip: validation; zk_g1seg.hip: segmented linear
+// combination): the Fq constants, the canonical-coordinate and sign tests and the complete G1 XYZZ doubling / addition with the doubling inlined.
 #pragma once
 #include "curve30.cuh"
 
@@ -8,6 +8,14 @@ namespace zk {
 namespace g1c {
 __host__ __device__ constexpr u32 FOUR(int i) {  // 4 (the curve's b), internal form
     constexpr u32 t[13] = {0x0347fcb8u, 0x27600000u, 0x12002b11u, 0x3803379bu, 0x090c7212u, 0x1a7e0e88u, 0x373e0376u, 0x26d0b683u, 0x17bb09b0u, 0x17663c4au, 0x12ca7c51u, 0x167f3e80u, 0x000577a6u};
+    return t[i];
+}
+__host__ __device__ constexpr u32 R2(int i) {  // 2^780 mod q: canonical integer -> internal form (x 2^390)
+    constexpr u32 t[13] = {0x0510070fu, 0x3b19070du, 0x0132243au, 0x299bb0e8u, 0x3507af6eu, 0x3b81ec77u, 0x21b145efu, 0x0a487bb4u, 0x370a4144u, 0x05dcb4cbu, 0x18c97900u, 0x3812b364u, 0x000f696eu};
+    return t[i];
+}
+__host__ __device__ constexpr u32 HALF(int i) {  // (q - 1) / 2, a plain integer
+    constexpr u32 t[13] = {0x3fffd555u, 0x33fdffffu, 0x0a9ffffdu, 0x157fffd6u, 0x187b120fu, 0x21a541edu, 0x2895fb39u, 0x29709e70u, 0x166bb23bu, 0x0f6c8697u, 0x34d258ddu, 0x3d472ffcu, 0x000d0088u};
     return t[i];
 }
 enum : unsigned char { kOk = 0, kBadEncoding = 1, kNotOnCurve = 2, kNotInG1 = 3 };
@@ -20,6 +28,8 @@ enum : unsigned char { kOk = 0, kBadEncoding = 1, kNotOnCurve = 2, kNotInG1 = 3 
         return r;                                                \
     }
 ZK_G1C_CONST(g1c_four, g1c::FOUR)
+ZK_G1C_CONST(g1c_r2, g1c::R2)
+ZK_G1C_CONST(g1c_one_ref, Q30::C384)  // 2^384 mod q: the reference form of 1
 
 // v < q for a normalised v < 2^384
 __device__ __forceinline__ bool g1c_lt_q(const Fq30& v) {
@@ -80,6 +90,14 @@ __device__ __forceinline__ Xyzz30 g1c_add(const Xyzz30& a, const Xyzz30& b) {
     r.zz = ZZ3;
     r.zzz = f30_mul(f30_mul(a.zzz, b.zzz), PPP);
     return r;
+}
+
+// v > (q - 1) / 2 for a canonical plain integer v
+__device__ __forceinline__ bool g1c_is_larger(const Fq30& v) {
+    u32 bw = 0;
+#pragma unroll
+    for (int i = 0; i < 13; i++) bw = (g1c::HALF(i) - v.l[i] - bw) >> 31;
+    return bw != 0;
 }
 
 // One 18-word Jacobian record (X, Y, Z), reference Montgomery form, any representative, as XYZZ: canonical coordinates and

@@ -760,6 +760,14 @@ int zk_g1_check(zk_ctx* ctx, size_t count, const uint64_t* h_points18, uint8_t* 
     NEED(ctx, count == 0 || (h_points18 && h_status));
     return g1_check(ctx, count, h_points18, h_status);
 }
+int zk_g2_decompress_check(zk_ctx* ctx, size_t count, const void* h_in96, uint64_t* h_out24, uint8_t* h_status) {
+    NEED(ctx, count == 0 || (h_in96 && h_out24 && h_status));
+    return g2_decompress_check(ctx, count, h_in96, h_out24, h_status);
+}
+int zk_g2_check(zk_ctx* ctx, size_t count, const void* h_g2, size_t g2_stride, uint8_t* h_status) {
+    NEED(ctx, count == 0 || (h_g2 && h_status));
+    return g2_check(ctx, count, h_g2, g2_stride, h_status);
+}
 int zk_g1_lincomb_seg(zk_ctx* ctx, size_t segments, const size_t* h_start, const uint64_t* h_points18, const uint64_t* h_scalars, uint64_t* h_out18) {
     NEED(ctx, segments == 0 || (h_start && h_out18));
     return g1_lincomb_seg(ctx, segments, h_start, h_points18, h_scalars, h_out18);

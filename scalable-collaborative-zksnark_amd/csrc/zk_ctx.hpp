@@ -362,6 +362,9 @@ int pcs_verify_agg(zk_ctx* ctx, const zk_pcs_vk* vk, size_t count, const size_t*
 // ---- zk_g1check.hip ----
 int g1_decompress_check(zk_ctx* ctx, size_t count, const void* h_in48, uint64_t* h_out18, uint8_t* h_status);
 int g1_check(zk_ctx* ctx, size_t count, const uint64_t* h_points18, uint8_t* h_status);
+// ---- zk_g2check.hip ----
+int g2_decompress_check(zk_ctx* ctx, size_t count, const void* h_in96, uint64_t* h_out24, uint8_t* h_status);
+int g2_check(zk_ctx* ctx, size_t count, const void* h_g2, size_t g2_stride, uint8_t* h_status);
 // ---- zk_g1seg.hip ----
 // h_bad, h_why (optional): the term a ZK_ERR_INVALID names (~0 otherwise) and what is wrong with it
 int g1_lincomb_seg(zk_ctx* ctx, size_t segments, const size_t* h_start, const uint64_t* h_points18, const uint64_t* h_scalars, uint64_t* h_out18,

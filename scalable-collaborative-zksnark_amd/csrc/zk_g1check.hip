@@ -21,18 +21,10 @@
 namespace zk {
 
 namespace g1c {
-__host__ __device__ constexpr u32 R2(int i) {  // 2^780 mod q: canonical integer -> internal form (x 2^390)
-    constexpr u32 t[13] = {0x0510070fu, 0x3b19070du, 0x0132243au, 0x299bb0e8u, 0x3507af6eu, 0x3b81ec77u, 0x21b145efu, 0x0a487bb4u, 0x370a4144u, 0x05dcb4cbu, 0x18c97900u, 0x3812b364u, 0x000f696eu};
-    return t[i];
-}
 // beta = 0x5f19672fdf76ce51ba69c6076a0f77eaddb3a93be6f89688de17d813620a00022e01fffffffefffe, internal form: the cube root of unity whose
 // endomorphism is multiplication by -x^2 on G1 (the other one belongs to x^2 - 1)
 __host__ __device__ constexpr u32 BETA(int i) {
     constexpr u32 t[13] = {0x229d39fcu, 0x11661b79u, 0x3a68a8f8u, 0x09dabbd8u, 0x12744b7eu, 0x22bc97d4u, 0x3c5ccd3eu, 0x1cf87540u, 0x0197e4f4u, 0x3433d1ecu, 0x0d20861fu, 0x33953662u, 0x000edc53u};
-    return t[i];
-}
-__host__ __device__ constexpr u32 HALF(int i) {  // (q - 1) / 2, a plain integer
-    constexpr u32 t[13] = {0x3fffd555u, 0x33fdffffu, 0x0a9ffffdu, 0x157fffd6u, 0x187b120fu, 0x21a541edu, 0x2895fb39u, 0x29709e70u, 0x166bb23bu, 0x0f6c8697u, 0x34d258ddu, 0x3d472ffcu, 0x000d0088u};
     return t[i];
 }
 // (q + 1) / 4 in 32-bit words, 379 bits
@@ -42,18 +34,9 @@ constexpr unsigned long long kXAbs = 0xd201000000010000ULL;
 constexpr int kBlk = 64;
 }  // namespace g1c
 
-ZK_G1C_CONST(g1c_r2, g1c::R2)
 ZK_G1C_CONST(g1c_beta, g1c::BETA)
-ZK_G1C_CONST(g1c_one_ref, Q30::C384)  // 2^384 mod q: the reference form of 1
 #undef ZK_G1C_CONST
 
-// v > (q - 1) / 2 for a canonical plain integer v
-__device__ __forceinline__ bool g1c_is_larger(const Fq30& v) {
-    u32 bw = 0;
-#pragma unroll
-    for (int i = 0; i < 13; i++) bw = (g1c::HALF(i) - v.l[i] - bw) >> 31;
-    return bw != 0;
-}
 __device__ __forceinline__ void g1c_store_words(void* base, size_t byte_off, int nwords16, u32 v) {  // nwords16 x 16 bytes of v
     uint4* p = reinterpret_cast<uint4*>(reinterpret_cast<char*>(base) + byte_off);
     for (int i = 0; i < nwords16; i++) p[i] = make_uint4(v, v, v, v);

@@ -5,7 +5,9 @@
 //
 //     bin/plonk_check --mu M [--seed S] [--gate wide] [--witness] [--lookup | --lookup-fn [--find] [--break-lookup K]] [--break-gate K | --break-wire K | --bad-input | --break K|all]
 //                     [--circuit-only | --sample-only [--time-sample R]] [--bytes [--dump-proof FILE] [--torsion K]]
-//     bin/plonk_check --g1check-time K [--reps R]
+//                     (with --bytes: [--dump-vk FILE] [--dump-public FILE] [--vk-torsion K])
+//     bin/plonk_check --g1check-time K [--reps R] | --g2check-time K [--reps R] | --vk-vectors
+//     bin/plonk_check --verify-files VK PROOF PUBLIC [--host-checks]
 //     bin/plonk_check --mu M [--seed S] [--gate wide] [--lookup] --verify-many K [--break-one J]
 //
 // --verify-many K verifies K proofs under ONE key with ONE pairing check (plonk_verify_many: zk_pcs_verify_agg).  The key, and with it the
@@ -21,6 +23,16 @@
 // the SHA-256 of the bytes -- one digest for one seed in both hosts -- and the verdict; --dump-proof FILE writes the bytes.  --torsion K adds
 // a point of order 3 to point K of the encoding (K counts the G1 points in the order of the bytes) before verifying: the point stays on the
 // curve and leaves G1, and the refusal names it ("refused: opening point 7 of v_batch: not in the subgroup", exit 1).
+// --bytes also encodes the verifying key (zkhost/vk_io.hpp: the byte format of zkhip/vk_io.py, the raw G2 keys in it) and prints its SHA-256
+// -- one digest for one seed in both hosts; --dump-vk FILE and --dump-public FILE write the key and the public inputs (l canonical 32-byte
+// Fr) beside --dump-proof.  --vk-torsion K adds a point of order 13 to G2 key K of the key's encoding and reads it back: the point stays on
+// the twist and leaves G2, and the refusal names it ("refused: G2 key 3: not in the subgroup", exit 1).
+// --verify-files VK PROOF PUBLIC verifies from three files in a process that never preprocesses: the key's points are validated on the device
+// (--host-checks: by the serial rules), the pairing keys rebuilt, then verify_bytes.  Prints the SHA-256 of each file and "verdict accepted"
+// (exit 0), "verdict rejected" (1) or "verdict refused: <cause>" (2): the lines of tools/plonk_verify.py.
+// --vk-vectors needs no GPU: the encoding of a synthetic key (commitments (3 + j) G1, keys (5 + 7 j) G2, mu = 4, l = 2) for both gate kinds
+// with and without a lookup, read back by the serial rules, and the refusal of key 3 plus a point of order 13; one line each.
+// --g2check-time K needs no GPU: g2_decompress_check_host on G2, 2 G2, .., K G2, as --g1check-time.
 // --g1check-time K needs no GPU: the host rule (g1_decompress_check_host, serial big integers) on the K points G, 2G, .., KG, warm-up 3,
 // the median of R (default 20) calls, one line in ms -- the compiled host's column of tools/g1check_time.py.
 // --lookup proves the test circuit with lookup rows (zkhip.plonk.sample_circuit_lookup, mu >= 3) under the label + "-lookup": three opening
@@ -60,6 +72,7 @@
 #include "zkhost/plonk.hpp"
 #include "zkhost/proof_io.hpp"
 #include "zkhost/sha256.hpp"
+#include "zkhost/vk_io.hpp"
 #include <chrono>
 
 using namespace zkhost;
@@ -73,8 +86,9 @@ static bool number(const char *s, long long &out) {
 struct Options {
     long long mu = -1, seed = 7, break_gate = -1, break_wire = -1, break_lookup = -1, break_part = -1;
     long long time_sample = 0, torsion = -1, g1check_time = 0, reps = 20, verify_many = 0, break_one = -1;
-    bool bytes = false;
-    std::string dump_proof;
+    long long vk_torsion = -1, g2check_time = 0;
+    bool bytes = false, vk_vectors = false, host_checks = false;
+    std::string dump_proof, dump_vk, dump_public, files[3];
     bool bad_input = false, wide = false, lookup = false, break_all = false, find = false, witness = false, lookup_fn = false;
 };
 
@@ -132,6 +146,127 @@ static int g1check_time(const Options &o) {
     return all_ok ? 0 : 1;
 }
 
+// ---- G2 on the host for the modes below ----
+static detail::Jac2 g2_generator() {
+    detail::Fq2 x{detail::fq_words(kG2Gen[0]), detail::fq_words(kG2Gen[1])}, y{detail::fq_words(kG2Gen[2]), detail::fq_words(kG2Gen[3])};
+    return {x, y, detail::Fq2::one()};
+}
+static G2Rec g2_affine_record(const detail::Jac2 &p) {
+    if (p.z.is_zero()) return G2Rec{};
+    const detail::Fq2 zi = detail::fq2_inverse(p.z), zi2 = zi * zi;
+    return detail::g2_record(p.x * zi2, p.y * zi2 * zi);
+}
+static detail::Jac2 g2_times(const detail::Jac2 &g, unsigned k) {
+    detail::Jac2 acc = detail::j2_inf();
+    for (unsigned i = 0; i < k; ++i) acc = detail::j2_add(acc, g);
+    return acc;
+}
+// a point of order 13 of the twist (tests/g2check_model.py, points(1)["order13"]), compressed
+static const char kOrder13[] = "950a3bc83828ad1e76601cd7f02dd2b6cf3d796cb9d253fb4890132f540cd4e032b00cb52033eb04480ae31d5cb2b53409d9acc6dfec295b33b81207e234d0806642df2fc6b3dce14c0c3ecc7380a280338c1b757d0411eaec597b1f6547a4fe";
+// key K of the encoding += that point
+static void add_vk_torsion(Bytes &vkb, size_t K) {
+    const ProofHeader h = parse_vk(vkb);
+    if (K >= h.mu + 2) throw std::invalid_argument("--vk-torsion names one of the key's " + std::to_string(h.mu + 2) + " G2 keys");
+    const size_t off = kProofHeaderBytes + 48 * vk_commitment_count(h.gate, h.lookup) + 96 * K;
+    uint8_t t[96];
+    for (int i = 0; i < 96; ++i) t[i] = (uint8_t)std::stoul(std::string(kOrder13 + 2 * i, 2), nullptr, 16);
+    detail::Fq2 x, y, tx, ty;
+    bool inf = false, tinf = false;
+    if (detail::g2_decode(&vkb[off], x, y, inf) || detail::g2_decode(t, tx, ty, tinf)) throw std::invalid_argument("--vk-torsion: key " + std::to_string(K) + " does not decode");
+    const detail::Jac2 sum = detail::j2_add(inf ? detail::j2_inf() : detail::Jac2{x, y, detail::Fq2::one()}, detail::Jac2{tx, ty, detail::Fq2::one()});
+    Bytes enc;
+    g2_serialize_compressed(g2_affine_record(sum), enc);
+    std::memcpy(&vkb[off], enc.data(), 96);
+}
+static std::string sha_hex(const Bytes &b) {
+    Sha256 h;
+    h.update(b.data(), b.size());
+    return h.hex();
+}
+
+static int g2check_time(const Options &o) {
+    const size_t k = (size_t)o.g2check_time;
+    const detail::Jac2 G = g2_generator();
+    detail::Jac2 acc = detail::j2_inf();
+    Bytes enc;
+    for (size_t i = 0; i < k; ++i) {
+        acc = detail::j2_add(acc, G);
+        g2_serialize_compressed(g2_affine_record(acc), enc);
+    }
+    std::vector<G2Rec> pts;
+    std::vector<uint8_t> st;
+    std::vector<double> t;
+    for (long long i = 0; i < 3 + o.reps; ++i) {
+        const auto t0 = std::chrono::steady_clock::now();
+        g2_decompress_check_host(enc.data(), k, pts, st);
+        if (i >= 3) t.push_back(std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+    }
+    bool all_ok = true;
+    for (uint8_t s : st) all_ok = all_ok && s == kG2Ok;
+    std::sort(t.begin(), t.end());
+    const size_t n = t.size();
+    Sha256 h;
+    h.update(pts.data(), 192 * pts.size());
+    std::printf("g2check host points %zu ms %.6f all_ok %d points_sha256 %s\n", k, n % 2 ? t[n / 2] : 0.5 * (t[n / 2 - 1] + t[n / 2]), all_ok ? 1 : 0, h.hex().c_str());
+    return all_ok ? 0 : 1;
+}
+
+static int vk_vectors() {
+    const G1Affine g = g1_deserialize_compressed((const uint8_t *)"\x97\xf1\xd3\xa7\x31\x97\xd7\x94\x26\x95\x63\x8c\x4f\xa9\xac\x0f\xc3\x68\x8c\x4f\x97\x74\xb9\x05"
+                                                                   "\xa1\x4e\x3a\x3f\x17\x1b\xac\x58\x6c\x55\xe8\x3f\xf9\x7a\x1a\xef\xfb\x3a\xf0\x0a\xdb\x22\xc6\xbb");
+    const detail::JacQ G1g{g.x, g.y, Fq::one()};
+    const detail::Jac2 G2g = g2_generator();
+    const size_t mu = 4;
+    bool all = true;
+    for (int kind = 0; kind < 2; ++kind)
+        for (int lookup = 0; lookup < 2; ++lookup) {
+            PlonkVk vk;
+            vk.gate = kind ? GateKind::wide : GateKind::basic, vk.lookup = lookup != 0, vk.mu = mu, vk.l = 2;
+            for (size_t j = 0; j < vk_commitment_count(vk.gate, vk.lookup); ++j) {
+                detail::JacQ acc{Fq::one(), Fq::one(), Fq::zero()};
+                for (size_t i = 0; i < 3 + j; ++i) acc = detail::jq_add(acc, G1g);
+                G1 w{};
+                std::memcpy(&w[0], acc.x.v, 48), std::memcpy(&w[6], acc.y.v, 48), std::memcpy(&w[12], acc.z.v, 48);  // (any representative)
+                vk.commitments.push_back(w);
+            }
+            for (size_t j = 0; j < mu + 2; ++j) vk.g2.push_back(g2_affine_record(g2_times(G2g, 5 + 7 * (unsigned)j)));
+            Bytes data = vk_to_bytes(vk);
+            const PlonkVk back = vk_from_bytes(nullptr, data, true);
+            const bool same = vk_to_bytes(back) == data && back.g2 == vk.g2 && data.size() == vk_size(vk.gate, vk.lookup, mu);
+            add_vk_torsion(data, 3);
+            std::string why = "accepted";
+            try {
+                vk_from_bytes(nullptr, data, true);
+            } catch (const std::invalid_argument &e) {
+                why = e.what();
+            }
+            std::printf("vk vectors gate=%s lookup=%d bytes %zu sha256 %s round_trip %d torsion: %s\n", kind ? "wide" : "basic", lookup, data.size(),
+                        sha_hex(vk_to_bytes(vk)).c_str(), same ? 1 : 0, why.c_str());
+            all = all && same && why == "G2 key 3: not in the subgroup";
+        }
+    return all ? 0 : 1;
+}
+
+// --verify-files: no preprocess in this process
+static int verify_from_files(const Options &o) {
+    Bytes data[3];
+    const char *names[3] = {"vk", "proof", "public"};
+    for (int i = 0; i < 3; ++i) {
+        data[i] = detail::read_file(o.files[i]);
+        std::printf("%s_sha256 %s bytes %zu\n", names[i], sha_hex(data[i]).c_str(), data[i].size());
+    }
+    Ctx be(0);
+    try {
+        std::string why;
+        const bool ok = verify_files(be, data[0], data[1], data[2], o.host_checks, &why);
+        std::printf(ok ? "verdict accepted\n" : "verdict rejected\n");
+        return ok ? 0 : 1;
+    } catch (const std::invalid_argument &e) {
+        std::printf("verdict refused: %s\n", e.what());
+        return 2;
+    }
+}
+
 // --bytes: encode, (--torsion K: point K += a point of order 3), verify the bytes
 static bool check_bytes(Ctx &be, const Options &o, const PcsVk &vk_mu, const PcsVk &vk_mu1, const PlonkVk &vk, const FrVec &pi, const PlonkProof &proof) {
     Bytes data = proof_to_bytes(proof);
@@ -139,6 +274,20 @@ static bool check_bytes(Ctx &be, const Options &o, const PcsVk &vk_mu, const Pcs
     h.update(data.data(), data.size());
     std::printf("bytes sha256 %s (%zu bytes)\n", h.hex().c_str(), data.size());
     if (!o.dump_proof.empty()) detail::write_file(o.dump_proof, data);
+    Bytes vkb = vk_to_bytes(vk);
+    std::printf("vk sha256 %s (%zu bytes)\n", sha_hex(vkb).c_str(), vkb.size());
+    if (!o.dump_vk.empty()) detail::write_file(o.dump_vk, vkb);
+    if (!o.dump_public.empty()) detail::write_file(o.dump_public, public_to_bytes(pi));
+    if (o.vk_torsion >= 0) {
+        add_vk_torsion(vkb, (size_t)o.vk_torsion);
+        std::printf("vk-torsion: a point of order 13 added to G2 key %lld\n", o.vk_torsion);
+        try {
+            vk_from_bytes(&be, vkb);
+        } catch (const std::invalid_argument &e) {
+            std::printf("refused: %s\n", e.what());
+            return false;
+        }
+    }
     if (o.torsion >= 0) {
         const ParsedProof pp = parse_proof(data);
         const size_t K = (size_t)o.torsion;
@@ -218,6 +367,11 @@ static int run(const Options &o) {
     std::shared_ptr<PcsVk> vk_mu1 = make_pcs_vk(be, good.s), vk_mu = make_pcs_vk(be, FrVec(good.s.begin() + 1, good.s.end()));
     PlonkVk vk;
     const PlonkPk pk = preprocess(be, cub.mature(), good, vk);
+    if (o.bytes) {  // the raw keys, for the key's encoding
+        const std::vector<uint64_t> pg2 = powers_of_g2(be, good.s);
+        vk.g2.resize(pg2.size() / 24);
+        std::memcpy(vk.g2.data(), pg2.data(), 8 * pg2.size());
+    }
     DevPtr idx;
     if (o.lookup && !o.find) {
         idx = be.alloc(4 * N);
@@ -295,7 +449,14 @@ int main(int argc, char **argv) {
         else if (k == "--find") o.find = true;
         else if (k == "--witness") o.witness = true;
         else if (k == "--bytes") o.bytes = true;
+        else if (k == "--vk-vectors") o.vk_vectors = true;
+        else if (k == "--host-checks") o.host_checks = true;
         else if (i + 1 < argc && k == "--dump-proof") o.dump_proof = argv[++i];
+        else if (i + 1 < argc && k == "--dump-vk") o.dump_vk = argv[++i];
+        else if (i + 1 < argc && k == "--dump-public") o.dump_public = argv[++i];
+        else if (i + 3 < argc && k == "--verify-files") o.files[0] = argv[i + 1], o.files[1] = argv[i + 2], o.files[2] = argv[i + 3], i += 3;
+        else if (i + 1 < argc && k == "--vk-torsion") usage = !number(argv[++i], o.vk_torsion);
+        else if (i + 1 < argc && k == "--g2check-time") usage = !number(argv[++i], o.g2check_time) || o.g2check_time < 1;
         else if (i + 1 < argc && k == "--torsion") usage = !number(argv[++i], o.torsion);
         else if (i + 1 < argc && k == "--g1check-time") usage = !number(argv[++i], o.g1check_time) || o.g1check_time < 1;
         else if (i + 1 < argc && k == "--verify-many") usage = !number(argv[++i], o.verify_many) || o.verify_many < 1 || o.verify_many > 256;
@@ -321,13 +482,34 @@ int main(int argc, char **argv) {
             return 2;
         }
     }
+    if ((o.g2check_time > 0 || o.vk_vectors) && !usage && mu < 0 && argc <= 5 && !(o.g2check_time > 0 && o.vk_vectors)) {
+        try {
+            return o.vk_vectors ? (argc == 2 ? vk_vectors() : 2) : g2check_time(o);
+        } catch (const std::exception &e) {
+            std::fprintf(stderr, "plonk_check: %s\n", e.what());
+            return 2;
+        }
+    }
+    if (!o.files[0].empty() && !usage && mu < 0 && argc == 5 + (o.host_checks ? 1 : 0)) {
+        if (zk_device_count() <= 0) {
+            std::fprintf(stderr, "plonk_check: no GPU visible -- this host has no CPU fallback\n");
+            return 2;
+        }
+        try {
+            return verify_from_files(o);
+        } catch (const std::exception &e) {
+            std::fprintf(stderr, "plonk_check: %s\n", e.what());
+            return 2;
+        }
+    }
+    usage = usage || o.g2check_time > 0 || o.vk_vectors || !o.files[0].empty() || o.host_checks || ((o.vk_torsion >= 0 || !o.dump_vk.empty() || !o.dump_public.empty()) && !o.bytes);
     usage = usage || (o.break_one >= 0 && o.break_one >= o.verify_many) ||
             (o.verify_many > 0 && (o.bytes || tamper || bad_input || o.witness || o.find || o.lookup_fn || break_gate >= 0 || break_wire >= 0 || o.break_lookup >= 0 || only_circuit));
     usage = usage || o.g1check_time > 0 || ((o.torsion >= 0 || !o.dump_proof.empty()) && !o.bytes) || (o.bytes && tamper);
     if (usage || mu < 0 || (break_gate >= 0) + (break_wire >= 0) + (bad_input ? 1 : 0) + (o.break_lookup >= 0) + (tamper ? 1 : 0) > 1 ||
         (o.break_all && o.break_part >= 0) || (o.break_lookup >= 0 && !o.lookup) || (o.find && !o.lookup) || (o.lookup && (break_gate >= 0 || break_wire >= 0)) ||
         (o.witness && (break_gate >= 0 || break_wire >= 0)) || (o.time_sample > 0 && !only_circuit) || (o.lookup_fn && (!wide || o.time_sample > 0))) {
-        std::fprintf(stderr, "usage: plonk_check --mu M [--seed S] [--gate wide] [--witness] [--lookup | --gate wide --lookup-fn [--find] [--break-lookup K]] [--break-gate K | --break-wire K | --bad-input | --break K|all] [--circuit-only | --sample-only [--time-sample R]] [--bytes [--dump-proof FILE] [--torsion K]] | --verify-many K [--break-one J] | --g1check-time K [--reps R]\n");
+        std::fprintf(stderr, "usage: plonk_check --mu M [--seed S] [--gate wide] [--witness] [--lookup | --gate wide --lookup-fn [--find] [--break-lookup K]] [--break-gate K | --break-wire K | --bad-input | --break K|all] [--circuit-only | --sample-only [--time-sample R]] [--bytes [--dump-proof FILE] [--torsion K] [--dump-vk FILE] [--dump-public FILE] [--vk-torsion K]] | --verify-many K [--break-one J] | --g1check-time K [--reps R] | --g2check-time K [--reps R] | --vk-vectors | --verify-files VK PROOF PUBLIC [--host-checks]\n");
         return 2;
     }
     if (mu < 2 || mu > 24) {

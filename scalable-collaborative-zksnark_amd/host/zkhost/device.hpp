@@ -46,6 +46,7 @@ struct CtxHandle {
 };
 using CtxRef = std::shared_ptr<CtxHandle>;
 using G2 = std::array<uint64_t, 36>;  // normalised G2 projective (3 x Fq2), as zk_msm_g2 returns it
+using G2Rec = std::array<uint64_t, 24>;  // affine G2 x.c0 | x.c1 | y.c0 | y.c1, Montgomery form; all zero: infinity (what zk_pcs_vk_create takes)
 
 // the verifying key of PolynomialCommitment held by the library (zk_pcs_vk: g1 and powers_of_g2)
 struct PcsVk {
@@ -787,6 +788,19 @@ class Ctx {
     std::vector<uint8_t> g1_check(const G1Vec &points) {
         std::vector<uint8_t> status(points.size(), 0);
         if (!points.empty()) check(zk_g1_check(h_, points.size(), points[0].data(), status.data()));
+        return status;
+    }
+    // zk_g2_decompress_check: k x 96 bytes of compressed G2 -> the affine records and one status per point (0 ok, 1 bad encoding,
+    // 2 x not on the twist, 3 not in G2); the check zk_pairing and zk_pcs_vk_create leave to their caller
+    void g2_decompress_check(const uint8_t *in96, size_t k, std::vector<G2Rec> &points, std::vector<uint8_t> &status) {
+        points.assign(k, G2Rec{});
+        status.assign(k, 0);
+        if (k) check(zk_g2_decompress_check(h_, k, in96, points[0].data(), status.data()));
+    }
+    // zk_g2_check: affine records -> one status per point
+    std::vector<uint8_t> g2_check(const std::vector<G2Rec> &points) {
+        std::vector<uint8_t> status(points.size(), 0);
+        if (!points.empty()) check(zk_g2_check(h_, points.size(), points[0].data(), 192, status.data()));
         return status;
     }
 

@@ -69,6 +69,7 @@ struct PlonkVk {
     size_t mu = 0, l = 0;
     G1Vec commitments;  // the selectors, ssigma_0, ssigma_1, ssigma_2; with a lookup then qk, t0, t1, t2
     bool lookup = false;
+    std::vector<G2Rec> g2;  // the mu + 2 raw keys [g2, s_0 g2, .., s_mu g2] when the caller has set them (pcs_vk.hpp powers_of_g2); read by vk_io.hpp only
 };
 struct PlonkPk {
     GateKind gate = GateKind::basic;

@@ -12,7 +12,7 @@
 // parse_proof refuses a wrong magic or version, an unknown gate kind or lookup flag, any length but the header's (trailing bytes
 // included) and any Fr >= r.  The points are refused by the rule of zk_g1_decompress_check (include/zkhip.h): on the device in ONE call
 // (Ctx::g1_decompress_check), or with host = true by g1_decompress_check_host below, the same rule in serial big-integer arithmetic.
-// NOT checked: the verifying key -- its commitments and G2 keys are the verifier's own -- any encoding of it, and G2 membership.
+// NOT checked here: the verifying key.  One that comes from outside is read and validated by vk_io.hpp.
 #pragma once
 #include <stdexcept>
 #include <string>

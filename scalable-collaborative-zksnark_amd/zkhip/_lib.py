@@ -131,6 +131,8 @@ SYMBOLS = [
     ("zk_pcs_verify_batch", _i, [_vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp]),
     ("zk_g1_decompress_check", _i, [_vp, _sz, _vp, _vp, _vp]),
     ("zk_g1_check", _i, [_vp, _sz, _vp, _vp]),
+    ("zk_g2_decompress_check", _i, [_vp, _sz, _vp, _vp, _vp]),
+    ("zk_g2_check", _i, [_vp, _sz, _vp, _sz, _vp]),
     ("zk_g1_lincomb_seg", _i, [_vp, _sz, _vp, _vp, _vp, _vp]),
     ("zk_pcs_verify_agg", _i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("zk_pcs_agg_weights", _i, [_sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

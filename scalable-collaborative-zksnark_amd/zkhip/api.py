@@ -997,6 +997,33 @@ class Ctx:
             self._check(self.lib.zk_g1_check(self.h, len(pts), _h(pts), _h(st)))
         return st
 
+    # ---- G2 points from outside: decompression and subgroup membership (csrc/zk_g2check.hip) ----
+    def g2_decompress_check(self, data) -> Tuple[np.ndarray, np.ndarray]:
+        """k compressed G2 points (bytes, or a uint8 array of k x 96) -> (points [k, 24] affine Montgomery records, status [k] uint8):
+        0 ok, 1 bad encoding, 2 x not on the twist, 3 on the twist but not in G2 (include/zkhip.h; points of status 1 and 2 and
+        infinity are zero)"""
+        raw = np.ascontiguousarray(np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else data, dtype=np.uint8).reshape(-1)
+        if raw.size % 96:
+            raise ValueError(f"{raw.size} bytes is not a whole number of 96-byte points")
+        k = raw.size // 96
+        out = np.zeros((k, 24), dtype=np.uint64)
+        st = np.zeros(k, dtype=np.uint8)
+        if k:
+            self._check(self.lib.zk_g2_decompress_check(self.h, k, _h(raw), _h(out), _h(st)))
+        return out, st
+
+    def g2_check(self, points, g2_stride: int = 192) -> np.ndarray:
+        """points [k, 24] affine Montgomery records (or raw records at g2_stride bytes, as Ctx.pairing takes them) -> status [k] uint8:
+        0 ok, 1 a coordinate >= q, 2 not on the twist, 3 not in G2"""
+        pts = np.ascontiguousarray(points)
+        if g2_stride < 192 or pts.nbytes % g2_stride:
+            raise ValueError(f"{pts.nbytes} bytes is not a whole number of records of {g2_stride} bytes (>= 192)")
+        k = pts.nbytes // g2_stride
+        st = np.zeros(k, dtype=np.uint8)
+        if k:
+            self._check(self.lib.zk_g2_check(self.h, k, _h(pts), g2_stride, _h(st)))
+        return st
+
     # ---- aggregated PCS verification: many openings, one pairing check (csrc/zk_g1seg.hip, csrc/zk_pairing.hip) ----
     def g1_lincomb_seg(self, starts, points, scalars_canon) -> np.ndarray:
         """out[s] = sum_{starts[s] <= t < starts[s+1]} k_t P_t on the device: starts [segments + 1] offsets from 0, points [terms, 18]

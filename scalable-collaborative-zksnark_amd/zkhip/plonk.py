@@ -106,6 +106,7 @@ from . import wiring as wr
 from .field import R_MOD, fr_from_mont, fr_mont
 from .proof_io import check_points, parse_proof, proof_from_bytes, proof_to_bytes, verify_bytes, verify_bytes_many  # noqa: F401  (proof bytes, re-exported)
 from .transcript import HostTranscript, Transcript
+from .vk_io import check_vk, g2_records, parse_vk, verify_files, vk_from_bytes, vk_to_bytes  # noqa: F401  (vk bytes and the file verifier, re-exported)
 from .verify import _ints, _u64, eq_eval, round_chain, round_poly_at  # noqa: F401  (round_poly_at: importable from here as before)
 from .zerocheck import gate_value, wide_gate_value
 
@@ -214,7 +215,8 @@ def preprocess(be, pcs, circuit: dict, powers_of_g2=None):
     circuit: {"mu", "l", "q1": [N, 4], "q2": [N, 4] Montgomery Fr, "sigma": [3N] slot numbers} -- or, with "gate": "wide", the six selectors
     qL, qR, qM, qO, qC, qH in the place of q1, q2 (the commitments then in GATES["wide"].vk_tables order, and pk, vk carry "gate"); pcs: the levels of a PolynomialCommitment
     over mu + 1 variables; powers_of_g2 (optional): the SRS's [g2, s_0 g2, .., s_mu g2], from which the pairing keys of `verify` are made.
-    -> (pk, vk): vk = {"mu", "l", "commitments": [5, 18] in VK_TABLES order, "pcs": (vk_mu, vk_mu1) or None}; pk keeps the device tables.
+    -> (pk, vk): vk = {"mu", "l", "commitments": [5, 18] in VK_TABLES order, "pcs": (vk_mu, vk_mu1) or None, "g2": the [mu + 2, 24]
+    Montgomery records of powers_of_g2 or None -- read by vk_io.vk_to_bytes / check_vk only}; pk keeps the device tables.
     A circuit with "lookup" (module text): qk is checked to hold only 0 and 1, qk, t0, t1, t2 are committed after the gate's tables, and pk, vk
     carry "lookup": True.
     """
@@ -240,7 +242,8 @@ def preprocess(be, pcs, circuit: dict, powers_of_g2=None):
         tabs.update({k: be.to_device(v) for k, v in lk.items()})
         names, tag = names + LOOKUP_VK_TABLES, dict(tag, lookup=True)
     comms = np.stack([_u64(dp.commit(be, pcs, tabs[k], N), 18) for k in names])
-    vk = {"mu": mu, "l": l, "commitments": comms, "pcs": wr.verifying_keys(be, powers_of_g2) if powers_of_g2 is not None else None, **tag}
+    vk = {"mu": mu, "l": l, "commitments": comms, "pcs": wr.verifying_keys(be, powers_of_g2) if powers_of_g2 is not None else None,
+          "g2": g2_records(powers_of_g2) if powers_of_g2 is not None else None, **tag}
     return {"mu": mu, "l": l, "tables": tabs, "commitments": comms, "pcs": pcs, **tag}, vk
 
 

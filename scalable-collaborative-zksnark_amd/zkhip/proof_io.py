@@ -21,8 +21,9 @@ There is ONE encoding per record: parse_proof refuses a wrong magic or version, 
 header's (trailing bytes included) and any Fr >= r; the points are refused by the rule of zk_g1_decompress_check (non-canonical
 encodings, x off the curve, points outside the prime-order subgroup), on the device in ONE call or, host=True, in Python integers.
 
-What is NOT checked here: the verifying key.  It is the verifier's own and stays trusted -- its commitments, its G2 keys
-(wiring.verifying_keys) and any encoding of the vk are out of scope; G2 membership is not tested anywhere.
+What is NOT checked here: the verifying key.  A vk made by preprocess in this process is the verifier's own and stays trusted; one that
+comes from outside is read by vk_io.vk_from_bytes (or checked by vk_io.check_vk), which validates its commitments by the same G1 rule and
+its G2 keys by zk_g2_decompress_check / zk_g2_check.  zk_pairing and zk_pcs_vk_create themselves still test no membership.
 """
 from __future__ import annotations
 

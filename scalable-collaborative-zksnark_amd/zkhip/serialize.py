@@ -284,3 +284,132 @@ def g1_decompress_check_host(data):
             if not g1_in_subgroup((rest, y)):
                 st[i] = G1_NOT_IN_SUBGROUP
     return pts, st
+
+
+# ---------------------------------------------------------------------------------------
+# G2 points from outside: the rule of zk_g2_decompress_check (include/zkhip.h) in Python integers, for callers without a
+# device.  A point of the twist y^2 = x^3 + 4 (1 + u) is ((x.c0, x.c1), (y.c0, y.c1)) as in pairing.py.  96 bytes big-endian, x.c1
+# first; the sign bit names the larger of (y, -y): c1 decides, c0 when y.c1 = 0.  The status values are the G1 ones.
+# ---------------------------------------------------------------------------------------
+G2_OK, G2_BAD_ENCODING, G2_NOT_ON_CURVE, G2_NOT_IN_SUBGROUP = 0, 1, 2, 3
+G2_STATUS_TEXT = {G2_OK: "ok", G2_BAD_ENCODING: "bad encoding", G2_NOT_ON_CURVE: "x is not on the curve", G2_NOT_IN_SUBGROUP: "not in the subgroup"}
+# psi(x, y) = (PSI_CX conj(x), PSI_CY conj(y)) is multiplication by q = -X_ABS (mod r) on G2: PSI_CX = (1 + u)^(-(q-1)/3),
+# PSI_CY = (1 + u)^(-(q-1)/2) (derived, and checked on the generator, in tests/g2check_model.py)
+PSI_CX = (0, 0x1A0111EA397FE699EC02408663D4DE85AA0D857D89759AD4897D29650FB85F9B409427EB4F49FFFD8BFD00000000AAAD)
+PSI_CY = (0x135203E60180A68EE2E9C448D77A2CD91C3DEDD930B1CF60EF396489F61EB45E304466CF3E67FA0AF1EE7B04121BDEA2,
+          0x06AF0E0437FF400B6831E36D6BD17FFE48395DABC2D3435E77F76E17009241C5EE67992F72EC05F4C81084FBEDE3CC09)
+_HALF_Q = (Q_MOD - 1) // 2
+
+
+def _f2mul(a, b):
+    return ((a[0] * b[0] - a[1] * b[1]) % Q_MOD, (a[0] * b[1] + a[1] * b[0]) % Q_MOD)
+
+
+def _f2pow(a, e: int):
+    r = (1, 0)
+    for bit in bin(e)[2:]:
+        r = _f2mul(r, r)
+        if bit == "1":
+            r = _f2mul(r, a)
+    return r
+
+
+def _sqrt_fq2(a):
+    """a root of a in Fq2 or None (q = 3 mod 4: the two-exponentiation method of csrc/zk_g2check.hip, the candidate checked by squaring)"""
+    a = (a[0] % Q_MOD, a[1] % Q_MOD)
+    a1 = _f2pow(a, (Q_MOD - 3) // 4)
+    x0 = _f2mul(a1, a)
+    alpha = _f2mul(a1, x0)
+    if alpha == (Q_MOD - 1, 0):
+        y = (-x0[1] % Q_MOD, x0[0])
+    else:
+        y = _f2mul(_f2pow(((alpha[0] + 1) % Q_MOD, alpha[1]), (Q_MOD - 1) // 2), x0)
+    return y if _f2mul(y, y) == a else None
+
+
+def _g2_rhs(x):
+    t = _f2mul(_f2mul(x, x), x)
+    return ((t[0] + 4) % Q_MOD, (t[1] + 4) % Q_MOD)
+
+
+def _g2_y_is_larger(y) -> bool:
+    return y[1] > _HALF_Q or (y[1] == 0 and y[0] > _HALF_Q)
+
+
+def g2_serialize_compressed(P) -> bytes:
+    if P is None:
+        return bytes([0xC0]) + bytes(95)
+    (x0, x1), y = P
+    b = bytearray(x1.to_bytes(48, "big") + x0.to_bytes(48, "big"))
+    b[0] |= 0x80 | (0x20 if _g2_y_is_larger(y) else 0)
+    return bytes(b)
+
+
+def g2_deserialize_compressed(b: bytes):
+    """96 bytes -> the point of the twist (None: infinity); ValueError for what is no encoding of one.  Membership in G2 is NOT
+    tested here: g2_in_subgroup, or g2_decompress_check_host for both"""
+    st, P = _g2_decode(bytes(b))
+    if st:
+        raise ValueError(G2_STATUS_TEXT[st])
+    return P
+
+
+def _g2_decode(b: bytes):
+    """(status 0 / 1 / 2, point)"""
+    if len(b) != 96:
+        raise ValueError(f"{len(b)} bytes: a compressed G2 point has 96")
+    x1 = int.from_bytes(bytes([b[0] & 0x1F]) + b[1:48], "big")
+    x0 = int.from_bytes(b[48:], "big")
+    if not b[0] & 0x80:
+        return G2_BAD_ENCODING, None
+    if b[0] & 0x40:
+        return (G2_BAD_ENCODING if b[0] & 0x20 or x0 or x1 else G2_OK), None
+    if x0 >= Q_MOD or x1 >= Q_MOD:
+        return G2_BAD_ENCODING, None
+    y = _sqrt_fq2(_g2_rhs((x0, x1)))
+    if y is None:
+        return G2_NOT_ON_CURVE, None
+    if _g2_y_is_larger(y) != bool(b[0] & 0x20):
+        y = (-y[0] % Q_MOD, -y[1] % Q_MOD)
+    return G2_OK, ((x0, x1), y)
+
+
+def g2_in_subgroup(P) -> bool:
+    """psi(P) == [x]P = -[X_ABS]P for a point of the twist (Scott's test, the one of csrc/zk_g2check.hip); infinity is a member"""
+    from . import pairing as pr
+
+    if P is None:
+        return True
+    x, y = P
+    psi = (_f2mul(PSI_CX, (x[0], -x[1] % Q_MOD)), _f2mul(PSI_CY, (y[0], -y[1] % Q_MOD)))
+    return pr.g2_neg(pr.g2_mul(P, X_ABS)) == psi  # (X_ABS < r: g2_mul's reduction of the scalar does not touch it)
+
+
+def g2_point_words(P):
+    """the affine record of a point: 24 u64 x.c0 | x.c1 | y.c0 | y.c1, Montgomery form; all zero for infinity"""
+    import numpy as np
+
+    from .field import fq_mont
+
+    if P is None:
+        return np.zeros(24, dtype=np.uint64)
+    return np.concatenate([fq_mont(P[0][0]), fq_mont(P[0][1]), fq_mont(P[1][0]), fq_mont(P[1][1])])
+
+
+def g2_decompress_check_host(data):
+    """k compressed points (bytes or a uint8 array of k x 96) -> (points [k, 24], status [k] uint8): the results of
+    Ctx.g2_decompress_check, bit for bit (the points of status 1 and 2 and infinity are zero)"""
+    import numpy as np
+
+    raw = bytes(data) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, dtype=np.uint8).tobytes()
+    if len(raw) % 96:
+        raise ValueError(f"{len(raw)} bytes is not a whole number of 96-byte points")
+    k = len(raw) // 96
+    pts, st = np.zeros((k, 24), dtype=np.uint64), np.zeros(k, dtype=np.uint8)
+    for i in range(k):
+        st[i], P = _g2_decode(raw[96 * i : 96 * i + 96])
+        if st[i] == G2_OK and P is not None:
+            pts[i] = g2_point_words(P)
+            if not g2_in_subgroup(P):
+                st[i] = G2_NOT_IN_SUBGROUP
+    return pts, st

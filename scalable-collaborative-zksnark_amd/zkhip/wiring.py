@@ -130,6 +130,9 @@ def verifying_keys(be, powers_of_g2):
     """powers_of_g2 = [g2, s_0 g2, .., s_mu g2] of the (mu + 1)-variate SRS -> (vk_mu, vk_mu1): mu-variate tables use the last mu variables"""
     from . import dist_primitive as dp
 
+    if isinstance(powers_of_g2, np.ndarray):  # [mu + 2, 24] Montgomery records (vk_io.vk_from_bytes)
+        rec = np.ascontiguousarray(powers_of_g2, dtype=np.uint64).reshape(-1, 24)
+        return dp.pcs_vk(be, np.concatenate([rec[:1], rec[2:]])), dp.pcs_vk(be, rec)
     pg2 = list(powers_of_g2)
     return dp.pcs_vk(be, [pg2[0]] + pg2[2:]), dp.pcs_vk(be, pg2)
 
