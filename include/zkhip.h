@@ -722,6 +722,48 @@ int zk_pcs_agg_weights(size_t count, const size_t *h_nvars, const size_t *h_skip
                        const uint64_t *h_cpoints18, const uint64_t *h_cscalars, const uint64_t *h_values, const uint64_t *h_proofs18,
                        const uint64_t *h_points, uint64_t *h_rho);
 
+/* ---- a structured parameter set from a file: validation, expansion and the consistency check on the device (csrc/zk_srsio.hip) -----
+ * zk_srs_powers builds powers_of_g from the trapdoor s; a prover that must never see s loads the TOP level L_n (2^n compressed points)
+ * and the keys [g2, s_0 g2, .., s_{n-1} g2] from a file instead.  With L_k = powers_of_g[k], for every k < n and j < 2^k
+ *     (A)  L_k[j] = L_{k+1}[j] + L_{k+1}[j + 2^k]
+ *     (B)  e(L_{k+1}[j + 2^k], g2) = e(L_k[j], s_{n-k-1} g2)
+ * so the lower levels are DERIVED by (A) (zk_srs_halve) and (B) is checked per level under random weights (zk_srs_check).  By induction
+ * from L_0 = [g], (A) and (B) for all k give L_n[x] = eq(s, x) g for the s the keys define.  This proves that the G1 points are
+ * consistent with the G2 keys; it does not prove that nobody knows s. */
+/* zk_g1_decompress_check on DEVICE memory, for counts of millions: d_in48: count x 48 bytes, the encoding and the rule of
+ * zk_g1_decompress_check (the same device functions); d_out96: count affine records x || y in the reference Montgomery form, as
+ * zk_srs_wrap_device takes them, written for status 0 and 3, all zero (the layout's infinity) for every other status and for infinity.
+ * Both buffers 16-byte aligned.  flags bit 0: a point at infinity is refused with status 4 (a well-formed SRS holds none); other bits:
+ * ZK_ERR_INVALID.  h_result = { the number of points whose status is not 0, the smallest such index (2^64 - 1: none), its status (0:
+ * none) }; the index is an atomic minimum and the status is read at that index afterwards, so the report does not depend on the order
+ * of the threads.  The kernels walk the points in a grid-stride loop (at most 2048 workgroups of 64 lanes).  ZK_OK whenever the call
+ * ran, count = 0 included; one synchronisation of the ctx stream. */
+#define ZK_G1_INFINITY_REFUSED 4
+int zk_g1_decompress_check_device(zk_ctx *ctx, size_t count, const void *d_in48, void *d_out96, uint32_t flags, uint64_t h_result[3]);
+/* (A): out[j] = level[j] + level[j + m], j < m, for a G1 level of 2m points, as a new level (free it with zk_srs_free).  The addition
+ * is complete: equal operands are a doubling, and the two halves need not be distinct points.  The sums are normalised with
+ * Montgomery's trick, one inversion per lane over a strided group of 64.  A sum at infinity: ZK_ERR_INVALID, zk_last_error gives "K of
+ * M sums are the point at infinity; the first is sum J" (no level of a well-formed SRS has one).  A level of 0 points or of an odd
+ * number, or a G2 level: ZK_ERR_INVALID.  Blocking. */
+int zk_srs_halve(zk_ctx *ctx, const zk_srs *level, zk_srs **out);
+/* d_out[j], j < n: the Montgomery form of the low 128 bits of SHA-256(seed (32 bytes) || domain (4 bytes, little-endian) || j (8 bytes,
+ * little-endian)).  Byte order: the digest is read as a little-endian 256-bit integer, as the transcript's challenges are, so the low 128
+ * bits are its FIRST 16 bytes, byte 0 the least significant.  One lane per element, one compression each.  ASYNCHRONOUS on the ctx
+ * stream (the seed is copied before the call returns). */
+int zk_fr_hash_expand(zk_ctx *ctx, const uint8_t h_seed32[32], uint32_t domain, size_t n, void *d_out);
+/* (B) for every level: levels[k], k = 0 .. n, holds 2^k points (anything else: ZK_ERR_INVALID; 1 <= n <= 30); h_powers_g2: the n + 1
+ * keys as zk_pairing takes them.  rho = zk_fr_hash_expand(seed, ZK_SRS_CHECK_DOMAIN, 2^(n-1)); level k uses its first 2^k values (one
+ * vector serves every level by the union bound: an error escapes with probability about n / 2^128).  With
+ *     A_k = sum_j rho_j levels[k+1][j + 2^k],     B_k = sum_j rho_j levels[k][j]
+ * h_ok[k] = ( e(A_k, g2) e(-B_k, powers_g2[n - k]) == 1 ), k < n: the 2n sums are ONE zk_msm_g1_batch (the upper halves through its
+ * offsets), the n products ONE zk_pairing_product_check of n groups of two pairs.  A level whose A_k, B_k or key is the point at
+ * infinity fails.  The seed must not be known before the points are fixed: the hosts take the SHA-256 of the file.
+ * NOT checked here: that the points and the keys lie in the prime-order subgroups -- zk_g1_decompress_check_device and
+ * zk_g2_decompress_check do that on the way in from a file; off-subgroup inputs give meaningless verdicts, never a fault. */
+#define ZK_SRS_CHECK_DOMAIN 1u
+int zk_srs_check(zk_ctx *ctx, const zk_srs *const *levels, size_t n, const void *h_powers_g2, size_t g2_stride,
+                 const uint8_t h_seed32[32], uint8_t *h_ok);
+
 /* (the zk_dbg_* test hooks of the library are declared in include/zkhip_test.h: they are not part of this surface) */
 
 #ifdef __cplusplus

@@ -30,6 +30,7 @@ static const TuneKey kTuneKeys[] = {
     {"msm_fixq", &Tuning::msm_fixq}, {"msm_quad", &Tuning::msm_quad}, {"msm_stage", &Tuning::msm_stage}, {"msm_split", &Tuning::msm_split},
     {"msm_np", &Tuning::msm_np}, {"msm_fused_min", &Tuning::msm_fused_min}, {"msm_l2_tiled", &Tuning::msm_l2_tiled}, {"msm_tab_spt", &Tuning::msm_tab_spt}, {"msm_idx_ahead", &Tuning::msm_idx_ahead}, {"msm_share_l1", &Tuning::msm_share_l1}, {"srs_table_batched", &Tuning::srs_table_batched}, {"msm_debug", &Tuning::msm_debug}, {"msm_serial", &Tuning::msm_serial}, {"msm_size_classes", &Tuning::msm_size_classes},
     {"g1_map_by_column", &Tuning::g1_map_by_column}, {"msm_share", &Tuning::msm_share}, {"srs_table_rec", &Tuning::srs_table_rec}, {"msm_size_class_min", &Tuning::msm_size_class_min}, {"msm_small_table_widths", &Tuning::msm_small_table_widths},
+    {"srsio_max_blocks", &Tuning::srsio_max_blocks},
 };
 static Tuning g_tuning;
 int tune_set(const char* key, long value) {
@@ -767,6 +768,23 @@ int zk_g2_decompress_check(zk_ctx* ctx, size_t count, const void* h_in96, uint64
 int zk_g2_check(zk_ctx* ctx, size_t count, const void* h_g2, size_t g2_stride, uint8_t* h_status) {
     NEED(ctx, count == 0 || (h_g2 && h_status));
     return g2_check(ctx, count, h_g2, g2_stride, h_status);
+}
+int zk_g1_decompress_check_device(zk_ctx* ctx, size_t count, const void* d_in48, void* d_out96, uint32_t flags, uint64_t h_result[3]) {
+    NEED(ctx, h_result && (count == 0 || (d_in48 && d_out96)));
+    return g1_decompress_check_device(ctx, count, d_in48, d_out96, flags, h_result);
+}
+int zk_srs_halve(zk_ctx* ctx, const zk_srs* level, zk_srs** out) {
+    NEED(ctx, level && out);
+    return srs_halve(ctx, level, out);
+}
+int zk_fr_hash_expand(zk_ctx* ctx, const uint8_t h_seed32[32], uint32_t domain, size_t n, void* d_out) {
+    NEED(ctx, h_seed32 && (n == 0 || d_out));
+    return fr_hash_expand(ctx, h_seed32, domain, n, d_out);
+}
+int zk_srs_check(zk_ctx* ctx, const zk_srs* const* levels, size_t n, const void* h_powers_g2, size_t g2_stride, const uint8_t h_seed32[32],
+                 uint8_t* h_ok) {
+    NEED(ctx, levels && h_powers_g2 && h_seed32 && h_ok);
+    return srs_check(ctx, levels, n, h_powers_g2, g2_stride, h_seed32, h_ok);
 }
 int zk_g1_lincomb_seg(zk_ctx* ctx, size_t segments, const size_t* h_start, const uint64_t* h_points18, const uint64_t* h_scalars, uint64_t* h_out18) {
     NEED(ctx, segments == 0 || (h_start && h_out18));

@@ -187,6 +187,8 @@ struct Tuning {
     long msm_share = 100;     // EXPERIMENT (profiles/r05g): percent of the resident workgroup slots k_accum_tiles may fill (persistent grid below 100)
     // SRS / PSS maps on points (zk_srs.hip)
     long g1_map_by_column = 1;  // zk_g1_apply_matrix: one lane per (output, column) when there are few outputs of many terms (0: always one lane per output)
+    // parameter sets from a file (zk_srsio.hip)
+    long srsio_max_blocks = 0;  // TEST SWITCH: v > 0 caps the grid of zk_g1_decompress_check_device at v workgroups of 64 lanes, so that a few hundred points walk the grid-stride loop (0: 2048)
 };
 Tuning& tuning();
 int tune_set(const char* key, long value);  // 0, or ZK_ERR_INVALID for an unknown key
@@ -362,6 +364,11 @@ int pcs_verify_agg(zk_ctx* ctx, const zk_pcs_vk* vk, size_t count, const size_t*
 // ---- zk_g1check.hip ----
 int g1_decompress_check(zk_ctx* ctx, size_t count, const void* h_in48, uint64_t* h_out18, uint8_t* h_status);
 int g1_check(zk_ctx* ctx, size_t count, const uint64_t* h_points18, uint8_t* h_status);
+// ---- zk_srsio.hip ----
+int g1_decompress_check_device(zk_ctx* ctx, size_t count, const void* d_in48, void* d_out96, uint32_t flags, uint64_t* h_result);
+int srs_halve(zk_ctx* ctx, const zk_srs* level, zk_srs** out);
+int fr_hash_expand(zk_ctx* ctx, const uint8_t* h_seed32, uint32_t domain, size_t n, void* d_out);
+int srs_check(zk_ctx* ctx, const zk_srs* const* levels, size_t n, const void* h_powers_g2, size_t g2_stride, const uint8_t* h_seed32, uint8_t* h_ok);
 // ---- zk_g2check.hip ----
 int g2_decompress_check(zk_ctx* ctx, size_t count, const void* h_in96, uint64_t* h_out24, uint8_t* h_status);
 int g2_check(zk_ctx* ctx, size_t count, const void* h_g2, size_t g2_stride, uint8_t* h_status);

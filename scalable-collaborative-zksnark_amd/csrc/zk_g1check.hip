@@ -21,20 +21,9 @@
 namespace zk {
 
 namespace g1c {
-// beta = 0x5f19672fdf76ce51ba69c6076a0f77eaddb3a93be6f89688de17d813620a00022e01fffffffefffe, internal form: the cube root of unity whose
-// endomorphism is multiplication by -x^2 on G1 (the other one belongs to x^2 - 1)
-__host__ __device__ constexpr u32 BETA(int i) {
-    constexpr u32 t[13] = {0x229d39fcu, 0x11661b79u, 0x3a68a8f8u, 0x09dabbd8u, 0x12744b7eu, 0x22bc97d4u, 0x3c5ccd3eu, 0x1cf87540u, 0x0197e4f4u, 0x3433d1ecu, 0x0d20861fu, 0x33953662u, 0x000edc53u};
-    return t[i];
-}
-// (q + 1) / 4 in 32-bit words, 379 bits
-__device__ const u32 kSqrtExp[12] = {0xffffeaabu, 0xee7fbfffu, 0xac54ffffu, 0x07aaffffu, 0x3dac3d89u, 0xd9cc34a8u, 0x3ce144afu, 0xd91dd2e1u, 0x90d2eb35u, 0x92c6e9edu, 0x8e5ff9a6u, 0x0680447au};
-constexpr int kSqrtBits = 379;
-constexpr unsigned long long kXAbs = 0xd201000000010000ULL;
 constexpr int kBlk = 64;
 }  // namespace g1c
 
-ZK_G1C_CONST(g1c_beta, g1c::BETA)
 #undef ZK_G1C_CONST
 
 __device__ __forceinline__ void g1c_store_words(void* base, size_t byte_off, int nwords16, u32 v) {  // nwords16 x 16 bytes of v
@@ -57,52 +46,19 @@ static __global__ void __launch_bounds__(g1c::kBlk) k_g1_decompress(size_t count
                                                                    void* __restrict__ out18, unsigned char* __restrict__ status) {
     const size_t i = (size_t)blockIdx.x * g1c::kBlk + threadIdx.x;
     if (i >= count) return;
-    // big-endian bytes -> little-endian words: word k of the integer is the byte-swapped word 11 - k of the record
-    u32 w[12];
-    const uint4* p = reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(in48) + i * 48);
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        const uint4 v = p[k];
-        w[11 - 4 * k] = __builtin_bswap32(v.x);
-        w[10 - 4 * k] = __builtin_bswap32(v.y);
-        w[9 - 4 * k] = __builtin_bswap32(v.z);
-        w[8 - 4 * k] = __builtin_bswap32(v.w);
-    }
-    const bool compressed = (w[11] >> 31) & 1u, inf = (w[11] >> 30) & 1u, sign = (w[11] >> 29) & 1u;
-    w[11] &= 0x1fffffffu;
-    u32 any = 0;
-#pragma unroll
-    for (int k = 0; k < 12; k++) any |= w[k];
-    const Fq30 xc = f30_from_words(w);
-    const bool bad = !compressed || (inf ? (sign || any != 0) : !g1c_lt_q(xc));
-    if (bad || inf) {
-        status[i] = bad ? g1c::kBadEncoding : g1c::kOk;
-        if (bad) {
+    Fq30 x, y;
+    bool inf;
+    const unsigned char st = g1c_decompress(in48, i, x, y, inf);  // (the rule itself is in g1c.cuh: zk_srsio.hip runs it too)
+    if (st != g1c::kOk || inf) {
+        status[i] = st;
+        if (st != g1c::kOk) {
             g1c_store_words(out18, i * 144, 9, 0u);
         } else {
-            g1c_store_jac(out18, i, xc, xc, true);
+            g1c_store_jac(out18, i, f30_zero(), f30_zero(), true);
             g1c_store_words(pts, i * 192, 12, 0u);  // ZZ = 0: infinity
         }
         return;
     }
-    const Fq30 x = f30_canon8(f30_mul(xc, g1c_r2()));                 // internal form, canonical
-    const Fq30 rhs = f30_add(f30_mul(f30_sqr(x), x), g1c_four());     // x^3 + 4 < 3q
-    Fq30 y = rhs;                                                     // rhs^((q+1)/4): the top bit, then 378 squarings
-#pragma unroll 1
-    for (int b = g1c::kSqrtBits - 2; b >= 0; b--) {
-        y = f30_sqr(y);
-        if ((g1c::kSqrtExp[b >> 5] >> (b & 31)) & 1u) y = f30_mul(y, rhs);  // (the same branch in every lane)
-    }
-    if (!g1c_same(f30_canon8(f30_sqr(y)), f30_canon8(rhs))) {
-        status[i] = g1c::kNotOnCurve;
-        g1c_store_words(out18, i * 144, 9, 0u);
-        return;
-    }
-    Fq30 unit = f30_zero();
-    unit.l[0] = 1;
-    const Fq30 y_plain = f30_canon8(f30_mul(y, unit));  // out of Montgomery form: "larger" is a property of the integer
-    y = f30_canon8(y);
-    if (g1c_is_larger(y_plain) != sign) y = f30_neg_canon(y);
     status[i] = g1c::kOk;
     g1c_store_jac(out18, i, f30_to_ref(x), f30_to_ref(y), false);
     f30_store(pts, i * 192, x);
@@ -150,26 +106,7 @@ static __global__ void __launch_bounds__(g1c::kBlk) k_g1_subgroup(size_t count, 
     P.zz = f30_load(pts, i * 192 + 96);
     P.zzz = f30_load(pts, i * 192 + 144);
     if (xyzz30_is_inf(P)) return;  // the neutral element is a member
-    Xyzz30 base = P, acc = P;
-#pragma unroll 1
-    for (int pass = 0; pass < 2; pass++) {  // acc = [|x|] base, twice: the top bit, then 63 doublings and 5 additions
-        acc = base;
-#pragma unroll 1
-        for (int b = 62; b >= 0; b--) {
-            acc = g1c_dbl(acc);
-            if ((g1c::kXAbs >> b) & 1ULL) acc = g1c_add(acc, base);
-        }
-        base = acc;
-    }
-    // (beta Px / Pzz, Py / Pzzz) == (Ax / Azz, -Ay / Azzz), cross-multiplied; infinity is no such point
-    bool ok = !xyzz30_is_inf(acc);
-    if (ok) {
-        const Fq30 l = f30_mul(f30_mul(g1c_beta(), P.x), acc.zz);  // q * 8q, then 2q * 2q
-        const Fq30 r = f30_mul(acc.x, P.zz);                       // 8q * 2q
-        const Fq30 s = f30_mul2add(P.y, acc.zzz, acc.y, P.zzz);    // 4q*2q + 4q*2q -> < 2q
-        ok = g1c_same(f30_canon8(l), f30_canon8(r)) && f30_is_zero_2q(s);
-    }
-    if (!ok) status[i] = g1c::kNotInG1;
+    if (!g1c_in_subgroup(P)) status[i] = g1c::kNotInG1;
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------------

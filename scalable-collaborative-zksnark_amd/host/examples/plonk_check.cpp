@@ -52,6 +52,11 @@
 // circuit, the public inputs and -- with --lookup -- the free values of the lookup rows; the digest is the one without the flag.  Not with
 // --break-gate / --break-wire, which break the sampler's wires.
 // --gate wide proves the test circuit of the wide gate (zkhip.plonk.sample_circuit_wide: six selectors and a fifth-power term) instead.
+// --dump-srs FILE writes the parameter set of the seed's trapdoor in the byte format of zkhip/srs_io.py (zkhost/srs_io.hpp; TEST MATERIAL: the
+// seed is a known trapdoor) and prints "srs_sha256 .. bytes .." -- one digest for one seed in both hosts.  --srs FILE proves on a parameter
+// set LOADED from such a file instead: validated, halved and pairing-checked on the device, cut down to mu + 1 variables, the pairing keys
+// made from its G2 keys; zk_srs_powers is not called.  It prints the srs_sha256 line and then what the run without the flag prints; a file
+// that is refused: "verdict refused: <cause>", exit 2 (the lines of tools/plonk_srs.py --check).
 // --break-gate K adds 1 to c[K]; --break-wire K (K past the input rows) changes a[K] and recomputes c[K], so that only the copy
 // constraint fails; --bad-input hands the verifier a public input the prover did not use.  The verifier rejects each.  Prints the proof
 // digest and accept / reject; exit 0 on accept, 1 on reject, 2 on error (arguments are checked before any device is touched).
@@ -72,6 +77,7 @@
 #include "zkhost/plonk.hpp"
 #include "zkhost/proof_io.hpp"
 #include "zkhost/sha256.hpp"
+#include "zkhost/srs_io.hpp"
 #include "zkhost/vk_io.hpp"
 #include <chrono>
 
@@ -88,7 +94,7 @@ struct Options {
     long long time_sample = 0, torsion = -1, g1check_time = 0, reps = 20, verify_many = 0, break_one = -1;
     long long vk_torsion = -1, g2check_time = 0;
     bool bytes = false, vk_vectors = false, host_checks = false;
-    std::string dump_proof, dump_vk, dump_public, files[3];
+    std::string dump_proof, dump_vk, dump_public, files[3], dump_srs, srs;
     bool bad_input = false, wide = false, lookup = false, break_all = false, find = false, witness = false, lookup_fn = false;
 };
 
@@ -362,16 +368,39 @@ static int run(const Options &o) {
     const uint64_t seed = (uint64_t)o.seed;
     const bool wide = o.wide, bad_input = o.bad_input;
     const PlonkCircuit good = sample(o, false), c = sample(o, true);
-    PolynomialCommitmentCub cub = PolynomialCommitmentCub::make(be, good.s);
+    PolynomialCommitmentCub cub;
+    std::vector<G2Rec> keys;  // the mu + 2 raw keys [g2, s_0 g2, .., s_mu g2]
+    if (!o.srs.empty()) {
+        // the parameter set comes from a file (zkhost/srs_io.hpp): loaded, checked on the device, cut down to mu + 1 variables; the trapdoor
+        // of the seed is not used for it
+        const Bytes data = detail::read_file(o.srs);
+        std::printf("srs_sha256 %s bytes %zu\n", sha_hex(data).c_str(), data.size());
+        try {
+            auto loaded = srs_from_bytes(be, data);
+            auto cut = srs_restrict(loaded.first, loaded.second, mu + 1);
+            cub.powers_of_g = cut.first, keys = cut.second;
+        } catch (const std::invalid_argument &e) {
+            std::printf("verdict refused: %s\n", e.what());
+            return 2;
+        }
+    } else {
+        cub = PolynomialCommitmentCub::make(be, good.s);
+        const std::vector<uint64_t> pg2 = powers_of_g2(be, good.s);
+        keys.resize(pg2.size() / 24);
+        std::memcpy(keys.data(), pg2.data(), 8 * pg2.size());
+        if (!o.dump_srs.empty()) {  // the seed's parameter set as a file: TEST MATERIAL, the seed is a known trapdoor
+            const Bytes data = srs_to_bytes(be, cub.mature(), pg2);
+            std::printf("srs_sha256 %s bytes %zu\n", sha_hex(data).c_str(), data.size());
+            detail::write_file(o.dump_srs, data);
+        }
+    }
     // level mu of the parameter set uses s_1 .. s_mu: its openings verify against [g2, s_1 g2, .., s_mu g2]
-    std::shared_ptr<PcsVk> vk_mu1 = make_pcs_vk(be, good.s), vk_mu = make_pcs_vk(be, FrVec(good.s.begin() + 1, good.s.end()));
+    std::vector<G2Rec> keys_mu{keys[0]};
+    keys_mu.insert(keys_mu.end(), keys.begin() + 2, keys.end());
+    std::shared_ptr<PcsVk> vk_mu1 = be.pcs_vk(nullptr, keys[0].data(), 192, keys.size()), vk_mu = be.pcs_vk(nullptr, keys_mu[0].data(), 192, keys_mu.size());
     PlonkVk vk;
     const PlonkPk pk = preprocess(be, cub.mature(), good, vk);
-    if (o.bytes) {  // the raw keys, for the key's encoding
-        const std::vector<uint64_t> pg2 = powers_of_g2(be, good.s);
-        vk.g2.resize(pg2.size() / 24);
-        std::memcpy(vk.g2.data(), pg2.data(), 8 * pg2.size());
-    }
+    if (o.bytes) vk.g2 = keys;  // the raw keys, for the key's encoding
     DevPtr idx;
     if (o.lookup && !o.find) {
         idx = be.alloc(4 * N);
@@ -454,6 +483,8 @@ int main(int argc, char **argv) {
         else if (i + 1 < argc && k == "--dump-proof") o.dump_proof = argv[++i];
         else if (i + 1 < argc && k == "--dump-vk") o.dump_vk = argv[++i];
         else if (i + 1 < argc && k == "--dump-public") o.dump_public = argv[++i];
+        else if (i + 1 < argc && k == "--dump-srs") o.dump_srs = argv[++i];
+        else if (i + 1 < argc && k == "--srs") o.srs = argv[++i];
         else if (i + 3 < argc && k == "--verify-files") o.files[0] = argv[i + 1], o.files[1] = argv[i + 2], o.files[2] = argv[i + 3], i += 3;
         else if (i + 1 < argc && k == "--vk-torsion") usage = !number(argv[++i], o.vk_torsion);
         else if (i + 1 < argc && k == "--g2check-time") usage = !number(argv[++i], o.g2check_time) || o.g2check_time < 1;
@@ -505,11 +536,12 @@ int main(int argc, char **argv) {
     usage = usage || o.g2check_time > 0 || o.vk_vectors || !o.files[0].empty() || o.host_checks || ((o.vk_torsion >= 0 || !o.dump_vk.empty() || !o.dump_public.empty()) && !o.bytes);
     usage = usage || (o.break_one >= 0 && o.break_one >= o.verify_many) ||
             (o.verify_many > 0 && (o.bytes || tamper || bad_input || o.witness || o.find || o.lookup_fn || break_gate >= 0 || break_wire >= 0 || o.break_lookup >= 0 || only_circuit));
+    usage = usage || (!o.dump_srs.empty() && !o.srs.empty()) || ((!o.dump_srs.empty() || !o.srs.empty()) && (only_circuit || o.verify_many > 0));
     usage = usage || o.g1check_time > 0 || ((o.torsion >= 0 || !o.dump_proof.empty()) && !o.bytes) || (o.bytes && tamper);
     if (usage || mu < 0 || (break_gate >= 0) + (break_wire >= 0) + (bad_input ? 1 : 0) + (o.break_lookup >= 0) + (tamper ? 1 : 0) > 1 ||
         (o.break_all && o.break_part >= 0) || (o.break_lookup >= 0 && !o.lookup) || (o.find && !o.lookup) || (o.lookup && (break_gate >= 0 || break_wire >= 0)) ||
         (o.witness && (break_gate >= 0 || break_wire >= 0)) || (o.time_sample > 0 && !only_circuit) || (o.lookup_fn && (!wide || o.time_sample > 0))) {
-        std::fprintf(stderr, "usage: plonk_check --mu M [--seed S] [--gate wide] [--witness] [--lookup | --gate wide --lookup-fn [--find] [--break-lookup K]] [--break-gate K | --break-wire K | --bad-input | --break K|all] [--circuit-only | --sample-only [--time-sample R]] [--bytes [--dump-proof FILE] [--torsion K] [--dump-vk FILE] [--dump-public FILE] [--vk-torsion K]] | --verify-many K [--break-one J] | --g1check-time K [--reps R] | --g2check-time K [--reps R] | --vk-vectors | --verify-files VK PROOF PUBLIC [--host-checks]\n");
+        std::fprintf(stderr, "usage: plonk_check --mu M [--seed S] [--gate wide] [--witness] [--lookup | --gate wide --lookup-fn [--find] [--break-lookup K]] [--break-gate K | --break-wire K | --bad-input | --break K|all] [--circuit-only | --sample-only [--time-sample R]] [--bytes [--dump-proof FILE] [--torsion K] [--dump-vk FILE] [--dump-public FILE] [--vk-torsion K]] [--dump-srs FILE | --srs FILE] | --verify-many K [--break-one J] | --g1check-time K [--reps R] | --g2check-time K [--reps R] | --vk-vectors | --verify-files VK PROOF PUBLIC [--host-checks]\n");
         return 2;
     }
     if (mu < 2 || mu > 24) {

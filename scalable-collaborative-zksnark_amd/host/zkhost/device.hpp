@@ -784,6 +784,41 @@ class Ctx {
         status.assign(k, 0);
         if (k) check(zk_g1_decompress_check(h_, k, in48, points[0].data(), status.data()));
     }
+    // ---- a parameter set from a file (csrc/zk_srsio.hip; zkhost/srs_io.hpp is the caller) ----
+    // zk_g1_decompress_check on device memory: count compressed points at in48 -> 96-byte affine records at out96 (as srs_wrap_device takes
+    // them); -> { points whose status is not 0, the smallest such index, its status (4: infinity, refused with refuse_infinity) }
+    std::array<uint64_t, 3> g1_decompress_check_device(const DevPtr &in48, size_t count, const DevPtr &out96, bool refuse_infinity = false) {
+        std::array<uint64_t, 3> res{};
+        check(zk_g1_decompress_check_device(h_, count, in48.get(), out96.get(), refuse_infinity ? 1u : 0u, res.data()));
+        return res;
+    }
+    SrsPtr srs_wrap_device(const DevPtr &bases96, size_t n) {
+        zk_srs *s = nullptr;
+        check(zk_srs_wrap_device(h_, bases96.get(), n, &s));
+        return std::make_shared<Srs>(ref_, s);
+    }
+    // out[j] = level[j] + level[j + m]; ZkError(ZK_ERR_INVALID) when a sum is the point at infinity
+    SrsPtr srs_halve(const Srs &level) {
+        zk_srs *s = nullptr;
+        check(zk_srs_halve(h_, level.handle(), &s));
+        return std::make_shared<Srs>(ref_, s);
+    }
+    // out[j] = the low 128 bits of SHA-256(seed || u32le(domain) || u64le(j)), Montgomery Fr
+    DevPtr fr_hash_expand(const uint8_t seed32[32], uint32_t domain, size_t n) {
+        DevPtr out = alloc_fr(n);
+        check(zk_fr_hash_expand(h_, seed32, domain, n, out.get()));
+        return out;
+    }
+    // relation (B) per level: levels 0 .. n, the n + 1 keys at g2_stride bytes -> ok[k], k < n
+    std::vector<uint8_t> srs_check(const std::vector<SrsPtr> &levels, const void *powers_g2, size_t g2_stride, const uint8_t seed32[32]) {
+        const size_t n = levels.size() - 1;
+        std::vector<const zk_srs *> h(levels.size());
+        for (size_t k = 0; k < levels.size(); ++k) h[k] = levels[k]->handle();
+        std::vector<uint8_t> ok(n ? n : 1, 0);
+        check(zk_srs_check(h_, h.data(), n, powers_g2, g2_stride, seed32, ok.data()));
+        ok.resize(n);
+        return ok;
+    }
     // zk_g1_check: Jacobian points in any representative -> one status per point
     std::vector<uint8_t> g1_check(const G1Vec &points) {
         std::vector<uint8_t> status(points.size(), 0);

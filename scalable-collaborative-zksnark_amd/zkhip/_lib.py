@@ -136,6 +136,10 @@ SYMBOLS = [
     ("zk_g1_lincomb_seg", _i, [_vp, _sz, _vp, _vp, _vp, _vp]),
     ("zk_pcs_verify_agg", _i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("zk_pcs_agg_weights", _i, [_sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("zk_g1_decompress_check_device", _i, [_vp, _sz, _vp, _vp, ctypes.c_uint32, _vp]),
+    ("zk_srs_halve", _i, [_vp, _vp, _pp]),
+    ("zk_fr_hash_expand", _i, [_vp, ctypes.c_char_p, ctypes.c_uint32, _sz, _vp]),
+    ("zk_srs_check", _i, [_vp, _vp, _sz, _vp, _sz, ctypes.c_char_p, _vp]),
 ]
 
 # include/zkhip_test.h: the zk_dbg_* test hooks -- not part of the ABI, resolved only when a test / tool asks (test_hooks())

@@ -1077,6 +1077,45 @@ class Ctx:
                                                None if r is None else _h(r), _h(ok)))
         return bool(ok[0])
 
+    # ---- a parameter set from a file: validation, halving and the consistency check on the device (csrc/zk_srsio.hip) ----
+    def g1_decompress_check_device(self, d_in48, count: int, out=None, refuse_infinity: bool = False):
+        """zk_g1_decompress_check on device memory: count compressed points at d_in48 -> (out: count x 96-byte affine records in the
+        reference layout, as srs_wrap_device takes them; (bad, first, status): the number of points whose status is not 0, the smallest
+        such index (None: none) and its status -- 4: a point at infinity, refused with refuse_infinity)"""
+        out = out or self.alloc(max(96 * count, 16))
+        res = np.zeros(3, dtype=np.uint64)
+        self._check(self.lib.zk_g1_decompress_check_device(self.h, count, _ptr(d_in48), _ptr(out), 1 if refuse_infinity else 0, _h(res)))
+        bad = int(res[0])
+        return out, (bad, int(res[1]) if bad else None, int(res[2]))
+
+    def srs_halve(self, level: Srs) -> Srs:
+        """out[j] = level[j] + level[j + m] for a level of 2m points; ZkError(ZK_ERR_INVALID) when a sum is the point at infinity"""
+        h = ctypes.c_void_p()
+        self._check(self.lib.zk_srs_halve(self.h, level.h, ctypes.byref(h)))
+        return Srs(self, h.value)
+
+    def fr_hash_expand(self, seed32: bytes, domain: int, n: int, out=None) -> DeviceBuffer:
+        """out[j] = the low 128 bits of SHA-256(seed || u32le(domain) || u64le(j)) (the digest as a little-endian integer), Montgomery Fr"""
+        seed32 = bytes(seed32)
+        if len(seed32) != 32:
+            raise ValueError(f"a seed of {len(seed32)} bytes, not 32")
+        out = out or self.alloc(max(32 * n, 1))
+        self._check(self.lib.zk_fr_hash_expand(self.h, seed32, domain, n, _ptr(out)))
+        return out
+
+    def srs_check(self, levels, powers_g2, seed32: bytes, g2_stride: int = 192) -> np.ndarray:
+        """relation (B) of include/zkhip.h per level: levels [n + 1] Srs of 2^k points, powers_g2 [n + 1, 24] -> ok [n] bool; ok[k] says
+        that level k + 1 matches the key powers_g2[n - k]"""
+        n = len(levels) - 1
+        seed32 = bytes(seed32)
+        g2 = np.ascontiguousarray(powers_g2)
+        if len(seed32) != 32 or g2.nbytes < (n + 1) * g2_stride:
+            raise ValueError("srs_check: a 32-byte seed and n + 1 keys for n + 1 levels")
+        h = (ctypes.c_void_p * (n + 1))(*[lv.h for lv in levels])
+        ok = np.zeros(max(n, 1), dtype=np.uint8)
+        self._check(self.lib.zk_srs_check(self.h, h, n, _h(g2), g2_stride, seed32, _h(ok)))
+        return ok[:n].astype(bool)
+
     # ---- party exchanges through the C ABI (RCCL communicator inside the ctx) ----
     def comm_unique_id(self) -> bytes:
         buf = (ctypes.c_uint8 * 128)()

@@ -105,6 +105,7 @@ from . import batch_open as bo
 from . import wiring as wr
 from .field import R_MOD, fr_from_mont, fr_mont
 from .proof_io import check_points, parse_proof, proof_from_bytes, proof_to_bytes, verify_bytes, verify_bytes_many  # noqa: F401  (proof bytes, re-exported)
+from .srs_io import check_srs, parse_srs, restrict, srs_check_host, srs_from_bytes, srs_to_bytes  # noqa: F401  (parameter-set bytes, re-exported)
 from .transcript import HostTranscript, Transcript
 from .vk_io import check_vk, g2_records, parse_vk, verify_files, vk_from_bytes, vk_to_bytes  # noqa: F401  (vk bytes and the file verifier, re-exported)
 from .verify import _ints, _u64, eq_eval, round_chain, round_poly_at  # noqa: F401  (round_poly_at: importable from here as before)
