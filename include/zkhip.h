@@ -764,6 +764,42 @@ int zk_fr_hash_expand(zk_ctx *ctx, const uint8_t h_seed32[32], uint32_t domain, 
 int zk_srs_check(zk_ctx *ctx, const zk_srs *const *levels, size_t n, const void *h_powers_g2, size_t g2_stride,
                  const uint8_t h_seed32[32], uint8_t *h_ok);
 
+/* ---- Poseidon over BLS12-381 Fr: permutation, 2-to-1 hash, Merkle tree (csrc/zk_poseidon.hip) --------------------------------------
+ * Width t = 3 (capacity 1, rate 2), S-box x^5, rf full rounds (rf / 2 first, rf / 2 last) around rp partial rounds.  The state is three
+ * Fr (s_0, s_1, s_2); one counter k indexes all rf + rp rounds; rc holds 3 (rf + rp) round constants, M is 3 x 3, row-major:
+ *     full round k      (k < rf / 2 or k >= rf / 2 + rp):  s_i += rc[3k + i] for i = 0, 1, 2;  every s_i <- s_i^5;  s <- M s
+ *     partial round k   (the rp rounds between):            s_i += rc[3k + i] for i = 0, 1, 2;  only  s_0 <- s_0^5;  s <- M s
+ *     hash2(l, r) = permute(0, l, r)[0];    a Merkle node = hash2(left child, right child).
+ * All values are Montgomery Fr, fully reduced, 32 bytes each; a state is 96 bytes.  Results are exact field elements, so they do not
+ * depend on how an implementation groups the arithmetic.
+ *
+ * The constants are DATA, handed over as a parameter object; t = 3 and the exponent 5 are all that is compiled in.  The project's own
+ * instance "zkhip-poseidon-v1" has rf = 8, rp = 57 (the Poseidon paper's round counts for a prime of about 255 bits, t = 3, alpha = 5 and
+ * 128-bit security) and
+ *     rc[k] = int_le( SHA-256(tag || u32le(k) || 0x00) || SHA-256(tag || u32le(k) || 0x01) ) mod r,  k < 195,  tag = "zkhip-poseidon-v1"
+ *     M[i][j] = 1 / (i + j + 3):  a Cauchy matrix on x = 0, 1, 2 and y = 3, 4, 5, hence MDS (every square submatrix is invertible).
+ * The hosts build these arrays (zkhip/poseidon.py params(), host/zkhost/poseidon.hpp).  The instance is SELF-DEFINED: it is not claimed
+ * to equal the constants of any other library, and the paper's further checks of the matrix (invariant-subspace trails) have NOT been
+ * done on it.  That is why the kernels take the constants as a parameter and do not bake them in. */
+typedef struct zk_poseidon_params zk_poseidon_params;
+/* Device copies of the constants, owned by the object: h_rc 3 (rf + rp) Fr, h_mds 9 Fr, both Montgomery and below r (else
+ * ZK_ERR_INVALID).  An odd rf, rf <= 0, rp < 0 or rf + rp > 256: ZK_ERR_INVALID.  Blocking.  The object belongs to ctx and must be
+ * freed before it. */
+int zk_poseidon_params_create(zk_ctx *ctx, int rf, int rp, const uint64_t *h_rc, const uint64_t *h_mds, zk_poseidon_params **out);
+void zk_poseidon_params_free(zk_poseidon_params *params);
+/* d_out[i] = permute(d_in[i]), i < n, on states of three Fr (96 bytes, 16-byte aligned).  d_out == d_in is allowed (no other overlap).
+ * One lane per state.  ASYNCHRONOUS on the ctx stream; n = 0 is ZK_OK and launches nothing. */
+int zk_poseidon_permute(zk_ctx *ctx, const zk_poseidon_params *params, const void *d_in, void *d_out, size_t n);
+/* d_out[i] = hash2(d_left[i], d_right[i]), i < n Fr each.  d_out may be d_left or d_right.  ASYNCHRONOUS on the ctx stream. */
+int zk_poseidon_hash2(zk_ctx *ctx, const zk_poseidon_params *params, const void *d_left, const void *d_right, void *d_out, size_t n);
+/* The Merkle tree of n = 2^k leaves, k >= 0 (anything else: ZK_ERR_INVALID).  d_tree: 2n - 1 Fr in the order of zk_product_tree's
+ * levels -- the n leaves, then n / 2 nodes, .., the root at index 2n - 2; node j of a level = hash2(nodes 2j, 2j + 1 of the level
+ * below).  d_leaves may be d_tree itself (the leaves already in place).  A level of more nodes than the tuning knob
+ * poseidon_tail_nodes (256) is one launch, one lane per node; all levels at or below it are ONE launch of one 256-lane workgroup with a
+ * barrier between levels.  No workgroup waits on another, no atomics.  ASYNCHRONOUS on the ctx stream: one copy and the launches are
+ * enqueued, the host reads nothing. */
+int zk_poseidon_merkle(zk_ctx *ctx, const zk_poseidon_params *params, const void *d_leaves, size_t n, void *d_tree);
+
 /* (the zk_dbg_* test hooks of the library are declared in include/zkhip_test.h: they are not part of this surface) */
 
 #ifdef __cplusplus

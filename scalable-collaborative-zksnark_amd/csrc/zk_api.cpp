@@ -30,7 +30,7 @@ static const TuneKey kTuneKeys[] = {
     {"msm_fixq", &Tuning::msm_fixq}, {"msm_quad", &Tuning::msm_quad}, {"msm_stage", &Tuning::msm_stage}, {"msm_split", &Tuning::msm_split},
     {"msm_np", &Tuning::msm_np}, {"msm_fused_min", &Tuning::msm_fused_min}, {"msm_l2_tiled", &Tuning::msm_l2_tiled}, {"msm_tab_spt", &Tuning::msm_tab_spt}, {"msm_idx_ahead", &Tuning::msm_idx_ahead}, {"msm_share_l1", &Tuning::msm_share_l1}, {"srs_table_batched", &Tuning::srs_table_batched}, {"msm_debug", &Tuning::msm_debug}, {"msm_serial", &Tuning::msm_serial}, {"msm_size_classes", &Tuning::msm_size_classes},
     {"g1_map_by_column", &Tuning::g1_map_by_column}, {"msm_share", &Tuning::msm_share}, {"srs_table_rec", &Tuning::srs_table_rec}, {"msm_size_class_min", &Tuning::msm_size_class_min}, {"msm_small_table_widths", &Tuning::msm_small_table_widths},
-    {"srsio_max_blocks", &Tuning::srsio_max_blocks},
+    {"srsio_max_blocks", &Tuning::srsio_max_blocks}, {"poseidon_tail_nodes", &Tuning::poseidon_tail_nodes},
 };
 static Tuning g_tuning;
 int tune_set(const char* key, long value) {
@@ -785,6 +785,24 @@ int zk_srs_check(zk_ctx* ctx, const zk_srs* const* levels, size_t n, const void*
                  uint8_t* h_ok) {
     NEED(ctx, levels && h_powers_g2 && h_seed32 && h_ok);
     return srs_check(ctx, levels, n, h_powers_g2, g2_stride, h_seed32, h_ok);
+}
+
+int zk_poseidon_params_create(zk_ctx* ctx, int rf, int rp, const uint64_t* h_rc, const uint64_t* h_mds, zk_poseidon_params** out) {
+    NEED(ctx, h_rc && h_mds && out);
+    return poseidon_params_create(ctx, rf, rp, h_rc, h_mds, out);
+}
+void zk_poseidon_params_free(zk_poseidon_params* params) { poseidon_params_free(params); }
+int zk_poseidon_permute(zk_ctx* ctx, const zk_poseidon_params* params, const void* d_in, void* d_out, size_t n) {
+    NEED(ctx, params && (n == 0 || (d_in && d_out)));
+    return poseidon_permute(ctx, params, d_in, d_out, n);
+}
+int zk_poseidon_hash2(zk_ctx* ctx, const zk_poseidon_params* params, const void* d_left, const void* d_right, void* d_out, size_t n) {
+    NEED(ctx, params && (n == 0 || (d_left && d_right && d_out)));
+    return poseidon_hash2(ctx, params, d_left, d_right, d_out, n);
+}
+int zk_poseidon_merkle(zk_ctx* ctx, const zk_poseidon_params* params, const void* d_leaves, size_t n, void* d_tree) {
+    NEED(ctx, params && d_leaves && d_tree);
+    return poseidon_merkle(ctx, params, d_leaves, n, d_tree);
 }
 int zk_g1_lincomb_seg(zk_ctx* ctx, size_t segments, const size_t* h_start, const uint64_t* h_points18, const uint64_t* h_scalars, uint64_t* h_out18) {
     NEED(ctx, segments == 0 || (h_start && h_out18));

@@ -189,6 +189,8 @@ struct Tuning {
     long g1_map_by_column = 1;  // zk_g1_apply_matrix: one lane per (output, column) when there are few outputs of many terms (0: always one lane per output)
     // parameter sets from a file (zk_srsio.hip)
     long srsio_max_blocks = 0;  // TEST SWITCH: v > 0 caps the grid of zk_g1_decompress_check_device at v workgroups of 64 lanes, so that a few hundred points walk the grid-stride loop (0: 2048)
+    // Poseidon Merkle tree (zk_poseidon.hip)
+    long poseidon_tail_nodes = 256;  // a level of more nodes than this is a launch of its own; all levels at or below it are ONE launch of one workgroup (< 1: every level its own launch)
 };
 Tuning& tuning();
 int tune_set(const char* key, long value);  // 0, or ZK_ERR_INVALID for an unknown key
@@ -376,6 +378,12 @@ int g2_check(zk_ctx* ctx, size_t count, const void* h_g2, size_t g2_stride, uint
 // h_bad, h_why (optional): the term a ZK_ERR_INVALID names (~0 otherwise) and what is wrong with it
 int g1_lincomb_seg(zk_ctx* ctx, size_t segments, const size_t* h_start, const uint64_t* h_points18, const uint64_t* h_scalars, uint64_t* h_out18,
                    size_t* h_bad = nullptr, const char** h_why = nullptr);
+// ---- zk_poseidon.hip ----
+int poseidon_params_create(zk_ctx* ctx, int rf, int rp, const uint64_t* h_rc, const uint64_t* h_mds, zk_poseidon_params** out);
+void poseidon_params_free(zk_poseidon_params* p);
+int poseidon_permute(zk_ctx* ctx, const zk_poseidon_params* p, const void* d_in, void* d_out, size_t n);
+int poseidon_hash2(zk_ctx* ctx, const zk_poseidon_params* p, const void* d_left, const void* d_right, void* d_out, size_t n);
+int poseidon_merkle(zk_ctx* ctx, const zk_poseidon_params* p, const void* d_leaves, size_t n, void* d_tree);
 // ---- zk_pairing.hip: test hooks ----
 int dbg_fq30_op(zk_ctx* ctx, int mode, const void* d_x, const void* d_kx, const void* d_y, const void* d_ky, void* d_out, void* d_flags,
                 size_t n);

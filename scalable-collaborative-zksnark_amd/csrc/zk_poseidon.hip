@@ -1,0 +1,199 @@
+// zk_poseidon.hip -- the Poseidon permutation over BLS12-381 Fr at width t = 3 (capacity 1, rate 2, S-box x^5), its 2-to-1 hash and a
+// Merkle tree of that hash, on the device.
+//   K28  permute   one lane per state of three Fr: the whole permutation in registers
+//   K29  hash2     one lane per pair: out = permute(0, left, right)[0]
+//   K30  level     ONE level of a Merkle tree with more than `poseidon_tail_nodes` nodes: one lane per node, node = hash2(left child, right child)
+//   K31  tail      every level of at most `poseidon_tail_nodes` nodes: ONE workgroup of kPosBlock lanes walks them, a fence and a barrier
+//                  between levels (the scheme of K23 in zk_witness.hip)
+//
+// The rule (the same in include/zkhip.h, zkhip/poseidon.py, host/zkhost/poseidon.hpp and tests/poseidon_model.py).  With rf full and rp partial
+// rounds, one counter k indexes all rf + rp rounds: rounds 0 .. rf/2 - 1 are full, the next rp are partial, the last rf/2 are full.
+//   full round k:     s_i += rc[3k + i] for i = 0, 1, 2;  every s_i <- s_i^5;  s <- M s
+//   partial round k:  s_i += rc[3k + i] for i = 0, 1, 2;  only  s_0 <- s_0^5;  s <- M s
+// (M s)_i = M[i][0] s_0 + M[i][1] s_1 + M[i][2] s_2, the products added left to right.  Everything is Montgomery Fr, fully reduced after
+// every operation, so the bits of a result do not depend on how the arithmetic is grouped: a sparse form of the partial rounds would give
+// the same bits.  This file uses the plain matrix product: 3 multiplications per S-box, 9 per linear layer, (9 + 9) rf + (3 + 9) rp of
+// them per permutation -- 828 for the instance zkhip-poseidon-v1 (rf = 8, rp = 57).
+//
+// The constants are DATA: a zk_poseidon_params object owns one device block [M: 9 Fr, row-major | rc: 3 (rf + rp) Fr] and every kernel
+// reads it through a const pointer at wave-uniform addresses.  Nothing about an instance is compiled in but t = 3 and the exponent 5.
+// The v1 constants are the project's own (SHA-256 derived round constants, a Cauchy matrix) and are not claimed to equal any other
+// library's; the Poseidon paper's further checks of the matrix (invariant-subspace trails) have not been done on it.  That is the reason
+// the constants are a parameter: an instance that has been through such an analysis is a different pair of arrays, not a different build.
+//
+// Order.  zk_poseidon_merkle copies the leaves and enqueues its launches on the ctx stream; no host read lies between them.  A node reads
+// only nodes of the level below: an earlier launch, or an earlier level of the same workgroup, whose stores are complete and visible at
+// workgroup scope after the fence and the barrier that close the level.  No workgroup ever waits on another; there are no atomics.
+//
+// Bounds.  A lane touches state i < n only; a Merkle lane of a level of cnt nodes reads tree[in + 2i], tree[in + 2i + 1] and writes
+// tree[out + i] for i < cnt with in + 2 cnt = out and out + cnt <= 2n - 1: all inside the 2n - 1 elements the caller provides.
+//
+// Registers (hipcc --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage): DESIGN.md, section 4.
+#include "fp.cuh"
+#include "zk_ctx.hpp"
+
+#include <algorithm>
+#include <cstring>
+
+struct zk_poseidon_params {
+    zk_ctx* ctx = nullptr;
+    void* d_consts = nullptr;  // 9 Fr of M, then 3 (rf + rp) Fr of round constants
+    uint32_t half = 0, rp = 0;  // rf / 2 full rounds on either side of rp partial ones
+};
+
+namespace zk {
+
+static constexpr int kPosBlock = 256;
+static constexpr unsigned kPosMaxBlocks = 1u << 16;  // the grid of the lane-per-item kernels (a grid-stride loop walks longer inputs)
+
+__device__ __forceinline__ Fr pos_pow5(const Fr& x) {
+    const Fr x2 = fr_mul(x, x);
+    return fr_mul(fr_mul(x2, x2), x);
+}
+
+// the permutation on (s0, s1, s2); consts: the params block.  Every address below is the same in all lanes.
+__device__ __forceinline__ void pos_permute(const void* __restrict__ consts, u32 half, u32 rp, Fr& s0, Fr& s1, Fr& s2) {
+    const u32 rounds = 2 * half + rp;
+#pragma unroll 1
+    for (u32 k = 0; k < rounds; k++) {
+        s0 = fr_add(s0, fr_load(consts, 9 + 3 * (size_t)k));
+        s1 = fr_add(s1, fr_load(consts, 10 + 3 * (size_t)k));
+        s2 = fr_add(s2, fr_load(consts, 11 + 3 * (size_t)k));
+        s0 = pos_pow5(s0);
+        if (k < half || k >= half + rp) {  // wave-uniform: a full round
+            s1 = pos_pow5(s1);
+            s2 = pos_pow5(s2);
+        }
+        const Fr t0 = fr_add(fr_add(fr_mul(fr_load(consts, 0), s0), fr_mul(fr_load(consts, 1), s1)), fr_mul(fr_load(consts, 2), s2));
+        const Fr t1 = fr_add(fr_add(fr_mul(fr_load(consts, 3), s0), fr_mul(fr_load(consts, 4), s1)), fr_mul(fr_load(consts, 5), s2));
+        const Fr t2 = fr_add(fr_add(fr_mul(fr_load(consts, 6), s0), fr_mul(fr_load(consts, 7), s1)), fr_mul(fr_load(consts, 8), s2));
+        s0 = t0, s1 = t1, s2 = t2;
+    }
+}
+__device__ __forceinline__ Fr pos_hash2(const void* __restrict__ consts, u32 half, u32 rp, const Fr& l, const Fr& r) {
+    Fr s0 = fp_zero<FrCfg>(), s1 = l, s2 = r;
+    pos_permute(consts, half, rp, s0, s1, s2);
+    return s0;
+}
+
+// ---------------------------------------------------------------------------------------
+// K28.  in and out may be the same array: a lane reads its own state before it writes it
+// ---------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(kPosBlock) k_pos_permute(const void* __restrict__ consts, u32 half, u32 rp, const void* in, void* out, size_t n) {
+    for (size_t i = (size_t)blockIdx.x * kPosBlock + threadIdx.x; i < n; i += (size_t)gridDim.x * kPosBlock) {
+        Fr s0 = fr_load(in, 3 * i), s1 = fr_load(in, 3 * i + 1), s2 = fr_load(in, 3 * i + 2);
+        pos_permute(consts, half, rp, s0, s1, s2);
+        fr_store(out, 3 * i, s0);
+        fr_store(out, 3 * i + 1, s1);
+        fr_store(out, 3 * i + 2, s2);
+    }
+}
+// ---------------------------------------------------------------------------------------
+// K29.  out may be left or right: a lane reads its own pair before it writes
+// ---------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(kPosBlock) k_pos_hash2(const void* __restrict__ consts, u32 half, u32 rp, const void* left, const void* right, void* out, size_t n) {
+    for (size_t i = (size_t)blockIdx.x * kPosBlock + threadIdx.x; i < n; i += (size_t)gridDim.x * kPosBlock)
+        fr_store(out, i, pos_hash2(consts, half, rp, fr_load(left, i), fr_load(right, i)));
+}
+// ---------------------------------------------------------------------------------------
+// K30.  one level: tree[out + i] = hash2(tree[in + 2i], tree[in + 2i + 1]), i < cnt
+// ---------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(kPosBlock) k_pos_level(const void* __restrict__ consts, u32 half, u32 rp, void* tree, size_t in, size_t out, size_t cnt) {
+    for (size_t i = (size_t)blockIdx.x * kPosBlock + threadIdx.x; i < cnt; i += (size_t)gridDim.x * kPosBlock)
+        fr_store(tree, out + i, pos_hash2(consts, half, rp, fr_load(tree, in + 2 * i), fr_load(tree, in + 2 * i + 1)));
+}
+// ---------------------------------------------------------------------------------------
+// K31.  ONE workgroup: the levels of cnt, cnt / 2, .., 1 nodes above the `2 cnt` nodes at tree[in ..)
+// ---------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(kPosBlock) k_pos_tail(const void* __restrict__ consts, u32 half, u32 rp, void* tree, size_t in, size_t cnt) {
+    for (; cnt >= 1; cnt >>= 1) {
+        const size_t out = in + 2 * cnt;
+        for (size_t i = threadIdx.x; i < cnt; i += kPosBlock)
+            fr_store(tree, out + i, pos_hash2(consts, half, rp, fr_load(tree, in + 2 * i), fr_load(tree, in + 2 * i + 1)));
+        __threadfence_block();
+        __syncthreads();
+        in = out;
+    }
+}
+
+static unsigned pos_blocks(size_t n) { return (unsigned)std::min<size_t>((n + kPosBlock - 1) / kPosBlock, kPosMaxBlocks); }
+
+// a < r, on four little-endian u64
+static bool pos_canonical(const uint64_t* a) {
+    static const uint64_t r[4] = {0xffffffff00000001ull, 0x53bda402fffe5bfeull, 0x3339d80809a1d805ull, 0x73eda753299d7d48ull};
+    for (int i = 3; i >= 0; i--)
+        if (a[i] != r[i]) return a[i] < r[i];
+    return false;
+}
+
+int poseidon_params_create(zk_ctx* ctx, int rf, int rp, const uint64_t* h_rc, const uint64_t* h_mds, zk_poseidon_params** out) {
+    *out = nullptr;
+    if (rf <= 0 || (rf & 1) || rp < 0 || rf + rp > 256)
+        return fail(ctx, ZK_ERR_INVALID, "poseidon: rf = %d full and rp = %d partial rounds (rf even and > 0, rp >= 0, rf + rp <= 256 are needed)", rf, rp);
+    const size_t n_rc = 3 * (size_t)(rf + rp);
+    for (size_t i = 0; i < 9; i++)
+        if (!pos_canonical(h_mds + 4 * i)) return fail(ctx, ZK_ERR_INVALID, "poseidon: matrix entry %zu is not below r", i);
+    for (size_t i = 0; i < n_rc; i++)
+        if (!pos_canonical(h_rc + 4 * i)) return fail(ctx, ZK_ERR_INVALID, "poseidon: round constant %zu is not below r", i);
+    ZK_HIP(ctx, hipSetDevice(ctx->device));
+    zk_poseidon_params* p = new zk_poseidon_params;
+    p->ctx = ctx;
+    p->half = (uint32_t)rf / 2;
+    p->rp = (uint32_t)rp;
+    hipError_t e = device_alloc(ctx, &p->d_consts, 32 * (9 + n_rc));
+    if (e == hipSuccess) e = hipMemcpy(p->d_consts, h_mds, 32 * 9, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy((char*)p->d_consts + 32 * 9, h_rc, 32 * n_rc, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        if (p->d_consts) hipFree(p->d_consts);
+        delete p;
+        return hip_fail(ctx, e, "poseidon params");
+    }
+    *out = p;
+    return ZK_OK;
+}
+void poseidon_params_free(zk_poseidon_params* p) {
+    if (!p) return;
+    if (p->d_consts) {
+        hipSetDevice(p->ctx->device);
+        hipStreamSynchronize(p->ctx->stream);
+        hipFree(p->d_consts);
+    }
+    delete p;
+}
+
+int poseidon_permute(zk_ctx* ctx, const zk_poseidon_params* p, const void* d_in, void* d_out, size_t n) {
+    if (p->ctx != ctx) return fail(ctx, ZK_ERR_INVALID, "poseidon: the params belong to another ctx");
+    if (n == 0) return ZK_OK;
+    ZK_HIP(ctx, hipSetDevice(ctx->device));
+    hipLaunchKernelGGL(k_pos_permute, dim3(pos_blocks(n)), dim3(kPosBlock), 0, ctx->stream, p->d_consts, p->half, p->rp, d_in, d_out, n);
+    ZK_HIP(ctx, hipGetLastError());
+    return ZK_OK;
+}
+int poseidon_hash2(zk_ctx* ctx, const zk_poseidon_params* p, const void* d_left, const void* d_right, void* d_out, size_t n) {
+    if (p->ctx != ctx) return fail(ctx, ZK_ERR_INVALID, "poseidon: the params belong to another ctx");
+    if (n == 0) return ZK_OK;
+    ZK_HIP(ctx, hipSetDevice(ctx->device));
+    hipLaunchKernelGGL(k_pos_hash2, dim3(pos_blocks(n)), dim3(kPosBlock), 0, ctx->stream, p->d_consts, p->half, p->rp, d_left, d_right, d_out, n);
+    ZK_HIP(ctx, hipGetLastError());
+    return ZK_OK;
+}
+int poseidon_merkle(zk_ctx* ctx, const zk_poseidon_params* p, const void* d_leaves, size_t n, void* d_tree) {
+    if (p->ctx != ctx) return fail(ctx, ZK_ERR_INVALID, "poseidon: the params belong to another ctx");
+    if (n == 0 || (n & (n - 1)) || n > ((size_t)1 << 40)) return fail(ctx, ZK_ERR_INVALID, "poseidon: a Merkle tree of %zu leaves (a power of two is needed)", n);
+    ZK_HIP(ctx, hipSetDevice(ctx->device));
+    if (d_leaves != d_tree) ZK_HIP(ctx, hipMemcpyAsync(d_tree, d_leaves, 32 * n, hipMemcpyDeviceToDevice, ctx->stream));
+    const long tail = tuning().poseidon_tail_nodes;
+    size_t in = 0;
+    for (size_t cnt = n / 2; cnt >= 1; in += 2 * cnt, cnt >>= 1) {
+        if (tail < 1 || cnt > (size_t)tail) {
+            hipLaunchKernelGGL(k_pos_level, dim3(pos_blocks(cnt)), dim3(kPosBlock), 0, ctx->stream, p->d_consts, p->half, p->rp, d_tree, in, in + 2 * cnt, cnt);
+        } else {
+            hipLaunchKernelGGL(k_pos_tail, dim3(1), dim3(kPosBlock), 0, ctx->stream, p->d_consts, p->half, p->rp, d_tree, in, cnt);
+            break;
+        }
+    }
+    ZK_HIP(ctx, hipGetLastError());
+    return ZK_OK;
+}
+
+}  // namespace zk

@@ -1,0 +1,125 @@
+// "I know a leaf and a path to this public root", end to end in the compiled host -- the mirror of tools/poseidon_merkle.py, flag for flag and
+// line for line:
+//     bin/poseidon_check --depth D [--seed S] [--break bit|sibling|root] [--sample-only]
+// A tree of 2^D SplitMix64(S) leaves on the device (zk_poseidon_merkle), the path of leaf S mod 2^D, poseidon_merkle_circuit(D), then
+// witness_plan -> plonk_witness -> preprocess -> plonk_prove -> proof bytes -> verify_bytes.  Prints
+//     circuit sha256 <built_circuit_digest>
+//     root <64 hex digits of the canonical integer>
+//     proof sha256 <proof_digest>
+//     verdict accept | reject             (or:  refused: <the library's message>  when the witness generator refuses the path; exit 1)
+// The SRS trapdoor is SplitMix64(S + 1), mu + 1 elements.  --sample-only: the circuit digest and the root by the host rule
+// (poseidon_merkle_host), without a device.  --time-host K: the serial host rule alone on K states / a tree of K leaves, milliseconds
+// (the CPU column of tools/poseidon_time.py).
+#include <chrono>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+
+#include "zkhost/hyperplonk.hpp"
+#include "zkhost/pcs_vk.hpp"
+#include "zkhost/poseidon.hpp"
+#include "zkhost/proof_io.hpp"
+
+using namespace zkhost;
+
+static std::string hex_of(const Fr &x) {
+    const Fr c = x.to_canonical();
+    char buf[65];
+    for (int i = 0; i < 4; ++i) std::snprintf(buf + 16 * i, 17, "%016llx", (unsigned long long)c.v[3 - i]);
+    return buf;
+}
+
+static int time_host(size_t k) {
+    const FrVec in = SplitMix64(1).fr_vec(3 * k);
+    auto t0 = std::chrono::steady_clock::now();
+    Fr acc = Fr::zero();
+    for (size_t i = 0; i < k; ++i) acc += poseidon_permute_host({in[3 * i], in[3 * i + 1], in[3 * i + 2]})[0];
+    auto t1 = std::chrono::steady_clock::now();
+    std::printf("host permute n=%zu ms %.3f (check %016llx)\n", k, std::chrono::duration<double, std::milli>(t1 - t0).count(), (unsigned long long)acc.v[0]);
+    if (!(k & (k - 1))) {
+        const FrVec leaves(in.begin(), in.begin() + k);
+        t0 = std::chrono::steady_clock::now();
+        const FrVec tree = poseidon_merkle_host(leaves);
+        t1 = std::chrono::steady_clock::now();
+        std::printf("host merkle n=%zu ms %.3f (root %s)\n", k, std::chrono::duration<double, std::milli>(t1 - t0).count(), hex_of(tree.back()).c_str());
+    }
+    return 0;
+}
+
+int main(int argc, char **argv) {
+    long long depth = -1, seed = 7, time_k = 0;
+    std::string brk;
+    bool sample_only = false, usage = argc < 2;
+    auto number = [](const char *s, long long &out) {
+        char *end = nullptr;
+        out = std::strtoll(s, &end, 10);
+        return *s && end && !*end && out >= 0;
+    };
+    for (int i = 1; i < argc && !usage; ++i) {
+        const std::string k = argv[i];
+        if (k == "--sample-only") sample_only = true;
+        else if (i + 1 < argc && k == "--depth") usage = !number(argv[++i], depth) || depth < 1 || depth > 40;
+        else if (i + 1 < argc && k == "--seed") usage = !number(argv[++i], seed);
+        else if (i + 1 < argc && k == "--time-host") usage = !number(argv[++i], time_k) || time_k < 1;
+        else if (i + 1 < argc && k == "--break") brk = argv[++i], usage = brk != "bit" && brk != "sibling" && brk != "root";
+        else usage = true;
+    }
+    if (!usage && time_k > 0 && depth < 0) return time_host((size_t)time_k);
+    if (usage || depth < 0 || time_k > 0) {
+        std::fprintf(stderr, "usage: poseidon_check --depth D [--seed S] [--break bit|sibling|root] [--sample-only] | --time-host K\n");
+        return 2;
+    }
+    try {
+        const size_t n = size_t(1) << depth, index = (size_t)seed % n;
+        CircuitLayout layout;
+        MerkleCircuitVars v;
+        const PlonkCircuit circuit = poseidon_merkle_circuit((size_t)depth, layout, v);
+        const FrVec leaves = SplitMix64((uint64_t)seed).fr_vec(n);
+        std::printf("circuit sha256 %s\n", built_circuit_digest(circuit).c_str());
+        if (sample_only) {
+            std::printf("root %s\n", hex_of(poseidon_merkle_host(leaves).back()).c_str());
+            return 0;
+        }
+        Ctx be(0);
+        const std::shared_ptr<PoseidonParams> pp = poseidon_params(be);
+        const FrVec tree = be.to_host(be.poseidon_merkle(*pp, be.to_device(leaves), n), 2 * n - 1);
+        const Fr root = tree.back();
+        std::printf("root %s\n", hex_of(root).c_str());
+        FrVec sibs;
+        std::vector<uint64_t> bits;
+        poseidon_merkle_path(tree, n, index, sibs, bits);
+        if (brk == "bit") bits[0] ^= 1;
+        if (brk == "sibling") sibs[0] += Fr::one();
+        const FrVec pi{brk == "root" ? root + Fr::one() : root};
+        const FrVec s = SplitMix64((uint64_t)seed + 1).fr_vec(circuit.mu + 1);
+        const PolynomialCommitmentCub cub = PolynomialCommitmentCub::make(be, s);
+        const std::vector<uint64_t> pg2 = powers_of_g2(be, s);
+        std::vector<G2Rec> keys(pg2.size() / 24);
+        std::memcpy(keys.data(), pg2.data(), 8 * pg2.size());
+        std::vector<G2Rec> keys_mu{keys[0]};
+        keys_mu.insert(keys_mu.end(), keys.begin() + 2, keys.end());
+        std::shared_ptr<PcsVk> vk_mu1 = be.pcs_vk(nullptr, keys[0].data(), 192, keys.size()), vk_mu = be.pcs_vk(nullptr, keys_mu[0].data(), 192, keys_mu.size());
+        PlonkVk vk;
+        const PlonkPk pk = preprocess(be, cub.mature(), circuit, vk);
+        const std::shared_ptr<WitnessPlan> plan = witness_plan(be, circuit);
+        const FrVec free = poseidon_merkle_witness_inputs(layout, v, tree[index], sibs, bits);
+        std::array<DevPtr, 3> w;
+        try {
+            w = plonk_witness(be, pk, *plan, pi, &free);
+        } catch (const ZkError &e) {
+            if (e.status != ZK_ERR_INVALID) throw;
+            const char *msg = std::strstr(e.what(), ": ");  // past ZkError's "zkhip error -1: "
+            std::printf("refused: %s\n", msg ? msg + 2 : e.what());
+            return 1;
+        }
+        const PlonkProof proof = plonk_prove(be, cub.mature(), pk, w[0], w[1], w[2], pi, DevPtr());
+        std::printf("proof sha256 %s\n", proof_digest(proof).c_str());
+        const bool ok = verify_bytes(be, *vk_mu, *vk_mu1, vk, pi, proof_to_bytes(proof));
+        std::printf("verdict %s\n", ok ? "accept" : "reject");
+        return ok ? 0 : 1;
+    } catch (const std::exception &e) {
+        std::fprintf(stderr, "poseidon_check: %s\n", e.what());
+        return 4;
+    }
+}

@@ -113,6 +113,14 @@ struct WitnessPlan {
         return v;
     }
 };
+// the constants of one Poseidon instance on the device (zk_poseidon_params); it holds its ctx
+struct PoseidonParams {
+    CtxRef ctx;
+    zk_poseidon_params *h = nullptr;
+    PoseidonParams(CtxRef c, zk_poseidon_params *h_) : ctx(std::move(c)), h(h_) {}
+    PoseidonParams(const PoseidonParams &) = delete;
+    ~PoseidonParams() { zk_poseidon_params_free(h); }
+};
 struct WitnessReport {  // zk_plonk_witness_check(_lookup): the counts and the smallest row / slot (~0: none); the lookups on a lookup plan only
     uint64_t bad_rows = 0, first_bad_row = ~0ull, bad_copies = 0, first_bad_copy = ~0ull, bad_lookups = 0, first_bad_lookup = ~0ull;
     bool ok() const { return !bad_rows && !bad_copies && !bad_lookups; }
@@ -671,6 +679,31 @@ class Ctx {
         G2 out;
         check(zk_msm_g2(h_, srs.handle(), offset, scalars.get(), n, out.data()));
         return out;
+    }
+    // ---- Poseidon at t = 3 (zk_poseidon_*; the rule and the instance: include/zkhip.h, zkhost/poseidon.hpp) ----
+    // rc: 3 (rf + rp) round constants, mds: 9 matrix entries row-major.  An odd rf, rf = 0 or rf + rp > 256: ZkError(ZK_ERR_INVALID)
+    std::shared_ptr<PoseidonParams> poseidon_params(int rf, int rp, const FrVec &rc, const FrVec &mds) {
+        need(rf + rp >= 0 && rc.size() == 3 * size_t(rf + rp) && mds.size() == 9, "poseidon_params: 3 (rf + rp) round constants and 9 matrix entries are needed");
+        zk_poseidon_params *p = nullptr;
+        check(zk_poseidon_params_create(h_, rf, rp, rc.empty() ? mds[0].v : rc[0].v, mds[0].v, &p));
+        return std::make_shared<PoseidonParams>(ref_, p);
+    }
+    // n states of three Fr; out may be the input itself (default: a new buffer).  Asynchronous
+    DevPtr poseidon_permute(const PoseidonParams &pp, const DevPtr &in, size_t n, const DevPtr *out = nullptr) {
+        DevPtr o = out ? *out : alloc_fr(3 * n);
+        check(zk_poseidon_permute(h_, pp.h, in.get(), o.get(), n));
+        return o;
+    }
+    DevPtr poseidon_hash2(const PoseidonParams &pp, const DevPtr &left, const DevPtr &right, size_t n, const DevPtr *out = nullptr) {
+        DevPtr o = out ? *out : alloc_fr(n);
+        check(zk_poseidon_hash2(h_, pp.h, left.get(), right.get(), o.get(), n));
+        return o;
+    }
+    // the tree of n = 2^k leaves: 2n - 1 Fr, the root last.  Asynchronous
+    DevPtr poseidon_merkle(const PoseidonParams &pp, const DevPtr &leaves, size_t n) {
+        DevPtr o = alloc_fr(n ? 2 * n - 1 : 1);
+        check(zk_poseidon_merkle(h_, pp.h, leaves.get(), n, o.get()));
+        return o;
     }
     // ---- Plonk witness (zk_witness_plan_create, zk_plonk_witness, zk_plonk_witness_check) ----
     // sigma: 3N slot numbers; out_sel: the wide gate's qO on the device (null: every row computes).  Rows that depend on their own output or a

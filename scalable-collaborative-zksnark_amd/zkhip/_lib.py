@@ -140,6 +140,11 @@ SYMBOLS = [
     ("zk_srs_halve", _i, [_vp, _vp, _pp]),
     ("zk_fr_hash_expand", _i, [_vp, ctypes.c_char_p, ctypes.c_uint32, _sz, _vp]),
     ("zk_srs_check", _i, [_vp, _vp, _sz, _vp, _sz, ctypes.c_char_p, _vp]),
+    ("zk_poseidon_params_create", _i, [_vp, _i, _i, _vp, _vp, _pp]),
+    ("zk_poseidon_params_free", None, [_vp]),
+    ("zk_poseidon_permute", _i, [_vp, _vp, _vp, _vp, _sz]),
+    ("zk_poseidon_hash2", _i, [_vp, _vp, _vp, _vp, _vp, _sz]),
+    ("zk_poseidon_merkle", _i, [_vp, _vp, _vp, _sz, _vp]),
 ]
 
 # include/zkhip_test.h: the zk_dbg_* test hooks -- not part of the ABI, resolved only when a test / tool asks (test_hooks())
