@@ -800,6 +800,37 @@ int zk_poseidon_hash2(zk_ctx *ctx, const zk_poseidon_params *params, const void 
  * enqueued, the host reads nothing. */
 int zk_poseidon_merkle(zk_ctx *ctx, const zk_poseidon_params *params, const void *d_leaves, size_t n, void *d_tree);
 
+/* ---- A Poseidon Merkle tree kept on the device: open, check and update (csrc/zk_poseidon.hip, K32-K36) -----------------------------
+ * d_tree is the tree of zk_poseidon_merkle: n = 2^d leaves, 2n - 1 Fr, level j (j = 0: the leaves) at lo_j = 2n - (2n >> j), the root
+ * at 2n - 2.  Leaf indices are HOST arrays of uint64_t; the library validates them on the host before anything is enqueued and stages
+ * them itself, so no call reads a status back from the device.  A refusal is ZK_ERR_INVALID with a message of the form
+ * "K of COUNT indices ..; the first is position P" (P: the smallest offending position in h_index) and enqueues nothing.  The three
+ * calls are ordered on the ctx stream like every other call (they wait for the stream once, before their index staging area is
+ * reused; the kernels themselves are enqueued and not waited for).  The largest count of every call is ZK_POSEIDON_MERKLE_MAX_COUNT.
+ * count = 0 is ZK_OK and enqueues nothing. */
+#define ZK_POSEIDON_MERKLE_MAX_COUNT ((size_t)1 << 26)
+/* A gather of `count` paths: d_siblings is [count][d] Fr, path k contiguous from the leaf level up,
+ *     d_siblings[k * d + j] = d_tree[lo_j + ((h_index[k] >> j) ^ 1)],  j < d.
+ * The bits of a path are the bits of its index (bit j set: the running node of level j is the RIGHT child); they are not written.
+ * Indices may repeat and come in any order; an index >= n is refused.  n = 1: empty paths, nothing is written.  n as for
+ * zk_poseidon_merkle. */
+int zk_poseidon_merkle_paths(zk_ctx *ctx, const void *d_tree, size_t n, const uint64_t *h_index, size_t count, void *d_siblings);
+/* d_roots[k] = the root of path k: cur = d_leaves[k]; for j < depth: cur = hash2(sib, cur) if bit j of h_index[k] is set, else
+ * hash2(cur, sib), sib = d_siblings[k * depth + j].  One lane per path.  depth <= 40; an index with a bit at or above `depth` is
+ * refused; depth = 0 copies the leaves.  The caller compares the roots.  d_roots may be d_leaves. */
+int zk_poseidon_merkle_roots(zk_ctx *ctx, const zk_poseidon_params *params, const void *d_leaves, const uint64_t *h_index, const void *d_siblings,
+                             size_t depth, size_t count, void *d_roots);
+/* d_tree[h_index[k]] = d_values[k] for k < count, then exactly the nodes with a written leaf below them are recomputed; every other
+ * element of d_tree keeps its bits.  h_index must be STRICTLY ASCENDING (a repeat or a descent is refused with the first offending
+ * position, an index >= n likewise): "last write wins" is the business of the caller.  The result is a function of the inputs alone:
+ * among the lanes that share a parent the one that hashes is taken from the sorted order (lane k leads at level j when k = 0 or
+ * h_index[k - 1] >> (j + 1) differs from its own), never from a race; no atomics, no workgroup waits on another.  Launches: one for
+ * the leaf writes; one per level while the level has more than poseidon_tail_nodes distinct parents; then ONE launch of one 256-lane
+ * workgroup for all remaining levels, a fence and a barrier between levels.  count = n equals zk_poseidon_merkle of the new leaves.
+ * d_values: fully reduced Montgomery Fr, no overlap with d_tree. */
+int zk_poseidon_merkle_update(zk_ctx *ctx, const zk_poseidon_params *params, void *d_tree, size_t n, const uint64_t *h_index, const void *d_values,
+                              size_t count);
+
 /* (the zk_dbg_* test hooks of the library are declared in include/zkhip_test.h: they are not part of this surface) */
 
 #ifdef __cplusplus

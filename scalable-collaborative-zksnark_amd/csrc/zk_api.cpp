@@ -804,6 +804,19 @@ int zk_poseidon_merkle(zk_ctx* ctx, const zk_poseidon_params* params, const void
     NEED(ctx, params && d_leaves && d_tree);
     return poseidon_merkle(ctx, params, d_leaves, n, d_tree);
 }
+int zk_poseidon_merkle_paths(zk_ctx* ctx, const void* d_tree, size_t n, const uint64_t* h_index, size_t count, void* d_siblings) {
+    NEED(ctx, count == 0 || (d_tree && h_index && (n == 1 || d_siblings)));
+    return poseidon_merkle_paths(ctx, d_tree, n, h_index, count, d_siblings);
+}
+int zk_poseidon_merkle_roots(zk_ctx* ctx, const zk_poseidon_params* params, const void* d_leaves, const uint64_t* h_index, const void* d_siblings, size_t depth, size_t count,
+                             void* d_roots) {
+    NEED(ctx, params && (count == 0 || (d_leaves && h_index && d_roots && (depth == 0 || d_siblings))));
+    return poseidon_merkle_roots(ctx, params, d_leaves, h_index, d_siblings, depth, count, d_roots);
+}
+int zk_poseidon_merkle_update(zk_ctx* ctx, const zk_poseidon_params* params, void* d_tree, size_t n, const uint64_t* h_index, const void* d_values, size_t count) {
+    NEED(ctx, params && (count == 0 || (d_tree && h_index && d_values)));
+    return poseidon_merkle_update(ctx, params, d_tree, n, h_index, d_values, count);
+}
 int zk_g1_lincomb_seg(zk_ctx* ctx, size_t segments, const size_t* h_start, const uint64_t* h_points18, const uint64_t* h_scalars, uint64_t* h_out18) {
     NEED(ctx, segments == 0 || (h_start && h_out18));
     return g1_lincomb_seg(ctx, segments, h_start, h_points18, h_scalars, h_out18);

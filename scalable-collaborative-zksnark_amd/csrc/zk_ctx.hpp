@@ -384,6 +384,10 @@ void poseidon_params_free(zk_poseidon_params* p);
 int poseidon_permute(zk_ctx* ctx, const zk_poseidon_params* p, const void* d_in, void* d_out, size_t n);
 int poseidon_hash2(zk_ctx* ctx, const zk_poseidon_params* p, const void* d_left, const void* d_right, void* d_out, size_t n);
 int poseidon_merkle(zk_ctx* ctx, const zk_poseidon_params* p, const void* d_leaves, size_t n, void* d_tree);
+// the tree kept on the device: a gather of paths, the roots of paths, a batch of leaf writes (h_index: host, validated before anything is enqueued)
+int poseidon_merkle_paths(zk_ctx* ctx, const void* d_tree, size_t n, const uint64_t* h_index, size_t count, void* d_siblings);
+int poseidon_merkle_roots(zk_ctx* ctx, const zk_poseidon_params* p, const void* d_leaves, const uint64_t* h_index, const void* d_siblings, size_t depth, size_t count, void* d_roots);
+int poseidon_merkle_update(zk_ctx* ctx, const zk_poseidon_params* p, void* d_tree, size_t n, const uint64_t* h_index, const void* d_values, size_t count);
 // ---- zk_pairing.hip: test hooks ----
 int dbg_fq30_op(zk_ctx* ctx, int mode, const void* d_x, const void* d_kx, const void* d_y, const void* d_ky, void* d_out, void* d_flags,
                 size_t n);

@@ -10,6 +10,9 @@
 // The SRS trapdoor is SplitMix64(S + 1), mu + 1 elements.  --sample-only: the circuit digest and the root by the host rule
 // (poseidon_merkle_host), without a device.  --time-host K: the serial host rule alone on K states / a tree of K leaves, milliseconds
 // (the CPU column of tools/poseidon_time.py).
+// --update COUNT: the state transition instead -- COUNT writes (leaf (S + 5k) mod 2^D takes SplitMix64(S + 2)[k]) applied one after another to the
+// device tree (poseidon_update), each path by Ctx::poseidon_merkle_paths, then poseidon_merkle_update_circuit(D, COUNT); prints circuit sha256 /
+// old root / new root / proof sha256 / verdict; --break leaf alters the first write's old leaf; --sample-only: the first three lines by the host rules.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -47,8 +50,75 @@ static int time_host(size_t k) {
     return 0;
 }
 
+// --update COUNT: COUNT writes one after another on the device tree, each path taken from the tree before its write, then
+// poseidon_merkle_update_circuit(D, COUNT) through the pipeline (tools/poseidon_merkle.py `update`, line for line)
+static int update_check(size_t depth, uint64_t seed, size_t count, const std::string &brk, bool sample_only) {
+    const size_t n = size_t(1) << depth;
+    CircuitLayout layout;
+    MerkleUpdateVars v;
+    const PlonkCircuit circuit = poseidon_merkle_update_circuit(depth, count, layout, v);
+    const FrVec leaves = SplitMix64(seed).fr_vec(n), fresh = SplitMix64(seed + 2).fr_vec(count);
+    std::vector<std::pair<uint64_t, Fr>> writes;
+    for (size_t k = 0; k < count; ++k) writes.push_back({(seed + 5 * k) % n, fresh[k]});
+    std::printf("circuit sha256 %s\n", built_circuit_digest(circuit).c_str());
+    if (sample_only) {
+        FrVec tree = poseidon_merkle_host(leaves);
+        std::printf("old root %s\n", hex_of(tree.back()).c_str());
+        for (const auto &w : writes) tree = poseidon_update_host(tree, n, {w});
+        std::printf("new root %s\n", hex_of(tree.back()).c_str());
+        return 0;
+    }
+    Ctx be(0);
+    const std::shared_ptr<PoseidonParams> pp = poseidon_params(be);
+    const DevPtr tree = be.poseidon_merkle(*pp, be.to_device(leaves), n);
+    const Fr old_root = be.to_host(tree.fr(2 * n - 2), 1)[0];
+    std::printf("old root %s\n", hex_of(old_root).c_str());
+    std::vector<MerkleUpdateStep> steps;
+    for (const auto &w : writes) {
+        MerkleUpdateStep s;
+        s.old_leaf = be.to_host(tree.fr((size_t)w.first), 1)[0];
+        s.new_leaf = w.second;
+        s.siblings = be.to_host(be.poseidon_merkle_paths(tree, n, {w.first}), depth);
+        for (size_t j = 0; j < depth; ++j) s.bits.push_back((w.first >> j) & 1);
+        steps.push_back(s);
+        poseidon_update(be, *pp, tree, n, {w});
+    }
+    const Fr new_root = be.to_host(tree.fr(2 * n - 2), 1)[0];
+    std::printf("new root %s\n", hex_of(new_root).c_str());
+    if (brk == "leaf") steps[0].old_leaf += Fr::one();
+    if (brk == "bit") steps[0].bits[0] ^= 1;
+    if (brk == "sibling") steps[0].siblings[0] += Fr::one();
+    const FrVec pi{old_root, brk == "root" ? new_root + Fr::one() : new_root};
+    const FrVec s = SplitMix64(seed + 1).fr_vec(circuit.mu + 1);
+    const PolynomialCommitmentCub cub = PolynomialCommitmentCub::make(be, s);
+    const std::vector<uint64_t> pg2 = powers_of_g2(be, s);
+    std::vector<G2Rec> keys(pg2.size() / 24);
+    std::memcpy(keys.data(), pg2.data(), 8 * pg2.size());
+    std::vector<G2Rec> keys_mu{keys[0]};
+    keys_mu.insert(keys_mu.end(), keys.begin() + 2, keys.end());
+    std::shared_ptr<PcsVk> vk_mu1 = be.pcs_vk(nullptr, keys[0].data(), 192, keys.size()), vk_mu = be.pcs_vk(nullptr, keys_mu[0].data(), 192, keys_mu.size());
+    PlonkVk vk;
+    const PlonkPk pk = preprocess(be, cub.mature(), circuit, vk);
+    const std::shared_ptr<WitnessPlan> plan = witness_plan(be, circuit);
+    const FrVec free = poseidon_merkle_update_inputs(layout, v, steps);
+    std::array<DevPtr, 3> w;
+    try {
+        w = plonk_witness(be, pk, *plan, pi, &free);
+    } catch (const ZkError &e) {
+        if (e.status != ZK_ERR_INVALID) throw;
+        const char *msg = std::strstr(e.what(), ": ");  // past ZkError's "zkhip error -1: "
+        std::printf("refused: %s\n", msg ? msg + 2 : e.what());
+        return 1;
+    }
+    const PlonkProof proof = plonk_prove(be, cub.mature(), pk, w[0], w[1], w[2], pi, DevPtr());
+    std::printf("proof sha256 %s\n", proof_digest(proof).c_str());
+    const bool ok = verify_bytes(be, *vk_mu, *vk_mu1, vk, pi, proof_to_bytes(proof));
+    std::printf("verdict %s\n", ok ? "accept" : "reject");
+    return ok ? 0 : 1;
+}
+
 int main(int argc, char **argv) {
-    long long depth = -1, seed = 7, time_k = 0;
+    long long depth = -1, seed = 7, time_k = 0, update = 0;
     std::string brk;
     bool sample_only = false, usage = argc < 2;
     auto number = [](const char *s, long long &out) {
@@ -62,15 +132,18 @@ int main(int argc, char **argv) {
         else if (i + 1 < argc && k == "--depth") usage = !number(argv[++i], depth) || depth < 1 || depth > 40;
         else if (i + 1 < argc && k == "--seed") usage = !number(argv[++i], seed);
         else if (i + 1 < argc && k == "--time-host") usage = !number(argv[++i], time_k) || time_k < 1;
-        else if (i + 1 < argc && k == "--break") brk = argv[++i], usage = brk != "bit" && brk != "sibling" && brk != "root";
+        else if (i + 1 < argc && k == "--update") usage = !number(argv[++i], update) || update < 1;
+        else if (i + 1 < argc && k == "--break") brk = argv[++i], usage = brk != "bit" && brk != "sibling" && brk != "root" && brk != "leaf";
         else usage = true;
     }
+    if (brk == "leaf" && update == 0) usage = true;
     if (!usage && time_k > 0 && depth < 0) return time_host((size_t)time_k);
     if (usage || depth < 0 || time_k > 0) {
-        std::fprintf(stderr, "usage: poseidon_check --depth D [--seed S] [--break bit|sibling|root] [--sample-only] | --time-host K\n");
+        std::fprintf(stderr, "usage: poseidon_check --depth D [--seed S] [--update COUNT] [--break bit|sibling|root|leaf (leaf: with --update)] [--sample-only] | --time-host K\n");
         return 2;
     }
     try {
+        if (update > 0) return update_check((size_t)depth, (uint64_t)seed, (size_t)update, brk, sample_only);
         const size_t n = size_t(1) << depth, index = (size_t)seed % n;
         CircuitLayout layout;
         MerkleCircuitVars v;

@@ -705,6 +705,25 @@ class Ctx {
         check(zk_poseidon_merkle(h_, pp.h, leaves.get(), n, o.get()));
         return o;
     }
+    // the tree kept on the device.  Indices are host integers, validated by the library (ZkError(ZK_ERR_INVALID) with its message).  Asynchronous
+    // [count][d] siblings of the leaves `index` (any order, repeats allowed), path k contiguous from the leaf level up
+    DevPtr poseidon_merkle_paths(const DevPtr &tree, size_t n, const std::vector<uint64_t> &index) {
+        size_t d = 0;
+        while ((size_t(1) << d) < n) ++d;
+        DevPtr o = alloc_fr(index.size() * d);
+        check(zk_poseidon_merkle_paths(h_, tree.get(), n, index.data(), index.size(), o.get()));
+        return o;
+    }
+    // the root each leaf reaches through its `depth` siblings with the bits of its index
+    DevPtr poseidon_merkle_roots(const PoseidonParams &pp, const DevPtr &leaves, const std::vector<uint64_t> &index, const DevPtr &siblings, size_t depth) {
+        DevPtr o = alloc_fr(index.size());
+        check(zk_poseidon_merkle_roots(h_, pp.h, leaves.get(), index.data(), siblings.get(), depth, index.size(), o.get()));
+        return o;
+    }
+    // tree[index[k]] = values[k] in place, then the nodes above the written leaves; index strictly ascending (zkhost::poseidon_update sorts)
+    void poseidon_merkle_update(const PoseidonParams &pp, const DevPtr &tree, size_t n, const std::vector<uint64_t> &index, const DevPtr &values) {
+        check(zk_poseidon_merkle_update(h_, pp.h, tree.get(), n, index.data(), values.get(), index.size()));
+    }
     // ---- Plonk witness (zk_witness_plan_create, zk_plonk_witness, zk_plonk_witness_check) ----
     // sigma: 3N slot numbers; out_sel: the wide gate's qO on the device (null: every row computes).  Rows that depend on their own output or a
     // sigma that is not a permutation: ZkError(ZK_ERR_INVALID)

@@ -12,7 +12,13 @@
 // constants are a value (PoseidonConsts) here and a parameter object on the device.
 // THE CIRCUIT: a round's constant addition is folded into the qC of the previous linear layer's rows, the first round's constants take
 // three lin rows; a full round is 9 rows, a partial round 7, the v1 permutation 474; a Merkle level is 480 rows (zkhip/poseidon.py).
+// A TREE KEPT ON THE DEVICE: poseidon_paths_host / poseidon_update_host (the rules), poseidon_update / poseidon_verify_paths over
+// Ctx::poseidon_merkle_paths / _roots / _update, and poseidon_merkle_update_circuit: 959 rows per level and write.
 #pragma once
+#include <algorithm>
+#include <cstring>
+#include <string>
+
 #include "circuit.hpp"
 
 namespace zkhost {
@@ -91,8 +97,74 @@ inline void poseidon_merkle_path(const FrVec &tree, size_t n, size_t index, FrVe
     }
 }
 
+
+// ---- a tree that is opened and updated: the host rules of zk_poseidon_merkle_paths / _update, with the library's refusals ----
+namespace detail {
+inline size_t merkle_depth(const FrVec &tree, size_t n) {
+    if (n == 0 || (n & (n - 1)) || tree.size() != 2 * n - 1) throw ZkError(ZK_ERR_INVALID, "a tree of n = 2^d leaves has 2n - 1 elements");
+    size_t d = 0;
+    while ((size_t(1) << d) < n) ++d;
+    return d;
+}
+inline void refuse_not_below(const char *what, const std::vector<uint64_t> &index, uint64_t n) {
+    size_t bad = 0, first = 0;
+    for (size_t k = index.size(); k-- > 0;)
+        if (index[k] >= n) ++bad, first = k;
+    if (bad)
+        throw ZkError(ZK_ERR_INVALID, std::string(what) + ": " + std::to_string(bad) + " of " + std::to_string(index.size()) + " indices are not below n = " + std::to_string(n) +
+                                          "; the first is position " + std::to_string(first));
+}
+}  // namespace detail
+// one vector of d siblings per index, from the leaf level up; the bits of a path are the bits of its index
+inline std::vector<FrVec> poseidon_paths_host(const FrVec &tree, size_t n, const std::vector<uint64_t> &index) {
+    detail::merkle_depth(tree, n);
+    detail::refuse_not_below("zk_poseidon_merkle_paths", index, n);
+    std::vector<FrVec> out(index.size());
+    std::vector<uint64_t> bits;
+    for (size_t k = 0; k < index.size(); ++k) poseidon_merkle_path(tree, n, (size_t)index[k], out[k], bits);
+    return out;
+}
+// a NEW tree: the writes (index, value) applied in order -- any order, repeats allowed, the last write of a leaf wins -- and only the nodes
+// above a written leaf hashed again
+inline FrVec poseidon_update_host(const FrVec &tree, size_t n, const std::vector<std::pair<uint64_t, Fr>> &writes, const PoseidonConsts &p = poseidon_v1()) {
+    const size_t d = detail::merkle_depth(tree, n);
+    std::vector<uint64_t> touched;
+    for (const auto &w : writes) touched.push_back(w.first);
+    detail::refuse_not_below("zk_poseidon_merkle_update", touched, n);
+    FrVec out = tree;
+    for (const auto &w : writes) out[(size_t)w.first] = w.second;
+    std::sort(touched.begin(), touched.end());
+    size_t lo = 0;
+    for (size_t j = 0; j < d; ++j) {
+        for (uint64_t &i : touched) i >>= 1;
+        touched.erase(std::unique(touched.begin(), touched.end()), touched.end());
+        for (uint64_t q : touched) out[lo + (n >> j) + q] = poseidon_hash2_host(out[lo + 2 * q], out[lo + 2 * q + 1], p);
+        lo += n >> j;
+    }
+    return out;
+}
+
 // ---- the device ----
 inline std::shared_ptr<PoseidonParams> poseidon_params(Ctx &be, const PoseidonConsts &p = poseidon_v1()) { return be.poseidon_params(p.rf, p.rp, p.rc, p.mds); }
+// writes in any order, repeats allowed: sorted by index (stable), the last write of a leaf kept, then Ctx::poseidon_merkle_update.  Asynchronous
+inline void poseidon_update(Ctx &be, const PoseidonParams &pp, const DevPtr &tree, size_t n, const std::vector<std::pair<uint64_t, Fr>> &writes) {
+    std::vector<size_t> order(writes.size());
+    for (size_t k = 0; k < order.size(); ++k) order[k] = k;
+    std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return writes[a].first < writes[b].first; });
+    std::vector<uint64_t> index;
+    FrVec values;
+    for (size_t k = 0; k < order.size(); ++k)
+        if (k + 1 == order.size() || writes[order[k + 1]].first != writes[order[k]].first) index.push_back(writes[order[k]].first), values.push_back(writes[order[k]].second);
+    be.poseidon_merkle_update(pp, tree, n, index, be.to_device(values));
+}
+// per path: does it reach `root`?  Blocking: the roots are read back
+inline std::vector<bool> poseidon_verify_paths(Ctx &be, const PoseidonParams &pp, const Fr &root, const DevPtr &leaves, const std::vector<uint64_t> &index, const DevPtr &siblings,
+                                               size_t depth) {
+    const FrVec got = be.to_host(be.poseidon_merkle_roots(pp, leaves, index, siblings, depth), index.size());
+    std::vector<bool> ok(got.size());
+    for (size_t k = 0; k < got.size(); ++k) ok[k] = std::memcmp(got[k].v, root.v, 32) == 0;
+    return ok;
+}
 
 // ---- the circuit ----
 inline std::array<Var, 3> poseidon_permutation_gadget(CircuitBuilder &b, const std::array<Var, 3> &state, const PoseidonConsts &p = poseidon_v1()) {
@@ -141,6 +213,78 @@ inline PlonkCircuit poseidon_merkle_circuit(size_t depth, CircuitLayout &layout,
     b.assert_equal(cur, v.root);
     v.out = cur;
     return b.build(layout);
+}
+
+// "`count` chained leaf writes take the public old root to the public new root" (zkhip.poseidon.merkle_update_circuit, row for row): two public
+// inputs; private, per write: old leaf, new leaf, `depth` siblings, `depth` bits.  Per level ONE assert_bool(bit) row, then the five selection rows
+// and the permutation (479 rows) on the old running node and again on the new one, against the same sibling and bit: 959 rows per level,
+// 2 + 959 depth count in all.  The first old chain joins the old root's copy class, every later old chain the new chain before it, the last new
+// chain the new root's.
+struct MerkleUpdateWrite {
+    Var old_leaf = kNoVar, new_leaf = kNoVar, old_out = kNoVar, new_out = kNoVar;
+    std::vector<Var> siblings, bits;
+};
+struct MerkleUpdateVars {
+    Var old_root = kNoVar, new_root = kNoVar;
+    std::vector<MerkleUpdateWrite> writes;
+};
+struct MerkleUpdateStep {  // one write of a chain, on the tree before it
+    Fr old_leaf, new_leaf;
+    FrVec siblings;
+    std::vector<uint64_t> bits;
+};
+namespace detail {
+inline Var merkle_level(CircuitBuilder &b, Var cur, Var sib, Var bit, const PoseidonConsts &p) {
+    const Fr one = Fr::one(), zero = Fr::zero(), minus = -Fr::one();
+    const Var d = b.lin(one, sib, minus, cur, zero);
+    const Var e = b.mul(bit, d);
+    const Var left = b.lin(one, cur, one, e, zero), right = b.lin(one, sib, minus, e, zero);
+    const Var z = b.lin(zero, kNoVar, zero, kNoVar, zero);
+    return poseidon_permutation_gadget(b, {z, left, right}, p)[0];
+}
+}  // namespace detail
+inline PlonkCircuit poseidon_merkle_update_circuit(size_t depth, size_t count, CircuitLayout &layout, MerkleUpdateVars &v, const PoseidonConsts &p = poseidon_v1()) {
+    if (depth < 1 || count < 1) throw ZkError(ZK_ERR_INVALID, "poseidon_merkle_update_circuit: depth >= 1 and count >= 1 are needed");
+    CircuitBuilder b;
+    v = MerkleUpdateVars();
+    v.old_root = b.pub();
+    v.new_root = b.pub();
+    v.writes.resize(count);
+    for (MerkleUpdateWrite &w : v.writes) {
+        w.old_leaf = b.priv();
+        w.new_leaf = b.priv();
+        for (size_t i = 0; i < depth; ++i) w.siblings.push_back(b.priv());
+        for (size_t i = 0; i < depth; ++i) w.bits.push_back(b.priv());
+    }
+    Var prev = kNoVar;
+    for (size_t k = 0; k < count; ++k) {
+        MerkleUpdateWrite &w = v.writes[k];
+        Var old_cur = w.old_leaf, new_cur = w.new_leaf;
+        for (size_t i = 0; i < depth; ++i) {
+            b.assert_bool(w.bits[i]);
+            old_cur = detail::merkle_level(b, old_cur, w.siblings[i], w.bits[i], p);
+            new_cur = detail::merkle_level(b, new_cur, w.siblings[i], w.bits[i], p);
+        }
+        b.assert_equal(old_cur, k == 0 ? v.old_root : prev);
+        w.old_out = old_cur, w.new_out = new_cur;
+        prev = new_cur;
+    }
+    b.assert_equal(prev, v.new_root);
+    return b.build(layout);
+}
+inline FrVec poseidon_merkle_update_inputs(const CircuitLayout &layout, const MerkleUpdateVars &v, const std::vector<MerkleUpdateStep> &steps) {
+    if (steps.size() != v.writes.size()) throw ZkError(ZK_ERR_INVALID, "poseidon_merkle_update_inputs: the chain does not have the circuit's number of writes");
+    std::vector<std::pair<Var, Fr>> values;
+    for (size_t k = 0; k < steps.size(); ++k) {
+        const MerkleUpdateWrite &w = v.writes[k];
+        const MerkleUpdateStep &s = steps[k];
+        if (s.siblings.size() != w.siblings.size() || s.bits.size() != w.bits.size()) throw ZkError(ZK_ERR_INVALID, "poseidon_merkle_update_inputs: the path does not have the circuit's depth");
+        values.push_back({w.old_leaf, s.old_leaf});
+        values.push_back({w.new_leaf, s.new_leaf});
+        for (size_t i = 0; i < s.siblings.size(); ++i) values.push_back({w.siblings[i], s.siblings[i]});
+        for (size_t i = 0; i < s.bits.size(); ++i) values.push_back({w.bits[i], Fr::from_u64(s.bits[i])});
+    }
+    return layout.free(values);
 }
 inline FrVec poseidon_merkle_witness_inputs(const CircuitLayout &layout, const MerkleCircuitVars &v, const Fr &leaf, const FrVec &siblings, const std::vector<uint64_t> &bits) {
     if (siblings.size() != v.siblings.size() || bits.size() != v.bits.size()) throw ZkError(ZK_ERR_INVALID, "poseidon_merkle_witness_inputs: the path does not have the circuit's depth");

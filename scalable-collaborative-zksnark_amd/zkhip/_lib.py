@@ -145,6 +145,9 @@ SYMBOLS = [
     ("zk_poseidon_permute", _i, [_vp, _vp, _vp, _vp, _sz]),
     ("zk_poseidon_hash2", _i, [_vp, _vp, _vp, _vp, _vp, _sz]),
     ("zk_poseidon_merkle", _i, [_vp, _vp, _vp, _sz, _vp]),
+    ("zk_poseidon_merkle_paths", _i, [_vp, _vp, _sz, _vp, _sz, _vp]),
+    ("zk_poseidon_merkle_roots", _i, [_vp, _vp, _vp, _vp, _vp, _sz, _sz, _vp]),
+    ("zk_poseidon_merkle_update", _i, [_vp, _vp, _vp, _sz, _vp, _vp, _sz]),
 ]
 
 # include/zkhip_test.h: the zk_dbg_* test hooks -- not part of the ABI, resolved only when a test / tool asks (test_hooks())

@@ -26,6 +26,17 @@ permutation 3 + 8 * 9 + 57 * 7 = 474 rows.  merkle_circuit(depth): one public in
 bits.  Per level: assert_bool(bit), d = sib - cur, e = bit d, left = cur + e, right = sib - e (bit = 1: the running node is the RIGHT
 child), a constant-0 row, the permutation on (0, left, right): 480 rows.  After the last level the output is put into the public
 root's copy class.  Depth 1 has 481 rows (mu = 9), depth 2 has 961 (mu = 10).
+
+A TREE KEPT ON THE DEVICE.  Poseidon.paths / roots / verify_paths / update open many leaves, hash many paths up to their roots and apply a
+batch of leaf writes to the tree in place, touching only the nodes above the written leaves (zk_poseidon_merkle_paths / _roots / _update;
+paths_host and update_host are the same rules on python integers, with the same refusals).  The bits of a path are the bits of its index.
+merkle_update_circuit(depth, count) is the statement "the tree with public root R became the tree with public root R' by `count` leaf
+writes, one after another, and nothing else changed": two public inputs (old root, new root); private, per write: old leaf, new leaf,
+`depth` siblings, `depth` bits.  Per level ONE assert_bool(bit) row, then the level of merkle_circuit without its assertion (d, e, left,
+right, the constant 0, the permutation: 5 + 474 = 479 rows) twice -- on the old running node and on the new one, against the SAME sibling
+and bit variables: 1 + 2 * 479 = 959 rows per level, 959 depth per write, 2 + 959 depth count in all.  The old chain of the first write is
+put into the old root's copy class, the old chain of every later write into the class of the new chain before it, the last new chain
+into the new root's.  (depth, count) = (1, 1) has 961 rows (mu = 10), (2, 1) has 1920 (mu = 11), (2, 2) has 3838 (mu = 12).
 """
 from __future__ import annotations
 
@@ -115,6 +126,45 @@ def path_root_host(leaf: int, siblings, bits, p: dict | None = None) -> int:
     return cur
 
 
+def _tree_depth(tree, n: int) -> int:
+    if n < 1 or n & (n - 1) or len(tree) != 2 * n - 1:
+        raise ValueError("a tree of n = 2^d leaves has 2n - 1 elements")
+    return n.bit_length() - 1
+
+
+def _refuse_not_below(what: str, indices, limit: int, text: str):
+    """the library's refusal of indices >= limit, with its message"""
+    bad = [k for k, i in enumerate(indices) if not 0 <= i < limit]
+    if bad:
+        raise ValueError(f"{what}: {len(bad)} of {len(indices)} indices {text}; the first is position {bad[0]}")
+
+
+def paths_host(tree, n: int, indices) -> list:
+    """the sibling lists of zk_poseidon_merkle_paths: one list of d siblings per index, from the leaf level up (the bits are the index's)"""
+    _tree_depth(tree, n)
+    indices = [int(i) for i in indices]
+    _refuse_not_below("zk_poseidon_merkle_paths", indices, n, f"are not below n = {n}")
+    return [merkle_path(tree, n, i)[0] for i in indices]
+
+
+def update_host(tree, n: int, writes, p: dict | None = None) -> list:
+    """a NEW tree list: the leaf writes (index, value) applied in order -- any order, repeats allowed, the last write of a leaf wins -- and
+    only the nodes above a written leaf hashed again (zk_poseidon_merkle_update after the wrapper's sort)"""
+    d = _tree_depth(tree, n)
+    writes = [(int(i), int(v) % R_MOD) for i, v in writes]
+    _refuse_not_below("zk_poseidon_merkle_update", [i for i, _ in writes], n, f"are not below n = {n}")
+    out = list(tree)
+    for i, v in writes:
+        out[i] = v
+    touched, lo = sorted({i for i, _ in writes}), 0
+    for j in range(d):
+        touched = sorted({i >> 1 for i in touched})
+        for q in touched:
+            out[lo + (n >> j) + q] = hash2_host(out[lo + 2 * q], out[lo + 2 * q + 1], p)
+        lo += n >> j
+    return out
+
+
 # ---- the device ----
 class Poseidon:
     """zk_poseidon_params of one instance on one Ctx, with the three device calls.  Arguments that name device memory are what Ctx takes
@@ -149,6 +199,50 @@ class Poseidon:
         out = out or self.be.alloc(32 * max(2 * n - 1, 1))
         self._check(self.be.lib.zk_poseidon_merkle(self.be.h, self.h, _ptr(leaves), n, _ptr(out)))
         return out
+
+    # ---- a tree kept on the device (zk_poseidon_merkle_paths / _roots / _update).  Indices are host integers; the library validates them ----
+    @staticmethod
+    def _indices(indices) -> np.ndarray:
+        return np.ascontiguousarray(np.asarray(indices, dtype=np.uint64).reshape(-1))
+
+    def paths(self, tree, n: int, indices, out=None):
+        """the sibling paths of the leaves `indices` (any order, repeats allowed) of the device tree of n leaves: [count][d] Fr, path k contiguous
+        from the leaf level up (asynchronous).  The bits of path k are the bits of indices[k]"""
+        idx = self._indices(indices)
+        out = out or self.be.alloc(max(32 * len(idx) * max(int(n).bit_length() - 1, 0), 1))
+        self._check(self.be.lib.zk_poseidon_merkle_paths(self.be.h, _ptr(tree), n, _h(idx), len(idx), _ptr(out)))
+        return out
+
+    def roots(self, leaves, indices, siblings, depth: int, out=None):
+        """out[k] = the root that leaf k reaches through siblings[k][0 .. depth) with the bits of indices[k] (asynchronous); out may be `leaves`"""
+        idx = self._indices(indices)
+        out = out or self.be.alloc(max(32 * len(idx), 1))
+        self._check(self.be.lib.zk_poseidon_merkle_roots(self.be.h, self.h, _ptr(leaves), _h(idx), _ptr(siblings), depth, len(idx), _ptr(out)))
+        return out
+
+    def verify_paths(self, root: int, leaves, indices, siblings, depth: int) -> np.ndarray:
+        """a boolean per path: does it reach `root` (a canonical integer)?  Blocking: the roots are read back"""
+        count = len(self._indices(indices))
+        got = self.roots(leaves, indices, siblings, depth).download((count, 4))
+        return (got == fr_mont(int(root) % R_MOD).reshape(1, 4)).all(axis=1)
+
+    def update(self, tree, n: int, indices, values):
+        """tree[indices[k]] = values[k], then the nodes above the written leaves are hashed again, in place (asynchronous).  values: a host
+        [count, 4] array of Montgomery limbs -- the indices may then come in any order and repeat, the LAST write of a leaf wins (a stable
+        numpy sort, then the library's strictly ascending form); or device memory, which is handed to the library as it is, so the indices
+        must already ascend strictly"""
+        idx = self._indices(indices)
+        if isinstance(values, np.ndarray):
+            values = np.ascontiguousarray(values, dtype=np.uint64).reshape(-1, 4)
+            if len(values) != len(idx):
+                raise ValueError("one value per index is needed")
+            order = np.argsort(idx, kind="stable")
+            last = np.ones(len(idx), dtype=bool)
+            last[:-1] = idx[order][1:] != idx[order][:-1]
+            order = order[last]
+            idx, values = np.ascontiguousarray(idx[order]), self.be.to_device(values[order])
+        self._check(self.be.lib.zk_poseidon_merkle_update(self.be.h, self.h, _ptr(tree), n, _h(idx), _ptr(values), len(idx)))
+        return tree
 
     def free(self):
         if self.h and getattr(self.be, "h", None):
@@ -199,6 +293,59 @@ def merkle_circuit(depth: int, p: dict | None = None):
     b.assert_equal(cur, root)
     circuit, layout = b.build()
     return circuit, layout, {"root": root, "leaf": leaf, "siblings": sibs, "bits": bits, "out": cur}
+
+
+def _merkle_level(b, cur, sib, bit, p):
+    """the rows of one level after the bit's assertion: left / right selected by the bit, then the hash -- 5 + permutation rows"""
+    d = b.lin(1, sib, -1, cur, 0)
+    e = b.mul(bit, d)
+    left, right = b.lin(1, cur, 1, e, 0), b.lin(1, sib, -1, e, 0)
+    zero = b.lin(0, None, 0, None, 0)
+    return permutation_gadget(b, (zero, left, right), p)[0]
+
+
+def merkle_update_circuit(depth: int, count: int = 1, p: dict | None = None):
+    """-> (circuit, layout, vars) of "`count` chained leaf writes take the public old root to the public new root" (module text).
+    vars = {"old_root", "new_root", "writes": [count x {"old_leaf", "new_leaf", "siblings": [depth], "bits": [depth], "old_out", "new_out"}]}"""
+    from .circuit import Builder
+
+    if depth < 1 or count < 1:
+        raise ValueError("depth >= 1 and count >= 1 are needed")
+    b = Builder()
+    old_root, new_root = b.public(), b.public()
+    writes = []
+    for _ in range(count):
+        w = {"old_leaf": b.private(), "new_leaf": b.private()}
+        w["siblings"], w["bits"] = [b.private() for _ in range(depth)], [b.private() for _ in range(depth)]
+        writes.append(w)
+    prev = None
+    for i, w in enumerate(writes):
+        old, new = w["old_leaf"], w["new_leaf"]
+        for sib, bit in zip(w["siblings"], w["bits"]):
+            b.assert_bool(bit)
+            old = _merkle_level(b, old, sib, bit, p)
+            new = _merkle_level(b, new, sib, bit, p)
+        b.assert_equal(old, old_root if i == 0 else prev)
+        w["old_out"], w["new_out"] = old, new
+        prev = new
+    b.assert_equal(prev, new_root)
+    circuit, layout = b.build()
+    return circuit, layout, {"old_root": old_root, "new_root": new_root, "writes": writes}
+
+
+def merkle_update_inputs(layout, vars: dict, steps) -> np.ndarray:
+    """the `free` array of plonk.witness for a chain of writes: steps = one (old_leaf, new_leaf, siblings, bits) per write, integers"""
+    steps = list(steps)
+    if len(steps) != len(vars["writes"]):
+        raise ValueError("the chain does not have the circuit's number of writes")
+    values = {}
+    for w, (old_leaf, new_leaf, siblings, bits) in zip(vars["writes"], steps):
+        if len(siblings) != len(w["siblings"]) or len(bits) != len(w["bits"]):
+            raise ValueError("the path does not have the circuit's depth")
+        values[w["old_leaf"]], values[w["new_leaf"]] = old_leaf, new_leaf
+        values.update(zip(w["siblings"], siblings))
+        values.update(zip(w["bits"], bits))
+    return layout.free(values)
 
 
 def merkle_witness_inputs(layout, vars: dict, leaf: int, siblings, bits) -> np.ndarray:

@@ -12,6 +12,13 @@ witness_plan -> witness -> preprocess -> prove -> proof bytes -> verify_bytes.  
 host/bin/poseidon_check takes the same flags and prints the same lines.  The SRS trapdoor is splitmix_fr(mu + 1, S + 1).
   --break bit | sibling | root    flip the leaf-level bit / add 1 to the leaf-level sibling / add 1 to the public root
   --sample-only                   the circuit digest and the root by the host rule (poseidon.merkle_host); no GPU
+
+  --update COUNT    the state transition instead: the same tree kept on the device, COUNT writes applied ONE AFTER ANOTHER -- write k puts
+                    splitmix_fr(COUNT, S + 2)[k] into leaf (S + 5k) mod 2^D with Poseidon.update, its path taken with Poseidon.paths from
+                    the tree before it -- then poseidon.merkle_update_circuit(D, COUNT) through the same pipeline.  Prints
+                        circuit sha256 .. / old root .. / new root .. / proof sha256 .. / verdict ..
+                    --break leaf | bit | sibling | root alters the first write's old leaf, leaf-level bit or sibling, or the public new
+                    root; --sample-only prints the first three lines by the host rules (merkle_host, update_host)
 """
 import argparse
 import os
@@ -23,13 +30,82 @@ sys.path.insert(0, os.path.join(ROOT, "scalable-collaborative-zksnark_amd"))
 import numpy as np  # noqa: E402
 
 
+def update(args) -> int:
+    """--update COUNT: the proved state transition (module text)"""
+    from zkhip import poseidon as ps
+    from zkhip.circuit import circuit_digest
+    from zkhip.field import R_MOD, fr_from_mont, fr_mont, splitmix_fr
+
+    ints = lambda a: [fr_from_mont(x) for x in np.asarray(a).reshape(-1, 4)]
+    depth, n, count = args.depth, 1 << args.depth, args.update
+    circuit, layout, v = ps.merkle_update_circuit(depth, count)
+    leaves = splitmix_fr(n, args.seed)
+    writes = [((args.seed + 5 * k) % n, x) for k, x in enumerate(ints(splitmix_fr(count, args.seed + 2)))]
+    print("circuit sha256", circuit_digest(circuit))
+    if args.sample_only:
+        tree = ps.merkle_host(ints(leaves))
+        print("old root %064x" % tree[-1])
+        for w in writes:
+            tree = ps.update_host(tree, n, [w])
+        print("new root %064x" % tree[-1])
+        return 0
+
+    import zkhip
+    from zkhip import dist_primitive as dp
+    from zkhip import pairing as pr
+    from zkhip import plonk
+
+    be = zkhip.Ctx(0)
+    pos = ps.Poseidon(be)
+    d_tree = pos.merkle(be.to_device(leaves), n)
+    root_of = lambda: ints(d_tree.download((1, 4), offset=32 * (2 * n - 2)))[0]
+    old_root = root_of()
+    print("old root %064x" % old_root)
+    steps = []
+    for i, x in writes:  # one after another: the old leaf and the path are those of the tree before the write
+        old_leaf = ints(d_tree.download((1, 4), offset=32 * i))[0]
+        sibs = ints(pos.paths(d_tree, n, [i]).download((depth, 4)))
+        steps.append([old_leaf, x, sibs, [(i >> j) & 1 for j in range(depth)]])
+        pos.update(d_tree, n, [i], fr_mont(x).reshape(1, 4))
+    new_root = root_of()
+    pos.free()
+    print("new root %064x" % new_root)
+    if args.brk == "leaf":
+        steps[0][0] = (steps[0][0] + 1) % R_MOD
+    if args.brk == "bit":
+        steps[0][3][0] ^= 1
+    if args.brk == "sibling":
+        steps[0][2][0] = (steps[0][2][0] + 1) % R_MOD
+    pi = np.stack([fr_mont(old_root), fr_mont((new_root + 1) % R_MOD if args.brk == "root" else new_root)])
+    s = splitmix_fr(circuit["mu"] + 1, args.seed + 1)
+    pcs = dp.PolynomialCommitmentCub.new(be, s).mature()
+    pk, vk = plonk.preprocess(be, pcs, circuit, pr.powers_of_g2(ints(s)))
+    plan = plonk.witness_plan(be, circuit)
+    try:
+        a, b, c = plonk.witness(be, pk, plan, pi, ps.merkle_update_inputs(layout, v, steps))
+    except ValueError as e:
+        print("refused:", e)
+        return 1
+    proof = plonk.prove(be, pk, a, b, c, pi)
+    print("proof sha256", plonk.proof_digest(proof))
+    ok = plonk.verify_bytes(be, vk, pi, plonk.proof_to_bytes(proof))
+    print("verdict", "accept" if ok else "reject")
+    be.close()
+    return 0 if ok else 1
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--depth", type=int, default=1)
     ap.add_argument("--seed", type=int, default=7)
-    ap.add_argument("--break", dest="brk", choices=("bit", "root", "sibling"))
+    ap.add_argument("--break", dest="brk", choices=("bit", "root", "sibling", "leaf"))
     ap.add_argument("--sample-only", action="store_true")
+    ap.add_argument("--update", type=int, default=0, metavar="COUNT")
     args = ap.parse_args()
+    if args.update < 0 or (args.brk == "leaf" and not args.update):
+        ap.error("--update takes a COUNT >= 1, and --break leaf goes with --update")
+    if args.update:
+        return update(args)
 
     from zkhip import poseidon as ps
     from zkhip.circuit import circuit_digest
