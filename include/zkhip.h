@@ -275,6 +275,20 @@ int zk_lookup3_find(zk_ctx *ctx, const void *const d_w[3], const void *const d_t
  *     c == t2[y].
  *     On generated wires the index zk_lookup3_find gives for a lookup-computing row is the y the generator used (a smaller index with an
  *     equal triple would have an equal pair), so the proof's multiplicities need nothing from the generator.
+ *   Advice (additive: a plan built without a non-zero code follows the rules above and nothing else).  A circuit may carry ADVICE: N u32
+ *     codes, one per row, 0 meaning none.  Advice is prover-side only: not preprocessed, not committed, in no vk, proof or digest of them.
+ *       ZK_ADV_INV0 = 1                              c = 1 / a mod r, and c = 0 when a = 0.  b is gathered and stored as usual, not used.
+ *       ZK_ADV_BITS(shift, width) = 2 | shift << 8 | width << 16
+ *                                                    c = (A >> shift) mod 2^width for the canonical integer A in [0, r) of a;
+ *                                                    0 <= shift, 1 <= width <= 64, shift + width <= 255.
+ *     Bits 24 .. 31 of a code are 0; anything else is an UNKNOWN code.
+ *     A row with a non-zero code is ADVICE-COMPUTING: a computing row like the other two kinds for the source of a class, the levels and
+ *     the refusal of rows that depend on their own output.  It must not also be gate-computing (wide gate: qO(x) = 0; the basic gate
+ *     computes on every row and so has no advice row: any non-zero code is refused) nor lookup-computing (qk(x) = 0).  It constrains
+ *     nothing by itself: soundness comes from ordinary gate rows next to it.  The CHECK does not test advice values -- h_bad keeps its
+ *     four (lookup plans: six) numbers -- so a witness may hold other advice where the constraints allow it (any c for INV0 of 0).
+ *     The outputs are fully reduced Montgomery forms, as every wire zk_plonk_witness writes; a free value or public input at or above r
+ *     is reduced before the advice acts on it.
  *
  * zk_witness_plan_create: the plan of one circuit, built once, on the host, in O(N): the cycles, the source of every slot, the levels
  * (Kahn's algorithm), the rows ordered by (level, row), the launch schedule; uploads 3N + N u32, the level offsets and, with d_out_sel,
@@ -295,6 +309,17 @@ int zk_witness_plan_create(zk_ctx *ctx, const uint64_t *h_sigma, const void *d_o
  * else as zk_witness_plan_create (the messages name this call).  Blocking.  zk_witness_plan_info and zk_witness_plan_free serve both. */
 int zk_witness_plan_create_lookup(zk_ctx *ctx, const uint64_t *h_sigma, const void *d_out_sel, const void *d_qk, const void *const d_t[3],
                                   size_t N, zk_witness_plan **out);
+/* The plan of a circuit WITH its advice codes (h_advice: N u32 on the host; the plan keeps a device copy), and with its lookup when d_qk
+ * and d_t are given (both NULL: no lookup).  With all codes zero the plan is the one zk_witness_plan_create / _create_lookup builds.
+ * Refusals beyond theirs (ZK_ERR_INVALID, nothing stays allocated; K and X are properties of the inputs): "K of N advice codes are
+ * unknown; the first is row X"; "K of N advice rows also compute by the gate or the table; the first is row X" (every advice row when
+ * d_out_sel is NULL); the rows that depend on their own output include the advice rows.  zk_plonk_witness (no lookup) and
+ * zk_plonk_witness_lookup run such a plan: an advice row takes its c in the level where its a becomes known; inside a level the advice
+ * rows stand together.  zk_witness_plan_info counts them as computing rows.  The check calls take such plans as they are. */
+#define ZK_ADV_INV0 1u
+#define ZK_ADV_BITS(shift, width) (2u | (uint32_t)(shift) << 8 | (uint32_t)(width) << 16)
+int zk_witness_plan_create_advice(zk_ctx *ctx, const uint64_t *h_sigma, const void *d_out_sel, const void *d_qk, const void *const d_t[3],
+                                  const uint32_t *h_advice, size_t N, zk_witness_plan **out);
 void zk_witness_plan_free(zk_witness_plan *plan);
 /* levels: how many levels the computing rows have (the largest level + 1); max_level_rows: the rows of the largest level; launches: the
  * level launches of one zk_plonk_witness -- a level of more than 256 rows is one launch of many workgroups, a run of consecutive

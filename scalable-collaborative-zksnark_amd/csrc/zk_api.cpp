@@ -476,12 +476,18 @@ int zk_lookup3_find(zk_ctx* ctx, const void* const d_w[3], const void* const d_t
 }
 int zk_witness_plan_create(zk_ctx* ctx, const uint64_t* h_sigma, const void* d_out_sel, size_t N, zk_witness_plan** out) {
     NEED(ctx, h_sigma && out);
-    return witness_plan_create(ctx, h_sigma, d_out_sel, nullptr, nullptr, N, out);
+    return witness_plan_create(ctx, "zk_witness_plan_create", h_sigma, d_out_sel, nullptr, nullptr, nullptr, N, out);
 }
 int zk_witness_plan_create_lookup(zk_ctx* ctx, const uint64_t* h_sigma, const void* d_out_sel, const void* d_qk, const void* const d_t[3], size_t N, zk_witness_plan** out) {
     NEED(ctx, h_sigma && d_qk && d_t && out);
     for (int j = 0; j < 3; j++) NEED(ctx, d_t[j]);
-    return witness_plan_create(ctx, h_sigma, d_out_sel, d_qk, d_t, N, out);
+    return witness_plan_create(ctx, "zk_witness_plan_create_lookup", h_sigma, d_out_sel, d_qk, d_t, nullptr, N, out);
+}
+int zk_witness_plan_create_advice(zk_ctx* ctx, const uint64_t* h_sigma, const void* d_out_sel, const void* d_qk, const void* const d_t[3], const uint32_t* h_advice, size_t N,
+                                  zk_witness_plan** out) {
+    NEED(ctx, h_sigma && h_advice && out && (d_qk != nullptr) == (d_t != nullptr));
+    for (int j = 0; d_t && j < 3; j++) NEED(ctx, d_t[j]);
+    return witness_plan_create(ctx, "zk_witness_plan_create_advice", h_sigma, d_out_sel, d_qk, d_t, h_advice, N, out);
 }
 void zk_witness_plan_free(zk_witness_plan* plan) { witness_plan_free(plan); }
 int zk_witness_plan_info(const zk_witness_plan* plan, size_t* levels, size_t* max_level_rows, size_t* launches) {

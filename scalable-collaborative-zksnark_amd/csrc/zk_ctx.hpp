@@ -108,6 +108,9 @@ struct zk_witness_plan {
     uint32_t* d_slots = nullptr;
     long force = -1;
     bool lookup = false;
+    // an advice plan (zk_witness_plan_create_advice with a non-zero code): the plan's own copy of the N codes; the advice-computing rows
+    // carry kWitAdvice in their d_order entry and stand AFTER the other rows of their level.  Null: the plan has no advice row.
+    uint32_t* d_advice = nullptr;
     size_t computing = 0, levels = 0, max_level_rows = 0;
     struct Launch {
         uint32_t lv0, lv1;  // the levels [lv0, lv1): ONE level of more than kWitBlock rows (a grid of workgroups), or a run of levels of at most kWitBlock rows each (one workgroup)
@@ -121,6 +124,7 @@ namespace zk {
 
 static constexpr uint32_t kWitFree = 0x80000000u;  // flag of zk_witness_plan::d_src (3N <= 3 * 2^29 stays below it)
 static constexpr uint32_t kWitLookup = 0x80000000u;  // flag of zk_witness_plan::d_order: a lookup-computing row (N <= 2^29 stays below it)
+static constexpr uint32_t kWitAdvice = 0x40000000u;  // flag of zk_witness_plan::d_order: an advice-computing row (N <= 2^29 leaves bit 30 free)
 static constexpr int kWitBlock = 256;
 
 // Experiment / diagnostics knobs of the whole library in ONE place.  Defaults are the shipped configuration; the only
@@ -271,8 +275,10 @@ int lookup_find(zk_ctx* ctx, const void* d_f, const void* d_t, size_t N, uint32_
 int lookup3_find(zk_ctx* ctx, const void* const* d_w, const void* const* d_t, const void* d_qk, size_t N, uint32_t* d_idx, void* d_m);
 
 // ---- zk_witness.cpp (the plan, on the host) / zk_witness.hip (the kernels) ----
-// d_qk, d_t: null (a plain plan), or the lookup selector and t0, t1, t2 (a lookup plan)
-int witness_plan_create(zk_ctx* ctx, const uint64_t* h_sigma, const void* d_out_sel, const void* d_qk, const void* const* d_t, size_t N, zk_witness_plan** out);
+// d_qk, d_t: null (a plain plan), or the lookup selector and t0, t1, t2 (a lookup plan); h_advice: null, or the N advice codes (name: the
+// export the messages name)
+int witness_plan_create(zk_ctx* ctx, const char* name, const uint64_t* h_sigma, const void* d_out_sel, const void* d_qk, const void* const* d_t, const uint32_t* h_advice,
+                        size_t N, zk_witness_plan** out);
 // zk_witness.hip: the slots of a lookup plan's key table built from (t0, t1) with the start slot `force`, then every entry's t2 compared
 // with the t2 of the first entry of its pair (blocking; the function rule of include/zkhip.h)
 int witness_key_table(zk_ctx* ctx, const char* name, const void* const* d_t, size_t N, long force, uint32_t* d_slots);

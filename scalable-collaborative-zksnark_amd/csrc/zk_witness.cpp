@@ -9,6 +9,10 @@
 // A LOOKUP plan (d_qk, d_t given) differs in two places: before step 1 the selector qk is read and checked (0 or 1), the key table of
 // (t0, t1) is built on the device (zk_witness.hip, witness_key_table) and the rows with qk = 1 that are not gate-computing become
 // LOOKUP-COMPUTING; steps 1 - 3 treat both kinds alike, and the order entry of a lookup-computing row carries kWitLookup.
+// An ADVICE plan (h_advice with a non-zero code) differs in three: the codes are checked (unknown ones, and rows that also compute by the
+// gate or the table, are refused), a row with a code is ADVICE-COMPUTING (kind 3 in comp) for steps 1 - 3, and step 3 orders a level by
+// (kind, row) with the advice rows last, so that they are contiguous; their order entries carry kWitAdvice and the plan keeps the codes
+// on the device.  With all codes zero every step does what it did.
 // Why on the host: it runs once per circuit and is serial on a deep circuit anyway; the per-proof work is zk_witness.hip.
 #include "fp.cuh"
 #include "zk_ctx.hpp"
@@ -27,6 +31,7 @@ void witness_plan_free(zk_witness_plan* plan) {
     if (plan->d_lvoff) (void)hipFree(plan->d_lvoff);
     if (plan->d_inv) (void)hipFree(plan->d_inv);
     if (plan->d_slots) (void)hipFree(plan->d_slots);
+    if (plan->d_advice) (void)hipFree(plan->d_advice);
     delete plan;
 }
 
@@ -46,11 +51,18 @@ int upload_u32(zk_ctx* ctx, const std::vector<uint32_t>& v, uint32_t** d_out) {
     if (!v.empty()) ZK_HIP(ctx, hipMemcpy(*d_out, v.data(), v.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     return ZK_OK;
 }
+// an advice code (include/zkhip.h): 0, ADV_INV0, or ADV_BITS with 1 <= width <= 64 and shift + width <= 255; bits 24 .. 31 are zero
+bool advice_code_known(uint32_t code) {
+    const uint32_t kind = code & 0xff, shift = (code >> 8) & 0xff, width = (code >> 16) & 0xff;
+    if (code >> 24) return false;
+    if (kind == 0 || kind == 1) return code == kind;
+    return kind == 2 && width >= 1 && width <= 64 && shift + width <= 255;
+}
 }  // namespace
 
-int witness_plan_create(zk_ctx* ctx, const uint64_t* h_sigma, const void* d_out_sel, const void* d_qk, const void* const* d_t, size_t N, zk_witness_plan** out) {
+int witness_plan_create(zk_ctx* ctx, const char* name, const uint64_t* h_sigma, const void* d_out_sel, const void* d_qk, const void* const* d_t, const uint32_t* h_advice,
+                        size_t N, zk_witness_plan** out) {
     *out = nullptr;
-    const char* name = d_qk ? "zk_witness_plan_create_lookup" : "zk_witness_plan_create";
     if (N < 2 || (N & (N - 1)) || N > ((size_t)1 << 29)) return fail(ctx, ZK_ERR_INVALID, "%s: N = %zu is not a power of two in [2, 2^29]", name, N);
     const size_t S = 3 * N;
     ZK_HIP(ctx, hipSetDevice(ctx->device));
@@ -60,6 +72,16 @@ int witness_plan_create(zk_ctx* ctx, const uint64_t* h_sigma, const void* d_out_
         const uint64_t t = h_sigma[s];
         if (t >= S || mark[t]) return fail(ctx, ZK_ERR_INVALID, "%s: sigma is not a permutation of the %zu wire slots (entry %zu)", name, S, s);
         mark[t] = 1;
+    }
+    // the advice codes: every one known.  A plan whose codes are all zero is a plan without advice
+    bool advice = false;
+    if (h_advice) {
+        size_t bad = 0, first = N;
+        for (size_t x = 0; x < N; x++) {
+            if (!advice_code_known(h_advice[x]) && !bad++) first = x;
+            advice |= h_advice[x] != 0;
+        }
+        if (bad) return fail(ctx, ZK_ERR_INVALID, "%s: %zu of %zu advice codes are unknown; the first is row %zu", name, bad, N, first);
     }
     // the gate-computing rows: all of them, or those with a non-zero output selector
     std::vector<uint8_t> comp(N, 1);
@@ -107,6 +129,16 @@ int witness_plan_create(zk_ctx* ctx, const uint64_t* h_sigma, const void* d_out_
         ZK_HIP(ctx, device_alloc(ctx, (void**)&plan->d_slots, 2 * N * sizeof(uint32_t)));
         const int rc = witness_key_table(ctx, name, d_t, N, force, plan->d_slots);
         if (rc != ZK_OK) return rc;
+    }
+    // an advice row computes by its code alone: neither by the gate nor by the table (kind 3 in comp)
+    if (advice) {
+        size_t bad = 0, first = N;
+        for (size_t x = 0; x < N; x++) {
+            if (!h_advice[x]) continue;
+            if (comp[x] && !bad++) first = x;
+            comp[x] = 3;
+        }
+        if (bad) return fail(ctx, ZK_ERR_INVALID, "%s: %zu of %zu advice rows also compute by the gate or the table; the first is row %zu", name, bad, N, first);
     }
     // 1. the cycles.  Slots are visited in ascending order, so a cycle is entered at its smallest slot
     std::vector<uint32_t> src(S);
@@ -165,7 +197,8 @@ int witness_plan_create(zk_ctx* ctx, const uint64_t* h_sigma, const void* d_out_
             if (comp[x] && indeg[x]) first = x;
         return fail(ctx, ZK_ERR_INVALID, "%s: %zu of %zu rows depend on their own output; the first is row %zu", name, nc - queue.size(), N, first);
     }
-    // 3. (level, row) order by a counting sort; the rows that compute nothing follow in ascending order
+    // 3. (level, row) order by a counting sort -- (level, advice or not, row) on an advice plan; the rows that compute nothing follow in
+    // ascending order
     plan->computing = nc;
     const size_t levels = nc ? (size_t)top + 1 : 0;
     plan->levels = levels;
@@ -178,9 +211,16 @@ int witness_plan_create(zk_ctx* ctx, const uint64_t* h_sigma, const void* d_out_
         lvoff[v + 1] += lvoff[v];
     }
     std::vector<uint32_t> order(N), at(lvoff.begin(), lvoff.end() - (levels ? 1 : 0));
+    std::vector<uint32_t> at_adv;  // where the advice rows of a level begin: after its other rows
+    if (advice) {
+        at_adv.assign(lvoff.begin() + 1, lvoff.end());
+        for (size_t x = 0; x < N; x++)
+            if (comp[x] == 3) at_adv[level[x]]--;
+    }
     size_t rest = nc;
     for (size_t x = 0; x < N; x++) {
-        if (comp[x]) order[at[level[x]]++] = (uint32_t)x | (comp[x] == 2 ? kWitLookup : 0);
+        if (comp[x] == 3) order[at_adv[level[x]]++] = (uint32_t)x | kWitAdvice;
+        else if (comp[x]) order[at[level[x]]++] = (uint32_t)x | (comp[x] == 2 ? kWitLookup : 0);
         else order[rest++] = (uint32_t)x;
     }
     for (size_t v = 0; v < levels;) {
@@ -196,6 +236,10 @@ int witness_plan_create(zk_ctx* ctx, const uint64_t* h_sigma, const void* d_out_
     if (rc == ZK_OK) rc = upload_u32(ctx, order, &plan->d_order);
     if (rc == ZK_OK) rc = upload_u32(ctx, lvoff, &plan->d_lvoff);
     if (rc != ZK_OK) return rc;
+    if (advice) {
+        ZK_HIP(ctx, device_alloc(ctx, (void**)&plan->d_advice, N * sizeof(uint32_t)));
+        ZK_HIP(ctx, hipMemcpy(plan->d_advice, h_advice, N * sizeof(uint32_t), hipMemcpyHostToDevice));
+    }
     if (d_out_sel) {
         // 1 / qO by the batch inversion: numerator 1 and denominator qO on the gate-computing rows, 0 / 1 elsewhere (no zero denominator)
         uint64_t one[4];

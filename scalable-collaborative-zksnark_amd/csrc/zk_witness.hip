@@ -23,6 +23,13 @@
 // The kernels of plans without a lookup are the ones above, unchanged: the lookup variants are kernels of their own, with an argument
 // block of their own (WitLk), and share the row functions.
 //
+// Advice plans (zk_witness_plan_create_advice with a non-zero code; the rules are in include/zkhip.h).  A row whose order entry carries
+// kWitAdvice gathers a and b as every row does and takes its c from its code and a: the inverse (0 for 0), or a field of the bits of a's
+// canonical integer.  K22 / K23 have a third variant for such plans, with and without a lookup (k_wit_level_adv<LK>, k_wit_run_adv<LK>):
+// gate rows, advice rows and, at LK = 1, lookup rows, on the row functions of the other variants.  The plan puts the advice rows of a
+// level behind its other rows, so a wave of a large level pays the inversion only when it holds such rows.  The check does not look at
+// the codes: an advice row constrains nothing by itself.
+//
 // Order.  The launches follow one another on the ctx stream; no host read lies between them.  A row reads only the c of rows of LOWER
 // levels: an earlier launch, or an earlier level of the same workgroup, whose stores are complete and visible at workgroup scope after
 // the fence and the barrier that close the level.  No kernel ever waits on another workgroup: no ready flags, no spin loops, no
@@ -128,6 +135,53 @@ __device__ __forceinline__ void wit_row_lk(const WitArgs& w, const WitLk& lk, u3
     fr_store(w.w[2], x, c);
 }
 
+// the c of an advice row.  a is fully reduced (wit_value).  INV0: 1 / a by Fermat, and an explicit 0 for 0.  BITS: out of Montgomery
+// form, fully reduced, then `width` <= 64 bits from bit `shift` -- a window of three 32-bit limbs (64 bits at any offset; the limbs past
+// the eighth are 0, and so is every bit from 255 up) -- and back into Montgomery form by one multiplication with R^2.  The limb is picked
+// by compares, not by a dynamic index: the limbs stay in registers.  The plan checked the code.
+__device__ __forceinline__ Fr wit_advice(u32 code, const Fr& a) {
+    if ((code & 0xff) == 1) {
+        if (fp_is_zero(a)) return fp_zero<FrCfg>();
+        return fp_inv<FrCfg>(a);
+    }
+    const u32 shift = (code >> 8) & 0xff, width = (code >> 16) & 0xff;
+    const Fr v = wit_canon(fp_from_mont<FrCfg>(a));
+    const u32 k0 = shift >> 5, off = shift & 31;
+    u32 l0 = 0, l1 = 0, l2 = 0;
+#pragma unroll
+    for (u32 k = 0; k < 8; k++) {
+        l0 = k == k0 ? v.l[k] : l0;
+        l1 = k == k0 + 1 ? v.l[k] : l1;
+        l2 = k == k0 + 2 ? v.l[k] : l2;
+    }
+    u64 f = (((u64)l1 << 32) | l0) >> off;
+    if (off) f |= (u64)l2 << (64 - off);
+    if (width < 64) f &= ((u64)1 << width) - 1;
+    Fr t = fp_zero<FrCfg>(), r2;
+    t.l[0] = (u32)f, t.l[1] = (u32)(f >> 32);
+#pragma unroll
+    for (int i = 0; i < 8; i++) r2.l[i] = FrCfg::R2(i);
+    return fr_mul(t, r2);
+}
+// a row of an advice plan (wide gate): e = the order entry, the row and the flag of an advice- or (LK) lookup-computing row
+template <int LK>
+__device__ __forceinline__ void wit_row_adv(const WitArgs& w, const WitLk& lk, const u32* __restrict__ adv, u32 e) {
+    const u32 x = e & ~(kWitLookup | kWitAdvice);
+    const Fr a = wit_value(w, w.src[x]), b = wit_value(w, w.src[w.N + x]);
+    Fr c;
+    if (e & kWitAdvice) {
+        c = wit_advice(adv[x], a);
+    } else if (LK && (e & kWitLookup)) {
+        u32 y;
+        c = wit_probe(lk, w.N, a, b, y) == 1 ? fr_load(lk.t2, y) : fp_zero<FrCfg>();
+    } else {
+        c = wit_out<1>(w, x, a, b);
+    }
+    fr_store(w.w[0], x, a);
+    fr_store(w.w[1], x, b);
+    fr_store(w.w[2], x, c);
+}
+
 // ---------------------------------------------------------------------------------------
 // K22.  order[begin .. end): one level
 // ---------------------------------------------------------------------------------------
@@ -137,6 +191,10 @@ __global__ void __launch_bounds__(kWitBlock) k_wit_level(WitArgs w, u32 begin, u
 }
 __global__ void __launch_bounds__(kWitBlock) k_wit_level_lk(WitArgs w, WitLk lk, u32 begin, u32 end) {
     for (size_t i = (size_t)begin + (size_t)blockIdx.x * kWitBlock + threadIdx.x; i < end; i += (size_t)gridDim.x * kWitBlock) wit_row_lk(w, lk, w.order[i]);
+}
+template <int LK>
+__global__ void __launch_bounds__(kWitBlock) k_wit_level_adv(WitArgs w, WitLk lk, const u32* __restrict__ adv, u32 begin, u32 end) {
+    for (size_t i = (size_t)begin + (size_t)blockIdx.x * kWitBlock + threadIdx.x; i < end; i += (size_t)gridDim.x * kWitBlock) wit_row_adv<LK>(w, lk, adv, w.order[i]);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -159,9 +217,18 @@ __global__ void __launch_bounds__(kWitBlock) k_wit_run_lk(WitArgs w, WitLk lk, u
         __syncthreads();
     }
 }
+template <int LK>
+__global__ void __launch_bounds__(kWitBlock) k_wit_run_adv(WitArgs w, WitLk lk, const u32* __restrict__ adv, u32 lv0, u32 lv1) {
+    for (u32 lv = lv0; lv < lv1; lv++) {
+        const u32 i = w.lvoff[lv] + threadIdx.x;
+        if (i < w.lvoff[lv + 1]) wit_row_adv<LK>(w, lk, adv, w.order[i]);  // the advice and the probe inside the branch, the barrier outside it
+        __threadfence_block();
+        __syncthreads();
+    }
+}
 
 // ---------------------------------------------------------------------------------------
-// K24.  order[begin .. N): the rows that compute nothing (neither gate- nor lookup-computing: their order entries carry no flag)
+// K24.  order[begin .. N): the rows that compute nothing (neither gate-, lookup- nor advice-computing: their order entries carry no flag)
 // ---------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(kWitBlock) k_wit_fill(WitArgs w, u32 begin) {
     for (size_t i = (size_t)begin + (size_t)blockIdx.x * kWitBlock + threadIdx.x; i < w.N; i += (size_t)gridDim.x * kWitBlock) {
@@ -379,15 +446,20 @@ int plonk_witness(zk_ctx* ctx, const zk_witness_plan* plan, int gate_kind, const
     w.free_ = d_free, w.w[0] = d_a, w.w[1] = d_b, w.w[2] = d_c;
     const size_t N = plan->N;
     const bool lk_rows = plan->lookup && gate_kind;  // the basic gate has no lookup-computing row: its order entries carry no flag
+    const u32* adv = plan->d_advice;                 // an advice plan is one of the wide gate (wit_args checked the kind against d_inv)
     for (const zk_witness_plan::Launch& L : plan->launches) {
         if (L.grid) {
             const u32 begin = plan->lvoff[L.lv0], end = plan->lvoff[L.lv1];
             const unsigned blocks = (unsigned)std::min<size_t>(((size_t)(end - begin) + kWitBlock - 1) / kWitBlock, (size_t)ctx->cu_count * 8);
-            if (lk_rows) hipLaunchKernelGGL(k_wit_level_lk, dim3(blocks), dim3(kWitBlock), 0, ctx->stream, w, lk, begin, end);
+            if (adv && plan->lookup) hipLaunchKernelGGL(k_wit_level_adv<1>, dim3(blocks), dim3(kWitBlock), 0, ctx->stream, w, lk, adv, begin, end);
+            else if (adv) hipLaunchKernelGGL(k_wit_level_adv<0>, dim3(blocks), dim3(kWitBlock), 0, ctx->stream, w, lk, adv, begin, end);
+            else if (lk_rows) hipLaunchKernelGGL(k_wit_level_lk, dim3(blocks), dim3(kWitBlock), 0, ctx->stream, w, lk, begin, end);
             else if (gate_kind) hipLaunchKernelGGL(k_wit_level<1>, dim3(blocks), dim3(kWitBlock), 0, ctx->stream, w, begin, end);
             else hipLaunchKernelGGL(k_wit_level<0>, dim3(blocks), dim3(kWitBlock), 0, ctx->stream, w, begin, end);
         } else {
-            if (lk_rows) hipLaunchKernelGGL(k_wit_run_lk, dim3(1), dim3(kWitBlock), 0, ctx->stream, w, lk, L.lv0, L.lv1);
+            if (adv && plan->lookup) hipLaunchKernelGGL(k_wit_run_adv<1>, dim3(1), dim3(kWitBlock), 0, ctx->stream, w, lk, adv, L.lv0, L.lv1);
+            else if (adv) hipLaunchKernelGGL(k_wit_run_adv<0>, dim3(1), dim3(kWitBlock), 0, ctx->stream, w, lk, adv, L.lv0, L.lv1);
+            else if (lk_rows) hipLaunchKernelGGL(k_wit_run_lk, dim3(1), dim3(kWitBlock), 0, ctx->stream, w, lk, L.lv0, L.lv1);
             else if (gate_kind) hipLaunchKernelGGL(k_wit_run<1>, dim3(1), dim3(kWitBlock), 0, ctx->stream, w, L.lv0, L.lv1);
             else hipLaunchKernelGGL(k_wit_run<0>, dim3(1), dim3(kWitBlock), 0, ctx->stream, w, L.lv0, L.lv1);
         }

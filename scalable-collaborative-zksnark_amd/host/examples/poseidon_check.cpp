@@ -13,6 +13,10 @@
 // --update COUNT: the state transition instead -- COUNT writes (leaf (S + 5k) mod 2^D takes SplitMix64(S + 2)[k]) applied one after another to the
 // device tree (poseidon_update), each path by Ctx::poseidon_merkle_paths, then poseidon_merkle_update_circuit(D, COUNT); prints circuit sha256 /
 // old root / new root / proof sha256 / verdict; --break leaf alters the first write's old leaf; --sample-only: the first three lines by the host rules.
+// --transfer [--bits B --amount A]: a proved transfer instead -- the leaves are BALANCES, leaf k holds 2^(B-2) + (13 S + 41 k) mod 2^(B-2) (4 <= B <= 64);
+// leaf S mod 2^D pays A (default 5) to leaf (S + 1) mod 2^D: two writes one after another on the device tree, each path taken from the tree before its
+// write, then poseidon_merkle_transfer_circuit(D, B), whose inverses and bits the witness generator makes on the device.  Prints circuit sha256 /
+// roots <old> <new> / proof sha256 / verdict; --break sibling alters the sender's leaf-level sibling; --sample-only: the first two lines by the host rules.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -117,10 +121,75 @@ static int update_check(size_t depth, uint64_t seed, size_t count, const std::st
     return ok ? 0 : 1;
 }
 
+// --transfer: tools/poseidon_merkle.py `transfer`, line for line
+static int transfer_check(size_t depth, uint64_t seed, size_t bits, uint64_t amount, const std::string &brk, bool sample_only) {
+    const size_t n = size_t(1) << depth;
+    CircuitLayout layout;
+    MerkleUpdateVars v;
+    Var amount_var = kNoVar;
+    const PlonkCircuit circuit = poseidon_merkle_transfer_circuit(depth, bits, layout, v, amount_var);
+    const uint64_t quarter = uint64_t(1) << (bits - 2);
+    FrVec leaves;
+    for (size_t k = 0; k < n; ++k) leaves.push_back(Fr::from_u64(quarter + (13 * seed + 41 * k) % quarter));
+    const uint64_t from = seed % n, to = (seed + 1) % n;
+    const Fr amt = Fr::from_u64(amount);
+    std::printf("circuit sha256 %s\n", built_circuit_digest(circuit).c_str());
+    if (sample_only) {
+        FrVec tree = poseidon_merkle_host(leaves);
+        const Fr old_root = tree.back();
+        tree = poseidon_update_host(tree, n, {{from, leaves[from] - amt}});
+        tree = poseidon_update_host(tree, n, {{to, leaves[to] + amt}});
+        std::printf("roots %s %s\n", hex_of(old_root).c_str(), hex_of(tree.back()).c_str());
+        return 0;
+    }
+    Ctx be(0);
+    const std::shared_ptr<PoseidonParams> pp = poseidon_params(be);
+    const DevPtr tree = be.poseidon_merkle(*pp, be.to_device(leaves), n);
+    const Fr old_root = be.to_host(tree.fr(2 * n - 2), 1)[0];
+    MerkleTransferSide side[2];
+    const std::pair<uint64_t, Fr> writes[2] = {{from, leaves[from] - amt}, {to, leaves[to] + amt}};
+    for (size_t k = 0; k < 2; ++k) {
+        side[k].old_leaf = be.to_host(tree.fr((size_t)writes[k].first), 1)[0];
+        side[k].siblings = be.to_host(be.poseidon_merkle_paths(tree, n, {writes[k].first}), depth);
+        for (size_t j = 0; j < depth; ++j) side[k].bits.push_back((writes[k].first >> j) & 1);
+        poseidon_update(be, *pp, tree, n, {writes[k]});
+    }
+    const Fr new_root = be.to_host(tree.fr(2 * n - 2), 1)[0];
+    std::printf("roots %s %s\n", hex_of(old_root).c_str(), hex_of(new_root).c_str());
+    if (brk == "sibling") side[0].siblings[0] += Fr::one();
+    const FrVec pi{old_root, new_root};
+    const FrVec s = SplitMix64(seed + 1).fr_vec(circuit.mu + 1);
+    const PolynomialCommitmentCub cub = PolynomialCommitmentCub::make(be, s);
+    const std::vector<uint64_t> pg2 = powers_of_g2(be, s);
+    std::vector<G2Rec> keys(pg2.size() / 24);
+    std::memcpy(keys.data(), pg2.data(), 8 * pg2.size());
+    std::vector<G2Rec> keys_mu{keys[0]};
+    keys_mu.insert(keys_mu.end(), keys.begin() + 2, keys.end());
+    std::shared_ptr<PcsVk> vk_mu1 = be.pcs_vk(nullptr, keys[0].data(), 192, keys.size()), vk_mu = be.pcs_vk(nullptr, keys_mu[0].data(), 192, keys_mu.size());
+    PlonkVk vk;
+    const PlonkPk pk = preprocess(be, cub.mature(), circuit, vk);
+    const std::shared_ptr<WitnessPlan> plan = witness_plan(be, circuit);
+    const FrVec free = poseidon_merkle_transfer_inputs(layout, v, amount_var, amt, side[0], side[1]);
+    std::array<DevPtr, 3> w;
+    try {
+        w = plonk_witness(be, pk, *plan, pi, &free);
+    } catch (const ZkError &e) {
+        if (e.status != ZK_ERR_INVALID) throw;
+        const char *msg = std::strstr(e.what(), ": ");  // past ZkError's "zkhip error -1: "
+        std::printf("refused: %s\n", msg ? msg + 2 : e.what());
+        return 1;
+    }
+    const PlonkProof proof = plonk_prove(be, cub.mature(), pk, w[0], w[1], w[2], pi, DevPtr());
+    std::printf("proof sha256 %s\n", proof_digest(proof).c_str());
+    const bool ok = verify_bytes(be, *vk_mu, *vk_mu1, vk, pi, proof_to_bytes(proof));
+    std::printf("verdict %s\n", ok ? "accept" : "reject");
+    return ok ? 0 : 1;
+}
+
 int main(int argc, char **argv) {
-    long long depth = -1, seed = 7, time_k = 0, update = 0;
+    long long depth = -1, seed = 7, time_k = 0, update = 0, bits = 64, amount = 5;
     std::string brk;
-    bool sample_only = false, usage = argc < 2;
+    bool sample_only = false, transfer = false, usage = argc < 2;
     auto number = [](const char *s, long long &out) {
         char *end = nullptr;
         out = std::strtoll(s, &end, 10);
@@ -129,6 +198,9 @@ int main(int argc, char **argv) {
     for (int i = 1; i < argc && !usage; ++i) {
         const std::string k = argv[i];
         if (k == "--sample-only") sample_only = true;
+        else if (k == "--transfer") transfer = true;
+        else if (i + 1 < argc && k == "--bits") usage = !number(argv[++i], bits) || bits < 4 || bits > 64;
+        else if (i + 1 < argc && k == "--amount") usage = !number(argv[++i], amount);
         else if (i + 1 < argc && k == "--depth") usage = !number(argv[++i], depth) || depth < 1 || depth > 40;
         else if (i + 1 < argc && k == "--seed") usage = !number(argv[++i], seed);
         else if (i + 1 < argc && k == "--time-host") usage = !number(argv[++i], time_k) || time_k < 1;
@@ -137,12 +209,15 @@ int main(int argc, char **argv) {
         else usage = true;
     }
     if (brk == "leaf" && update == 0) usage = true;
+    if (transfer && (update > 0 || (!brk.empty() && brk != "sibling"))) usage = true;
     if (!usage && time_k > 0 && depth < 0) return time_host((size_t)time_k);
     if (usage || depth < 0 || time_k > 0) {
-        std::fprintf(stderr, "usage: poseidon_check --depth D [--seed S] [--update COUNT] [--break bit|sibling|root|leaf (leaf: with --update)] [--sample-only] | --time-host K\n");
+        std::fprintf(stderr, "usage: poseidon_check --depth D [--seed S] [--update COUNT | --transfer [--bits B] [--amount A]] [--break bit|sibling|root|leaf (leaf: with --update; --transfer: sibling)] "
+                             "[--sample-only] | --time-host K\n");
         return 2;
     }
     try {
+        if (transfer) return transfer_check((size_t)depth, (uint64_t)seed, (size_t)bits, (uint64_t)amount, brk, sample_only);
         if (update > 0) return update_check((size_t)depth, (uint64_t)seed, (size_t)update, brk, sample_only);
         const size_t n = size_t(1) << depth, index = (size_t)seed % n;
         CircuitLayout layout;

@@ -7,9 +7,14 @@
 //     pow5(x, kc)                             c = x^5 + kc
 //     assert_zero_of(ka, x, kb, y, km, kc)    a non-computing row (qO = 0): ka x + kb y + km x y + kc = 0; its c is tied to nothing
 //     assert_bool(x)                          x x - x = 0
+//     inv0(x)                                 an ADVICE row (include/zkhip.h): every selector 0, code ZK_ADV_INV0, c = 1 / x, or 0 for x = 0
+//     bits_of(x, shift, width)                an advice row, code ZK_ADV_BITS(shift, width): c = bits shift .. shift + width - 1 of x
+// An advice row constrains nothing; the gadgets on it add the gate rows that do (rows appended in brackets; zkhip/circuit.py has the text):
+//     inverse(x) [2], div(n, d) [3], assert_nonzero(x) [2], is_zero(x) [3], is_equal(x, y) [4], select(bit, x, y) [3],
+//     to_bits(x, n) [3n - 1; 1 <= n <= 253; x a computed value], assert_range(x, n) [3n - 1], less_than(x, y, n) [3n + 4; n <= 252]
 // priv() is a free variable (no row; its value comes from free[smallest slot of its class]); assert_equal(x, y) joins two copy classes.
 // build(): the public rows padded with zero input rows to l = 2^k (1 without any), then the rows in call order; mu the smallest with
-// N >= rows and N >= 2 l (mu >= 1); unused rows all-zero.  sigma: ONE cycle per class over its slots (column * N + row) in increasing
+// N >= rows and N >= 2 l (mu >= 1); unused rows all-zero; PlonkCircuit::advice is filled only when an advice row was used.  sigma: ONE cycle per class over its slots (column * N + row) in increasing
 // order, every other slot a fixed point -- the same array as the Python builder's, so both hosts print one digest.
 #pragma once
 #include <algorithm>
@@ -61,6 +66,48 @@ class CircuitBuilder {
         row({ka, kb, km, Fr::zero(), kc, Fr::zero()}, var(x, !ka.is_zero() || !km.is_zero()), var(y, !kb.is_zero() || !km.is_zero()), false);
     }
     void assert_bool(Var x) { assert_zero_of(-Fr::one(), x, Fr::zero(), x, Fr::one(), Fr::zero()); }
+    // ---- advice rows and the gadgets on them ----
+    Var inv0(Var x) { return row(no_sel(), var(x, true), kNoVar, true, ZK_ADV_INV0); }
+    Var bits_of(Var x, size_t shift, size_t width) {
+        if (width < 1 || width > 64 || shift + width > 255) throw ZkError(ZK_ERR_INVALID, "circuit builder: no advice code for this shift and width");
+        return row(no_sel(), var(x, true), kNoVar, true, ZK_ADV_BITS(shift, width));
+    }
+    Var inverse(Var x) {
+        const Var i = inv0(x);
+        assert_zero_of(Fr::zero(), x, Fr::zero(), i, Fr::one(), -Fr::one());
+        return i;
+    }
+    Var div(Var n, Var d) { return mul(n, inverse(d)); }
+    void assert_nonzero(Var x) { inverse(x); }
+    Var is_zero(Var x) {
+        const Var z = mul(x, inv0(x), -Fr::one(), Fr::one());
+        assert_zero_of(Fr::zero(), x, Fr::zero(), z, Fr::one(), Fr::zero());
+        return z;
+    }
+    Var is_equal(Var x, Var y) { return is_zero(lin(Fr::one(), x, -Fr::one(), y)); }
+    Var select(Var bit, Var x, Var y) { return lin(Fr::one(), y, Fr::one(), mul(bit, lin(Fr::one(), x, -Fr::one(), y))); }
+    std::vector<Var> to_bits(Var x, size_t n) {
+        if (n < 1 || n > 253) throw ZkError(ZK_ERR_INVALID, "circuit builder: to_bits takes 1 <= n <= 253 bits: above that the decomposition would not be unique");
+        std::vector<Var> bits;
+        for (size_t k = 0; k < n; ++k) bits.push_back(bits_of(x, k, 1));
+        for (Var v : bits) assert_bool(v);
+        Var acc = bits[0];
+        Fr pw = Fr::one();
+        for (size_t k = 1; k < n; ++k) {
+            pw += pw;
+            acc = lin(Fr::one(), acc, pw, bits[k]);
+        }
+        assert_equal(acc, x);
+        return bits;
+    }
+    void assert_range(Var x, size_t n) { to_bits(x, n); }
+    Var less_than(Var x, Var y, size_t n) {
+        if (n < 1 || n > 252) throw ZkError(ZK_ERR_INVALID, "circuit builder: less_than takes 1 <= n <= 252 bits");
+        Fr pw = Fr::one();
+        for (size_t k = 0; k < n; ++k) pw += pw;
+        const Var top = to_bits(lin(Fr::one(), x, -Fr::one(), y, pw), n + 1)[n];
+        return lin(-Fr::one(), top, Fr::zero(), kNoVar, Fr::one());
+    }
     void assert_equal(Var x, Var y) {
         const size_t rx = find((size_t)var(x, true)), ry = find((size_t)var(y, true));
         if (rx != ry) parent_[std::max(rx, ry)] = std::min(rx, ry);
@@ -88,6 +135,10 @@ class CircuitBuilder {
         for (size_t i = 0; i < rows_.size(); ++i) {
             const size_t x = l + i;
             for (size_t k = 0; k < 6; ++k) c.sel[k][x] = rows_[i].sel[k];
+            if (rows_[i].advice) {
+                if (c.advice.empty()) c.advice.assign(N, 0);
+                c.advice[x] = rows_[i].advice;
+            }
             if (rows_[i].a != kNoVar) slots[find((size_t)rows_[i].a)].push_back(x);
             if (rows_[i].b != kNoVar) slots[find((size_t)rows_[i].b)].push_back(N + x);
         }
@@ -110,7 +161,9 @@ class CircuitBuilder {
     struct Row {
         std::array<Fr, 6> sel;  // qL, qR, qM, qO, qC, qH
         Var a, b;
+        uint32_t advice;
     };
+    static std::array<Fr, 6> no_sel() { return {Fr::zero(), Fr::zero(), Fr::zero(), Fr::zero(), Fr::zero(), Fr::zero()}; }
     Var fresh() {
         parent_.push_back(parent_.size());
         c_row_.push_back({false, kNone});
@@ -128,13 +181,13 @@ class CircuitBuilder {
         if (v < 0 || (size_t)v >= parent_.size()) throw ZkError(ZK_ERR_INVALID, "circuit builder: not a variable of this builder");
         return v;
     }
-    Var row(const std::array<Fr, 6> &sel, Var a, Var b, bool computing) {
+    Var row(const std::array<Fr, 6> &sel, Var a, Var b, bool computing, uint32_t advice = 0) {
         Var c = kNoVar;
         if (computing) {
             c = fresh();
             c_row_[(size_t)c] = {false, rows_.size()};
         }
-        rows_.push_back({sel, a, b});
+        rows_.push_back({sel, a, b, advice});
         return c;
     }
     size_t publics_ = 0;
@@ -143,13 +196,15 @@ class CircuitBuilder {
     std::vector<std::pair<bool, size_t>> c_row_;  // per variable: (an input row?, its index) or kNone
 };
 
-// SHA-256 of a built circuit: mu and l (one u64 each), the six selectors, sigma (u64), little-endian (zkhip.circuit.circuit_digest)
+// SHA-256 of a built circuit: mu and l (one u64 each), the six selectors, sigma (u64) and, only when it has them, the advice codes (u32),
+// little-endian (zkhip.circuit.circuit_digest)
 inline std::string built_circuit_digest(const PlonkCircuit &c) {
     Sha256 h;
     const uint64_t head[2] = {c.mu, c.l};
     h.update(head, 16);
     for (const FrVec &q : c.sel) h.update(q.data(), 32 * q.size());
     h.update(c.sigma.data(), 8 * c.sigma.size());
+    if (!c.advice.empty()) h.update(c.advice.data(), 4 * c.advice.size());
     return h.hex();
 }
 

@@ -784,6 +784,19 @@ class Ctx {
         r.bad_rows = bad[0], r.first_bad_row = bad[1], r.bad_copies = bad[2], r.first_bad_copy = bad[3], r.bad_lookups = bad[4], r.first_bad_lookup = bad[5];
         return r;
     }
+    // ---- a plan with the circuit's advice codes (zk_witness_plan_create_advice): N u32 (0: none, ZK_ADV_INV0, ZK_ADV_BITS(shift, width)); qk and
+    // table as witness_plan_lookup takes them, or both null.  Beyond the refusals of those two: unknown codes, advice rows that also compute by
+    // the gate or the table.  plonk_witness / plonk_witness_lookup and the checks take the plan as they take the others
+    std::shared_ptr<WitnessPlan> witness_plan_advice(const std::vector<uint64_t> &sigma, size_t N, const DevPtr *out_sel, const std::vector<uint32_t> &advice,
+                                                     const DevPtr *qk = nullptr, const std::array<DevPtr, 3> *table = nullptr) {
+        need(sigma.size() == 3 * N && advice.size() == N, "witness_plan_advice: sigma must hold 3N slot numbers and advice N codes");
+        need((qk != nullptr) == (table != nullptr), "witness_plan_advice: a lookup needs qk and the table");
+        const void *t[3] = {nullptr, nullptr, nullptr};
+        for (size_t j = 0; table && j < 3; ++j) t[j] = (*table)[j].get();
+        zk_witness_plan *p = nullptr;
+        check(zk_witness_plan_create_advice(h_, sigma.data(), out_sel ? out_sel->get() : nullptr, qk ? qk->get() : nullptr, table ? t : nullptr, advice.data(), N, &p));
+        return std::make_shared<WitnessPlan>(ref_, p, N, out_sel != nullptr, qk != nullptr);
+    }
     // g1_96: powers_of_g[0][0] as a 96-byte affine record (nullptr: the generator); powers_g2: n_g2 affine records at `stride`
     std::shared_ptr<PcsVk> pcs_vk(const void *g1_96, const void *powers_g2, size_t stride, size_t n_g2) {
         zk_pcs_vk *vk = nullptr;

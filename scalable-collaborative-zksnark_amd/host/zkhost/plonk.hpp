@@ -62,6 +62,7 @@ struct PlonkCircuit {
     bool lookup = false;
     FrVec qk, t0, t1, t2;               // with a lookup: the selector and the table, N elements each
     std::vector<uint32_t> idx;          // with a lookup: the prover's row-to-table indices
+    std::vector<uint32_t> advice;       // the advice codes, N of them (empty: none): prover-side only, read by witness_plan alone
     FrVec free;                         // sample_circuit_lookup_fn only: the free values at their slots (3N elements, 0 elsewhere); not in the digest
 };
 struct PlonkVk {
@@ -124,14 +125,22 @@ inline Fr gate_closed_form(GateKind k, const Fr &eq, const FrVec &g, const Fr &i
 // ---- witness (zkhip.plonk.witness_plan / witness / check_witness; the rules: include/zkhip.h) ----
 // the plan of a circuit: built once, on the host inside the library; the wide gate's output selector qO is sel[3].  lookup: the plan of
 // the circuit WITH its lookup (required then; the key table of (t0, t1) is built on the device) -- plonk_witness / plonk_check_witness
-// dispatch on the plan.  The default ignores a lookup the circuit may carry
-inline std::shared_ptr<WitnessPlan> witness_plan(Ctx &be, const PlonkCircuit &c, bool lookup = false) {
+// dispatch on the plan.  The default ignores a lookup the circuit may carry.  advice: -1 uses the circuit's advice codes when it has
+// them (Ctx::witness_plan_advice), 0 ignores them, 1 requires them
+inline std::shared_ptr<WitnessPlan> witness_plan(Ctx &be, const PlonkCircuit &c, bool lookup = false, int advice = -1) {
     const size_t N = size_t(1) << c.mu;
     DevPtr qo;
     if (c.gate == GateKind::wide) qo = be.to_device(c.sel[3]);
     const DevPtr *out_sel = c.gate == GateKind::wide ? &qo : nullptr;
-    if (!lookup) return be.witness_plan(c.sigma, N, out_sel);
+    if (advice > 0 && c.advice.empty()) throw ZkError(ZK_ERR_INVALID, "witness_plan: an advice plan needs a circuit with advice codes");
+    const bool adv = advice != 0 && !c.advice.empty();
+    if (!lookup) return adv ? be.witness_plan_advice(c.sigma, N, out_sel, c.advice) : be.witness_plan(c.sigma, N, out_sel);
     if (!c.lookup) throw ZkError(ZK_ERR_INVALID, "witness_plan: a lookup plan needs a circuit with a lookup");
+    if (adv) {
+        const DevPtr qk = be.to_device(c.qk);
+        const std::array<DevPtr, 3> t = {be.to_device(c.t0), be.to_device(c.t1), be.to_device(c.t2)};
+        return be.witness_plan_advice(c.sigma, N, out_sel, c.advice, &qk, &t);
+    }
     return be.witness_plan_lookup(c.sigma, N, out_sel, be.to_device(c.qk), {be.to_device(c.t0), be.to_device(c.t1), be.to_device(c.t2)});
 }
 inline void witness_need(bool ok, const char *what) {

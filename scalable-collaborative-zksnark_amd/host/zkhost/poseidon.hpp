@@ -286,6 +286,67 @@ inline FrVec poseidon_merkle_update_inputs(const CircuitLayout &layout, const Me
     }
     return layout.free(values);
 }
+// "the tree with public root R became the tree with public root R' by moving a private non-zero amount from one leaf to another; the amount
+// and both new balances lie below 2^bits" (zkhip.poseidon.merkle_transfer_circuit, row for row): the update circuit with count = 2 whose new
+// leaves are computed -- amt = amount (a lin copy), new_from = old_from - amt, new_to = old_to + amt, assert_nonzero(amt), assert_range of amt,
+// new_from, new_to -- before the two writes' levels.  Every inverse and bit is advice, generated on the device.  v.writes[k].new_leaf names
+// the computed row; write 0 is the sender, write 1 the receiver (its path is one of the tree after write 0)
+struct MerkleTransferSide {  // one side of a transfer, on the tree before its write
+    Fr old_leaf;
+    FrVec siblings;
+    std::vector<uint64_t> bits;
+};
+inline PlonkCircuit poseidon_merkle_transfer_circuit(size_t depth, size_t bits, CircuitLayout &layout, MerkleUpdateVars &v, Var &amount, const PoseidonConsts &p = poseidon_v1()) {
+    if (depth < 1 || bits < 1 || bits > 253) throw ZkError(ZK_ERR_INVALID, "poseidon_merkle_transfer_circuit: depth >= 1 and 1 <= bits <= 253 are needed");
+    CircuitBuilder b;
+    v = MerkleUpdateVars();
+    v.old_root = b.pub();
+    v.new_root = b.pub();
+    v.writes.resize(2);
+    for (MerkleUpdateWrite &w : v.writes) {
+        w.old_leaf = b.priv();
+        for (size_t i = 0; i < depth; ++i) w.siblings.push_back(b.priv());
+        for (size_t i = 0; i < depth; ++i) w.bits.push_back(b.priv());
+    }
+    amount = b.priv();
+    const Fr one = Fr::one(), zero = Fr::zero();
+    const Var amt = b.lin(one, amount, zero, kNoVar, zero);
+    v.writes[0].new_leaf = b.lin(one, v.writes[0].old_leaf, -one, amt, zero);
+    v.writes[1].new_leaf = b.lin(one, v.writes[1].old_leaf, one, amt, zero);
+    b.assert_nonzero(amt);
+    b.assert_range(amt, bits);
+    b.assert_range(v.writes[0].new_leaf, bits);
+    b.assert_range(v.writes[1].new_leaf, bits);
+    Var prev = kNoVar;
+    for (size_t k = 0; k < 2; ++k) {
+        MerkleUpdateWrite &w = v.writes[k];
+        Var old_cur = w.old_leaf, new_cur = w.new_leaf;
+        for (size_t i = 0; i < depth; ++i) {
+            b.assert_bool(w.bits[i]);
+            old_cur = detail::merkle_level(b, old_cur, w.siblings[i], w.bits[i], p);
+            new_cur = detail::merkle_level(b, new_cur, w.siblings[i], w.bits[i], p);
+        }
+        b.assert_equal(old_cur, k == 0 ? v.old_root : prev);
+        w.old_out = old_cur, w.new_out = new_cur;
+        prev = new_cur;
+    }
+    b.assert_equal(prev, v.new_root);
+    return b.build(layout);
+}
+inline FrVec poseidon_merkle_transfer_inputs(const CircuitLayout &layout, const MerkleUpdateVars &v, Var amount, const Fr &amount_value, const MerkleTransferSide &sender,
+                                             const MerkleTransferSide &receiver) {
+    std::vector<std::pair<Var, Fr>> values{{amount, amount_value}};
+    const MerkleTransferSide *sides[2] = {&sender, &receiver};
+    for (size_t k = 0; k < 2; ++k) {
+        const MerkleUpdateWrite &w = v.writes[k];
+        const MerkleTransferSide &s = *sides[k];
+        if (s.siblings.size() != w.siblings.size() || s.bits.size() != w.bits.size()) throw ZkError(ZK_ERR_INVALID, "poseidon_merkle_transfer_inputs: the path does not have the circuit's depth");
+        values.push_back({w.old_leaf, s.old_leaf});
+        for (size_t i = 0; i < s.siblings.size(); ++i) values.push_back({w.siblings[i], s.siblings[i]});
+        for (size_t i = 0; i < s.bits.size(); ++i) values.push_back({w.bits[i], Fr::from_u64(s.bits[i])});
+    }
+    return layout.free(values);
+}
 inline FrVec poseidon_merkle_witness_inputs(const CircuitLayout &layout, const MerkleCircuitVars &v, const Fr &leaf, const FrVec &siblings, const std::vector<uint64_t> &bits) {
     if (siblings.size() != v.siblings.size() || bits.size() != v.bits.size()) throw ZkError(ZK_ERR_INVALID, "poseidon_merkle_witness_inputs: the path does not have the circuit's depth");
     std::vector<std::pair<Var, Fr>> values{{v.leaf, leaf}};

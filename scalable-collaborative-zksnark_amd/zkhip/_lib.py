@@ -59,6 +59,7 @@ SYMBOLS = [
     ("zk_plonk_witness", _i, [_vp, _vp, _i, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
     ("zk_plonk_witness_check", _i, [_vp, _vp, _i, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
     ("zk_witness_plan_create_lookup", _i, [_vp, _vp, _vp, _vp, _vp, _sz, _pp]),
+    ("zk_witness_plan_create_advice", _i, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _pp]),
     ("zk_plonk_witness_lookup", _i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
     ("zk_plonk_witness_check_lookup", _i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
     ("zk_lookup3_terms", _i, [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),

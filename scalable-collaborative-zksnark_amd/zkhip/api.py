@@ -193,7 +193,7 @@ class WitnessPlan:
     """zk_witness_plan: the witness plan of one Plonk circuit (sources, levels, launch schedule and, built with qk and ts, the key table
     of its lookup), held by the library"""
 
-    def __init__(self, ctx: "Ctx", sigma, N: int, out_sel=None, qk=None, ts=None):
+    def __init__(self, ctx: "Ctx", sigma, N: int, out_sel=None, qk=None, ts=None, advice=None):
         self.ctx, self.h, self.N = ctx, 0, int(N)
         sg = np.ascontiguousarray(sigma, dtype=np.uint64).reshape(-1)
         if len(sg) != 3 * self.N:
@@ -201,7 +201,12 @@ class WitnessPlan:
         if (qk is None) != (ts is None) or (ts is not None and len(ts) != 3):
             raise ValueError("a lookup plan needs qk and the three table columns")
         h = ctypes.c_void_p()
-        if qk is None:
+        if advice is not None:
+            adv = np.ascontiguousarray(advice, dtype=np.uint32).reshape(-1)
+            if len(adv) != self.N:
+                raise ValueError(f"advice must hold {self.N} codes")
+            rc = ctx.lib.zk_witness_plan_create_advice(ctx.h, _h(sg), _ptr(out_sel), _ptr(qk), ctx._ptr_array(ts) if ts is not None else None, _h(adv), self.N, ctypes.byref(h))
+        elif qk is None:
             rc = ctx.lib.zk_witness_plan_create(ctx.h, _h(sg), _ptr(out_sel), self.N, ctypes.byref(h))
         else:
             rc = ctx.lib.zk_witness_plan_create_lookup(ctx.h, _h(sg), _ptr(out_sel), _ptr(qk), ctx._ptr_array(ts), self.N, ctypes.byref(h))
@@ -642,6 +647,13 @@ class Ctx:
         the device): qk and ts = (t0, t1, t2) device buffers of N Fr.  Beyond witness_plan's refusals: a qk entry that is neither 0 nor 1,
         a table that is no function of (t0, t1) -- ValueError with the library's message."""
         return WitnessPlan(self, sigma, N, out_sel, qk, ts)
+
+    def witness_plan_advice(self, sigma, N: int, out_sel, advice, qk=None, ts=None) -> WitnessPlan:
+        """the witness plan of a circuit with its advice codes (zk_witness_plan_create_advice): advice N u32 on the host (0: none,
+        plonk.ADV_INV0, plonk.adv_bits(shift, width)); qk and ts as witness_plan_lookup takes them, or both None.  Beyond the refusals of
+        those two: unknown codes, advice rows that also compute by the gate or the table -- ValueError with the library's message.
+        plonk_witness / plonk_witness_check take the plan as they take the others (with qk and ts when it has a lookup)."""
+        return WitnessPlan(self, sigma, N, out_sel, qk, ts, advice)
 
     def plonk_witness(self, plan: WitnessPlan, sels, public_inputs: np.ndarray, free=None, out=None, qk=None, ts=None):
         """a, b, c generated on the device (zk_plonk_witness; blocking): sels the gate's selectors (2: basic, 6: wide) as device buffers,

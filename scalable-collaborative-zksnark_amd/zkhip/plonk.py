@@ -89,6 +89,21 @@ and nothing else):
     of N rows with qk = 1 hold a triple that is no table entry" and the smallest such row);
   * on generated wires the index zk_lookup3_find gives for a lookup-computing row is the y the generator used, so
     prove(..., idx=FIND) on them needs nothing from the generator.
+A circuit may carry ADVICE, "advice": N u32 codes, one per row, 0 meaning none (zk_witness_plan_create_advice; additive -- a circuit
+without it follows the rules above and nothing else).  Advice is prover-side only: not preprocessed, not committed, in no vk, proof or
+existing digest.
+  * ADV_INV0 = 1: c = 1 / a mod r, and c = 0 when a = 0; b is gathered and stored as usual, not used.  adv_bits(shift, width) =
+    2 | shift << 8 | width << 16: c = (A >> shift) mod 2^width for the canonical integer A in [0, r) of a; 0 <= shift,
+    1 <= width <= 64, shift + width <= 255.  Bits 24 .. 31 are 0; anything else is an unknown code and the plan is refused ("K of N
+    advice codes are unknown" and the smallest such row);
+  * a row with a code is ADVICE-COMPUTING: a computing row like the other two kinds for sources, levels and the refusal of rows that depend
+    on their own output.  It must not also compute by the gate (wide gate: qO(x) = 0; the basic gate computes on every row, so every
+    non-zero code is refused) or by the table (qk(x) = 0): "K of N advice rows also compute by the gate or the table";
+  * it constrains nothing by itself -- soundness comes from ordinary gate rows next to it (circuit.Builder's gadgets) -- and the check
+    does not test advice values: it keeps its four (lookup plans: six) numbers, and a witness may hold other advice where the
+    constraints allow it (any c for ADV_INV0 of 0);
+  * the outputs are fully reduced Montgomery forms like every generated wire; a free value or public input at or above r is reduced
+    before the advice acts on it.
 
 Record: {"mu", "l", "commitments": [3, 18] (a, b, c), "v_commitment": [18], "p_rounds": [mu, 6, 4], "g_rounds": [mu, 5, 4],
          "g_values": [5, 4], "p_values": [6, 4], "v_values": [5, 4], "batch": {"rounds": [mu, 3, 4], "opening": [mu, 18]},
@@ -355,21 +370,37 @@ def prove(be, pk: dict, a, b, c, public_inputs, idx=None, timing: dict | None = 
 
 
 # ---- witness ----
-def witness_plan(be, circuit: dict, lookup: bool = False):
+ADV_INV0 = 1
+
+
+def adv_bits(shift: int, width: int) -> int:
+    """the advice code "bits shift .. shift + width - 1 of a's canonical integer" (module text, WITNESS)"""
+    if not (0 <= shift and 1 <= width <= 64 and shift + width <= 255):
+        raise ValueError(f"no advice code for shift {shift}, width {width}: 0 <= shift, 1 <= width <= 64 and shift + width <= 255 are needed")
+    return 2 | shift << 8 | width << 16
+
+
+def witness_plan(be, circuit: dict, lookup: bool = False, advice: bool | None = None):
     """the witness plan of a circuit {"mu", "sigma", and with "gate": "wide" the output selector "qO"} (module text, WITNESS): built once per
     circuit on the host inside the library (Ctx.witness_plan).  A sigma that is not a permutation, or rows that depend on their own
     output: ValueError.  lookup=True: the plan of the circuit WITH its "lookup" (required then; Ctx.witness_plan_lookup builds the key
     table of (t0, t1) on the device) -- a qk that is not 0 / 1 or a table that is no function of (t0, t1): ValueError.  The default
-    ignores a lookup the circuit may carry."""
+    ignores a lookup the circuit may carry.  advice: None uses the circuit's "advice" codes when it has them (Ctx.witness_plan_advice;
+    unknown codes, or advice rows that also compute by the gate or the table: ValueError), False ignores them, True requires them."""
     gate = gate_of(circuit)
     N = 1 << int(circuit["mu"])
+    if advice and "advice" not in circuit:
+        raise ValueError("advice=True needs a circuit with advice codes")
+    adv = circuit["advice"] if advice is not False and "advice" in circuit else None
     qo = be.to_device(_u64(circuit["qO"], N, 4)) if gate.kind == "wide" else None
     sigma = np.ascontiguousarray(circuit["sigma"], dtype=np.uint64).reshape(-1)
     if not lookup:
-        return be.witness_plan(sigma, N, qo)
+        return be.witness_plan(sigma, N, qo) if adv is None else be.witness_plan_advice(sigma, N, qo, adv)
     if not has_lookup(circuit):
         raise ValueError("lookup=True needs a circuit with a lookup")
     lk = {k: be.to_device(_u64(circuit["lookup"][k], N, 4)) for k in LOOKUP_VK_TABLES}
+    if adv is not None:
+        return be.witness_plan_advice(sigma, N, qo, adv, lk["qk"], [lk[k] for k in LOOKUP_VK_TABLES[1:]])
     return be.witness_plan_lookup(sigma, N, qo, lk["qk"], [lk[k] for k in LOOKUP_VK_TABLES[1:]])
 
 

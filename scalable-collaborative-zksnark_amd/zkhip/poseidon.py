@@ -348,6 +348,63 @@ def merkle_update_inputs(layout, vars: dict, steps) -> np.ndarray:
     return layout.free(values)
 
 
+def merkle_transfer_circuit(depth: int, bits: int = 64, p: dict | None = None):
+    """-> (circuit, layout, vars) of "the tree with public root R became the tree with public root R' by moving a private non-zero amount
+    from one leaf to another; the amount and both new balances lie below 2^bits".  merkle_update_circuit with count = 2, except that the
+    new leaves are COMPUTED: after the private variables come the rows
+        amt = amount (a lin copy: to_bits wants a computed value), new_from = old_from - amt, new_to = old_to + amt,
+        assert_nonzero(amt), assert_range(amt, bits), assert_range(new_from, bits), assert_range(new_to, bits)
+    -- 3 + 2 + 3 (3 bits - 1) rows -- and then the two writes' levels.  An amount above the sender's balance wraps new_from round r, far
+    above 2^bits.  Every inverse and every bit is advice (circuit.Builder), generated on the device: the caller gives balances, amount
+    and paths only.  The old balances are not range-checked: that they lie below 2^bits is the invariant the statement keeps.
+    vars = {"old_root", "new_root", "amount", "writes": [2 x {"old_leaf", "new_leaf", "siblings", "bits", "old_out", "new_out"}]} (write
+    0: the sender, write 1: the receiver, whose path is one of the tree AFTER write 0)"""
+    from .circuit import Builder
+
+    if depth < 1 or not 1 <= bits <= 253:
+        raise ValueError("depth >= 1 and 1 <= bits <= 253 are needed")
+    b = Builder()
+    old_root, new_root = b.public(), b.public()
+    writes = []
+    for _ in range(2):
+        w = {"old_leaf": b.private()}
+        w["siblings"], w["bits"] = [b.private() for _ in range(depth)], [b.private() for _ in range(depth)]
+        writes.append(w)
+    amount = b.private()
+    amt = b.lin(1, amount, 0, None, 0)
+    writes[0]["new_leaf"] = b.lin(1, writes[0]["old_leaf"], -1, amt, 0)
+    writes[1]["new_leaf"] = b.lin(1, writes[1]["old_leaf"], 1, amt, 0)
+    b.assert_nonzero(amt)
+    for v in (amt, writes[0]["new_leaf"], writes[1]["new_leaf"]):
+        b.assert_range(v, bits)
+    prev = None
+    for i, w in enumerate(writes):
+        old, new = w["old_leaf"], w["new_leaf"]
+        for sib, bit in zip(w["siblings"], w["bits"]):
+            b.assert_bool(bit)
+            old = _merkle_level(b, old, sib, bit, p)
+            new = _merkle_level(b, new, sib, bit, p)
+        b.assert_equal(old, old_root if i == 0 else prev)
+        w["old_out"], w["new_out"] = old, new
+        prev = new
+    b.assert_equal(prev, new_root)
+    circuit, layout = b.build()
+    return circuit, layout, {"old_root": old_root, "new_root": new_root, "amount": amount, "writes": writes}
+
+
+def merkle_transfer_inputs(layout, vars: dict, amount: int, sender, receiver) -> np.ndarray:
+    """the `free` array of plonk.witness for one transfer: the amount, and sender / receiver = (old balance, siblings, bits), integers; the
+    receiver's siblings are those of the tree after the sender's leaf was written"""
+    values = {vars["amount"]: amount}
+    for w, (old_leaf, siblings, bits) in zip(vars["writes"], (sender, receiver)):
+        if len(siblings) != len(w["siblings"]) or len(bits) != len(w["bits"]):
+            raise ValueError("the path does not have the circuit's depth")
+        values[w["old_leaf"]] = old_leaf
+        values.update(zip(w["siblings"], siblings))
+        values.update(zip(w["bits"], bits))
+    return layout.free(values)
+
+
 def merkle_witness_inputs(layout, vars: dict, leaf: int, siblings, bits) -> np.ndarray:
     """the `free` array ([3N, 4] Montgomery Fr) of plonk.witness for one path: integers, bits as 0 / 1 (any integer is stored as given)"""
     if len(siblings) != len(vars["siblings"]) or len(bits) != len(vars["bits"]):

@@ -19,6 +19,14 @@ host/bin/poseidon_check takes the same flags and prints the same lines.  The SRS
                         circuit sha256 .. / old root .. / new root .. / proof sha256 .. / verdict ..
                     --break leaf | bit | sibling | root alters the first write's old leaf, leaf-level bit or sibling, or the public new
                     root; --sample-only prints the first three lines by the host rules (merkle_host, update_host)
+
+  --transfer [--bits B --amount A]
+                    a proved transfer instead: the leaves are BALANCES, leaf k holds 2^(B-2) + (13 S + 41 k) mod 2^(B-2) (4 <= B <= 64); leaf
+                    S mod 2^D pays A (default 5) to leaf (S + 1) mod 2^D -- two writes one after another with Poseidon.update, each path
+                    from the tree before its write -- then poseidon.merkle_transfer_circuit(D, B), whose inverses and bits the witness
+                    generator makes on the device.  Prints
+                        circuit sha256 .. / roots <old> <new> / proof sha256 .. / verdict ..
+                    --break sibling alters the sender's leaf-level sibling; --sample-only prints the first two lines by the host rules
 """
 import argparse
 import os
@@ -94,6 +102,66 @@ def update(args) -> int:
     return 0 if ok else 1
 
 
+def transfer(args) -> int:
+    """--transfer: the proved transfer (module text)"""
+    from zkhip import poseidon as ps
+    from zkhip.circuit import circuit_digest
+    from zkhip.field import R_MOD, fr_from_mont, fr_mont, splitmix_fr
+
+    ints = lambda a: [fr_from_mont(x) for x in np.asarray(a).reshape(-1, 4)]
+    depth, n, quarter = args.depth, 1 << args.depth, 1 << (args.bits - 2)
+    circuit, layout, v = ps.merkle_transfer_circuit(depth, args.bits)
+    balances = [quarter + (13 * args.seed + 41 * k) % quarter for k in range(n)]
+    i, j = args.seed % n, (args.seed + 1) % n
+    writes = [(i, (balances[i] - args.amount) % R_MOD), (j, (balances[j] + args.amount) % R_MOD)]
+    print("circuit sha256", circuit_digest(circuit))
+    if args.sample_only:
+        tree = ps.merkle_host(balances)
+        old_root = tree[-1]
+        for w in writes:
+            tree = ps.update_host(tree, n, [w])
+        print("roots %064x %064x" % (old_root, tree[-1]))
+        return 0
+
+    import zkhip
+    from zkhip import dist_primitive as dp
+    from zkhip import pairing as pr
+    from zkhip import plonk
+
+    be = zkhip.Ctx(0)
+    pos = ps.Poseidon(be)
+    d_tree = pos.merkle(be.to_device(np.stack([fr_mont(x) for x in balances])), n)
+    root_of = lambda: ints(d_tree.download((1, 4), offset=32 * (2 * n - 2)))[0]
+    old_root = root_of()
+    sides = []
+    for k, x in writes:  # one after another: the old leaf and the path are those of the tree before the write
+        old_leaf = ints(d_tree.download((1, 4), offset=32 * k))[0]
+        sibs = ints(pos.paths(d_tree, n, [k]).download((depth, 4)))
+        sides.append((old_leaf, sibs, [(k >> t) & 1 for t in range(depth)]))
+        pos.update(d_tree, n, [k], fr_mont(x).reshape(1, 4))
+    new_root = root_of()
+    pos.free()
+    print("roots %064x %064x" % (old_root, new_root))
+    if args.brk == "sibling":
+        sides[0][1][0] = (sides[0][1][0] + 1) % R_MOD
+    pi = np.stack([fr_mont(old_root), fr_mont(new_root)])
+    s = splitmix_fr(circuit["mu"] + 1, args.seed + 1)
+    pcs = dp.PolynomialCommitmentCub.new(be, s).mature()
+    pk, vk = plonk.preprocess(be, pcs, circuit, pr.powers_of_g2(ints(s)))
+    plan = plonk.witness_plan(be, circuit)
+    try:
+        a, b, c = plonk.witness(be, pk, plan, pi, ps.merkle_transfer_inputs(layout, v, args.amount, *sides))
+    except ValueError as e:
+        print("refused:", e)
+        return 1
+    proof = plonk.prove(be, pk, a, b, c, pi)
+    print("proof sha256", plonk.proof_digest(proof))
+    ok = plonk.verify_bytes(be, vk, pi, plonk.proof_to_bytes(proof))
+    print("verdict", "accept" if ok else "reject")
+    be.close()
+    return 0 if ok else 1
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--depth", type=int, default=1)
@@ -101,7 +169,14 @@ def main() -> int:
     ap.add_argument("--break", dest="brk", choices=("bit", "root", "sibling", "leaf"))
     ap.add_argument("--sample-only", action="store_true")
     ap.add_argument("--update", type=int, default=0, metavar="COUNT")
+    ap.add_argument("--transfer", action="store_true")
+    ap.add_argument("--bits", type=int, default=64)
+    ap.add_argument("--amount", type=int, default=5)
     args = ap.parse_args()
+    if args.transfer:
+        if args.update or args.brk not in (None, "sibling") or not 4 <= args.bits <= 64 or not 0 <= args.amount < 1 << 63:
+            ap.error("--transfer goes without --update, with --break sibling only, 4 <= --bits <= 64 and 0 <= --amount < 2^63")
+        return transfer(args)
     if args.update < 0 or (args.brk == "leaf" and not args.update):
         ap.error("--update takes a COUNT >= 1, and --break leaf goes with --update")
     if args.update:
