@@ -856,6 +856,39 @@ int zk_poseidon_merkle_roots(zk_ctx *ctx, const zk_poseidon_params *params, cons
 int zk_poseidon_merkle_update(zk_ctx *ctx, const zk_poseidon_params *params, void *d_tree, size_t n, const uint64_t *h_index, const void *d_values,
                               size_t count);
 
+/* ---- Jubjub over BLS12-381 Fr and the Schnorr signature "zkhip-schnorr-v1" (csrc/zk_jubjub.hip, K37-K40) ---------------------------
+ * The twisted Edwards curve -x^2 + y^2 = 1 + d x^2 y^2 over Fr with d = -10240 / 10241 (a non-square: the addition law
+ *     (x1, y1) + (x2, y2) = ((x1 y2 + y1 x2) / (1 + d x1 x2 y1 y2), (y1 y2 + x1 x2) / (1 - d x1 x2 y1 y2))
+ * is complete), identity (0, 1), -(x, y) = (-x, y), cofactor 8, prime subgroup order
+ *     l = 0x0e7db4ea6533afa906673b0101343b00a6682093ccc81082d0970e5ed6f72cb7.
+ * The generator G is derived by rule: the smallest integer y >= 2 for which x^2 = (y^2 - 1) / (1 + d y^2) is a square (y = 3), the
+ * smaller root x, the point times 8.  A point is [2] Fr (x, y), affine, Montgomery, fully reduced, 64 bytes, 16-byte aligned; a
+ * coordinate that is not below r makes the point "not on the curve".  A scalar is 4 little-endian uint64_t, a PLAIN integer; every
+ * 256-bit value is allowed.  One lane per item, 256-lane workgroups, a grid-stride loop; every loop length is fixed by the call, table
+ * entries are selected without branches.  All launches go on the ctx stream; no workgroup waits on another; no atomics but the count
+ * and minimum of the refusal below. */
+/* d_out[i] = [d_scalars[i]] d_points[i], i < n; d_points = NULL: the fixed base G.  256 double-and-add steps in extended
+ * coordinates, one inversion at the end.  Every input point is checked first: if any is not on the curve nothing is written and the
+ * call fails with ZK_ERR_INVALID, zk_last_error gives "K of N points are not on the curve; the first is I" (I: the smallest such
+ * index, an atomic minimum).  With points the call waits for that check (one synchronisation of the ctx stream) and then enqueues the
+ * multiplication; with NULL it is ASYNCHRONOUS.  d_out may be d_points. */
+int zk_jubjub_mul(zk_ctx *ctx, const void *d_points, const void *d_scalars, void *d_out, size_t n);
+/* d_status[i] (uint32_t), i < n: 0 the point is in the prime-order subgroup (the identity is), 2 it is not on the curve, 3 it is on
+ * the curve but [l] P is not the identity -- the numbers of zk_g1_check.  ASYNCHRONOUS on the ctx stream. */
+int zk_jubjub_check(zk_ctx *ctx, const void *d_points, uint32_t *d_status, size_t n);
+/* Signatures.  Secret key sk in [1, l), public key PK = [sk] G; a signature on a message m (one Fr) is (R, s) with
+ *     e = hash2(hash2(hash2(R.x, R.y), hash2(PK.x, PK.y)), m)    (hash2 of `params`; the scalar is e's canonical integer below r,
+ *                                                                  not reduced by hand: the group reduces it)
+ *     [s] G = R + [e] PK.
+ * d_pk: [n][2] Fr, d_msg: [n] Fr, d_sig: [n][3] 32-byte words -- R.x, R.y (Montgomery) and s (a plain 256-bit integer).  d_status[i]
+ * (uint32_t) is the FIRST of these that applies: 1 s >= l; 2 PK or R not on the curve; 3 PK outside the subgroup, or PK the identity;
+ * 4 the equation fails (a message that is not below r also gives 4); 0 valid.  There is no cofactor multiplication: an R with a
+ * torsion part fails the equality.  One lane per signature: four permutations, the subgroup test [l] PK and ONE joint double-and-add
+ * of 255 steps over the bits of s and e with the table {O, G, -PK, G - PK}, compared with R projectively (no inversion).  Signing is
+ * host code (zkhip/jubjub.py).  ASYNCHRONOUS on the ctx stream. */
+int zk_schnorr_verify(zk_ctx *ctx, const zk_poseidon_params *params, const void *d_pk, const void *d_msg, const void *d_sig, uint32_t *d_status,
+                      size_t n);
+
 /* (the zk_dbg_* test hooks of the library are declared in include/zkhip_test.h: they are not part of this surface) */
 
 #ifdef __cplusplus

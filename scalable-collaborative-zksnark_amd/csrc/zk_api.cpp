@@ -823,6 +823,18 @@ int zk_poseidon_merkle_update(zk_ctx* ctx, const zk_poseidon_params* params, voi
     NEED(ctx, params && (count == 0 || (d_tree && h_index && d_values)));
     return poseidon_merkle_update(ctx, params, d_tree, n, h_index, d_values, count);
 }
+int zk_jubjub_mul(zk_ctx* ctx, const void* d_points, const void* d_scalars, void* d_out, size_t n) {
+    NEED(ctx, n == 0 || (d_scalars && d_out));
+    return jubjub_mul(ctx, d_points, d_scalars, d_out, n);
+}
+int zk_jubjub_check(zk_ctx* ctx, const void* d_points, uint32_t* d_status, size_t n) {
+    NEED(ctx, n == 0 || (d_points && d_status));
+    return jubjub_check(ctx, d_points, d_status, n);
+}
+int zk_schnorr_verify(zk_ctx* ctx, const zk_poseidon_params* params, const void* d_pk, const void* d_msg, const void* d_sig, uint32_t* d_status, size_t n) {
+    NEED(ctx, params && (n == 0 || (d_pk && d_msg && d_sig && d_status)));
+    return schnorr_verify(ctx, params, d_pk, d_msg, d_sig, d_status, n);
+}
 int zk_g1_lincomb_seg(zk_ctx* ctx, size_t segments, const size_t* h_start, const uint64_t* h_points18, const uint64_t* h_scalars, uint64_t* h_out18) {
     NEED(ctx, segments == 0 || (h_start && h_out18));
     return g1_lincomb_seg(ctx, segments, h_start, h_points18, h_scalars, h_out18);

@@ -394,6 +394,10 @@ int poseidon_merkle(zk_ctx* ctx, const zk_poseidon_params* p, const void* d_leav
 int poseidon_merkle_paths(zk_ctx* ctx, const void* d_tree, size_t n, const uint64_t* h_index, size_t count, void* d_siblings);
 int poseidon_merkle_roots(zk_ctx* ctx, const zk_poseidon_params* p, const void* d_leaves, const uint64_t* h_index, const void* d_siblings, size_t depth, size_t count, void* d_roots);
 int poseidon_merkle_update(zk_ctx* ctx, const zk_poseidon_params* p, void* d_tree, size_t n, const uint64_t* h_index, const void* d_values, size_t count);
+// ---- zk_jubjub.hip ----
+int jubjub_mul(zk_ctx* ctx, const void* d_points, const void* d_scalars, void* d_out, size_t n);
+int jubjub_check(zk_ctx* ctx, const void* d_points, uint32_t* d_status, size_t n);
+int schnorr_verify(zk_ctx* ctx, const zk_poseidon_params* p, const void* d_pk, const void* d_msg, const void* d_sig, uint32_t* d_status, size_t n);
 // ---- zk_pairing.hip: test hooks ----
 int dbg_fq30_op(zk_ctx* ctx, int mode, const void* d_x, const void* d_kx, const void* d_y, const void* d_ky, void* d_out, void* d_flags,
                 size_t n);

@@ -17,6 +17,13 @@
 // leaf S mod 2^D pays A (default 5) to leaf (S + 1) mod 2^D: two writes one after another on the device tree, each path taken from the tree before its
 // write, then poseidon_merkle_transfer_circuit(D, B), whose inverses and bits the witness generator makes on the device.  Prints circuit sha256 /
 // roots <old> <new> / proof sha256 / verdict; --break sibling alters the sender's leaf-level sibling; --sample-only: the first two lines by the host rules.
+// --schnorr: "I know a signature under this public key on this public message" -- sk = S + 1, m = S + 1000, jubjub_sign_host, the native check on the
+// device (Ctx::schnorr_verify must say 0), then jubjub_schnorr_circuit through the pipeline.  Prints circuit sha256 / signature sha256 (of
+// R.x || R.y || s) / proof sha256 / verdict; --sample-only: the first two lines, without a device.
+// --signed-transfer [--bits B --amount A --forge]: the transfer on leaves hash2(hash2(PK.x, PK.y), balance) -- leaf k belongs to the secret key
+// S + 1 + k, balances as for --transfer; the sender signs m = hash2(hash2(receiver key hash, A), old root); --forge signs with the RECEIVER's key.
+// Prints circuit sha256 / signature sha256 / roots <old> <new> / proof sha256 / verdict; --sample-only: the first three lines by the host rules.
+// --time-schnorr K: jubjub_verify_host on K signatures, serial, milliseconds (the CPU column of tools/jubjub_time.py).
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -24,6 +31,7 @@
 #include <string>
 
 #include "zkhost/hyperplonk.hpp"
+#include "zkhost/jubjub.hpp"
 #include "zkhost/pcs_vk.hpp"
 #include "zkhost/poseidon.hpp"
 #include "zkhost/proof_io.hpp"
@@ -186,10 +194,126 @@ static int transfer_check(size_t depth, uint64_t seed, size_t bits, uint64_t amo
     return ok ? 0 : 1;
 }
 
+// witness_plan -> plonk_witness -> preprocess -> plonk_prove -> proof bytes -> verify_bytes, with the two lines (or the refusal) they print
+static int prove_and_verify(Ctx &be, const PlonkCircuit &circuit, const FrVec &pi, const FrVec &free, uint64_t seed) {
+    const FrVec s = SplitMix64(seed + 1).fr_vec(circuit.mu + 1);
+    const PolynomialCommitmentCub cub = PolynomialCommitmentCub::make(be, s);
+    const std::vector<uint64_t> pg2 = powers_of_g2(be, s);
+    std::vector<G2Rec> keys(pg2.size() / 24);
+    std::memcpy(keys.data(), pg2.data(), 8 * pg2.size());
+    std::vector<G2Rec> keys_mu{keys[0]};
+    keys_mu.insert(keys_mu.end(), keys.begin() + 2, keys.end());
+    std::shared_ptr<PcsVk> vk_mu1 = be.pcs_vk(nullptr, keys[0].data(), 192, keys.size()), vk_mu = be.pcs_vk(nullptr, keys_mu[0].data(), 192, keys_mu.size());
+    PlonkVk vk;
+    const PlonkPk pk = preprocess(be, cub.mature(), circuit, vk);
+    const std::shared_ptr<WitnessPlan> plan = witness_plan(be, circuit);
+    std::array<DevPtr, 3> w;
+    try {
+        w = plonk_witness(be, pk, *plan, pi, &free);
+    } catch (const ZkError &e) {
+        if (e.status != ZK_ERR_INVALID) throw;
+        const char *msg = std::strstr(e.what(), ": ");  // past ZkError's "zkhip error -1: "
+        std::printf("refused: %s\n", msg ? msg + 2 : e.what());
+        return 1;
+    }
+    const PlonkProof proof = plonk_prove(be, cub.mature(), pk, w[0], w[1], w[2], pi, DevPtr());
+    std::printf("proof sha256 %s\n", proof_digest(proof).c_str());
+    const bool ok = verify_bytes(be, *vk_mu, *vk_mu1, vk, pi, proof_to_bytes(proof));
+    std::printf("verdict %s\n", ok ? "accept" : "reject");
+    return ok ? 0 : 1;
+}
+
+static int time_schnorr(size_t k) {
+    std::vector<JjPoint> pks;
+    std::vector<JjSignature> sigs;
+    for (size_t i = 0; i < 4; ++i) {
+        pks.push_back(jubjub_keygen_host({3 + i, 0, 0, 0}));
+        sigs.push_back(jubjub_sign_host({3 + i, 0, 0, 0}, Fr::from_u64(1000 + i)));
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    int bad = 0;
+    for (size_t i = 0; i < k; ++i) bad += jubjub_verify_host(pks[i % 4], Fr::from_u64(1000 + i % 4), sigs[i % 4]);
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    std::printf("host schnorr verify n=%zu ms %.3f (%.4f ms per signature, %d refused)\n", k, ms, ms / (double)k, bad);
+    return bad ? 1 : 0;
+}
+
+// --schnorr: tools/poseidon_merkle.py `schnorr`, line for line
+static int schnorr_check(uint64_t seed, bool sample_only) {
+    CircuitLayout layout;
+    SchnorrVars v;
+    const PlonkCircuit circuit = jubjub_schnorr_circuit(layout, v);
+    const JjScalar sk = {seed + 1, 0, 0, 0};
+    const Fr m = Fr::from_u64(seed + 1000);
+    const JjPoint pk = jubjub_keygen_host(sk);
+    const JjSignature sig = jubjub_sign_host(sk, m);
+    std::printf("circuit sha256 %s\n", built_circuit_digest(circuit).c_str());
+    std::printf("signature sha256 %s\n", jubjub_signature_digest(sig).c_str());
+    if (sample_only) return jubjub_verify_host(pk, m, sig) == 0 ? 0 : 1;
+    Ctx be(0);
+    const std::shared_ptr<PoseidonParams> pp = poseidon_params(be);
+    Fr s_raw;
+    for (size_t i = 0; i < 4; ++i) s_raw.v[i] = sig.s[i];
+    const std::vector<uint32_t> st = be.schnorr_verify(*pp, be.to_device(FrVec{pk.x, pk.y}), be.to_device(FrVec{m}), be.to_device(FrVec{sig.R.x, sig.R.y, s_raw}), 1);
+    if (st[0] != 0) {
+        std::printf("refused: zk_schnorr_verify: status %u\n", st[0]);
+        return 1;
+    }
+    return prove_and_verify(be, circuit, FrVec{pk.x, pk.y, m, Fr::zero()}, jubjub_schnorr_inputs(layout, v, sig), seed);
+}
+
+// --signed-transfer: tools/poseidon_merkle.py `signed_transfer`, line for line
+static int signed_transfer_check(size_t depth, uint64_t seed, size_t bits, uint64_t amount, bool forge, bool sample_only) {
+    const size_t n = size_t(1) << depth;
+    CircuitLayout layout;
+    SignedTransferVars v;
+    const PlonkCircuit circuit = jubjub_merkle_signed_transfer_circuit(depth, bits, layout, v);
+    const uint64_t quarter = uint64_t(1) << (bits - 2);
+    std::vector<uint64_t> balances;
+    std::vector<JjPoint> pks;
+    FrVec keys, leaves;
+    for (size_t k = 0; k < n; ++k) {
+        balances.push_back(quarter + (13 * seed + 41 * k) % quarter);
+        pks.push_back(jubjub_keygen_host({seed + 1 + k, 0, 0, 0}));
+        keys.push_back(poseidon_hash2_host(pks[k].x, pks[k].y));
+        leaves.push_back(poseidon_hash2_host(keys[k], Fr::from_u64(balances[k])));
+    }
+    const uint64_t from = seed % n, to = (seed + 1) % n;
+    const Fr amt = Fr::from_u64(amount);
+    const std::pair<uint64_t, Fr> writes[2] = {{from, poseidon_hash2_host(keys[from], Fr::from_u64(balances[from]) - amt)},
+                                               {to, poseidon_hash2_host(keys[to], Fr::from_u64(balances[to]) + amt)}};
+    std::printf("circuit sha256 %s\n", built_circuit_digest(circuit).c_str());
+    auto sign = [&](const Fr &old_root) { return jubjub_sign_host({seed + 1 + (forge ? to : from), 0, 0, 0}, jubjub_signed_transfer_message(keys[to], amt, old_root)); };
+    if (sample_only) {
+        FrVec tree = poseidon_merkle_host(leaves);
+        const Fr old_root = tree.back();
+        std::printf("signature sha256 %s\n", jubjub_signature_digest(sign(old_root)).c_str());
+        for (const auto &w : writes) tree = poseidon_update_host(tree, n, {w});
+        std::printf("roots %s %s\n", hex_of(old_root).c_str(), hex_of(tree.back()).c_str());
+        return 0;
+    }
+    Ctx be(0);
+    const std::shared_ptr<PoseidonParams> pp = poseidon_params(be);
+    const DevPtr tree = be.poseidon_merkle(*pp, be.to_device(leaves), n);
+    const Fr old_root = be.to_host(tree.fr(2 * n - 2), 1)[0];
+    const JjSignature sig = sign(old_root);
+    std::printf("signature sha256 %s\n", jubjub_signature_digest(sig).c_str());
+    SignedTransferSide side[2];
+    for (size_t k = 0; k < 2; ++k) {
+        side[k].balance = Fr::from_u64(balances[writes[k].first]);
+        side[k].siblings = be.to_host(be.poseidon_merkle_paths(tree, n, {writes[k].first}), depth);
+        for (size_t j = 0; j < depth; ++j) side[k].bits.push_back((writes[k].first >> j) & 1);
+        poseidon_update(be, *pp, tree, n, {writes[k]});
+    }
+    const Fr new_root = be.to_host(tree.fr(2 * n - 2), 1)[0];
+    std::printf("roots %s %s\n", hex_of(old_root).c_str(), hex_of(new_root).c_str());
+    return prove_and_verify(be, circuit, FrVec{old_root, new_root}, jubjub_merkle_signed_transfer_inputs(layout, v, amt, pks[from], keys[to], sig, side[0], side[1]), seed);
+}
+
 int main(int argc, char **argv) {
-    long long depth = -1, seed = 7, time_k = 0, update = 0, bits = 64, amount = 5;
+    long long depth = -1, seed = 7, time_k = 0, time_s = 0, update = 0, bits = 64, amount = 5;
     std::string brk;
-    bool sample_only = false, transfer = false, usage = argc < 2;
+    bool sample_only = false, transfer = false, schnorr = false, signed_transfer = false, forge = false, usage = argc < 2;
     auto number = [](const char *s, long long &out) {
         char *end = nullptr;
         out = std::strtoll(s, &end, 10);
@@ -199,6 +323,10 @@ int main(int argc, char **argv) {
         const std::string k = argv[i];
         if (k == "--sample-only") sample_only = true;
         else if (k == "--transfer") transfer = true;
+        else if (k == "--schnorr") schnorr = true;
+        else if (k == "--signed-transfer") signed_transfer = true;
+        else if (k == "--forge") forge = true;
+        else if (i + 1 < argc && k == "--time-schnorr") usage = !number(argv[++i], time_s) || time_s < 1;
         else if (i + 1 < argc && k == "--bits") usage = !number(argv[++i], bits) || bits < 4 || bits > 64;
         else if (i + 1 < argc && k == "--amount") usage = !number(argv[++i], amount);
         else if (i + 1 < argc && k == "--depth") usage = !number(argv[++i], depth) || depth < 1 || depth > 40;
@@ -210,10 +338,20 @@ int main(int argc, char **argv) {
     }
     if (brk == "leaf" && update == 0) usage = true;
     if (transfer && (update > 0 || (!brk.empty() && brk != "sibling"))) usage = true;
+    if ((schnorr || signed_transfer) && (transfer || update > 0 || !brk.empty() || (schnorr && signed_transfer))) usage = true;
+    if (forge && !signed_transfer) usage = true;
     if (!usage && time_k > 0 && depth < 0) return time_host((size_t)time_k);
-    if (usage || depth < 0 || time_k > 0) {
+    try {
+        if (!usage && time_s > 0 && depth < 0) return time_schnorr((size_t)time_s);
+        if (!usage && schnorr && time_k == 0 && time_s == 0) return schnorr_check((uint64_t)seed, sample_only);
+        if (!usage && signed_transfer && depth >= 1 && time_k == 0 && time_s == 0) return signed_transfer_check((size_t)depth, (uint64_t)seed, (size_t)bits, (uint64_t)amount, forge, sample_only);
+    } catch (const std::exception &e) {
+        std::fprintf(stderr, "poseidon_check: %s\n", e.what());
+        return 4;
+    }
+    if (usage || depth < 0 || time_k > 0 || time_s > 0) {
         std::fprintf(stderr, "usage: poseidon_check --depth D [--seed S] [--update COUNT | --transfer [--bits B] [--amount A]] [--break bit|sibling|root|leaf (leaf: with --update; --transfer: sibling)] "
-                             "[--sample-only] | --time-host K\n");
+                             "[--sample-only] | --schnorr [--seed S] [--sample-only] | --depth D --signed-transfer [--bits B] [--amount A] [--forge] [--sample-only] | --time-host K | --time-schnorr K\n");
         return 2;
     }
     try {

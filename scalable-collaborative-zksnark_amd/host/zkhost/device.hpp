@@ -724,6 +724,31 @@ class Ctx {
     void poseidon_merkle_update(const PoseidonParams &pp, const DevPtr &tree, size_t n, const std::vector<uint64_t> &index, const DevPtr &values) {
         check(zk_poseidon_merkle_update(h_, pp.h, tree.get(), n, index.data(), values.get(), index.size()));
     }
+    // ---- Jubjub and Schnorr verification (zk_jubjub_*, zk_schnorr_verify; the rule: include/zkhip.h, zkhost/jubjub.hpp) ----
+    // out[i] = [scalars[i]] points[i]: points n x 2 Fr (a null DevPtr: the fixed base G), scalars n x 4 uint64_t plain integers.  An off-curve
+    // point: ZkError(ZK_ERR_INVALID) with the library's "K of N points are not on the curve; the first is I", nothing written
+    DevPtr jubjub_mul(const DevPtr &points, const DevPtr &scalars, size_t n) {
+        DevPtr o = alloc_fr(n ? 2 * n : 1);
+        check(zk_jubjub_mul(h_, points.get(), scalars.get(), o.get(), n));
+        return o;
+    }
+    // one status per point: 0 in the prime-order subgroup, 2 not on the curve, 3 on the curve but outside the subgroup.  Blocking
+    std::vector<uint32_t> jubjub_check(const DevPtr &points, size_t n) {
+        std::vector<uint32_t> status(n, 0);
+        DevPtr st = alloc(n ? 4 * n : 4);
+        check(zk_jubjub_check(h_, points.get(), static_cast<uint32_t *>(st.get()), n));
+        download(status.data(), st, 4 * n);
+        return status;
+    }
+    // one status per signature (0 valid, 1 s >= l, 2 off the curve, 3 PK outside the subgroup or the identity, 4 the equation): pk n x 2 Fr,
+    // msg n Fr, sig n x 3 words (R.x, R.y Montgomery; s a plain integer).  Blocking
+    std::vector<uint32_t> schnorr_verify(const PoseidonParams &pp, const DevPtr &pk, const DevPtr &msg, const DevPtr &sig, size_t n) {
+        std::vector<uint32_t> status(n, 0);
+        DevPtr st = alloc(n ? 4 * n : 4);
+        check(zk_schnorr_verify(h_, pp.h, pk.get(), msg.get(), sig.get(), static_cast<uint32_t *>(st.get()), n));
+        download(status.data(), st, 4 * n);
+        return status;
+    }
     // ---- Plonk witness (zk_witness_plan_create, zk_plonk_witness, zk_plonk_witness_check) ----
     // sigma: 3N slot numbers; out_sel: the wide gate's qO on the device (null: every row computes).  Rows that depend on their own output or a
     // sigma that is not a permutation: ZkError(ZK_ERR_INVALID)

@@ -149,6 +149,9 @@ SYMBOLS = [
     ("zk_poseidon_merkle_paths", _i, [_vp, _vp, _sz, _vp, _sz, _vp]),
     ("zk_poseidon_merkle_roots", _i, [_vp, _vp, _vp, _vp, _vp, _sz, _sz, _vp]),
     ("zk_poseidon_merkle_update", _i, [_vp, _vp, _vp, _sz, _vp, _vp, _sz]),
+    ("zk_jubjub_mul", _i, [_vp, _vp, _vp, _vp, _sz]),
+    ("zk_jubjub_check", _i, [_vp, _vp, _vp, _sz]),
+    ("zk_schnorr_verify", _i, [_vp, _vp, _vp, _vp, _vp, _vp, _sz]),
 ]
 
 # include/zkhip_test.h: the zk_dbg_* test hooks -- not part of the ABI, resolved only when a test / tool asks (test_hooks())

@@ -30,6 +30,15 @@ rows that make the value mean something.  They are plain calls of the rows above
                                             x must name a COMPUTED value (a row's c, a public input): tied to a private variable alone, the
                                             sum would become the source of x's class and the bits_of rows would depend on their own output
                                             -- the witness plan refuses that.  Pass lin(1, x, 0, None) for a private x.
+    to_bits_strict(x) -> [255 bits]  [1018] the bits of x's CANONICAL integer and of no other: 255 rows bits_of(x, k, 1), 255 assert_bool rows, 254 lin
+                                            rows of the sum, assert_equal(sum, x) -- which alone would also admit the bits of x + r (2^255 > r) --
+                                            and 254 rows that compare the bit vector with the constant r - 1 from the top bit down: with e = "every
+                                            higher bit equals that of r - 1" (e starts as bit 254, which r - 1 has set), a position where r - 1 has
+                                            a 1 is the row e <- e b_k, a position where it has a 0 is the assertion e b_k = 0.  The bits of x + r
+                                            exceed r - 1, so they meet such an assertion with e = 1: NO witness.  x must name a computed value,
+                                            as for to_bits.
+    assert_bits_at_most(bits, c)  [n - 1]   for n boolean variables (the caller's assertion), least significant first, and a constant c of exactly n
+                                            bits: the integer of the bits is <= c, by the comparison to_bits_strict describes
     assert_range(x, n)         [3n - 1]     to_bits(x, n), its bits dropped: x < 2^n
     less_than(x, y, n) -> bit  [3n + 4]     for x, y < 2^n (the caller's assertion), n <= 252: d = x - y + 2^n, to_bits(d, n + 1), bit = 1 - its
                                             top bit: 1 iff x < y
@@ -200,6 +209,28 @@ class Builder:
             acc = self.lin(1, acc, 1 << k, bits[k], 0)
         self.assert_equal(acc, x)
         return bits
+
+    def to_bits_strict(self, x) -> list:
+        bits = [self.bits_of(x, k, 1) for k in range(255)]
+        for v in bits:
+            self.assert_bool(v)
+        acc = bits[0]
+        for k in range(1, 255):
+            acc = self.lin(1, acc, 1 << k, bits[k], 0)
+        self.assert_equal(acc, x)
+        self.assert_bits_at_most(bits, R_MOD - 1)
+        return bits
+
+    def assert_bits_at_most(self, bits, c: int) -> None:
+        n = len(bits)
+        if n < 2 or not (1 << (n - 1)) <= c < (1 << n):
+            raise ValueError("assert_bits_at_most takes n >= 2 bits and a constant of exactly n bits")
+        e = bits[n - 1]  # c has its top bit set
+        for k in range(n - 2, -1, -1):
+            if (c >> k) & 1:
+                e = self.mul(e, bits[k])
+            else:
+                self.assert_zero_of(0, e, 0, bits[k], 1, 0)
 
     def assert_range(self, x, n: int) -> None:
         self.to_bits(x, n)
