@@ -87,6 +87,7 @@ int zk_memcpy_d2h(zk_ctx *ctx, void *h_dst, const void *d_src, size_t bytes);
 int zk_memcpy_d2d(zk_ctx *ctx, void *d_dst, const void *d_src, size_t bytes); /* asynchronous, on the ctx stream */
 
 /* ---- element-wise Fr (hyperplonk/src/dhyperplonk.rs:233-238,251-256,326-339) -------- */
+/* zk_fr_add / sub / mul / axpb: d_out may be d_a or d_b itself (the same address, not a shifted overlap): a lane reads row i of both inputs before it stores row i. */
 int zk_fr_add(zk_ctx *ctx, const void *d_a, const void *d_b, void *d_out, size_t n);
 int zk_fr_sub(zk_ctx *ctx, const void *d_a, const void *d_b, void *d_out, size_t n);
 int zk_fr_mul(zk_ctx *ctx, const void *d_a, const void *d_b, void *d_out, size_t n);
